@@ -27,6 +27,11 @@ Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N > 1 
   publishes (24 + 2 x legs x dof x 8 B per robot), K = cycles of the launch; duration = HIP events around the launch / K.
 * ``cpu_baseline``: the CPU oracle (a scalar restatement of the reference loop, "port") timed on this box's host
   cores on a bounded sample of the same workload.
+* A plain run measures the headline figure only: set-up, warm-up, the ``--steps`` timed steps, the line.  ``--full`` adds
+  everything else - ``roofline`` (kernel-time runs of its own), ``parity``, ``cpu_baseline``, the launch-per-cycle and posted-input
+  figures of resident mode, the fused-K probes, the N > 1 reference runs and the secondary workloads under ``also``.
+* ``--dump-outputs DIR``: the joint state the timed path computed in its last step (``q``, ``qd``; N > 1: the gathered ``q``) as
+  ``DIR/<name>.npy`` in float64.  The inputs depend on the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -421,7 +426,8 @@ class Watchdog:
         return False
 
 
-def time_resident(eng, n, steps, warmup, stream, depth=16, final_gather=None, host_barrier=None, parity=None, gather_after_end=None):
+def time_resident(eng, n, steps, warmup, stream, depth=16, final_gather=None, host_barrier=None, parity=None, gather_after_end=None, kernel_time=True,
+                  outputs=None):
     """Timed region of resident mode: `steps` ticks of the doorbell, one control cycle each, bracketed by synchronisation.
     N > 1 (final_gather): the region ends with the all-gather of the LAST cycle's joints.  It is queued on the engine's stream behind a
     device-side wait for that cycle (shc_engine_resident_get_joint_state_async) before the first tick, so only its execution - not
@@ -430,7 +436,9 @@ def time_resident(eng, n, steps, warmup, stream, depth=16, final_gather=None, ho
     joints are gathered - no collective kernel ever has to be scheduled next to a persistent loop; the region contains the ticks, the end
     of the loop and the gather.
     parity: a ParityWindow factory; the window is warm-up + timed ticks (the state record is taken before the loop starts).
-    Returns (elapsed seconds for `steps` cycles, seconds per cycle of one long launch from HIP events on the launch stream, parity dict)."""
+    outputs: a dict that receives q / qd of the last timed cycle from the output ring (N = 1).
+    Returns (elapsed seconds for `steps` cycles, seconds per cycle of one long launch from HIP events on the launch stream - None unless
+    kernel_time -, parity dict)."""
     import ctypes
     import torch
     pw = parity() if parity else None
@@ -468,12 +476,16 @@ def time_resident(eng, n, steps, warmup, stream, depth=16, final_gather=None, ho
     if ended:
         q_last = eng.joints()[0] if pw else None   # (the state the loop wrote back: q of the window's last cycle)
     else:
-        if pw:
-            q_last = eng.resident_joints(max(warmup, 1) + steps - 1)[0]   # the output ring still holds the window's last cycle
+        if pw or outputs is not None:
+            q_last, qd_last = eng.resident_joints(max(warmup, 1) + steps - 1)   # the output ring still holds the window's last cycle
+            if outputs is not None:
+                outputs.update(q=q_last, qd=qd_last)
         eng.resident_end()
     if pw:
         par = pw.evaluate(max(warmup, 1) + steps, q_last)
         par["window"] = f"{max(warmup, 1)} warm-up + {steps} timed doorbell ticks of the resident loop; the engine's joints are the output ring's slot of the last cycle"
+    if not kernel_time:
+        return elapsed, None, par
     # kernel time per cycle: one launch of m cycles released at once, HIP events on the launch stream around it
     m = 4000
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -487,9 +499,11 @@ def time_resident(eng, n, steps, warmup, stream, depth=16, final_gather=None, ho
 
 
 def run_workload(name, n, steps, warmup, cps, seed, dist_ctx=None, gather_every=0, fused_probe=True, want_cpu_baseline=False, joint_efforts=False,
-                 mode="auto", gather_under_loop=False, want_parity=True, gather_form="rccl"):
+                 mode="auto", gather_under_loop=False, want_parity=True, gather_form="rccl", full=True, outputs=None):
     """One workload on this rank's GPU: prepare (untimed), time `steps` steps, measure the kernel with HIP events.
-    dist_ctx = (world, rank, local_rank) when the RCCL path is active."""
+    dist_ctx = (world, rank, local_rank) when the RCCL path is active.
+    full=False: the timed steps only - no kernel-time runs (roofline), secondary figures or N > 1 reference runs.
+    outputs: a dict that receives the joint state of the last timed step (q, qd; N > 1: the gathered q)."""
     import torch
     import torch.distributed as dist
     from syropod_highlevel_controller_amd.engine import BatchEngine
@@ -574,6 +588,8 @@ def run_workload(name, n, steps, warmup, cps, seed, dist_ctx=None, gather_every=
         for _ in range(warmup):
             step_once()
         fk = fused_k_probe(eng, p, n, lin, ang, extra, key, stream, K=K, reps=max(4, steps // K), want_parity=want_parity)
+        if outputs is not None:
+            outputs["q"], outputs["qd"] = eng.step_k_joints(K - 1)
         q, _ = eng.joints()
         finite = bool(np.isfinite(q).all())
         eng.close()
@@ -617,15 +633,16 @@ def run_workload(name, n, steps, warmup, cps, seed, dist_ctx=None, gather_every=
         torch.cuda.synchronize()
         gather_close()
         dist.barrier()   # while a resident loop is alive no device-wide synchronisation may be issued
-    if resident:   # the launch-per-cycle figure of the same engine first (secondary), then the resident one
-        for _ in range(warmup):
-            step_once()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for i in range(steps):
-            step_once()
-        torch.cuda.synchronize()
-        launch_elapsed = time.perf_counter() - t0
+    if resident:   # the launch-per-cycle figure of the same engine first (secondary, --full), then the resident one
+        if full:
+            for _ in range(warmup):
+                step_once()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(steps):
+                step_once()
+            torch.cuda.synchronize()
+            launch_elapsed = time.perf_counter() - t0
         if use_dist:
             dist.barrier()
         torch.cuda.synchronize()
@@ -637,7 +654,8 @@ def run_workload(name, n, steps, warmup, cps, seed, dist_ctx=None, gather_every=
                 eng.resident_joints_async(cycle, qshard.data_ptr())
                 all_gather_joints(qshard, world, out=gathered)
             with Watchdog(180, "resident region with the all-gather queued under the live loop", rank, wd_meta):
-                res_elapsed, res_cycle_s, parity = time_resident(eng, n, steps, warmup, stream, final_gather=final_gather, host_barrier=host_barrier, parity=pfac)
+                res_elapsed, res_cycle_s, parity = time_resident(eng, n, steps, warmup, stream, final_gather=final_gather, host_barrier=host_barrier, parity=pfac,
+                                                                 kernel_time=full)
         elif use_dist:   # N > 1 default: end the loop, then gather - no collective kernel next to a persistent loop
             with Watchdog(180, "resident region, loop ended before the all-gather", rank, wd_meta):
                 def gather_and_close():
@@ -645,15 +663,18 @@ def run_workload(name, n, steps, warmup, cps, seed, dist_ctx=None, gather_every=
                     if peer:
                         stream.synchronize()
                         gather_close()
-                res_elapsed, res_cycle_s, parity = time_resident(eng, n, steps, warmup, stream, gather_after_end=gather_and_close, host_barrier=host_barrier, parity=pfac)
+                res_elapsed, res_cycle_s, parity = time_resident(eng, n, steps, warmup, stream, gather_after_end=gather_and_close, host_barrier=host_barrier, parity=pfac,
+                                                                 kernel_time=full)
         else:
-            res_elapsed, res_cycle_s, parity = time_resident(eng, n, steps, warmup, stream, parity=pfac)
+            res_elapsed, res_cycle_s, parity = time_resident(eng, n, steps, warmup, stream, parity=pfac, kernel_time=full, outputs=outputs)
         elapsed = res_elapsed
+        if outputs is not None and use_dist:
+            outputs["q"] = gathered.cpu().numpy().reshape(world * n, -1)
         # secondary figure: a NEW velocity command for every robot in every cycle, from arrays resident in HBM.  Direct posts (ABI 4): two
         # bound input sets, alternated as a node's callbacks would fill one message while the controller reads the other; a post is a 16-byte
         # record in host-mapped memory (no kernel launch) that the relay wavefront turns into the cycle's header, the workers read the arrays.
         posted_value = posted_launch_value = None
-        if not use_dist and not os.environ.get("SHC_BENCH_NO_POSTED_PROBE"):   # (profiling runs skip it: one K-cycle launch to attribute counters to)
+        if full and not use_dist and not os.environ.get("SHC_BENCH_NO_POSTED_PROBE"):   # (profiling runs skip it: one K-cycle launch to attribute counters to)
             d_sets = [(torch.from_numpy(np.ascontiguousarray(lin)).cuda(), torch.from_numpy(np.ascontiguousarray(ang)).cuda()) for _ in range(2)]
             for k, (dl, da) in enumerate(d_sets):
                 eng.resident_bind_inputs(k, velocity=(dl.data_ptr(), da.data_ptr()))
@@ -703,10 +724,15 @@ def run_workload(name, n, steps, warmup, cps, seed, dist_ctx=None, gather_every=
             gather_close()
             elapsed = time.perf_counter() - t0  # this rank's K steps + its part of the gather; the MAX over ranks below is the job's time
         state["window"] = None
+        if outputs is not None:   # the last timed step's joints, before anything else steps the engine
+            if use_dist:
+                outputs["q"] = gathered.cpu().numpy().reshape(world * n, -1)
+            else:
+                outputs["q"], outputs["qd"] = eng.joints()
         if pw:
             parity = pw.evaluate(steps * cps, eng.joints()[0])
             parity["window"] = f"the {steps} timed steps ({steps * cps} control cycles, one launch of the fused cycle kernel per step)"
-        if use_dist:   # the same K steps without the gather, and the gather on its own (reported next to `value`, which contains both)
+        if use_dist and full:   # the same K steps without the gather, and the gather on its own (reported next to `value`, which contains both)
             with Watchdog(300, "steps without the gather / gather alone", rank, wd_meta):
                 dist.barrier()
                 torch.cuda.synchronize()
@@ -752,30 +778,32 @@ def run_workload(name, n, steps, warmup, cps, seed, dist_ctx=None, gather_every=
             efficiency = {"with_gather": (world * n * steps * cps / elapsed) / (world * ref), "without_gather": (world * n * steps * cps / nogather_elapsed) / (world * ref),
                           "is": "job value / (n_gpus x scale_reference.value): `value` contains the all-gather of the final joint buffer inside a region of only `steps` steps"}
 
-    # ---- kernel duration of the cycle kernel, HIP events on the launch stream.  Two upper bounds on the true duration:
-    #      (a) one event pair per launch (adds the event-record latency), (b) one pair around m back-to-back launches
-    #      (adds the inter-kernel gaps).  The smaller one is reported; rocprofv3's kernel-trace average agrees with it.
-    m = min(steps, 200)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(m)]
-    for a, b in evs:
-        a.record(stream)
-        eng.step(cps)
-        eng.join()      # (large batches: the second half of the step runs on the engine's internal stream)
-        b.record(stream)
-    torch.cuda.synchronize()
-    per_launch_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    for _ in range(m):
-        eng.step(cps)
-    eng.join()
-    e1.record(stream)
-    torch.cuda.synchronize()
-    kern_ms = min(per_launch_ms, e0.elapsed_time(e1) / m)
+    kern_ms = None
+    if full:
+        # ---- (--full) kernel duration of the cycle kernel, HIP events on the launch stream.  Two upper bounds on the true duration:
+        #      (a) one event pair per launch (adds the event-record latency), (b) one pair around m back-to-back launches
+        #      (adds the inter-kernel gaps).  The smaller one is reported; rocprofv3's kernel-trace average agrees with it.
+        m = min(steps, 200)
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(m)]
+        for a, b in evs:
+            a.record(stream)
+            eng.step(cps)
+            eng.join()      # (large batches: the second half of the step runs on the engine's internal stream)
+            b.record(stream)
+        torch.cuda.synchronize()
+        per_launch_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(m):
+            eng.step(cps)
+        eng.join()
+        e1.record(stream)
+        torch.cuda.synchronize()
+        kern_ms = min(per_launch_ms, e0.elapsed_time(e1) / m)
     # ---- secondary figure: 16 control cycles fused per launch (inputs held, state in registers between cycles)
     fused_value = None
     fused_k = None
-    if cps == 1 and world == 1 and fused_probe:
+    if cps == 1 and world == 1 and fused_probe and full:
         fc, reps = 16, max(64, steps // 16)   # (64 launches of 16 cycles: 25 - 125 ms per workload - a steady-state figure like the 300+ single launches above)
         for _ in range(3):
             eng.step(fc)
@@ -793,7 +821,7 @@ def run_workload(name, n, steps, warmup, cps, seed, dist_ctx=None, gather_every=
     # ---- secondary figure for batches large enough for the engine's two-stream split (shc_engine_step): the same steps as ONE launch
     #      each on the engine's stream (SHC_FEAT_SINGLE_STREAM), i.e. what round 2 measured as the primary figure
     single_stream = None
-    if cps == 1 and world == 1 and fused_probe and n_waves >= 4096:
+    if cps == 1 and world == 1 and fused_probe and full and n_waves >= 4096:
         from syropod_highlevel_controller_amd.params import FEAT_DEFAULT, FEAT_SINGLE_STREAM
         eng.set_features(FEAT_DEFAULT | FEAT_SINGLE_STREAM)
         for _ in range(20):
@@ -811,31 +839,33 @@ def run_workload(name, n, steps, warmup, cps, seed, dist_ctx=None, gather_every=
     q, _ = eng.joints()
     finite = bool(np.isfinite(q).all())
     eng.close()
-    # measured joint torques: per leg the torques themselves (dof x 8 B read) and the filtered tip-force estimate Leg::calculateTipForce keeps (24 B read + 24 B written)
-    effort_bytes = p.leg_count * (p.leg_dof[0] * 8 + 48) if joint_efforts else 0
-    alg_bytes = (ALG_BYTES_PER_CYCLE[key] + effort_bytes) * n * cps
-    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
-    launch_roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                       "traffic": measured_traffic(name + ("+efforts" if joint_efforts else ""), n, cps), "kernel": ("shc_cycle_half_kernel<walker half> + <model half> (a rotation-constrained cycle is two launches, two wavefronts per SIMD each)" if name in ("gravity", "gravity3") and n_waves >= 2048 else "shc_cycle_kernel")
-                                 + (" (a step = that for each half of the batch, the halves on two streams)" if n_waves >= 4096 else ""),
-                       "kernel_ms": kern_ms, "algorithmic_bytes_per_launch": alg_bytes,
-                       "algorithmic_bytes_are": f"SURVEY.md 8(d): {ALG_BYTES_PER_CYCLE[key]} B per robot and cycle" + (f" + {effort_bytes} B of joint torques read and tip-force estimate read + written" if effort_bytes else "")}
-    launch_roofline = with_issue_side(launch_roofline, measured_valu(name + ("+efforts" if joint_efforts else ""), n, cps), kern_ms * 1e-3)
-    if resident:
-        rb = resident_bytes_per_cycle(p) * n
-        r_ach = rb / res_cycle_s / 1e9
-        roofline = {"bound": "hbm", "achieved": r_ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": r_ach / HBM_PEAK_GBS,
-                    "traffic": measured_traffic(name + ":resident", n, cps), "kernel": "shc_resident2_kernel (one launch, K = 4000 cycles; two wavefronts per robot group)",
-                    "kernel_ms": res_cycle_s * 1e3, "kernel_ms_is": "per cycle: HIP events around one launch of K cycles / K",
-                    "algorithmic_bytes_per_launch": rb, "algorithmic_bytes_are": "per cycle, SURVEY.md 8(d) with the state on the chip: velocity input + published q, qd",
-                    "bound_note": ("the resident cycle is bound by one wavefront's dependent-issue latency, not by HBM (frac is small by construction): 592 VALU + 157 SALU + "
-                                   "50 LDS instructions per wave and cycle in 5 650 wave clocks, VALU issue share 0.43 of the wave's lifetime on 824 of the chip's 1 024 SIMDs "
-                                   "(profiles/r05_config2_resident_rocprofv3.txt); attribution of the loop skeleton in profiles/r05_probe_resident_skeleton.txt"),
-                    "state_streaming_equivalent_frac": ALG_BYTES_PER_CYCLE[key] * n / res_cycle_s / 1e9 / HBM_PEAK_GBS,
-                    "one_launch_per_cycle": launch_roofline}
-        roofline = with_issue_side(roofline, measured_valu(name + ":resident", n, cps), res_cycle_s)
-    else:
-        roofline = launch_roofline
+    roofline = None   # (--full: from the kernel-time runs above)
+    if full:
+        # measured joint torques: per leg the torques themselves (dof x 8 B read) and the filtered tip-force estimate Leg::calculateTipForce keeps (24 B read + 24 B written)
+        effort_bytes = p.leg_count * (p.leg_dof[0] * 8 + 48) if joint_efforts else 0
+        alg_bytes = (ALG_BYTES_PER_CYCLE[key] + effort_bytes) * n * cps
+        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
+        launch_roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                           "traffic": measured_traffic(name + ("+efforts" if joint_efforts else ""), n, cps), "kernel": ("shc_cycle_half_kernel<walker half> + <model half> (a rotation-constrained cycle is two launches, two wavefronts per SIMD each)" if name in ("gravity", "gravity3") and n_waves >= 2048 else "shc_cycle_kernel")
+                                     + (" (a step = that for each half of the batch, the halves on two streams)" if n_waves >= 4096 else ""),
+                           "kernel_ms": kern_ms, "algorithmic_bytes_per_launch": alg_bytes,
+                           "algorithmic_bytes_are": f"SURVEY.md 8(d): {ALG_BYTES_PER_CYCLE[key]} B per robot and cycle" + (f" + {effort_bytes} B of joint torques read and tip-force estimate read + written" if effort_bytes else "")}
+        launch_roofline = with_issue_side(launch_roofline, measured_valu(name + ("+efforts" if joint_efforts else ""), n, cps), kern_ms * 1e-3)
+        if resident:
+            rb = resident_bytes_per_cycle(p) * n
+            r_ach = rb / res_cycle_s / 1e9
+            roofline = {"bound": "hbm", "achieved": r_ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": r_ach / HBM_PEAK_GBS,
+                        "traffic": measured_traffic(name + ":resident", n, cps), "kernel": "shc_resident2_kernel (one launch, K = 4000 cycles; two wavefronts per robot group)",
+                        "kernel_ms": res_cycle_s * 1e3, "kernel_ms_is": "per cycle: HIP events around one launch of K cycles / K",
+                        "algorithmic_bytes_per_launch": rb, "algorithmic_bytes_are": "per cycle, SURVEY.md 8(d) with the state on the chip: velocity input + published q, qd",
+                        "bound_note": ("the resident cycle is bound by one wavefront's dependent-issue latency, not by HBM (frac is small by construction): 592 VALU + 157 SALU + "
+                                       "50 LDS instructions per wave and cycle in 5 650 wave clocks, VALU issue share 0.43 of the wave's lifetime on 824 of the chip's 1 024 SIMDs "
+                                       "(profiles/r05_config2_resident_rocprofv3.txt); attribution of the loop skeleton in profiles/r05_probe_resident_skeleton.txt"),
+                        "state_streaming_equivalent_frac": ALG_BYTES_PER_CYCLE[key] * n / res_cycle_s / 1e9 / HBM_PEAK_GBS,
+                        "one_launch_per_cycle": launch_roofline}
+            roofline = with_issue_side(roofline, measured_valu(name + ":resident", n, cps), res_cycle_s)
+        else:
+            roofline = launch_roofline
     res = {
         "value": world * n * steps * cps / elapsed, "elapsed": elapsed, "ms_per_step": elapsed / steps * 1e3, "parity": parity,
         "host_issue_ms_per_step": (enqueue_s / steps * 1e3) if enqueue_s else None,   # launch mode: the host's time to issue a step's launches (asynchronous)
@@ -889,11 +919,11 @@ def config5_bytes(legs, dof):
     return 2 * (sum((2 * d + 24) * 8 + 4 for d in dofs) + 28) + 24
 
 
-def run_config5(n, steps, warmup, seed, want_parity=True):
+def run_config5(n, steps, warmup, seed, want_parity=True, full=True, outputs=None):
     """BASELINE.json configs[4]: mixed morphologies (4 / 6 / 8 legs, 3 - 5 joints - one bin with legs of 3, 5 and 4 joints in the same
     robot -, all four gaits), instance i has morphology i mod 6 - the worst interleaving for a one-kernel design.  shc_fleet_create bins the instances (one engine + one HIP stream
     per morphology), so the device work is the same whatever the order; the interleaved and the sorted ("binned") order differ
-    only in the host-side permutation of the boundary arrays, reported separately."""
+    only in the host-side permutation of the boundary arrays, reported separately (--full)."""
     import torch
     from syropod_highlevel_controller_amd.fleet import MixedFleet
     from syropod_highlevel_controller_amd.parallel import velocity_inputs
@@ -902,7 +932,7 @@ def run_config5(n, steps, warmup, seed, want_parity=True):
     out = {}
     alg = 0
     parity = None
-    for order in ("interleaved", "binned"):
+    for order in ("interleaved", "binned") if full else ("interleaved",):
         mid = np.arange(n) % len(morphs) if order == "interleaved" else np.sort(np.arange(n) % len(morphs))
         fleet = MixedFleet(morphs, mid)
         t0 = time.perf_counter()
@@ -926,8 +956,10 @@ def run_config5(n, steps, warmup, seed, want_parity=True):
         fleet.synchronize()
         elapsed = time.perf_counter() - t0
         t0 = time.perf_counter()
-        q, _ = fleet.joints()
+        q, qd = fleet.joints()
         t_out = time.perf_counter() - t0
+        if outputs is not None and order == "interleaved":
+            outputs.update(q=q, qd=qd)
         if windows:
             per_bin = []
             for mk, view, pw in windows:
@@ -957,12 +989,12 @@ def run_config5(n, steps, warmup, seed, want_parity=True):
                                          "algorithmic_bytes_per_launch": alg}, measured_valu("config5", n, 1), r["ms_per_step"] * 1e-3)}
 
 
-def run_config4_full(steps, warmup, seed, gather_form="rccl", want_parity=True, shards=8):
+def run_config4_full(steps, warmup, seed, gather_form="rccl", want_parity=True, shards=8, full=True, outputs=None):
     """BASELINE.json configs[3] at its STATED size on ONE MI355X: 2^20 synthetic octopods (8 legs x 5 DOF), ripple gait, as the eight
     contiguous shards of 131 072 the 8-GPU job would own - one engine + HIP stream per shard (shc_fleet_create with the device id repeated), inputs keyed
     by the global instance id, nothing exchanged while stepping - followed by the exchange at its TRUE message size: shc_fleet_all_gather_joints fills a
     gathered [2^20][8][5] buffer (335.5 MB) for every shard slot, device-to-device copies (on one device they run over HBM instead of xGMI).
-    value = the stepping alone (comparable with the config-4 share line); gather_ms and value_with_gather are reported next to it."""
+    value = the stepping alone (comparable with the config-4 share line); gather_ms and value_with_gather are reported next to it (--full)."""
     import torch
     from syropod_highlevel_controller_amd import synthetic_octopod_params
     from syropod_highlevel_controller_amd.engine import BatchEngine
@@ -997,16 +1029,18 @@ def run_config4_full(steps, warmup, seed, gather_form="rccl", want_parity=True, 
         fleet.step(1)
     fleet.synchronize()
     elapsed = time.perf_counter() - t0
-    # the exchange at its true size (untimed first call allocates the gathered buffers)
-    fleet.all_gather_joints()
-    fleet.synchronize()
-    torch.cuda.synchronize()
-    reps = 5
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        bufs = fleet.all_gather_joints()
+    gather_s = None
+    if full:
+        # the exchange at its true size (untimed first call allocates the gathered buffers)
+        fleet.all_gather_joints()
         fleet.synchronize()
-    gather_s = (time.perf_counter() - t0) / reps
+        torch.cuda.synchronize()
+        reps = 5
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            bufs = fleet.all_gather_joints()
+            fleet.synchronize()
+        gather_s = (time.perf_counter() - t0) / reps
     gather_bytes = n * p.leg_count * p.leg_dof[0] * 8
     parity = None
     if pw:
@@ -1016,12 +1050,16 @@ def run_config4_full(steps, warmup, seed, gather_form="rccl", want_parity=True, 
                       instances=sum(r["instances"] for r in rs), well_posed_fraction=float(np.mean([r["well_posed_fraction"] for r in rs])),
                       window=f"the {steps} timed fleet steps; the first {PARITY_INSTANCES} robots of the first and of the last shard")
     # the gathered buffer of slot 0 against the joints the getter returns (instance order, all 2^20 robots)
-    q, _ = fleet.joints()
-    import ctypes
-    got = np.empty((n, p.leg_count, p.leg_dof[0]))
-    hip = ctypes.CDLL("libamdhip64.so")
-    rc = hip.hipMemcpy(ctypes.c_void_p(got.ctypes.data), ctypes.c_void_p(bufs[0]), ctypes.c_size_t(got.nbytes), 2)
-    gathered_ok = bool(rc == 0 and np.array_equal(got, q))
+    q, qd = fleet.joints()   # (the gather and the parity replay do not step the fleet: the joints of the last timed step)
+    if outputs is not None:
+        outputs.update(q=q, qd=qd)
+    gathered_ok = None
+    if full:
+        import ctypes
+        got = np.empty((n, p.leg_count, p.leg_dof[0]))
+        hip = ctypes.CDLL("libamdhip64.so")
+        rc = hip.hipMemcpy(ctypes.c_void_p(got.ctypes.data), ctypes.c_void_p(bufs[0]), ctypes.c_size_t(got.nbytes), 2)
+        gathered_ok = bool(rc == 0 and np.array_equal(got, q))
     moving = float((fleet.walk_state() == 1).mean())
     finite = bool(np.isfinite(q).all())
     fleet.close()
@@ -1033,15 +1071,15 @@ def run_config4_full(steps, warmup, seed, gather_form="rccl", want_parity=True, 
            "short": SHORT["config4full"], "mode": "one launch of the fused cycle kernel per shard and step (each shard's halves on two streams)", "instances_per_gpu": n,
            "legs": p.leg_count, "dof": p.leg_dof[0], "seed": seed, "shards": shards, "moving_fraction": moving, "finite": finite,
            "gather": "shc_fleet_all_gather_joints after the timed steps", "gather_form": "device-to-device copies, one buffer per shard slot (one device: over HBM)",
-           "gather_ms": gather_s * 1e3, "gather_bytes_per_rank": gather_bytes // shards, "gathered_buffer_bytes": gather_bytes, "gathered_buffers": shards,
+           "gather_ms": gather_s * 1e3 if full else None, "gather_bytes_per_rank": gather_bytes // shards, "gathered_buffer_bytes": gather_bytes, "gathered_buffers": shards,
            "gathered_buffer_matches_getter": gathered_ok, "value_without_gather": n * steps / elapsed,
-           "value_with_gather": n * steps / (elapsed + gather_s), "steps": steps}
+           "value_with_gather": n * steps / (elapsed + gather_s) if full else None, "steps": steps}
     roof = with_issue_side({"bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": measured_traffic("config4full", n, 1),
                             "kernel": f"shc_cycle_kernel<8,5> x {shards} shards on concurrent streams (wall clock per fleet step)", "kernel_ms": ms,
                             "algorithmic_bytes_per_launch": alg}, measured_valu("config4full", n, 1), ms * 1e-3)
-    assert gathered_ok, "the gathered buffer differs from the joints the getter returns"
+    assert gathered_ok is not False, "the gathered buffer differs from the joints the getter returns"
     return {"workload": cfg["workload"], "value": n * steps / elapsed, "unit": "control-cycles/s", "steps": steps, "ms_per_step": ms, "config": cfg, "roofline": roof,
-            "parity": parity, "gather_ms": gather_s * 1e3}
+            "parity": parity, "gather_ms": cfg["gather_ms"]}
 
 
 LINE_LIMIT = 4096          # hard limit of the final stdout line (the driver keeps a bounded tail of stdout and parses its last line)
@@ -1138,6 +1176,22 @@ def compact_line(full):
         line = json.dumps(out, separators=(",", ":"))
     assert len(line.encode()) < LINE_LIMIT, len(line)
     return line
+
+
+DUMP_LIMIT = 64 * 10**6    # --dump-outputs: bytes of array data in all
+
+
+def dump_outputs(directory, arrays, seed):
+    """--dump-outputs: every array as DIR/<name>.npy in float64, rows = instances.  When the arrays together exceed DUMP_LIMIT, each keeps the same fixed,
+    seeded sample of its rows (sorted instance ids drawn with `seed`), so that two runs with the same arguments write the same rows."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total, rows = sum(a.nbytes for a in arrays.values()), len(next(iter(arrays.values())))
+    keep = None
+    if total > DUMP_LIMIT - 4096:   # (room for the .npy headers)
+        keep = np.sort(np.random.default_rng(seed).choice(rows, max(1, rows * (DUMP_LIMIT - 4096) // total), replace=False))
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a if keep is None else a[keep])
 
 
 def flush_c_stdio():
@@ -1257,6 +1311,11 @@ def main(argv=None):
                     help="auto: resident mode where the batch fits the chip once (config 2), one launch per step otherwise; step_k: 16 cycles per launch with a new "
                          "input set in every cycle (shc_engine_step_k) as the timed form")
     ap.add_argument("--seed", type=int, default=0xC0FFEE)
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: roofline (kernel-time runs of its own), parity against the CPU oracle, "
+                    "cpu_baseline, the launch-per-cycle / posted-input / fused-K figures, the N > 1 reference runs and the secondary workloads under `also` "
+                    "(--no-* options still drop parts of it); a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the joint state of the last one (q, qd; N > 1: the gathered q) "
+                    "to DIR/<name>.npy, float64; a fixed, seeded sample of the instances when larger than 64 MB")
     args = ap.parse_args(argv)
 
     plan = resolve_world(args, argv)
@@ -1305,16 +1364,22 @@ def main(argv=None):
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic"}
     import gc
     gc.disable()   # no collector pass inside a timed region (a 20-tick region is 65 us long); collected by hand between the workloads
+    outputs = {} if (args.dump_outputs and rank == 0) else None
+    want_parity = rank == 0 and args.full and not args.no_parity
     if args.workload == "config5":
         if world > 1:
             raise SystemExit("config5 is a single-GPU workload here (the fleet shards in-process: shc_fleet_create device_ids)")
-        r = run_config5(n, args.steps, args.warmup, args.seed, want_parity=not args.no_parity)
+        r = run_config5(n, args.steps, args.warmup, args.seed, want_parity=want_parity, full=args.full, outputs=outputs)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs, args.seed)
         cfg = {k: v for k, v in r.items() if k not in ("value", "roofline", "ms_per_step", "parity")}
         cfg.update({"short": SHORT["config5"], "mode": "one launch per morphology bin and step, bins on concurrent streams", "instances_per_gpu": n, "seed": args.seed})
         emit(dict(head, value=r["value"], ms_per_step=r["ms_per_step"], config=cfg, roofline=r["roofline"], parity=r["parity"]))
         return 0
     if args.workload == "config4full":   # BASELINE.json configs[3] at its stated size on ONE device: 8 shards of 131 072 octopods + the full-size exchange
-        r = run_config4_full(args.steps, args.warmup, args.seed, gather_form=args.gather, want_parity=not args.no_parity)
+        r = run_config4_full(args.steps, args.warmup, args.seed, gather_form=args.gather, want_parity=want_parity, full=args.full, outputs=outputs)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs, args.seed)
         emit(dict(head, value=r["value"], ms_per_step=r["ms_per_step"], config=r["config"], roofline=r["roofline"], parity=r["parity"]))
         return 0
     # Measured joint torques are part of the primary workload (a node always receives them from jointStatesCallback and the
@@ -1322,13 +1387,15 @@ def main(argv=None):
     primary_efforts = not args.no_joint_efforts
     res = run_workload(args.workload, n, args.steps, args.warmup, args.cycles_per_step, args.seed,
                        dist_ctx=(world, rank, local_rank) if use_dist else None, gather_every=args.gather_every,
-                       fused_probe=not args.no_fused_probe, want_cpu_baseline=(rank == 0 and world == 1 and not args.no_cpu_baseline),
+                       fused_probe=not args.no_fused_probe, want_cpu_baseline=(rank == 0 and world == 1 and args.full and not args.no_cpu_baseline),
                        joint_efforts=primary_efforts and (args.workload == "config2" or args.joint_efforts), mode=args.mode,
-                       gather_under_loop=args.gather_under_loop, want_parity=(rank == 0 and not args.no_parity), gather_form=args.gather)
+                       gather_under_loop=args.gather_under_loop, want_parity=want_parity, gather_form=args.gather, full=args.full, outputs=outputs)
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs, args.seed)
     # The other single-GPU BASELINE.json configurations, measured in the same process (N = 1 default run only):
     # config 3 (65 536 hexapods, all four components of north_star), one GPU's share of config 4 (131 072 octopods) and config 4 at its full size.
     also = []
-    if world == 1 and not use_dist and args.workload == "config2" and not args.instances and not args.no_also:
+    if args.full and world == 1 and not use_dist and args.workload == "config2" and not args.instances and not args.no_also:
         for name, efforts in (("config2", not primary_efforts), ("config3", False), ("config4", False), ("config4", True), ("rough", False), ("gravity", False), ("gravity3", False)):
             k = max(300, min(args.steps, 1000))   # long enough that first-touch and clock ramp are outside the figure
             gc.collect()

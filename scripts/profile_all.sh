@@ -33,11 +33,11 @@ ls -la $S
 if [ -n "${ONLY:-}" ]; then exit 0; fi
 # the driver-shaped default run (every kernel of the bench line incl. the batch form of shc_engine_step_k), kernel trace + stats only
 cd /tmp; export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_default -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $S/default.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $S/../prof_default -- python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $S/default.log 2>&1
 python - <<PY > $S/r06_bench_default_rocprofv3.txt
 import glob, os
 f = sorted(glob.glob("$R/gpurun_out/prof_default/**/*_kernel_stats.csv", recursive=True), key=os.path.getmtime)
-print("== rocprofv3 --kernel-trace --stats -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline : kernel_stats.csv (the driver's N = 1 command)")
+print("== rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline : kernel_stats.csv (every kernel of the full bench line)")
 print(open(f[-1]).read() if f else "no kernel_stats.csv")
 PY
 grep -h '^{' $S/default.log | tail -1 > $S/r06_bench_default_line.json

@@ -9,7 +9,7 @@ G2="SQ_WAVES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_FLAT SQ_ACTIVE_IN
 G3="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_FLAT SQ_INST_CYCLES_SALU"
 run() { # name, bench args
   local name=$1; shift
-  local B="python $R/bench.py --steps 300 --warmup 40 --no-cpu-baseline --no-fused-probe --no-also --no-parity $*"
+  local B="python $R/bench.py --full --steps 300 --warmup 40 --no-cpu-baseline --no-fused-probe --no-also --no-parity $*"
   for g in 1 2 3; do
     eval "C=\$G$g"
     SHC_BENCH_NO_POSTED_PROBE=1 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/${name}_g$g -- $B > $O/${name}_g$g.log 2>&1

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -136,3 +137,17 @@ def test_launcher_world_size_must_match_gpus():
     assert r.returncode == 0 and json.loads(r.stdout) == {"action": "run", "world": 2, "rank": 1, "local_rank": 1}
     r = run_bench("--dry-launch")
     assert json.loads(r.stdout) == {"action": "run", "world": 1, "rank": 0, "local_rank": 0}
+
+
+def test_dump_outputs_writes_float64_and_samples_the_same_rows(tmp_path, monkeypatch):
+    q, qd = np.arange(18 * 40.0).reshape(40, 18), -np.arange(18 * 40.0).reshape(40, 18)
+    bench.dump_outputs(str(tmp_path / "whole"), {"q": q, "qd": qd}, 7)
+    assert np.array_equal(np.load(str(tmp_path / "whole" / "q.npy")), q) and np.load(str(tmp_path / "whole" / "qd.npy")).dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 4096 + 64 * 18 * 8 * 2)   # room for 64 of the 1000 rows of each array
+    big = np.random.default_rng(0).normal(size=(1000, 18))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"q": big, "qd": 2 * big}, 7)
+    a, b = (np.load(str(tmp_path / d / "q.npy")) for d in ("a", "b"))
+    assert a.shape == (64, 18) and np.array_equal(a, b) and np.array_equal(np.load(str(tmp_path / "a" / "qd.npy")), 2 * a)
+    rows = [int(np.flatnonzero((big == r).all(axis=1))[0]) for r in a]
+    assert rows == sorted(set(rows))
