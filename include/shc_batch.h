@@ -288,7 +288,9 @@ int shc_engine_join(shc_engine *e);
  *       consumes them = cycles whose outputs stay readable; max_cycles (1..2^31-2): hard bound of this launch; idle_timeout_ms
  *       (0 = 5 000): the device loop stops by itself when everything released has run and the doorbell has not moved for this long
  *       (a host that went away cannot leave the GPU spinning; every device-side wait is bounded).  SHC_ERR_UNSUPPORTED: the batch does not fit the chip once, or
- *       the configuration runs on a manual-leg kernel (a leg toggled, planner mode).  Rough terrain mode, tip rotations and the tip-align
+ *       the configuration runs on a manual-leg kernel (a leg toggled, planner mode), or a shc_engine_adjust_parameter of swing_height /
+ *       virtual_mass / virtual_stiffness / virtual_damping_ratio / force_gain waits for its cycle (call shc_engine_step(e, 1) first: the
+ *       resident kernel runs every cycle on one parameter block, the posing part of that cycle needs the old one).  Rough terrain mode, tip rotations and the tip-align
  *       pose (gravity_aligned_tips on <= 3-DOF legs, since round 5) have a resident form: one wavefront per robot group, up to ~990 wavefronts.  Until shc_engine_resident_end every other
  *       entry point that touches the engine's state returns SHC_ERR_BUSY.
  *   shc_engine_resident_post(e, inputs, cycle)
@@ -461,8 +463,15 @@ int shc_engine_change_gait(shc_engine *e, const shc_params *new_gait, int64_t *s
  *   NULL) receives the number of instances still outside and the caller calls again after the next cycle, as runningState retries on every loop while
  *   parameter_adjust_flag_ is set (:411-414).  On acceptance (*pending = 0) the legs of walking robots are mapped onto the new cycle
  *   (LegStepper::updatePhase, walk_controller.cpp:862-867) INSIDE the next control cycle, between its posing part and updateWalk, where the reference's
- *   loop has it; that cycle runs alone in its launch on the runtime-flag kernels.  Until it has run, shc_engine_step_k and resident mode map the phases
- *   before they start (the one-loop ordering against the posing part is then not kept).  The auto-pose phase tables keep the old step period
+ *   loop has it; that cycle runs alone in its launch on the runtime-flag kernels.  The posing part of that next cycle (updateStiffness / updateAdmittance)
+ *   still runs on the old swing_height, virtual_mass / stiffness / damping_ratio and force_gain, and a leg toggle, plan step or sequence step that is
+ *   that next loop runs its own kernels on the old values too (adjustParameter stores them after legStateToggle / executePlan, :396-414).  The loops
+ *   that consume the change for every instance are those that reach runningState in the reference: shc_engine_step, shc_engine_step_k (its first
+ *   cycle runs as one shc_engine_step), shc_engine_toggle_leg_state, shc_engine_execute_plan, shc_engine_execute_sequence(SHUT_DOWN).
+ *   execute_sequence(START_UP) (from READY) and shc_engine_step_to_new_stance run on the old values and leave the change pending.
+ *   shc_engine_get_state / set_state do not: a record shows the phases still in the old period, and injected phases are mapped inside the next loop.
+ *   Resident mode maps a pending step-cycle change's phases before it starts (the one-loop ordering against the posing part is then not kept) and
+ *   refuses to start (SHC_ERR_UNSUPPORTED) while old posing values are held: step once first.  The auto-pose phase tables keep the old step period
  *   (setAutoPoseParams is not called by adjustParameter).  SHC_ERR_UNSUPPORTED for step_frequency in rough_terrain_mode, with gravity_aligned_tips or with a
  *   non-zero stance_span_modifier (the posing part / the limit generation read stepper state there that this ordering cannot reproduce); the other eight
  *   parameters have no such restriction.  Synchronises the engine's stream; SHC_ERR_BUSY in resident mode.
@@ -801,10 +810,13 @@ int shc_engine_set_target_body_pose(shc_engine *e, int64_t first, int64_t count,
 int shc_engine_execute_plan(shc_engine *e, int32_t *progress, int32_t *plan_step);
 
 int64_t shc_sizeof_instance_state(void);
-/* Instances [first, first + count) -> states[0 .. count) (host array).  Synchronises the engine's stream. */
+/* Instances [first, first + count) -> states[0 .. count) (host array).  Synchronises the engine's stream.  Read-only: a change made by
+ * shc_engine_adjust_parameter that waits for the next loop stays pending (the legs' phases and progress are reported in the step cycle they still
+ * count in), so a snapshot taken between the two does not change the run. */
 int shc_engine_get_state(shc_engine *e, int64_t first, int64_t count, shc_instance_state *states);
 /* states[0 .. count) (host array) -> instances [first, first + count).  Inputs (velocity, IMU, forces, efforts, pose
- * inputs' reset mode) are not part of the state and stay as set. */
+ * inputs' reset mode) are not part of the state and stay as set.  A pending shc_engine_adjust_parameter stays pending: injected phases
+ * count in the old step period and are mapped onto the new one inside the next loop, as those of the replaced state would have been. */
 int shc_engine_set_state(shc_engine *e, int64_t first, int64_t count, const shc_instance_state *states);
 
 /*

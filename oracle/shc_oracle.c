@@ -2790,9 +2790,9 @@ static void walker_update_manual_pose(orc_robot *r);
 int orc_adjust_parameter(orc_robot *r, int which, double value);
 void orc_adjust_parameter_commit(orc_robot *r, int which);
 void orc_request_parameter_adjust(orc_robot *r, int which, double value);
-static void state_running_state(orc_robot *r)
+/* "Dynamically adjust parameters" (:411-414): after the posing part of this loop and after legStateToggle / executePlan (:396-405), before updateWalk */
+static void state_serve_parameter_adjust(orc_robot *r)
 {
-  /* "Dynamically adjust parameters" (:411-414): after the posing part of this loop, before updateWalk */
   if (r->adjust_commit_due)
   {
     orc_adjust_parameter_commit(r, r->adjust_commit_due);
@@ -2802,6 +2802,10 @@ static void state_running_state(orc_robot *r)
   {
     if (orc_adjust_parameter(r, r->dynamic_parameter, r->new_parameter_value) != 0) r->parameter_adjust_flag = 0;
   }
+}
+static void state_running_state(orc_robot *r)
+{
+  state_serve_parameter_adjust(r);
   walker_update_walk(r, r->linear_velocity_input, r->angular_velocity_input);
   walker_update_manual_velocity(r); /* :433-434 */
   walker_update_manual_pose(r);     /* :439-440 */
@@ -3849,7 +3853,14 @@ void orc_sequence_prologue(orc_robot *r)
     admittance_update_admittance(r);
   }
 }
-int orc_execute_sequence(orc_robot *r, int sequence) { return poser_execute_sequence(r, sequence); }
+int orc_execute_sequence(orc_robot *r, int sequence)
+{
+  int progress = poser_execute_sequence(r, sequence);
+  /* SHUT_DOWN runs from RUNNING inside runningState (state_controller.cpp:384-388, :328-352): adjustParameter follows in the same loop (:411-414).
+   * START_UP runs from READY (:184-187, :314), where runningState - and with it adjustParameter - is not reached (:189-192). */
+  if (sequence == SEQ_SHUT_DOWN) state_serve_parameter_adjust(r);
+  return progress;
+}
 int orc_step_to_new_stance(orc_robot *r) { return poser_step_to_new_stance(r); }
 int orc_sequence_failed(const orc_robot *r) { return r->sequence_failed; }
 int orc_pack_legs(orc_robot *r, const double *packed_positions, int number_pack_steps, double time_to_pack)
@@ -3902,6 +3913,7 @@ int orc_execute_plan(orc_robot *r)
   orc_sequence_prologue(r);
   int result = state_execute_plan(r);
   if (result == -1) state_running_state(r);
+  else state_serve_parameter_adjust(r); /* runningState reaches adjustParameter after executePlan too (state_controller.cpp:401-414) */
   return result;
 }
 int orc_get_plan_step(const orc_robot *r) { return r->plan_step; }
@@ -3914,6 +3926,7 @@ int orc_leg_state_toggle(orc_robot *r, int leg)
   orc_sequence_prologue(r);
   int result = state_leg_state_toggle(r, leg);
   if (result == -1) state_running_state(r);
+  else state_serve_parameter_adjust(r); /* runningState reaches adjustParameter after legStateToggle too (state_controller.cpp:396-414) */
   return result;
 }
 int orc_get_leg_manipulation_state(const orc_robot *r, int leg) { return r->leg[leg].leg_state; }

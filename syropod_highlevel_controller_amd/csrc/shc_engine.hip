@@ -272,6 +272,8 @@ struct shc_engine {
   bool span_dirty = true;
   bool step_remap_pending = false;      // an accepted step-frequency change waits for the next cycle (shc_engine_adjust_parameter)
   bool pose_params_held = false;        // the posing part of the next cycle still runs on the parameter values a just-adjusted parameter had (ditto)
+  shc_step_cycle remap_old_step{};      // step_remap_pending: the step cycle the legs' phases still count in
+  shc_params held_params{};             // pose_params_held: the parameters as they were before the change (their posing values: rebuild_cycle_params)
   bool fresh_pose_controller = false;   // init_state for shc_engine_begin_sequence_startup: no direct start-up has run, the auto posers have not been called yet
   struct Resident *res = nullptr;       // resident mode (shc_resident.hpp)
   const double *bound_inputs[kBoundSets][BND_COUNT] = {}; // shc_engine_resident_bind_inputs: the caller's device arrays for direct posts
@@ -291,6 +293,8 @@ static void resident_shutdown(shc_engine *e); // stop a running resident loop an
 // While the resident kernel owns the engine's stream and state, every other entry point that would touch them is refused.
 static int join_side(shc_engine *e);
 static int flush_step_remap(shc_engine *e); // an accepted step-frequency change no cycle has consumed yet: map the phases now
+static void rebuild_cycle_params(shc_engine *e);
+static int consume_pending_adjustment(shc_engine *e);
 #define SHC_BUSY_ONLY(e)                                                                                                       \
   do {                                                                                                                         \
     if ((e) && resident_active(e))                                                                                             \
@@ -979,7 +983,7 @@ extern "C" int shc_engine_set_features(shc_engine *e, uint32_t features) {
   SHC_BUSY_GUARD(e);
   if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
   e->features = features;
-  build_cycle_params(e->params, e->tables, e->features, e->rt_flags, e->cp);
+  rebuild_cycle_params(e);
   return upload_consts(e);
 }
 
@@ -1182,7 +1186,7 @@ extern "C" int shc_engine_set_tip_force(shc_engine *e, const double *tip_force, 
 static int effort_live(shc_engine *e) {
   if (e->rt_flags & RT_EFFORT_LIVE) return SHC_OK;
   e->rt_flags |= RT_EFFORT_LIVE;
-  build_cycle_params(e->params, e->tables, e->features, e->rt_flags, e->cp);
+  rebuild_cycle_params(e);
   return upload_consts(e);
 }
 
@@ -1343,7 +1347,7 @@ extern "C" int shc_engine_step(shc_engine *e, int n_cycles) {
     int rc = shc_engine_step(e, 1);
     e->features = keep;
     if (rc == SHC_OK) rc = join_side(e);
-    build_cycle_params(e->params, e->tables, e->features, e->rt_flags, e->cp);
+    rebuild_cycle_params(e);
     if (rc == SHC_OK) rc = upload_consts(e); // (ordered behind the cycle above on the engine's stream, and synchronises it)
     if (rc != SHC_OK || n_cycles == 1) return rc;
     --n_cycles;
@@ -1560,10 +1564,11 @@ __global__ void step_remap_kernel(int32_t *legi, const int32_t *robi, int rpw, i
   legi[slot_of(rob, leg, L)] = (w & ~(3 | (LW_PHASE_MASK << LW_PHASE_SHIFT))) | st | (ph << LW_PHASE_SHIFT);
 }
 static int flush_step_remap(shc_engine *e) {
+  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
   if (!e->step_remap_pending) {
     if (!e->pose_params_held) return SHC_OK;
     e->pose_params_held = false; // (the next cycle is not a shc_engine_step: the new values are in force for all of it)
-    build_cycle_params(e->params, e->tables, e->features, e->rt_flags, e->cp);
+    rebuild_cycle_params(e);
     return upload_consts(e);
   }
   e->step_remap_pending = e->pose_params_held = false;
@@ -1574,10 +1579,34 @@ static int flush_step_remap(shc_engine *e) {
   }
   const int64_t threads = e->n * e->L;
   const shc_step_cycle &s = e->tables.step;
-  step_remap_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(e->st.legi, e->st.robi, 64 / e->L, e->n, e->L, e->cp.remap_old_period, s.period,
+  step_remap_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(e->st.legi, e->st.robi, 64 / e->L, e->n, e->L, e->remap_old_step.period, s.period,
                                                                                        s.swing_start, s.swing_end, s.stance_end, s.stance_start);
   HIP_TRY(hipGetLastError());
+  rebuild_cycle_params(e);
+  return upload_consts(e);
+}
+// The launch-uniform parameter block of the engine's parameters, with what an adjustParameter still waiting for its loop leaves of the old ones: the
+// posing part's values of the parameters before the change (pose_params_held) and the period the phases still count in (step_remap_pending).
+static void rebuild_cycle_params(shc_engine *e) {
   build_cycle_params(e->params, e->tables, e->features, e->rt_flags, e->cp);
+  if (e->step_remap_pending) e->cp.remap_old_period = e->remap_old_step.period;
+  if (e->pose_params_held) {
+    CycleParams h;
+    build_cycle_params(e->held_params, e->tables, e->features, e->rt_flags, h);
+    e->cp.adm_m00 = h.adm_m00, e->cp.adm_m01 = h.adm_m01, e->cp.adm_m10 = h.adm_m10, e->cp.adm_m11 = h.adm_m11;
+    e->cp.adm_g0 = h.adm_g0, e->cp.adm_g1 = h.adm_g1;
+    e->cp.virtual_stiffness = h.virtual_stiffness, e->cp.pose_force_gain = h.pose_force_gain, e->cp.pose_swing_height = h.pose_swing_height;
+  }
+}
+// A loop-level call (leg toggle, plan step, SHUT_DOWN sequence step) has run the loop that an adjustParameter waited for: runningState reaches
+// adjustParameter after transitionRobotState / legStateToggle / executePlan (state_controller.cpp:384-414), for every robot of the batch.  Its pose pass and its
+// marked launch ran on the held block and remapped the phases of the robots that walked in it; from here on the new values are in force for all.
+static int consume_pending_adjustment(shc_engine *e) {
+  if (!e->step_remap_pending && !e->pose_params_held) return SHC_OK;
+  e->step_remap_pending = e->pose_params_held = false;
+  const int rc = join_side(e);
+  if (rc != SHC_OK) return rc;
+  rebuild_cycle_params(e);
   return upload_consts(e);
 }
 
@@ -1658,23 +1687,15 @@ static int adjust_step_frequency(shc_engine *e, double value, int64_t *pending) 
   if (waiting) return upload_consts(e); // not yet: the new speed maps / phase offsets are in force, the step cycle and the acceleration maps are the old ones
   // accepted: walker_->generateStepCycle() + generateLimits() (:491-492).  setAutoPoseParams is NOT called (only init / changeGait do): the auto-pose phase
   // tables keep counting in the old step period, as in the reference.
-  const int old_period = e->tables.step.period;
+  const shc_step_cycle old_step = e->tables.step;
   e->tables.step = ns;
   for (int b = 0; b < SHC_N_BEARINGS; ++b) {
     e->tables.max_linear_acceleration[b] = tn.max_linear_acceleration[b];
     e->tables.max_angular_acceleration[b] = tn.max_angular_acceleration[b];
   }
-  {
-    const CycleParams before = e->cp;
-    build_cycle_params(e->params, e->tables, e->features, e->rt_flags, e->cp);
-    if (e->pose_params_held) { // (a direct parameter was adjusted since the last cycle: its old value still belongs to the next cycle's posing part)
-      e->cp.adm_m00 = before.adm_m00, e->cp.adm_m01 = before.adm_m01, e->cp.adm_m10 = before.adm_m10, e->cp.adm_m11 = before.adm_m11;
-      e->cp.adm_g0 = before.adm_g0, e->cp.adm_g1 = before.adm_g1;
-      e->cp.virtual_stiffness = before.virtual_stiffness, e->cp.pose_force_gain = before.pose_force_gain, e->cp.pose_swing_height = before.pose_swing_height;
-    }
-  }
-  e->cp.remap_old_period = old_period; // generateStepCycle's updatePhase for MOVING robots: inside the next cycle (shc_engine_step)
+  e->remap_old_step = old_step; // generateStepCycle's updatePhase for MOVING robots: inside the next cycle (cp.remap_old_period, shc_engine_step)
   e->step_remap_pending = true;
+  rebuild_cycle_params(e);
   return upload_consts(e);
 }
 
@@ -1685,6 +1706,7 @@ extern "C" int shc_engine_adjust_parameter(shc_engine *e, int which, double valu
   if (!(value == value) || fabs(value) > 1e300) return fail(SHC_ERR_INVALID_ARG, "parameter value is not finite");
   HIP_TRY(hipSetDevice(e->device));
   shc_params &p = e->params;
+  const shc_params old = p;
   switch (which) {
     case SHC_PARAM_STEP_FREQUENCY: return adjust_step_frequency(e, value, pending);
     case SHC_PARAM_SWING_HEIGHT: p.swing_height = value; break;          // LegStepper::updateStride's swing clearance, the dynamic-stiffness reference, sequence step heights
@@ -1708,17 +1730,12 @@ extern "C" int shc_engine_adjust_parameter(shc_engine *e, int which, double valu
   // ... except where the POSING part of the loop reads them (updateStiffness / updateAdmittance run before runningState, state_controller.cpp:170-180): the
   // virtual spring's constants, the force gain as the admittance input scales it and the swing height as the dynamic-stiffness reference divides by it stay
   // what they were for the posing part of the next cycle (the tip-force estimate and the stepper of that same cycle use the new values), then follow.
-  const CycleParams before = e->cp;
-  build_cycle_params(e->params, e->tables, e->features, e->rt_flags, e->cp);
-  e->cp.remap_old_period = before.remap_old_period;
-  e->cp.adm_m00 = before.adm_m00, e->cp.adm_m01 = before.adm_m01, e->cp.adm_m10 = before.adm_m10, e->cp.adm_m11 = before.adm_m11;
-  e->cp.adm_g0 = before.adm_g0, e->cp.adm_g1 = before.adm_g1;
-  e->cp.virtual_stiffness = before.virtual_stiffness;
-  e->cp.pose_force_gain = before.pose_force_gain;
-  e->cp.pose_swing_height = before.pose_swing_height;
   if (which == SHC_PARAM_SWING_HEIGHT || which == SHC_PARAM_VIRTUAL_MASS || which == SHC_PARAM_VIRTUAL_STIFFNESS || which == SHC_PARAM_VIRTUAL_DAMPING ||
-      which == SHC_PARAM_FORCE_GAIN)
+      which == SHC_PARAM_FORCE_GAIN) {
+    if (!e->pose_params_held) e->held_params = old; // (the values the last cycle's posing part ran on)
     e->pose_params_held = true;
+  }
+  rebuild_cycle_params(e);
   return upload_consts(e);
 }
 
@@ -2518,10 +2535,13 @@ static int ensure_seq(shc_engine *e) { // the per-robot PoseController records o
 }
 static SeqParams seq_params(const shc_engine *e) {
   SeqParams P{};
+  // A direct parameter adjusted since the last cycle is stored by adjustParameter AFTER legStateToggle / executePlan / transitionRobotState in the
+  // loop that serves it (state_controller.cpp:384-414): the loop-level kernels of that loop still read the old value.
+  const shc_params &q = e->pose_params_held ? e->held_params : e->params;
   P.step_frequency = e->params.step_frequency;
-  P.swing_height = e->params.swing_height;
+  P.swing_height = q.swing_height;
   P.dt = e->params.time_delta;
-  P.force_gain = e->params.force_gain;
+  P.force_gain = q.force_gain;
   P.clamp_vel = e->params.clamp_joint_velocities;
   P.clamp_pos = e->params.clamp_joint_positions;
   P.tip_force = e->cp.tip_force;
@@ -2590,7 +2610,11 @@ static int sequence_launch(shc_engine *e, int which /* 0 / 1: executeSequence(ST
   }
   if (progress) HIP_TRY(hipMemcpyAsync(progress, d_progress, size_t(e->n) * 4, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
-  return SHC_OK;
+  // A pending adjustParameter is served only where the reference reaches it: SHUT_DOWN runs from RUNNING, inside runningState's transitionRobotState
+  // (state_controller.cpp:384-388, :328-352), and adjustParameter follows in the same loop (:411-414).  START_UP runs from READY in loop() (:184-187,
+  // :314) - runningState is not reached (:189-192) - and stepToNewStance is no loop of the StateController at all: the change stays pending (the
+  // sequence kernels above and the pose pass read the old values, seq_params) until the next loop that reaches runningState.
+  return which == SHC_SEQUENCE_SHUT_DOWN ? consume_pending_adjustment(e) : SHC_OK;
 }
 
 extern "C" int shc_engine_execute_sequence(shc_engine *e, int sequence, int32_t *progress) {
@@ -2635,10 +2659,11 @@ extern "C" int shc_engine_toggle_leg_state(shc_engine *e, const int32_t *leg_sel
   HIP_TRY(hipMemcpyAsync(d_sel, leg_selection, size_t(e->n) * 4, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemsetAsync(d_cycle, 0, 4, e->stream));
   const SeqParams P = seq_params(e);
+  const double virtual_stiffness = (e->pose_params_held ? e->held_params : e->params).virtual_stiffness; // (see seq_params)
   const dim3 grid((unsigned)((e->n + 63) / 64)), block(64);
   int phase = LOOP_WHOLE;
 #define CALL(L_, NJ_)                                                                                                                              \
-  leg_state_toggle_kernel<L_, NJ_><<<grid, block, 0, e->stream>>>(e->st, (const SharedConsts<L_, NJ_> *)e->d_consts, d_sel, P, e->params.virtual_stiffness, \
+  leg_state_toggle_kernel<L_, NJ_><<<grid, block, 0, e->stream>>>(e->st, (const SharedConsts<L_, NJ_> *)e->d_consts, d_sel, P, virtual_stiffness,       \
                                                                   e->params.swing_stiffness_scaler, e->params.load_stiffness_scaler,                \
                                                                   e->params.admittance_control && e->params.dynamic_stiffness, d_res, d_cycle, phase)
   if (posing_needs_pose_pass(e)) { // mark the robots that stand with a request, run the posing part of their loop in the cycle kernel
@@ -2662,7 +2687,7 @@ extern "C" int shc_engine_toggle_leg_state(shc_engine *e, const int32_t *leg_sel
     if (rc != SHC_OK) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
   }
-  return SHC_OK;
+  return consume_pending_adjustment(e);
 }
 
 extern "C" int shc_engine_set_manual_inputs(shc_engine *e, const int32_t *primary_leg, const double *primary_tip_velocity, const double *primary_tip_position,
@@ -2789,7 +2814,7 @@ extern "C" int shc_engine_execute_plan(shc_engine *e, int32_t *progress, int32_t
     if (rc != SHC_OK) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
   }
-  return SHC_OK;
+  return consume_pending_adjustment(e);
 }
 
 // PoseController::packLegs / unpackLegs (pose_controller.cpp:615-707)
@@ -2921,7 +2946,7 @@ extern "C" int shc_engine_finish_sequence_startup(shc_engine *e) {
   if (!ok) return fail(SHC_ERR_INVALID_ARG, "init chain failed for the configuration the sequence ended on");
   e->tables = t;
   e->span_dirty = true;
-  build_cycle_params(e->params, e->tables, e->features, e->rt_flags, e->cp);
+  rebuild_cycle_params(e); // (a change still pending is served by the runningState() below: shc_engine_step's held cycle)
   if ((rc = upload_consts(e)) != SHC_OK) return rc;
   // walker_->init() (:306): fresh LegSteppers / walk state; the joints stay where the sequence left them
   const int n_joint_planes = (2 * e->NJ + 1) / 2 + 1; // planes holding Q and QD (Fields: Q = 0, QD = NJ, TIP = 2 NJ)
@@ -2967,11 +2992,9 @@ extern "C" int shc_engine_finish_sequence_startup(shc_engine *e) {
 extern "C" int64_t shc_sizeof_instance_state(void) { return (int64_t)sizeof(shc_instance_state); }
 
 // Snapshot records travel through a temporary device buffer (checkpoint / injection are not per-cycle operations).
+// Neither direction consumes an adjustParameter that waits for its loop: a record shows the legs' phases in the period they still count in (as the
+// reference's state between the two loops), an injected record's phases are mapped onto the new period inside the accepting loop.
 static int state_transfer(shc_engine *e, int64_t first, int64_t count, shc_instance_state *out, const shc_instance_state *in) {
-  { // (a state record shows / replaces the legs' phases as the accepting loop leaves them)
-    const int rc_remap = flush_step_remap(e);
-    if (rc_remap != SHC_OK) return rc_remap;
-  }
   if (!e || (!out && !in)) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
   if (first < 0 || count < 0 || first + count > e->n) return fail(SHC_ERR_INVALID_ARG, "instance range out of bounds");
   if (count == 0) return SHC_OK;
@@ -2990,6 +3013,12 @@ static int state_transfer(shc_engine *e, int64_t first, int64_t count, shc_insta
     }
   }
   const int touchdown = (e->rt_flags & RT_TOUCHDOWN) ? 1 : 0;
+  CycleParams cp = e->cp; // (get_state_kernel derives swing / stance progress from the phase: in the step cycle the phase counts in)
+  if (e->step_remap_pending) {
+    const shc_step_cycle &s = e->remap_old_step;
+    cp.period = s.period, cp.swing_period = s.swing_period, cp.stance_period = s.stance_period;
+    cp.stance_end = s.stance_end, cp.swing_start = s.swing_start, cp.swing_end = s.swing_end, cp.stance_start = s.stance_start;
+  }
   unsigned long_legs = 0;
   for (int l = 0; l < e->L; ++l) long_legs |= e->params.leg_dof[l] > 3 ? 1u << l : 0u;
   HIP_TRY(hipSetDevice(e->device));
@@ -3001,14 +3030,14 @@ static int state_transfer(shc_engine *e, int64_t first, int64_t count, shc_insta
   if (in) err = hipMemcpyAsync(d, in, bytes, hipMemcpyHostToDevice, e->stream);
   if (err == hipSuccess) {
     switch (e->NJ) {
-      case 3: if (in) set_state_kernel<3><<<grid, block, 0, e->stream>>>(d, e->st, e->cp, e->L, first, count, long_legs);
-              else get_state_kernel<3><<<grid, block, 0, e->stream>>>(d, e->st, e->cp, e->L, first, count, touchdown, long_legs);
+      case 3: if (in) set_state_kernel<3><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, long_legs);
+              else get_state_kernel<3><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, touchdown, long_legs);
               break;
-      case 4: if (in) set_state_kernel<4><<<grid, block, 0, e->stream>>>(d, e->st, e->cp, e->L, first, count, long_legs);
-              else get_state_kernel<4><<<grid, block, 0, e->stream>>>(d, e->st, e->cp, e->L, first, count, touchdown, long_legs);
+      case 4: if (in) set_state_kernel<4><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, long_legs);
+              else get_state_kernel<4><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, touchdown, long_legs);
               break;
-      default: if (in) set_state_kernel<5><<<grid, block, 0, e->stream>>>(d, e->st, e->cp, e->L, first, count, long_legs);
-               else get_state_kernel<5><<<grid, block, 0, e->stream>>>(d, e->st, e->cp, e->L, first, count, touchdown, long_legs);
+      default: if (in) set_state_kernel<5><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, long_legs);
+               else get_state_kernel<5><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, touchdown, long_legs);
                break;
     }
     err = hipGetLastError();

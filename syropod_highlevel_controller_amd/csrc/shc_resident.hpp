@@ -202,6 +202,12 @@ extern "C" int shc_engine_resident_begin(shc_engine *e, int ring_depth, int64_t 
   if (max_cycles < 1 || max_cycles > 0x7ffffffe) return fail(SHC_ERR_INVALID_ARG, "max_cycles must be 1..2^31-2");
   if (idle_timeout_ms < 0 || idle_timeout_ms > 600000) return fail(SHC_ERR_INVALID_ARG, "idle_timeout_ms must be 0..600000");
   if (e->starting_up) return fail(SHC_ERR_UNSUPPORTED, "resident mode starts from a running engine (finish the start-up first)");
+  // The resident kernel reads one parameter block for its whole life.  By design it is not given a second block and a switch after cycle 1 (that would
+  // change the kernel of the headline loop for a one-cycle case): the loop that still runs its posing part on the values before a
+  // shc_engine_adjust_parameter is a shc_engine_step.
+  if (e->pose_params_held)
+    return fail(SHC_ERR_UNSUPPORTED, "resident mode cannot start while an adjusted parameter waits for its cycle (the posing part of the next cycle runs on "
+                                     "the old value): call shc_engine_step(e, 1) once first");
   {
     const int rc_remap = flush_step_remap(e);
     if (rc_remap != SHC_OK) return rc_remap;
@@ -744,10 +750,6 @@ extern "C" int shc_engine_step_k(shc_engine *e, int n_cycles, const shc_cycle_in
   if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
   if (n_cycles < 1 || n_cycles > 4096) return fail(SHC_ERR_INVALID_ARG, "shc_engine_step_k: 1 .. 4096 cycles per launch");
   if (e->starting_up) return fail(SHC_ERR_UNSUPPORTED, "shc_engine_step_k starts from a running engine (finish the start-up first)");
-  {
-    const int rc_remap = flush_step_remap(e);
-    if (rc_remap != SHC_OK) return rc_remap;
-  }
   unsigned mask = 0;
   if (in) {
     if (!in->on_device) return fail(SHC_ERR_INVALID_ARG, "shc_engine_step_k: the K-deep input arrays are device arrays (on_device = 1)");
@@ -784,19 +786,29 @@ extern "C" int shc_engine_step_k(shc_engine *e, int n_cycles, const shc_cycle_in
     if (rc != SHC_OK) return rc;
   }
   if (!fit.batch || (e->features & SHC_FEAT_STEP_K_SERIAL)) return step_k_serial(e, n_cycles, in);
+  // An adjustParameter waits for its loop (shc_engine_adjust_parameter): cycle 1 runs as shc_engine_step runs it - on the held parameter block, the phases
+  // mapped inside it - through the serial form (input row 0, ring slot 0); the batch kernel takes the other K - 1 cycles on the new block.
+  int k0 = 0;
+  if (e->step_remap_pending || e->pose_params_held) {
+    const int rc = step_k_serial(e, 1, in);
+    if (rc != SHC_OK) return rc;
+    if (n_cycles == 1) return SHC_OK;
+    k0 = 1;
+  }
   e->plan_poser_tips_current = false;
   ResidentArgs A{};
-  if (in) {
-    A.bound[0][BND_LIN] = in->linear_xy, A.bound[0][BND_ANG] = in->angular;
-    A.bound[0][BND_IMUQ] = in->imu_orientation_wxyz, A.bound[0][BND_IMUW] = in->imu_angular_velocity;
-    A.bound[0][BND_FORCE] = in->tip_force, A.bound[0][BND_EFFORT] = in->joint_effort;
-  }
   A.kstride[BND_LIN] = e->n * 2, A.kstride[BND_ANG] = e->n, A.kstride[BND_IMUQ] = e->n * 4, A.kstride[BND_IMUW] = e->n * 3;
   A.kstride[BND_FORCE] = e->n * e->L * 3, A.kstride[BND_EFFORT] = e->n * e->L * e->NJ;
-  A.out = e->k_out;
-  A.depth = n_cycles;
-  A.max_cycles = unsigned(n_cycles);
-  A.batch_cycles = unsigned(n_cycles);
+  if (in) {
+    const auto row = [&](const double *a, int which) { return a ? a + k0 * A.kstride[which] : a; };
+    A.bound[0][BND_LIN] = row(in->linear_xy, BND_LIN), A.bound[0][BND_ANG] = row(in->angular, BND_ANG);
+    A.bound[0][BND_IMUQ] = row(in->imu_orientation_wxyz, BND_IMUQ), A.bound[0][BND_IMUW] = row(in->imu_angular_velocity, BND_IMUW);
+    A.bound[0][BND_FORCE] = row(in->tip_force, BND_FORCE), A.bound[0][BND_EFFORT] = row(in->joint_effort, BND_EFFORT);
+  }
+  A.out = e->k_out + size_t(k0) * size_t(e->NJ) * e->n_slots * 2;
+  A.depth = n_cycles - k0;
+  A.max_cycles = unsigned(n_cycles - k0);
+  A.batch_cycles = unsigned(n_cycles - k0);
   A.batch_mask = mask;
   A.n_waves = e->n_waves;
   A.idle_ticks = 0, A.ticks_per_ms = 100000;

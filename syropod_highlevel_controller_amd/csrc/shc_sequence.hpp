@@ -117,7 +117,8 @@ template <int NJ>
 __device__ __forceinline__ void admittance_prologue_dev(const LegIO<NJ> &io, const LegConst<NJ> &lc, const CycleParams &P) {
   using FD = Fields<NJ>;
   if (!P.admittance_control) return;
-  const V3 f = (P.use_joint_effort ? io.get3(FD::TF) : io.get3(FD::FORCE_IN)) * P.force_gain;
+  // (pose_force_gain: the posing part's force gain - the old one in the loop that serves a force_gain adjustment, shc_engine_adjust_parameter)
+  const V3 f = (P.use_joint_effort ? io.get3(FD::TF) : io.get3(FD::FORCE_IN)) * P.pose_force_gain;
   double a0 = io.get(FD::ADM), a1 = io.get(FD::ADM + 1);
   const double fi[3] = {f.x, f.y, f.z};
   double d[3];

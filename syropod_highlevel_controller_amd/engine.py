@@ -421,7 +421,7 @@ class BatchEngine:
         self.L = lib()
         if self.L.shc_device_count() < 1:
             raise ShcError("no HIP device visible: the batched engine has no CPU fallback")
-        self.params, self.n = params, int(n)
+        self.params, self.n = Params.from_buffer_copy(params), int(n)   # (the engine's own: adjust_parameter updates it)
         self.legs, self.dof = params.leg_count, max(params.leg_dof[l] for l in range(params.leg_count))   # joint arrays are [legs][longest leg's DOF]
         self.features = FEAT_DEFAULT
         h = C.c_void_p()
@@ -675,14 +675,17 @@ class BatchEngine:
         still = C.c_int64(0)
         _check(self.L.shc_engine_change_gait(self.h, C.byref(new_gait), C.byref(still)), "change_gait")
         if still.value == 0:
-            self.params = new_gait
+            self.params = Params.from_buffer_copy(new_gait)
         return int(still.value)
 
     def adjust_parameter(self, which: int, value: float) -> int:
         """StateController::adjustParameter for the whole batch (which: params.PARAM_*, enum ParameterSelection).  Returns the number of instances
-        whose desired velocity is still outside the new limits (step_frequency only: call again after the next cycle); 0 = the value is set."""
+        whose desired velocity is still outside the new limits (step_frequency only: call again after the next cycle); 0 = the value is set.
+        self.params follows: the engine stores the value at once, a step_frequency that still waits included (state_controller.cpp:454)."""
         pending = C.c_int64(0)
         _check(self.L.shc_engine_adjust_parameter(self.h, int(which), float(value), C.byref(pending)), "adjust_parameter")
+        from .params import PARAM_FIELD
+        setattr(self.params, PARAM_FIELD[int(which)], float(value))
         return int(pending.value)
 
     def leg_state_msg(self, instance: int):

@@ -19,9 +19,12 @@ from test_gpu_teacher_forced import Engine, as_np, compare_records, config3_para
 pytestmark = pytest.mark.gpu
 
 
-def run_with_adjustments(Engine, p, n, inp, cycles, adjustments, velocity_events=(), forced=True, label="", tol_q=1e-12, features=FEAT_DEFAULT):
+def run_with_adjustments(Engine, p, n, inp, cycles, adjustments, velocity_events=(), forced=True, label="", tol_q=1e-12, features=FEAT_DEFAULT,
+                         inject_after_adjust=False):
     """adjustments: {cycle: (which, value)} - requested before that loop and, like runningState while parameter_adjust_flag_ is set, again before every
-    following loop until it is set.  Returns (loops each step_frequency change waited, worst |dq|)."""
+    following loop until it is set.  inject_after_adjust (teacher-forced): the oracle's state is injected once more between the adjustment and the loop
+    that serves it (a pending change must survive shc_engine_set_state, the injected phases be mapped inside that loop).  Returns (engine, oracle, loops
+    each step_frequency change waited, step periods seen)."""
     ob = OracleBatch(p, n)
     # Teacher-forced: the engine takes the oracle's tables (shc_engine_create_with_tables).  The acceptance test compares the desired velocity with a target that
     # the walker has, as a rule, just reached EXACTLY (updateWalk evaluates the same expression); with each side's own init chain the limit maps agree to
@@ -56,6 +59,8 @@ def run_with_adjustments(Engine, p, n, inp, cycles, adjustments, velocity_events
                 if which == PARAM_STEP_FREQUENCY:
                     waited.append(pending[1] - 1)
                 pending = None
+            if forced and inject_after_adjust:
+                eng.set_state(ob.get_state())
         eng.step(1)
         ob.step(1, 8)
         if tw:

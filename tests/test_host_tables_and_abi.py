@@ -159,3 +159,64 @@ def test_product_does_not_reference_the_oracle():
             if f.endswith((".py", ".hip", ".hpp", ".h")):
                 src = open(os.path.join(root, f)).read()
                 assert "liboracle" not in src and "oracle_lib" not in src and "shc_oracle" not in src, f
+
+
+_NULL_SWEEP = r'''
+import ctypes as C, json, re, sys
+sys.path.insert(0, sys.argv[1])
+from syropod_highlevel_controller_amd import engine
+lib = C.CDLL(engine.build_library())
+decls, pointers = json.loads(sys.argv[2]), sys.argv[3] == "buffers"
+scratch = C.create_string_buffer(1 << 20)          # what a pointer argument points at in the second pass (zeroed, larger than any one call reads)
+INT = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "double": C.c_double}
+out = {}
+for name, ret, args in decls:
+    f = getattr(lib, name)
+    f.restype = INT[ret]
+    types, vals = [C.c_void_p], [None]
+    for a in args[1:]:
+        if "*" in a:
+            types.append(C.c_void_p)
+            vals.append(C.addressof(scratch) if pointers else None)
+        else:
+            t = INT[re.sub(r"\bconst\b", "", a).split()[0]]
+            types.append(t)
+            vals.append(t(1 if pointers else 0))
+    f.argtypes = types
+    print("calling", name, flush=True)              # (a crash names its entry point in the child's output)
+    out[name] = int(f(*vals))
+print("RESULT " + json.dumps(out), flush=True)
+'''
+
+
+def _engine_entry_points():
+    """Every shc_engine_* declaration of the public header that takes the engine first: (name, return type, [argument declarations])."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "shc_batch.h")).read(), flags=re.S)
+    decls = []
+    for m in re.finditer(r"\b(int|int64_t)\s+(shc_engine_\w+)\s*\(([^)]*)\)\s*;", hdr):
+        args = [" ".join(a.split()) for a in m.group(3).split(",")]
+        if re.match(r"(const\s+)?shc_engine\s*\*\s*e$", args[0]):
+            decls.append((m.group(2), m.group(1), args))
+    return decls
+
+
+@pytest.mark.parametrize("pointers", ["null", "buffers"])
+def test_every_entry_point_rejects_a_null_engine(pointers):
+    """A NULL engine with NULL / zero arguments (and again with valid host buffers and ones): every shc_engine_* call that takes the engine first
+    returns SHC_ERR_INVALID_ARG before it touches anything - no call dereferences first (the state transfer flushed a pending step-frequency remap
+    through the engine pointer before its check).  The exceptions: shc_engine_destroy(NULL) is a no-op, and the size / index queries that return
+    int64_t answer "nothing" (0 instances, 0 bytes, index -1).  The calls run in a fresh interpreter so that a crash fails this test instead of the suite."""
+    import json
+    import subprocess
+    import sys
+    decls = _engine_entry_points()
+    assert len(decls) >= 60 and {"shc_engine_get_state", "shc_engine_set_state", "shc_engine_adjust_parameter"} <= {d[0] for d in decls}
+    r = subprocess.run([sys.executable, "-c", _NULL_SWEEP, ROOT, json.dumps(decls), pointers], capture_output=True, text=True, timeout=300)
+    lines = r.stdout.splitlines()
+    assert r.returncode == 0, f"the child died (status {r.returncode}) after: {lines[-1:] }\n{r.stderr[-2000:]}"
+    got = json.loads(next(l for l in lines if l.startswith("RESULT "))[7:])
+    expect = {name: engine.SHC_ERR_INVALID_ARG for name, _, _ in decls}
+    expect["shc_engine_destroy"] = engine.SHC_OK
+    expect.update(shc_engine_instances=0, shc_engine_aux_state_bytes=0, shc_engine_joint_index=-1)   # (the three size / index queries: nothing there)
+    wrong = {k: (v, expect[k]) for k, v in got.items() if v != expect[k]}
+    assert not wrong, wrong
