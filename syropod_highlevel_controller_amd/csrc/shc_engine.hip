@@ -12,6 +12,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace shc;
@@ -60,7 +61,6 @@ __device__ __forceinline__ int64_t slot_of(int64_t rob, int leg, int L) {
   return w * 64 + gi * L + leg;
 }
 
-#include "shc_snapshot.hpp" // get_state / set_state kernels (use rob_index / slot_of)
 #include "shc_leg_api.hpp"  // per-leg Leg methods, batched
 #include "shc_sequence.hpp" // executeSequence / stepToNewStance: per-robot state machines over the per-leg primitives
 
@@ -247,6 +247,8 @@ __global__ void init_state_kernel(DevState st, const double *leg_template /*[L][
 
 constexpr int64_t kPlanePadSlots = 192;
 
+#include "shc_adjust.hpp" // struct PendingAdjust (the operations on it: included again below)
+
 struct shc_engine {
   shc_params params;
   shc_tables tables;
@@ -270,10 +272,7 @@ struct shc_engine {
   double *d_span = nullptr;             // SpanTable (rough terrain mode with a stance span modifier), rebuilt with the tables
   int half_steps = 0;                   // CycleLaunch::half_steps (development switch SHC_ROT_SPLIT = 0 / 1: never / always; unset: by launch size)
   bool span_dirty = true;
-  bool step_remap_pending = false;      // an accepted step-frequency change waits for the next cycle (shc_engine_adjust_parameter)
-  bool pose_params_held = false;        // the posing part of the next cycle still runs on the parameter values a just-adjusted parameter had (ditto)
-  shc_step_cycle remap_old_step{};      // step_remap_pending: the step cycle the legs' phases still count in
-  shc_params held_params{};             // pose_params_held: the parameters as they were before the change (their posing values: rebuild_cycle_params)
+  PendingAdjust adjust{};               // a shc_engine_adjust_parameter that waits for its loop (shc_adjust.hpp)
   bool fresh_pose_controller = false;   // init_state for shc_engine_begin_sequence_startup: no direct start-up has run, the auto posers have not been called yet
   struct Resident *res = nullptr;       // resident mode (shc_resident.hpp)
   const double *bound_inputs[kBoundSets][BND_COUNT] = {}; // shc_engine_resident_bind_inputs: the caller's device arrays for direct posts
@@ -292,23 +291,45 @@ static bool resident_active(const shc_engine *e);
 static void resident_shutdown(shc_engine *e); // stop a running resident loop and free its buffers (shc_engine_destroy)
 // While the resident kernel owns the engine's stream and state, every other entry point that would touch them is refused.
 static int join_side(shc_engine *e);
-static int flush_step_remap(shc_engine *e); // an accepted step-frequency change no cycle has consumed yet: map the phases now
 static void rebuild_cycle_params(shc_engine *e);
-static int consume_pending_adjustment(shc_engine *e);
-#define SHC_BUSY_ONLY(e)                                                                                                       \
+// Every entry point begins with one of these, before it does anything with `e`: a NULL engine is refused, and so is an engine in resident mode ...
+#define SHC_ENTER(e)                                                                                                           \
   do {                                                                                                                         \
-    if ((e) && resident_active(e))                                                                                             \
+    if (!(e)) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");                                                              \
+    if (resident_active(e))                                                                                                    \
       return fail(SHC_ERR_BUSY, "the engine is in resident mode: only shc_engine_resident_* calls are valid until shc_engine_resident_end"); \
   } while (0)
-// ... and whatever an entry point enqueues on the engine's stream is ordered after the second halves of earlier split steps
-#define SHC_BUSY_GUARD(e)                                                                                                      \
+// ... and whatever the entry point enqueues on the engine's stream is ordered after the second halves of earlier split steps - unless its input can ride
+// the split streams (RIDES: split_inputs(), a join drains both halves)
+#define SHC_ENTER_JOINED_UNLESS(e, RIDES)                                                                                      \
   do {                                                                                                                         \
-    SHC_BUSY_ONLY(e);                                                                                                          \
-    if (e) {                                                                                                                   \
+    SHC_ENTER(e);                                                                                                              \
+    if (!(RIDES)) {                                                                                                            \
       const int rc_join_ = join_side(e);                                                                                       \
       if (rc_join_ != SHC_OK) return rc_join_;                                                                                 \
     }                                                                                                                          \
   } while (0)
+#define SHC_ENTER_JOINED(e) SHC_ENTER_JOINED_UNLESS(e, false)
+
+// The kernel specialisation of the engine's morphology: CALL(legs, joints), a macro the caller defines around the dispatch, runs for the entry of
+// SHC_FOR_EACH_MORPHOLOGY (shc_cycle_launch.hpp: the one list of the morphologies this build has kernels for) that matches.
+#define SHC_DISPATCH_CASE(L_, NJ_) if (shc_l_ == L_ && shc_nj_ == NJ_) { CALL(L_, NJ_); } else
+#define SHC_DISPATCH(L, NJ)                                                                   \
+  do {                                                                                        \
+    const int shc_l_ = (L), shc_nj_ = (NJ);                                                   \
+    SHC_FOR_EACH_MORPHOLOGY(SHC_DISPATCH_CASE)                                                \
+    return fail(SHC_ERR_UNSUPPORTED, "no kernel specialisation for this (legs, dof)");        \
+  } while (0)
+// ... and of the joint count alone (validate_params: 3 .. 5): fn(std::integral_constant<int, joints>)
+template <class Fn>
+static auto dispatch_nj(int NJ, Fn &&fn) {
+  switch (NJ) {
+    case 3: return fn(std::integral_constant<int, 3>{});
+    case 4: return fn(std::integral_constant<int, 4>{});
+    default: return fn(std::integral_constant<int, 5>{});
+  }
+}
+#define LEG_FIELD(e, NAME) dispatch_nj((e)->NJ, [](auto nj) { return int(Fields<decltype(nj)::value>::NAME); })
 
 template <int L, int NJ>
 static void build_shared_consts(const shc_params &p, const shc_tables &t, const CycleParams &cp, SharedConsts<L, NJ> &c) {
@@ -380,17 +401,15 @@ static shc_params normalised_params(const shc_params &in) {
     }
   return p;
 }
+static void set_step_cycle(CycleParams &c, const shc_step_cycle &s) { // the phase boundaries of a step cycle
+  c.period = s.period, c.swing_period = s.swing_period, c.stance_period = s.stance_period;
+  c.stance_end = s.stance_end, c.swing_start = s.swing_start, c.swing_end = s.swing_end, c.stance_start = s.stance_start;
+}
 static void build_cycle_params(const shc_params &p, const shc_tables &t, uint32_t features, unsigned rt_flags, CycleParams &c) {
   memset(&c, 0, sizeof c);
   const shc_step_cycle &s = t.step;
   c.dt = p.time_delta;
-  c.period = s.period;
-  c.swing_period = s.swing_period;
-  c.stance_period = s.stance_period;
-  c.stance_end = s.stance_end;
-  c.swing_start = s.swing_start;
-  c.swing_end = s.swing_end;
-  c.stance_start = s.stance_start;
+  set_step_cycle(c, s);
   int swing_iterations = int((double(s.swing_period) / s.period) / (s.frequency * p.time_delta)); // walk_controller.cpp:1035
   swing_iterations = round_to_even_int(swing_iterations);
   c.swing_iterations = swing_iterations;
@@ -566,12 +585,7 @@ extern "C" int shc_generate_tables(const shc_params *params, shc_tables *out) {
   if (rc != SHC_OK) return rc;
   if (!out) return fail(SHC_ERR_INVALID_ARG, "out is NULL");
   const shc_params np = normalised_params(*params);
-  switch (NJ) {
-    case 3: return generate_tables_nj<3>(&np, out);
-    case 4: return generate_tables_nj<4>(&np, out);
-    case 5: return generate_tables_nj<5>(&np, out);
-  }
-  return fail(SHC_ERR_UNSUPPORTED, "dof");
+  return dispatch_nj(NJ, [&](auto nj) { return generate_tables_nj<decltype(nj)::value>(&np, out); });
 }
 
 // ---- init chain on the device: the same host + device functions as shc_generate_tables, fanned out over morphologies
@@ -645,23 +659,6 @@ extern "C" int shc_generate_tables_batch(const shc_params *params, int64_t count
   return SHC_OK;
 }
 
-#define SHC_DISPATCH(L_, NJ_, CALL)                                   \
-  do {                                                                \
-    if (L_ == 3 && NJ_ == 3) { CALL(3, 3); }                          \
-    else if (L_ == 4 && NJ_ == 3) { CALL(4, 3); }                     \
-    else if (L_ == 4 && NJ_ == 4) { CALL(4, 4); }                     \
-    else if (L_ == 4 && NJ_ == 5) { CALL(4, 5); }                     \
-    else if (L_ == 5 && NJ_ == 3) { CALL(5, 3); }                     \
-    else if (L_ == 6 && NJ_ == 3) { CALL(6, 3); }                     \
-    else if (L_ == 6 && NJ_ == 4) { CALL(6, 4); }                     \
-    else if (L_ == 6 && NJ_ == 5) { CALL(6, 5); }                     \
-    else if (L_ == 7 && NJ_ == 3) { CALL(7, 3); }                     \
-    else if (L_ == 8 && NJ_ == 3) { CALL(8, 3); }                     \
-    else if (L_ == 8 && NJ_ == 4) { CALL(8, 4); }                     \
-    else if (L_ == 8 && NJ_ == 5) { CALL(8, 5); }                     \
-    else return fail(SHC_ERR_UNSUPPORTED, "no kernel specialisation for this (legs, dof)"); \
-  } while (0)
-
 // rough terrain mode with a stance span modifier: LegStepper::calculateStanceSpanChange interpolates the layered workspace at the
 // default tip's height at every swing / stance start - the planes of every leg's workspace, searched again from the default
 // configuration the tables hold (the init chain itself only keeps the plane at height 0)
@@ -697,7 +694,7 @@ static int build_span_table(shc_engine *e) {
 
 static int upload_consts(shc_engine *e) {
   if (e->span_dirty) {
-    const int rc = e->NJ == 3 ? build_span_table<3>(e) : (e->NJ == 4 ? build_span_table<4>(e) : build_span_table<5>(e));
+    const int rc = dispatch_nj(e->NJ, [&](auto nj) { return build_span_table<decltype(nj)::value>(e); });
     if (rc != SHC_OK) return rc;
   }
 #define CALL(L_, NJ_)                                                                                   \
@@ -708,7 +705,7 @@ static int upload_consts(shc_engine *e) {
     HIP_TRY(hipMemcpyAsync(e->d_consts, &c, sizeof c, hipMemcpyHostToDevice, e->stream));               \
     HIP_TRY(hipStreamSynchronize(e->stream));                                                           \
   }
-  SHC_DISPATCH(e->L, e->NJ, CALL);
+  SHC_DISPATCH(e->L, e->NJ);
 #undef CALL
   return SHC_OK;
 }
@@ -832,11 +829,7 @@ static void build_templates(const shc_engine *e, std::vector<double> &legt, std:
 static int init_state(shc_engine *e) {
   std::vector<double> legt, robt;
   std::vector<int32_t> legw, robi;
-  switch (e->NJ) {
-    case 3: build_templates<3>(e, legt, legw, robt, robi); break;
-    case 4: build_templates<4>(e, legt, legw, robt, robi); break;
-    case 5: build_templates<5>(e, legt, legw, robt, robi); break;
-  }
+  dispatch_nj(e->NJ, [&](auto nj) { build_templates<decltype(nj)::value>(e, legt, legw, robt, robi); });
   double *d_legt = nullptr, *d_robt = nullptr;
   int32_t *d_legw = nullptr, *d_robi = nullptr;
   auto release = [&]() {
@@ -916,7 +909,7 @@ static int engine_create(const shc_params *params, const shc_tables *tables, int
   // 135.7 -> 129.2, 65 536 hexapods 45.8 -> 44.4, neutral at 4 096 (64 ... 65 600 slots all give the same).
   e->n_slots = e->n_waves * 64 + kPlanePadSlots;
   e->n_rob_pad = e->n_waves * rpw; // robots incl. the padding of the last wave's tile
-  e->n_leg_fields = NJ == 3 ? Fields<3>::COUNT : (NJ == 4 ? Fields<4>::COUNT : Fields<5>::COUNT);
+  e->n_leg_fields = LEG_FIELD(e, COUNT);
   e->st.n_slots = e->n_slots;
   e->st.n_rob_pad = e->n_rob_pad;
   e->st.n_robots = e->n;
@@ -973,15 +966,13 @@ extern "C" int shc_engine_destroy(shc_engine *e) {
 }
 
 extern "C" int shc_engine_set_stream(shc_engine *e, void *stream) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   e->stream = (hipStream_t)stream;
   return SHC_OK;
 }
 
 extern "C" int shc_engine_set_features(shc_engine *e, uint32_t features) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   e->features = features;
   rebuild_cycle_params(e);
   return upload_consts(e);
@@ -1036,50 +1027,37 @@ static int64_t split_first_instance_of_second_half(const shc_engine *e) { // as 
   return r < e->n ? r : e->n;
 }
 
-static int scatter_rob(shc_engine *e, const double *src, int K, int f0, int on_device, int normalize_quat = 0) {
+// One input array of the caller into the state.  launch(stream, array, r0, r1): the scatter kernel over instances [r0, r1)
+template <class Launch>
+static int scatter_input(shc_engine *e, const double *src, size_t doubles_per_instance, int on_device, Launch &&launch) {
   if (!src) return SHC_OK;
   HIP_TRY(hipSetDevice(e->device));
   if (split_inputs(e, on_device)) {
     const int rc = split_inputs_begin(e);
     if (rc != SHC_OK) return rc;
     const int64_t mid = split_first_instance_of_second_half(e);
-    scatter_rob_kernel<<<dim3((unsigned)((mid + 255) / 256)), dim3(256), 0, e->half_stream[0]>>>(src, e->st.robd, 64 / e->L, mid, K, f0, normalize_quat, 0);
-    if (e->n > mid)
-      scatter_rob_kernel<<<dim3((unsigned)((e->n - mid + 255) / 256)), dim3(256), 0, e->half_stream[1]>>>(src, e->st.robd, 64 / e->L, e->n, K, f0, normalize_quat, mid);
+    launch(e->half_stream[0], src, int64_t(0), mid);
+    if (e->n > mid) launch(e->half_stream[1], src, mid, e->n);
     HIP_TRY(hipGetLastError());
     return split_inputs_end(e);
   }
   const double *d;
-  int rc = to_device(e, src, size_t(e->n) * K, on_device, &d);
+  int rc = to_device(e, src, size_t(e->n) * doubles_per_instance, on_device, &d);
   if (rc != SHC_OK) return rc;
-  scatter_rob_kernel<<<dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, e->stream>>>(d, e->st.robd, 64 / e->L, e->n, K, f0,
-                                                                                      normalize_quat);
+  launch(e->stream, d, int64_t(0), e->n);
   HIP_TRY(hipGetLastError());
   if (!on_device) HIP_TRY(hipStreamSynchronize(e->stream)); // the staging buffer is reused by the next call
   return SHC_OK;
 }
-
+static int scatter_rob(shc_engine *e, const double *src, int K, int f0, int on_device, int normalize_quat = 0) {
+  return scatter_input(e, src, size_t(K), on_device, [=](hipStream_t stream, const double *d, int64_t r0, int64_t r1) {
+    scatter_rob_kernel<<<dim3((unsigned)((r1 - r0 + 255) / 256)), dim3(256), 0, stream>>>(d, e->st.robd, 64 / e->L, r1, K, f0, normalize_quat, r0);
+  });
+}
 static int scatter_leg(shc_engine *e, const double *src, int K, int f0, int on_device) {
-  if (!src) return SHC_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  if (split_inputs(e, on_device)) {
-    const int rc = split_inputs_begin(e);
-    if (rc != SHC_OK) return rc;
-    const int64_t mid = split_first_instance_of_second_half(e);
-    scatter_leg_kernel<<<dim3((unsigned)((mid * e->L + 255) / 256)), dim3(256), 0, e->half_stream[0]>>>(src, e->st.legd, e->n_slots, mid, e->L, K, f0, 0);
-    if (e->n > mid)
-      scatter_leg_kernel<<<dim3((unsigned)(((e->n - mid) * e->L + 255) / 256)), dim3(256), 0, e->half_stream[1]>>>(src, e->st.legd, e->n_slots, e->n, e->L, K, f0, mid);
-    HIP_TRY(hipGetLastError());
-    return split_inputs_end(e);
-  }
-  const double *d;
-  int rc = to_device(e, src, size_t(e->n) * e->L * K, on_device, &d);
-  if (rc != SHC_OK) return rc;
-  int64_t threads = e->n * e->L;
-  scatter_leg_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(d, e->st.legd, e->n_slots, e->n, e->L, K, f0);
-  HIP_TRY(hipGetLastError());
-  if (!on_device) HIP_TRY(hipStreamSynchronize(e->stream));
-  return SHC_OK;
+  return scatter_input(e, src, size_t(e->L) * K, on_device, [=](hipStream_t stream, const double *d, int64_t r0, int64_t r1) {
+    scatter_leg_kernel<<<dim3((unsigned)(((r1 - r0) * e->L + 255) / 256)), dim3(256), 0, stream>>>(d, e->st.legd, e->n_slots, r1, e->L, K, f0, r0);
+  });
 }
 
 static int gather_leg(shc_engine *e, double *dst, int K, int f0, int on_device) {
@@ -1110,27 +1088,16 @@ static int gather_rob(shc_engine *e, double *dst, int K, int f0, int on_device) 
 }
 
 static int derive_tips(shc_engine *e);
-#define LEG_FIELD(e, NAME) ((e)->NJ == 3 ? Fields<3>::NAME : ((e)->NJ == 4 ? Fields<4>::NAME : Fields<5>::NAME))
 
 extern "C" int shc_engine_set_velocity(shc_engine *e, const double *linear_xy, const double *angular, int on_device) {
-  SHC_BUSY_ONLY(e);
-  if (e && !split_inputs(e, on_device)) {
-    const int rc_join_ = join_side(e);
-    if (rc_join_ != SHC_OK) return rc_join_;
-  }
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED_UNLESS(e, split_inputs(e, on_device));
   int rc = scatter_rob(e, linear_xy, 2, RobotFields::VIN, on_device);
   if (rc != SHC_OK) return rc;
   return scatter_rob(e, angular, 1, RobotFields::WIN, on_device);
 }
 
 extern "C" int shc_engine_set_imu(shc_engine *e, const double *orientation_wxyz, const double *angular_velocity, int on_device) {
-  SHC_BUSY_ONLY(e);
-  if (e && !split_inputs(e, on_device)) {
-    const int rc_join_ = join_side(e);
-    if (rc_join_ != SHC_OK) return rc_join_;
-  }
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED_UNLESS(e, split_inputs(e, on_device));
   int rc = scatter_rob(e, orientation_wxyz, 4, RobotFields::IMUQ, on_device, 1);
   if (rc != SHC_OK) return rc;
   return scatter_rob(e, angular_velocity, 3, RobotFields::GYRO, on_device);
@@ -1161,12 +1128,7 @@ __global__ void touchdown_detection_kernel(DevState st, const SharedConsts<L, NJ
 }
 
 extern "C" int shc_engine_set_tip_force(shc_engine *e, const double *tip_force, int on_device) {
-  SHC_BUSY_ONLY(e);
-  if (e && !split_inputs(e, on_device && !e->params.rough_terrain_mode)) {
-    const int rc_join_ = join_side(e);
-    if (rc_join_ != SHC_OK) return rc_join_;
-  }
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED_UNLESS(e, split_inputs(e, on_device && !e->params.rough_terrain_mode));
   int rc = scatter_leg(e, tip_force, 3, LEG_FIELD(e, FORCE_IN), on_device);
   if (rc != SHC_OK || !tip_force) return rc;
   e->rt_flags |= RT_TOUCHDOWN; // LegStepper::setTouchdownDetection(true) (state_controller.cpp:1642)
@@ -1175,7 +1137,7 @@ extern "C" int shc_engine_set_tip_force(shc_engine *e, const double *tip_force, 
 #define CALL(L_, NJ_)                                                                                                           \
   touchdown_detection_kernel<L_, NJ_><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(                      \
       e->st, (const SharedConsts<L_, NJ_> *)e->d_consts, e->params.touchdown_threshold, e->params.liftoff_threshold)
-    SHC_DISPATCH(e->L, e->NJ, CALL);
+    SHC_DISPATCH(e->L, e->NJ);
 #undef CALL
     HIP_TRY(hipGetLastError());
   }
@@ -1191,12 +1153,7 @@ static int effort_live(shc_engine *e) {
 }
 
 extern "C" int shc_engine_set_joint_effort(shc_engine *e, const double *joint_effort, int on_device) {
-  SHC_BUSY_ONLY(e);
-  if (e && !split_inputs(e, on_device && (e->rt_flags & RT_EFFORT_LIVE))) {
-    const int rc_join_ = join_side(e);
-    if (rc_join_ != SHC_OK) return rc_join_;
-  }
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED_UNLESS(e, split_inputs(e, on_device && (e->rt_flags & RT_EFFORT_LIVE)));
   if (joint_effort) { // Leg::calculateTipForce has something to filter from now on
     const int rc = effort_live(e);
     if (rc != SHC_OK) return rc;
@@ -1206,12 +1163,7 @@ extern "C" int shc_engine_set_joint_effort(shc_engine *e, const double *joint_ef
 
 extern "C" int shc_engine_set_pose_input(shc_engine *e, const double *translation_velocity, const double *rotation_velocity,
                                          int on_device) {
-  SHC_BUSY_ONLY(e);
-  if (e && !split_inputs(e, on_device)) {
-    const int rc_join_ = join_side(e);
-    if (rc_join_ != SHC_OK) return rc_join_;
-  }
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED_UNLESS(e, split_inputs(e, on_device));
   if (translation_velocity || rotation_velocity) e->rt_flags |= RT_MANUAL_LIVE;
   int rc = scatter_rob(e, translation_velocity, 3, RobotFields::TVI, on_device);
   if (rc != SHC_OK) return rc;
@@ -1219,8 +1171,7 @@ extern "C" int shc_engine_set_pose_input(shc_engine *e, const double *translatio
 }
 
 extern "C" int shc_engine_set_pose_reset_mode(shc_engine *e, const int32_t *mode, int on_device) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   if (!mode) return SHC_OK;
   e->rt_flags |= RT_MANUAL_LIVE;
   HIP_TRY(hipSetDevice(e->device));
@@ -1318,8 +1269,7 @@ static int join_side(shc_engine *e) {
   return SHC_OK;
 }
 extern "C" int shc_engine_join(shc_engine *e) {
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
-  SHC_BUSY_ONLY(e);
+  SHC_ENTER(e);
   return join_side(e);
 }
 
@@ -1330,28 +1280,29 @@ extern "C" int shc_engine_join(shc_engine *e) {
 // hexapods with admittance + IMU 57.7 -> 48.8 us per step, 131 072 octopods 106 -> 98.7 us).
 constexpr int64_t kSplitWaves = 4096;
 
+#include "shc_adjust.hpp" // the operations on a pending shc_engine_adjust_parameter, and the entry point itself
+// The launch-uniform parameter block of the engine's parameters, with what a change still waiting for its loop leaves of the old ones.
+static void rebuild_cycle_params(shc_engine *e) {
+  build_cycle_params(e->params, e->tables, e->features, e->rt_flags, e->cp);
+  adjust_overlay(e, e->cp);
+}
+
 extern "C" int shc_engine_step(shc_engine *e, int n_cycles) {
-  SHC_BUSY_ONLY(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER(e);
   if (n_cycles < 1) return SHC_OK;
   HIP_TRY(hipSetDevice(e->device));
-  if ((e->step_remap_pending || e->pose_params_held) && !(e->rt_flags & (RT_SKIP_MARKED | RT_POSE_MARKED))) {
-    // The loop in which adjustParameter set a new value (state_controller.cpp:411-414, after the posing part of that loop, before updateWalk): its cycle runs
-    // alone in its launch on a parameter block of its own - the posing part still on the old force gain / virtual spring / swing height (pose_params_held),
-    // the phases of walking robots mapped onto a new step cycle between the posing part and updateWalk (step_remap_pending: cycle_front, on the
-    // runtime-flag kernels) - and the plain block of the new values follows it.
-    const bool remap = e->step_remap_pending;
-    e->step_remap_pending = e->pose_params_held = false;
-    const uint32_t keep = e->features;
-    if (remap) e->features |= SHC_FEAT_GENERIC_KERNEL;
-    int rc = shc_engine_step(e, 1);
-    e->features = keep;
-    if (rc == SHC_OK) rc = join_side(e);
-    rebuild_cycle_params(e);
-    if (rc == SHC_OK) rc = upload_consts(e); // (ordered behind the cycle above on the engine's stream, and synchronises it)
+  const bool marked = (e->rt_flags & (RT_SKIP_MARKED | RT_POSE_MARKED)) != 0; // (the launch of a loop-level call: that call serves the change)
+  const bool generic = (e->features & SHC_FEAT_GENERIC_KERNEL) != 0;
+  if (adjust_pending(e) && !marked) { // shc_adjust.hpp, row "shc_engine_step, first cycle"
+    const int rc = adjust_serve_in_cycle(e, generic);
     if (rc != SHC_OK || n_cycles == 1) return rc;
     --n_cycles;
   }
+  return launch_cycles(e, n_cycles, generic);
+}
+
+// n control cycles in one launch (generic: on the runtime-flag kernel)
+static int launch_cycles(shc_engine *e, int n_cycles, bool generic) {
   if (!(e->rt_flags & (RT_SKIP_MARKED | RT_POSE_MARKED))) e->plan_poser_tips_current = false; // PoseController::updateStance rewrites every LegPoser's tip pose
   // One wave per workgroup while the batch has about as many waves as the chip has SIMDs (1 024): the dispatcher then spreads
   // them one per SIMD (two-wave groups put pairs on the same SIMDs: 12.9 instead of 9.4 us at 768 waves, 12.2 instead of 10.2 at
@@ -1366,11 +1317,11 @@ extern "C" int shc_engine_step(shc_engine *e, int n_cycles) {
     if (rc != SHC_OK) return rc;
   }
   const int64_t half = split ? ((e->n_waves / 2 + waves_per_block - 1) / waves_per_block) * waves_per_block : e->n_waves;
-  CycleLaunch a{e->st, e->d_consts, &e->cp, e->rt_flags, (e->features & SHC_FEAT_GENERIC_KERNEL) != 0, e->stream,
+  CycleLaunch a{e->st, e->d_consts, &e->cp, e->rt_flags, generic, e->stream,
                 (unsigned)((half + waves_per_block - 1) / waves_per_block), block, n_cycles, nullptr, nullptr, 0, e->half_steps};
 #define CALL(L_, NJ_) shc_launch_cycle_##L_##_##NJ_(a)
   if (!split) {
-    SHC_DISPATCH(e->L, e->NJ, CALL);
+    SHC_DISPATCH(e->L, e->NJ);
     HIP_TRY(hipGetLastError());
     return SHC_OK;
   }
@@ -1396,19 +1347,19 @@ extern "C" int shc_engine_step(shc_engine *e, int n_cycles) {
     // both halves take the same time from then on, so the stagger stays until the next join.
     const int64_t quarter = ((half / 2 + waves_per_block - 1) / waves_per_block) * waves_per_block; // (a quarter or three quarters of a half instead: the same step time within 1 %, profiles/r04_probe_build_variants.txt)
     a.grid = (unsigned)(quarter / waves_per_block);
-    SHC_DISPATCH(e->L, e->NJ, CALL);
+    SHC_DISPATCH(e->L, e->NJ);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e->ev_half[0], e->half_stream[0]));
     HIP_TRY(hipStreamWaitEvent(e->half_stream[1], e->ev_half[0], 0));
     a.wave0 = quarter;
     a.grid = (unsigned)((half - quarter + waves_per_block - 1) / waves_per_block);
   }
-  SHC_DISPATCH(e->L, e->NJ, CALL);
+  SHC_DISPATCH(e->L, e->NJ);
   HIP_TRY(hipGetLastError());
   a.stream = e->half_stream[1];
   a.wave0 = half;
   a.grid = (unsigned)((e->n_waves - half + waves_per_block - 1) / waves_per_block);
-  SHC_DISPATCH(e->L, e->NJ, CALL);
+  SHC_DISPATCH(e->L, e->NJ);
   HIP_TRY(hipGetLastError());
   e->side_busy = true;
 #undef CALL
@@ -1416,8 +1367,7 @@ extern "C" int shc_engine_step(shc_engine *e, int n_cycles) {
 }
 
 extern "C" int shc_engine_synchronize(shc_engine *e) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipStreamSynchronize(e->stream));
   return SHC_OK;
@@ -1437,16 +1387,15 @@ static void resident_shutdown(shc_engine *e) {
 }
 
 extern "C" int shc_engine_get_joint_state(shc_engine *e, double *q, double *qd, int on_device) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   int rc = gather_leg(e, q, e->NJ, LEG_FIELD(e, Q), on_device);
   if (rc != SHC_OK) return rc;
   return gather_leg(e, qd, e->NJ, LEG_FIELD(e, QD), on_device);
 }
 
 extern "C" int shc_engine_joint_buffer(shc_engine *e, double **device_ptr, int64_t *n_doubles) {
-  SHC_BUSY_GUARD(e);
-  if (!e || !device_ptr || !n_doubles) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
+  SHC_ENTER_JOINED(e);
+  if (!device_ptr || !n_doubles) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
   *device_ptr = e->st.legd; // fields Q (and, for odd DOF, the first QD) occupy the first ceil(NJ / 2) paired planes of the leg state
   *n_doubles = int64_t((e->NJ + 1) / 2) * e->n_slots * 2;
   return SHC_OK;
@@ -1462,8 +1411,7 @@ extern "C" int64_t shc_engine_joint_index(const shc_engine *e, int64_t instance,
 
 extern "C" int shc_engine_get_leg_state(shc_engine *e, double *walker_tip, double *poser_tip, double *model_tip, double *tip_force,
                                         double *admittance, int32_t *leg_status, int on_device) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   int rc;
   if ((rc = gather_leg(e, walker_tip, 3, LEG_FIELD(e, TIP), on_device)) != SHC_OK) return rc;
   if ((poser_tip || model_tip) && (rc = derive_tips(e)) != SHC_OK) return rc; // derived on demand from q / walker tip / body pose
@@ -1486,8 +1434,8 @@ extern "C" int shc_engine_get_leg_state(shc_engine *e, double *walker_tip, doubl
 }
 
 extern "C" int shc_engine_change_gait(shc_engine *e, const shc_params *ng, int64_t *still_walking) {
-  SHC_BUSY_GUARD(e);
-  if (!e || !ng) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
+  SHC_ENTER_JOINED(e);
+  if (!ng) return fail(SHC_ERR_INVALID_ARG, "new gait is NULL");
   HIP_TRY(hipSetDevice(e->device));
   const unsigned grid = (unsigned)((e->n + 255) / 256);
   const int rpw = 64 / e->L;
@@ -1534,7 +1482,7 @@ extern "C" int shc_engine_change_gait(shc_engine *e, const shc_params *ng, int64
   e->params = p;
   e->tables = t;
   e->span_dirty = true;
-  e->step_remap_pending = e->pose_params_held = false; // (every robot is STOPPED: nothing is left of an adjustParameter in flight)
+  adjust_drop(e); // shc_adjust.hpp, row "change_gait with every robot STOPPED"
   build_cycle_params(e->params, e->tables, e->features, e->rt_flags, e->cp);
   if ((rc = upload_consts(e)) != SHC_OK) return rc;
   if (p.auto_posing) { // setAutoPoseParams builds fresh AutoPosers: their start / end checks are reset (pose_controller.cpp:39-61)
@@ -1544,204 +1492,8 @@ extern "C" int shc_engine_change_gait(shc_engine *e, const shc_params *ng, int64
   return shc_engine_synchronize(e);
 }
 
-// An accepted step-frequency change that no cycle has consumed yet (the caller went on to something other than shc_engine_step): the phases are mapped
-// here instead, by a kernel of their own - the same arithmetic as in cycle_front, without the reference's ordering against the posing part of that loop.
-__global__ void step_remap_kernel(int32_t *legi, const int32_t *robi, int rpw, int64_t n, int L, int old_period, int period, int swing_start, int swing_end,
-                                  int stance_end, int stance_start) {
-  const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t >= n * L) return;
-  const int64_t rob = t / L;
-  const int leg = int(t - rob * L);
-  if ((robi[rob_index(rob, RobotFields::I_WORD, rpw, RobotFields::I_COUNT)] & 3) != WS_MOVING) return;
-  int w = legi[slot_of(rob, leg, L)];
-  int ph = (w >> LW_PHASE_SHIFT) & LW_PHASE_MASK, st = w & 3;
-  const double step_progress = double(ph) / double(old_period);
-  ph = int(step_progress * double(period));
-  if (st != SS_FORCE_STOP) {
-    if (ph >= swing_start && ph < swing_end && st != SS_FORCE_STANCE) st = SS_SWING;
-    else if (ph < stance_end || ph >= stance_start) st = SS_STANCE;
-  }
-  legi[slot_of(rob, leg, L)] = (w & ~(3 | (LW_PHASE_MASK << LW_PHASE_SHIFT))) | st | (ph << LW_PHASE_SHIFT);
-}
-static int flush_step_remap(shc_engine *e) {
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
-  if (!e->step_remap_pending) {
-    if (!e->pose_params_held) return SHC_OK;
-    e->pose_params_held = false; // (the next cycle is not a shc_engine_step: the new values are in force for all of it)
-    rebuild_cycle_params(e);
-    return upload_consts(e);
-  }
-  e->step_remap_pending = e->pose_params_held = false;
-  HIP_TRY(hipSetDevice(e->device));
-  {
-    const int rc = join_side(e);
-    if (rc != SHC_OK) return rc;
-  }
-  const int64_t threads = e->n * e->L;
-  const shc_step_cycle &s = e->tables.step;
-  step_remap_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(e->st.legi, e->st.robi, 64 / e->L, e->n, e->L, e->remap_old_step.period, s.period,
-                                                                                       s.swing_start, s.swing_end, s.stance_end, s.stance_start);
-  HIP_TRY(hipGetLastError());
-  rebuild_cycle_params(e);
-  return upload_consts(e);
-}
-// The launch-uniform parameter block of the engine's parameters, with what an adjustParameter still waiting for its loop leaves of the old ones: the
-// posing part's values of the parameters before the change (pose_params_held) and the period the phases still count in (step_remap_pending).
-static void rebuild_cycle_params(shc_engine *e) {
-  build_cycle_params(e->params, e->tables, e->features, e->rt_flags, e->cp);
-  if (e->step_remap_pending) e->cp.remap_old_period = e->remap_old_step.period;
-  if (e->pose_params_held) {
-    CycleParams h;
-    build_cycle_params(e->held_params, e->tables, e->features, e->rt_flags, h);
-    e->cp.adm_m00 = h.adm_m00, e->cp.adm_m01 = h.adm_m01, e->cp.adm_m10 = h.adm_m10, e->cp.adm_m11 = h.adm_m11;
-    e->cp.adm_g0 = h.adm_g0, e->cp.adm_g1 = h.adm_g1;
-    e->cp.virtual_stiffness = h.virtual_stiffness, e->cp.pose_force_gain = h.pose_force_gain, e->cp.pose_swing_height = h.pose_swing_height;
-  }
-}
-// A loop-level call (leg toggle, plan step, SHUT_DOWN sequence step) has run the loop that an adjustParameter waited for: runningState reaches
-// adjustParameter after transitionRobotState / legStateToggle / executePlan (state_controller.cpp:384-414), for every robot of the batch.  Its pose pass and its
-// marked launch ran on the held block and remapped the phases of the robots that walked in it; from here on the new values are in force for all.
-static int consume_pending_adjustment(shc_engine *e) {
-  if (!e->step_remap_pending && !e->pose_params_held) return SHC_OK;
-  e->step_remap_pending = e->pose_params_held = false;
-  const int rc = join_side(e);
-  if (rc != SHC_OK) return rc;
-  rebuild_cycle_params(e);
-  return upload_consts(e);
-}
-
-// WalkController::getLimit (walk_controller.cpp:414-436) on the host, for the acceptance test of a step-frequency change: per leg the bearing of its
-// stride velocity (linear + angular x the tip's lever arm), rounded to whole degrees, picks the two neighbouring entries of the 45-degree table; the
-// interpolation input is an int / int division in the reference (0 except on a table bearing), the smallest value over the legs is the limit.
-static double host_get_limit(const double *tips /* [L][3] walker tip positions */, int L, double lx, double ly, double ang, const double *limit /* [9] */) {
-  double lowest = kUnassigned;
-  for (int l = 0; l < L; ++l) {
-    const double sx = lx + ang * -tips[l * 3 + 1], sy = ly + ang * tips[l * 3 + 0];
-    int bearing = mod_i(round_to_int(atan2(sy, sx) * (180.0 / M_PI)), 360);
-    int upper = ((bearing + 44) / 45) * 45;
-    const int lower = mod_i(upper - 45, 360);
-    if (bearing < lower) bearing += 360;
-    if (upper < lower) upper += 360;
-    const double c = double((bearing - lower) / (upper - lower));
-    const double lo = limit[lower / 45], hi = limit[mod_i(upper, 360) / 45];
-    lowest = fmin(lowest, lo * (1.0 - c) + hi * c);
-  }
-  return lowest;
-}
-
-static int adjust_step_frequency(shc_engine *e, double value, int64_t *pending) {
-  shc_params &p = e->params;
-  // What the posing part of the accepting loop reads from the legs' steppers must not depend on the step cycle's constants (it runs on the old cycle in the
-  // reference, on the new constants here): the walk-plane blend of rough terrain mode and the tip rotations / tip-align pose of gravity_aligned_tips do.
-  // WalkController::generateLimits takes its stance radius from leg 0's CURRENT default tip (walk_controller.cpp:322-326), which a stance span modifier moves.
-  if (p.rough_terrain_mode || p.gravity_aligned_tips || p.stance_span_modifier != 0.0)
-    return fail(SHC_ERR_UNSUPPORTED, "step_frequency cannot be adjusted at run time in rough_terrain_mode, with gravity_aligned_tips or with a stance span modifier "
-                                     "(the other eight parameters can); change it between runs, shc_engine_create");
-  if (!(value > 0.0)) return fail(SHC_ERR_INVALID_ARG, "step_frequency must be positive");
-  int rc = flush_step_remap(e); // (two changes without a cycle between them)
-  if (rc != SHC_OK) return rc;
-  shc_params np = p;
-  np.step_frequency = value;
-  const shc_step_cycle ns = hostinit::generate_step_cycle(np);
-  if (ns.period <= 0 || ns.period > LW_PHASE_MASK) return fail(SHC_ERR_INVALID_ARG, "step_frequency gives a degenerate step cycle");
-  p.step_frequency = value; // p->current_value = new_parameter_value_ (:454): the sequence / transition timings read it from now on, accepted or not
-  shc_tables tn = e->tables;
-  tn.step = ns;
-  hostinit::generate_limits(p, tn); // the four limit maps + the legs' phase offsets of the new cycle
-  // :462-463 and generateLimits' setPhaseOffset (walk_controller.cpp:277): the speed maps and the phase offsets are the new cycle's from here on, whether the
-  // change is accepted in this loop or not - the walker slows down to them (updateWalk :456-482), which is what makes a later call succeed
-  for (int b = 0; b < SHC_N_BEARINGS; ++b) {
-    e->tables.max_linear_speed[b] = tn.max_linear_speed[b];
-    e->tables.max_angular_speed[b] = tn.max_angular_speed[b];
-  }
-  for (int l = 0; l < e->L; ++l) e->tables.phase_offset[l] = tn.phase_offset[l];
-  // the test of :464-489, for every instance: desired body velocity inside what its velocity input maps to under the new limits
-  std::vector<double> vin(size_t(e->n) * 3), vel(size_t(e->n) * 3), tips(size_t(e->n) * e->L * 3);
-  if ((rc = gather_rob(e, vin.data(), 3, RobotFields::VIN, 0)) != SHC_OK) return rc;
-  if ((rc = gather_rob(e, vel.data(), 3, RobotFields::VLIN, 0)) != SHC_OK) return rc;
-  if ((rc = gather_leg(e, tips.data(), 3, LEG_FIELD(e, TIP), 0)) != SHC_OK) return rc;
-  int64_t waiting = 0;
-  for (int64_t i = 0; i < e->n; ++i) {
-    const double *in = &vin[size_t(i) * 3], *v = &vel[size_t(i) * 3], *tp = &tips[size_t(i) * e->L * 3];
-    const double max_lin = host_get_limit(tp, e->L, in[0], in[1], in[2], tn.max_linear_speed);
-    const double max_ang = host_get_limit(tp, e->L, in[0], in[1], in[2], tn.max_angular_speed);
-    double tx, ty, ta;
-    if (p.velocity_input_mode == SHC_VEL_THROTTLE) {
-      const double nrm = sqrt(in[0] * in[0] + in[1] * in[1]);
-      const double k = nrm > 1.0 ? 1.0 / nrm : 1.0; // clamped(vector, 1.0)
-      tx = in[0] * k * max_lin;
-      ty = in[1] * k * max_lin;
-      ta = clampd(in[2], -1.0, 1.0) * max_ang;
-      tx *= 1.0 - fabs(in[2]);
-      ty *= 1.0 - fabs(in[2]);
-    } else {
-      const double nrm = sqrt(in[0] * in[0] + in[1] * in[1]);
-      const double k = nrm > max_lin ? max_lin / nrm : 1.0;
-      tx = in[0] * k;
-      ty = in[1] * k;
-      ta = clampd(in[2], -max_ang, max_ang);
-    }
-    if (!(v[0] <= tx && v[1] <= ty && fabs(v[2]) <= fabs(ta))) ++waiting; // (signed comparisons of the linear components: as the reference has them)
-  }
-  if (pending) *pending = waiting;
-  if (waiting) return upload_consts(e); // not yet: the new speed maps / phase offsets are in force, the step cycle and the acceleration maps are the old ones
-  // accepted: walker_->generateStepCycle() + generateLimits() (:491-492).  setAutoPoseParams is NOT called (only init / changeGait do): the auto-pose phase
-  // tables keep counting in the old step period, as in the reference.
-  const shc_step_cycle old_step = e->tables.step;
-  e->tables.step = ns;
-  for (int b = 0; b < SHC_N_BEARINGS; ++b) {
-    e->tables.max_linear_acceleration[b] = tn.max_linear_acceleration[b];
-    e->tables.max_angular_acceleration[b] = tn.max_angular_acceleration[b];
-  }
-  e->remap_old_step = old_step; // generateStepCycle's updatePhase for MOVING robots: inside the next cycle (cp.remap_old_period, shc_engine_step)
-  e->step_remap_pending = true;
-  rebuild_cycle_params(e);
-  return upload_consts(e);
-}
-
-extern "C" int shc_engine_adjust_parameter(shc_engine *e, int which, double value, int64_t *pending) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
-  if (pending) *pending = 0;
-  if (!(value == value) || fabs(value) > 1e300) return fail(SHC_ERR_INVALID_ARG, "parameter value is not finite");
-  HIP_TRY(hipSetDevice(e->device));
-  shc_params &p = e->params;
-  const shc_params old = p;
-  switch (which) {
-    case SHC_PARAM_STEP_FREQUENCY: return adjust_step_frequency(e, value, pending);
-    case SHC_PARAM_SWING_HEIGHT: p.swing_height = value; break;          // LegStepper::updateStride's swing clearance, the dynamic-stiffness reference, sequence step heights
-    case SHC_PARAM_SWING_WIDTH: p.swing_width = value; break;            // generateSecondarySwingControlNodes' lateral shift (walk_controller.cpp:1243)
-    case SHC_PARAM_STEP_DEPTH: p.step_depth = value; break;              // the proactive step-plane target (:1099)
-    case SHC_PARAM_STANCE_SPAN_MODIFIER: p.stance_span_modifier = value; e->span_dirty = true; break; // calculateStanceSpanChange (:966), applied at the next stop / swing start
-    case SHC_PARAM_VIRTUAL_MASS:
-      if (!(value > 0.0)) return fail(SHC_ERR_INVALID_ARG, "virtual_mass must be positive");
-      p.virtual_mass = value;
-      break;
-    case SHC_PARAM_VIRTUAL_STIFFNESS:
-      if (!(value > 0.0)) return fail(SHC_ERR_INVALID_ARG, "virtual_stiffness must be positive");
-      p.virtual_stiffness = value;
-      break;
-    case SHC_PARAM_VIRTUAL_DAMPING: p.virtual_damping_ratio = value; break;
-    case SHC_PARAM_FORCE_GAIN: p.force_gain = value; break;              // admittance input (admittance_controller.cpp:32), tip-force estimate (model.cpp:705), LegState tip force
-    default: return fail(SHC_ERR_INVALID_ARG, "unknown adjustable parameter (SHC_PARAM_*)");
-  }
-  // The eight parameters the control cycle reads as they are (params_.*.current_value): a new launch-uniform block, in force from the next cycle; no table is
-  // regenerated and no state is touched.
-  // ... except where the POSING part of the loop reads them (updateStiffness / updateAdmittance run before runningState, state_controller.cpp:170-180): the
-  // virtual spring's constants, the force gain as the admittance input scales it and the swing height as the dynamic-stiffness reference divides by it stay
-  // what they were for the posing part of the next cycle (the tip-force estimate and the stepper of that same cycle use the new values), then follow.
-  if (which == SHC_PARAM_SWING_HEIGHT || which == SHC_PARAM_VIRTUAL_MASS || which == SHC_PARAM_VIRTUAL_STIFFNESS || which == SHC_PARAM_VIRTUAL_DAMPING ||
-      which == SHC_PARAM_FORCE_GAIN) {
-    if (!e->pose_params_held) e->held_params = old; // (the values the last cycle's posing part ran on)
-    e->pose_params_held = true;
-  }
-  rebuild_cycle_params(e);
-  return upload_consts(e);
-}
-
 extern "C" int shc_engine_get_odometry(shc_engine *e, double *pose, int on_device) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   if (!e->cp.odometry) return fail(SHC_ERR_UNSUPPORTED, "SHC_FEAT_ODOMETRY is off");
   if (!pose) return SHC_OK;
   HIP_TRY(hipSetDevice(e->device));
@@ -1756,8 +1508,7 @@ extern "C" int shc_engine_get_odometry(shc_engine *e, double *pose, int on_devic
 }
 
 extern "C" int shc_engine_get_virtual_stiffness(shc_engine *e, double *stiffness, int on_device) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   if (!e->params.admittance_control) return fail(SHC_ERR_UNSUPPORTED, "admittance_control is off: updateStiffness never runs");
   return gather_leg(e, stiffness, 1, LEG_FIELD(e, ADM_DELTA) + 3, on_device);
 }
@@ -1770,7 +1521,7 @@ static int derive_tips(shc_engine *e) {
 #define CALL(L_, NJ_)                                                                                             \
   derive_tips_kernel<L_, NJ_><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(                \
       e->st, (const SharedConsts<L_, NJ_> *)e->d_consts, derive_poser, keep_marked)
-  SHC_DISPATCH(e->L, e->NJ, CALL);
+  SHC_DISPATCH(e->L, e->NJ);
 #undef CALL
   HIP_TRY(hipGetLastError());
   return SHC_OK;
@@ -1840,18 +1591,16 @@ static Pose host_fk_tip_pose(const shc_params &p, int leg, const double *q) {
 }
 
 extern "C" int shc_engine_read_leg_state_msg(shc_engine *e, int64_t instance, shc_leg_state_msg *legs) {
-  SHC_BUSY_GUARD(e);
-  if (!e || !legs) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
+  SHC_ENTER_JOINED(e);
+  if (!legs) return fail(SHC_ERR_INVALID_ARG, "legs is NULL");
   if (instance < 0 || instance >= e->n) return fail(SHC_ERR_INVALID_ARG, "instance out of range");
   int rc = derive_tips(e);
   if (rc != SHC_OK) return rc;
   const int L = e->L, NJ = e->NJ, per_leg = 12 + 4 * NJ + 8;
   std::vector<double> h(size_t(L) * per_leg + 10);
-  switch (NJ) {
-    case 3: read_instance_kernel<3><<<dim3(1), dim3(64), 0, e->stream>>>(e->d_stage, e->st, L, instance, e->params.admittance_control); break;
-    case 4: read_instance_kernel<4><<<dim3(1), dim3(64), 0, e->stream>>>(e->d_stage, e->st, L, instance, e->params.admittance_control); break;
-    default: read_instance_kernel<5><<<dim3(1), dim3(64), 0, e->stream>>>(e->d_stage, e->st, L, instance, e->params.admittance_control); break;
-  }
+  dispatch_nj(NJ, [&](auto nj) {
+    read_instance_kernel<decltype(nj)::value><<<dim3(1), dim3(64), 0, e->stream>>>(e->d_stage, e->st, L, instance, e->params.admittance_control);
+  });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(h.data(), e->d_stage, h.size() * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
@@ -1884,7 +1633,7 @@ extern "C" int shc_engine_read_leg_state_msg(shc_engine *e, int64_t instance, sh
     }
     { // actual_tip_pose: Leg::applyFK(false, true) on the measured joint positions (:839)
       const double *qm = &o[20 + 3 * NJ];
-      const Pose tp = NJ == 3 ? host_fk_tip_pose<3>(e->params, l, qm) : (NJ == 4 ? host_fk_tip_pose<4>(e->params, l, qm) : host_fk_tip_pose<5>(e->params, l, qm));
+      const Pose tp = dispatch_nj(NJ, [&](auto nj) { return host_fk_tip_pose<decltype(nj)::value>(e->params, l, qm); });
       m.actual_tip_pose[0] = tp.p.x, m.actual_tip_pose[1] = tp.p.y, m.actual_tip_pose[2] = tp.p.z;
       m.actual_tip_pose[3] = tp.r.w, m.actual_tip_pose[4] = tp.r.x, m.actual_tip_pose[5] = tp.r.y, m.actual_tip_pose[6] = tp.r.z;
     }
@@ -1979,8 +1728,7 @@ static int upload_offsets(shc_engine *e, const double **d_off) {
 }
 
 extern "C" int shc_engine_set_joint_states_msg(shc_engine *e, const double *position, const double * /*velocity*/, const double *effort, int on_device) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   HIP_TRY(hipSetDevice(e->device));
   int rc = SHC_OK;
   if (position) {
@@ -1998,8 +1746,7 @@ extern "C" int shc_engine_set_joint_states_msg(shc_engine *e, const double *posi
 }
 
 extern "C" int shc_engine_set_tip_states_msg(shc_engine *e, const double *wrench_force, const double *step_plane, int on_device) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   int rc = SHC_OK;
   if (wrench_force && (rc = shc_engine_set_tip_force(e, wrench_force, on_device)) != SHC_OK) return rc;
   if (step_plane) {
@@ -2010,7 +1757,7 @@ extern "C" int shc_engine_set_tip_states_msg(shc_engine *e, const double *wrench
     const int64_t threads = e->n * e->L;
 #define CALL(L_, NJ_) \
   step_plane_range_kernel<L_, NJ_><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(e->st, (const SharedConsts<L_, NJ_> *)e->d_consts, d)
-    SHC_DISPATCH(e->L, e->NJ, CALL);
+    SHC_DISPATCH(e->L, e->NJ);
 #undef CALL
     HIP_TRY(hipGetLastError());
     if (!on_device) HIP_TRY(hipStreamSynchronize(e->stream));
@@ -2080,7 +1827,6 @@ static int ensure_seq(shc_engine *e);
 static int ensure_manual(shc_engine *e, bool planner);
 static int ensure_manual_records(shc_engine *e);
 static int external_select(shc_engine *e, int which, int64_t first, int64_t count, int leg, int64_t *rows_out) {
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
   if (which != SHC_EXTERNAL_TARGET && which != SHC_EXTERNAL_DEFAULT && which != SHC_EXTERNAL_PLANNER_TARGET)
     return fail(SHC_ERR_INVALID_ARG, "which must be SHC_EXTERNAL_TARGET, SHC_EXTERNAL_DEFAULT or SHC_EXTERNAL_PLANNER_TARGET");
   if (first < 0 || count < 0 || first + count > e->n || leg >= e->L) return fail(SHC_ERR_INVALID_ARG, "instance range / leg out of bounds");
@@ -2122,7 +1868,7 @@ static int external_write(shc_engine *e, int which, int64_t first, int64_t count
 
 extern "C" int shc_engine_set_external_target(shc_engine *e, int which, int64_t first, int64_t count, int leg, const shc_external_target *rows,
                                               int64_t *ignored) {
-  SHC_BUSY_GUARD(e);
+  SHC_ENTER_JOINED(e);
   int64_t n_rows = 0;
   int rc = external_select(e, which, first, count, leg, &n_rows);
   if (rc != SHC_OK) return rc;
@@ -2143,7 +1889,7 @@ extern "C" int shc_engine_set_external_target(shc_engine *e, int which, int64_t 
 }
 
 extern "C" int shc_engine_set_external_transform(shc_engine *e, int which, int64_t first, int64_t count, int leg, const double *transform) {
-  SHC_BUSY_GUARD(e);
+  SHC_ENTER_JOINED(e);
   int64_t n_rows = 0;
   int rc = external_select(e, which, first, count, leg, &n_rows);
   if (rc != SHC_OK) return rc;
@@ -2156,7 +1902,7 @@ extern "C" int shc_engine_set_external_transform(shc_engine *e, int which, int64
 }
 
 extern "C" int shc_engine_get_external_target(shc_engine *e, int which, int64_t first, int64_t count, int leg, shc_external_target *rows) {
-  SHC_BUSY_GUARD(e);
+  SHC_ENTER_JOINED(e);
   int64_t n_rows = 0;
   int rc = external_select(e, which, first, count, leg, &n_rows);
   if (rc != SHC_OK) return rc;
@@ -2181,8 +1927,7 @@ extern "C" int shc_engine_get_external_target(shc_engine *e, int which, int64_t 
 }
 
 extern "C" int shc_engine_get_joint_commands(shc_engine *e, double *position, double *velocity, double *effort, double *position_command, int on_device) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   HIP_TRY(hipSetDevice(e->device));
   const double *d_off;
   int rc = upload_offsets(e, &d_off);
@@ -2228,7 +1973,6 @@ struct LegCall {
   }
   int init(shc_engine *eng, int64_t first, int64_t count, int leg) {
     e = eng;
-    if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
     if (first < 0 || count < 0 || first + count > e->n) return fail(SHC_ERR_INVALID_ARG, "instance range out of bounds");
     if (leg < -1 || leg >= e->L) return fail(SHC_ERR_INVALID_ARG, "leg out of range (-1 = every leg)");
     sel = LegSel{first, count, leg, e->L};
@@ -2267,7 +2011,7 @@ struct LegCall {
 template <class Fn>
 static int leg_dispatch(shc_engine *e, Fn &&fn) {
 #define CALL(L_, NJ_) fn(std::integral_constant<int, L_>{}, std::integral_constant<int, NJ_>{})
-  SHC_DISPATCH(e->L, e->NJ, CALL);
+  SHC_DISPATCH(e->L, e->NJ);
 #undef CALL
   return SHC_OK;
 }
@@ -2279,7 +2023,7 @@ static int leg_dispatch(shc_engine *e, Fn &&fn) {
 
 extern "C" int shc_leg_set_desired_tip_pose(shc_engine *e, int64_t first, int64_t count, int leg, const double *tip_pose, int apply_delta,
                                             int on_device) {
-  SHC_BUSY_GUARD(e);
+  SHC_ENTER_JOINED(e);
   LegCall c;
   int rc = c.init(e, first, count, leg);
   if (rc != SHC_OK) return rc;
@@ -2292,7 +2036,7 @@ extern "C" int shc_leg_set_desired_tip_pose(shc_engine *e, int64_t first, int64_
 
 extern "C" int shc_leg_solve_ik(shc_engine *e, int64_t first, int64_t count, int leg, const double *delta, int solve_rotation,
                                 double *joint_delta, int on_device) {
-  SHC_BUSY_GUARD(e);
+  SHC_ENTER_JOINED(e);
   if (!delta || !joint_delta) return fail(SHC_ERR_INVALID_ARG, "delta / joint_delta is NULL");
   LegCall c;
   int rc = c.init(e, first, count, leg);
@@ -2306,7 +2050,7 @@ extern "C" int shc_leg_solve_ik(shc_engine *e, int64_t first, int64_t count, int
 
 extern "C" int shc_leg_update_joint_positions(shc_engine *e, int64_t first, int64_t count, int leg, const double *joint_delta, int simulation,
                                               double *limit_proximity, int on_device) {
-  SHC_BUSY_GUARD(e);
+  SHC_ENTER_JOINED(e);
   if (!joint_delta) return fail(SHC_ERR_INVALID_ARG, "joint_delta is NULL");
   LegCall c;
   int rc = c.init(e, first, count, leg);
@@ -2321,7 +2065,7 @@ extern "C" int shc_leg_update_joint_positions(shc_engine *e, int64_t first, int6
 }
 
 extern "C" int shc_leg_apply_ik(shc_engine *e, int64_t first, int64_t count, int leg, int simulation, double *ik_result, int on_device) {
-  SHC_BUSY_GUARD(e);
+  SHC_ENTER_JOINED(e);
   LegCall c;
   int rc = c.init(e, first, count, leg);
   if (rc != SHC_OK) return rc;
@@ -2335,7 +2079,7 @@ extern "C" int shc_leg_apply_ik(shc_engine *e, int64_t first, int64_t count, int
 
 extern "C" int shc_leg_apply_fk(shc_engine *e, int64_t first, int64_t count, int leg, const double *joint_position, double *tip_pose,
                                 int on_device) {
-  SHC_BUSY_GUARD(e);
+  SHC_ENTER_JOINED(e);
   if (!tip_pose) return fail(SHC_ERR_INVALID_ARG, "tip_pose is NULL");
   LegCall c;
   int rc = c.init(e, first, count, leg);
@@ -2350,7 +2094,7 @@ extern "C" int shc_leg_apply_fk(shc_engine *e, int64_t first, int64_t count, int
 // ---- sequences
 extern "C" int shc_leg_step_to_position(shc_engine *e, int64_t first, int64_t count, int leg, const double *target_tip_pose, const double *target_pose,
                                         double lift_height, double time_to_step, int apply_delta, double *tip_pose, int32_t *progress, int on_device) {
-  SHC_BUSY_GUARD(e);
+  SHC_ENTER_JOINED(e);
   if (!target_pose || !tip_pose) return fail(SHC_ERR_INVALID_ARG, "target_pose / tip_pose is NULL");
   if (!(time_to_step >= 0.0)) return fail(SHC_ERR_INVALID_ARG, "time_to_step must be >= 0");
   LegCall c;
@@ -2379,7 +2123,7 @@ extern "C" int shc_leg_step_to_position(shc_engine *e, int64_t first, int64_t co
 
 extern "C" int shc_leg_transition_configuration(shc_engine *e, int64_t first, int64_t count, int leg, const double *desired_configuration,
                                                 double transition_time, int32_t *progress, int on_device) {
-  SHC_BUSY_GUARD(e);
+  SHC_ENTER_JOINED(e);
   if (!desired_configuration) return fail(SHC_ERR_INVALID_ARG, "desired_configuration is NULL");
   LegCall c;
   int rc = c.init(e, first, count, leg);
@@ -2425,8 +2169,7 @@ __global__ void restore_joints_kernel(DevState st, const double2 *saved_planes, 
 }
 
 extern "C" int shc_engine_begin_direct_startup(shc_engine *e) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   int rc = init_state(e);
   if (rc != SHC_OK) return rc;
   std::vector<double> q0(size_t(e->L) * e->NJ);
@@ -2435,11 +2178,7 @@ extern "C" int shc_engine_begin_direct_startup(shc_engine *e) {
   HIP_TRY(hipMemcpyAsync(e->d_stage, q0.data(), q0.size() * 8, hipMemcpyHostToDevice, e->stream));
   const int64_t threads = e->n * e->L;
   const dim3 grid((unsigned)((threads + 255) / 256));
-  switch (e->NJ) {
-    case 3: set_initial_joints_kernel<3><<<grid, dim3(256), 0, e->stream>>>(e->st, e->d_stage, e->L); break;
-    case 4: set_initial_joints_kernel<4><<<grid, dim3(256), 0, e->stream>>>(e->st, e->d_stage, e->L); break;
-    default: set_initial_joints_kernel<5><<<grid, dim3(256), 0, e->stream>>>(e->st, e->d_stage, e->L); break;
-  }
+  dispatch_nj(e->NJ, [&](auto nj) { set_initial_joints_kernel<decltype(nj)::value><<<grid, dim3(256), 0, e->stream>>>(e->st, e->d_stage, e->L); });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->stream));
   e->startup_calls = 0;
@@ -2448,8 +2187,7 @@ extern "C" int shc_engine_begin_direct_startup(shc_engine *e) {
 }
 
 extern "C" int shc_engine_direct_startup(shc_engine *e, int32_t *progress) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   if (!e->starting_up) return fail(SHC_ERR_INVALID_ARG, "call shc_engine_begin_direct_startup first");
   HIP_TRY(hipSetDevice(e->device));
   // desired_configuration_ of every leg = the joints the simulated start-up solve ended on (pose_controller.cpp:476-510):
@@ -2496,8 +2234,7 @@ __global__ void set_joint_positions_kernel(DevState st, const double *q, int per
 }
 
 extern "C" int shc_engine_begin_sequence_startup(shc_engine *e, const double *joint_positions, int per_instance) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   // (arguments first: an INVALID_ARG return leaves the batch as it was)
   if (per_instance && !joint_positions) return fail(SHC_ERR_INVALID_ARG, "per_instance needs joint_positions");
   const size_t rows = per_instance ? size_t(e->n) * e->L : size_t(e->L);
@@ -2535,9 +2272,7 @@ static int ensure_seq(shc_engine *e) { // the per-robot PoseController records o
 }
 static SeqParams seq_params(const shc_engine *e) {
   SeqParams P{};
-  // A direct parameter adjusted since the last cycle is stored by adjustParameter AFTER legStateToggle / executePlan / transitionRobotState in the
-  // loop that serves it (state_controller.cpp:384-414): the loop-level kernels of that loop still read the old value.
-  const shc_params &q = e->pose_params_held ? e->held_params : e->params;
+  const shc_params &q = posing_params(e); // shc_adjust.hpp, row "seq_params, toggle_leg_state"
   P.step_frequency = e->params.step_frequency;
   P.swing_height = q.swing_height;
   P.dt = e->params.time_delta;
@@ -2564,8 +2299,7 @@ static int pose_pass(shc_engine *e) { // the marked robots' PoseController::upda
 }
 
 static int sequence_launch(shc_engine *e, int which /* 0 / 1: executeSequence(START_UP / SHUT_DOWN), 2: stepToNewStance */, int32_t *progress) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   int rc = ensure_seq(e);
   if (rc != SHC_OK) return rc;
   SeqParams P = seq_params(e);
@@ -2600,7 +2334,7 @@ static int sequence_launch(shc_engine *e, int which /* 0 / 1: executeSequence(ST
 #define CALL(L_, NJ_)                                                                                                                        \
   if (which == 2) step_to_new_stance_kernel<L_, NJ_><<<grid, block, 0, e->stream>>>(e->st, (const SharedConsts<L_, NJ_> *)e->d_consts, e->d_seq, P, d_progress); \
   else execute_sequence_kernel<L_, NJ_><<<grid, block, 0, e->stream>>>(e->st, (const SharedConsts<L_, NJ_> *)e->d_consts, e->d_seq, which, P, d_progress)
-  SHC_DISPATCH(e->L, e->NJ, CALL);
+  SHC_DISPATCH(e->L, e->NJ);
 #undef CALL
   HIP_TRY(hipGetLastError());
   if (own_clock) {
@@ -2610,15 +2344,11 @@ static int sequence_launch(shc_engine *e, int which /* 0 / 1: executeSequence(ST
   }
   if (progress) HIP_TRY(hipMemcpyAsync(progress, d_progress, size_t(e->n) * 4, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
-  // A pending adjustParameter is served only where the reference reaches it: SHUT_DOWN runs from RUNNING, inside runningState's transitionRobotState
-  // (state_controller.cpp:384-388, :328-352), and adjustParameter follows in the same loop (:411-414).  START_UP runs from READY in loop() (:184-187,
-  // :314) - runningState is not reached (:189-192) - and stepToNewStance is no loop of the StateController at all: the change stays pending (the
-  // sequence kernels above and the pose pass read the old values, seq_params) until the next loop that reaches runningState.
-  return which == SHC_SEQUENCE_SHUT_DOWN ? consume_pending_adjustment(e) : SHC_OK;
+  return which == SHC_SEQUENCE_SHUT_DOWN ? adjust_served_by_loop(e) : SHC_OK; // shc_adjust.hpp, rows "SHUT_DOWN" / "START_UP sequence step, step_to_new_stance"
 }
 
 extern "C" int shc_engine_execute_sequence(shc_engine *e, int sequence, int32_t *progress) {
-  SHC_BUSY_GUARD(e);
+  SHC_ENTER_JOINED(e);
   if (sequence != SHC_SEQUENCE_START_UP && sequence != SHC_SEQUENCE_SHUT_DOWN) return fail(SHC_ERR_INVALID_ARG, "sequence must be SHC_SEQUENCE_START_UP or SHC_SEQUENCE_SHUT_DOWN");
   return sequence_launch(e, sequence, progress);
 }
@@ -2641,7 +2371,6 @@ static int ensure_manual_records(shc_engine *e) { // the per-robot ManualRobot r
   return SHC_OK;
 }
 static int ensure_manual(shc_engine *e, bool planner) {
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
   if (e->cp.tip_align)
     return fail(SHC_ERR_UNSUPPORTED, "manual leg manipulation / planner mode with the tip-align pose (gravity_aligned_tips on <= 3-DOF legs)");
   const int rc = ensure_manual_records(e);
@@ -2651,7 +2380,7 @@ static int ensure_manual(shc_engine *e, bool planner) {
 }
 
 extern "C" int shc_engine_toggle_leg_state(shc_engine *e, const int32_t *leg_selection, int32_t *result) {
-  SHC_BUSY_GUARD(e);
+  SHC_ENTER_JOINED(e);
   int rc = ensure_manual(e, false);
   if (rc != SHC_OK) return rc;
   if (!leg_selection) return fail(SHC_ERR_INVALID_ARG, "leg_selection is NULL");
@@ -2659,7 +2388,7 @@ extern "C" int shc_engine_toggle_leg_state(shc_engine *e, const int32_t *leg_sel
   HIP_TRY(hipMemcpyAsync(d_sel, leg_selection, size_t(e->n) * 4, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemsetAsync(d_cycle, 0, 4, e->stream));
   const SeqParams P = seq_params(e);
-  const double virtual_stiffness = (e->pose_params_held ? e->held_params : e->params).virtual_stiffness; // (see seq_params)
+  const double virtual_stiffness = posing_params(e).virtual_stiffness; // (as seq_params)
   const dim3 grid((unsigned)((e->n + 63) / 64)), block(64);
   int phase = LOOP_WHOLE;
 #define CALL(L_, NJ_)                                                                                                                              \
@@ -2668,12 +2397,12 @@ extern "C" int shc_engine_toggle_leg_state(shc_engine *e, const int32_t *leg_sel
                                                                   e->params.admittance_control && e->params.dynamic_stiffness, d_res, d_cycle, phase)
   if (posing_needs_pose_pass(e)) { // mark the robots that stand with a request, run the posing part of their loop in the cycle kernel
     phase = LOOP_MARK;
-    SHC_DISPATCH(e->L, e->NJ, CALL);
+    SHC_DISPATCH(e->L, e->NJ);
     HIP_TRY(hipGetLastError());
     if ((rc = pose_pass(e)) != SHC_OK) return rc;
     phase = LOOP_AFTER_POSE;
   }
-  SHC_DISPATCH(e->L, e->NJ, CALL);
+  SHC_DISPATCH(e->L, e->NJ);
 #undef CALL
   HIP_TRY(hipGetLastError());
   int32_t cycle = 0;
@@ -2687,12 +2416,12 @@ extern "C" int shc_engine_toggle_leg_state(shc_engine *e, const int32_t *leg_sel
     if (rc != SHC_OK) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
   }
-  return consume_pending_adjustment(e);
+  return adjust_served_by_loop(e); // shc_adjust.hpp, row "toggle_leg_state, execute_plan"
 }
 
 extern "C" int shc_engine_set_manual_inputs(shc_engine *e, const int32_t *primary_leg, const double *primary_tip_velocity, const double *primary_tip_position,
                                             const int32_t *secondary_leg, const double *secondary_tip_velocity, const double *secondary_tip_position) {
-  SHC_BUSY_GUARD(e);
+  SHC_ENTER_JOINED(e);
   int rc = ensure_manual(e, false);
   if (rc != SHC_OK) return rc;
   // staging layout: [primary leg | secondary leg] ints, then four [n][3] double blocks
@@ -2716,8 +2445,8 @@ extern "C" int shc_engine_set_manual_inputs(shc_engine *e, const int32_t *primar
 }
 
 extern "C" int shc_engine_get_leg_manipulation_state(shc_engine *e, int32_t *states) {
-  SHC_BUSY_GUARD(e);
-  if (!e || !states) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
+  SHC_ENTER_JOINED(e);
+  if (!states) return fail(SHC_ERR_INVALID_ARG, "states is NULL");
   HIP_TRY(hipSetDevice(e->device));
   int32_t *d = reinterpret_cast<int32_t *>(e->d_stage);
   const int64_t rows = e->n * e->L;
@@ -2761,25 +2490,24 @@ static int plan_inputs(shc_engine *e, int64_t first, int64_t count, int reset_pl
 }
 
 extern "C" int shc_engine_set_planner_mode(shc_engine *e, int on) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   if ((on != 0) == e->planner_mode) return SHC_OK; // plannerModeCallback acts on a change only (state_controller.cpp:1267)
   e->planner_mode = on != 0;
   return on ? plan_inputs(e, 0, e->n, 1, nullptr, nullptr) : SHC_OK; // plan_step_ = 0 (:1273)
 }
 extern "C" int shc_engine_set_target_configuration(shc_engine *e, int64_t first, int64_t count, const double *configuration) {
-  SHC_BUSY_GUARD(e);
-  if (!e || !configuration) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
+  SHC_ENTER_JOINED(e);
+  if (!configuration) return fail(SHC_ERR_INVALID_ARG, "configuration is NULL");
   return plan_inputs(e, first, count, 0, configuration, nullptr);
 }
 extern "C" int shc_engine_set_target_body_pose(shc_engine *e, int64_t first, int64_t count, const double *pose) {
-  SHC_BUSY_GUARD(e);
-  if (!e || !pose) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
+  SHC_ENTER_JOINED(e);
+  if (!pose) return fail(SHC_ERR_INVALID_ARG, "pose is NULL");
   return plan_inputs(e, first, count, 0, nullptr, pose);
 }
 
 extern "C" int shc_engine_execute_plan(shc_engine *e, int32_t *progress, int32_t *plan_step) {
-  SHC_BUSY_GUARD(e);
+  SHC_ENTER_JOINED(e);
   int rc = ensure_planner(e);
   if (rc != SHC_OK) return rc;
   int32_t *d_progress = reinterpret_cast<int32_t *>(e->d_stage), *d_step = d_progress + e->n, *d_walking = d_step + e->n;
@@ -2793,12 +2521,12 @@ extern "C" int shc_engine_execute_plan(shc_engine *e, int32_t *progress, int32_t
                                                               d_step, d_walking, phase)
   if (posing_needs_pose_pass(e)) { // mark the robots that stand, run the posing part of their loop in the cycle kernel
     phase = LOOP_MARK;
-    SHC_DISPATCH(e->L, e->NJ, CALL);
+    SHC_DISPATCH(e->L, e->NJ);
     HIP_TRY(hipGetLastError());
     if ((rc = pose_pass(e)) != SHC_OK) return rc;
     phase = LOOP_AFTER_POSE;
   }
-  SHC_DISPATCH(e->L, e->NJ, CALL);
+  SHC_DISPATCH(e->L, e->NJ);
 #undef CALL
   HIP_TRY(hipGetLastError());
   e->plan_poser_tips_current = true;
@@ -2814,12 +2542,11 @@ extern "C" int shc_engine_execute_plan(shc_engine *e, int32_t *progress, int32_t
     if (rc != SHC_OK) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
   }
-  return consume_pending_adjustment(e);
+  return adjust_served_by_loop(e); // shc_adjust.hpp, row "toggle_leg_state, execute_plan"
 }
 
 // PoseController::packLegs / unpackLegs (pose_controller.cpp:615-707)
 static int pack_transition(shc_engine *e, const double *packed_positions, int n_pack_steps, double transition_time, bool unpack, int32_t *progress) {
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
   if (!packed_positions || n_pack_steps < 1) return fail(SHC_ERR_INVALID_ARG, "packed_positions / n_pack_steps");
   if (!(transition_time > 0)) return fail(SHC_ERR_INVALID_ARG, "transition time must be > 0");
   HIP_TRY(hipSetDevice(e->device));
@@ -2867,12 +2594,12 @@ static int pack_transition(shc_engine *e, const double *packed_positions, int n_
 }
 
 extern "C" int shc_engine_pack_legs(shc_engine *e, const double *packed_positions, int n_pack_steps, double time_to_pack, int32_t *progress) {
-  SHC_BUSY_GUARD(e);
+  SHC_ENTER_JOINED(e);
   return pack_transition(e, packed_positions, n_pack_steps, time_to_pack, false, progress);
 }
 
 extern "C" int shc_engine_unpack_legs(shc_engine *e, const double *packed_positions, int n_pack_steps, double time_to_unpack, int32_t *progress) {
-  SHC_BUSY_GUARD(e);
+  SHC_ENTER_JOINED(e);
   return pack_transition(e, packed_positions, n_pack_steps, time_to_unpack, true, progress);
 }
 
@@ -2882,8 +2609,7 @@ __global__ void copy_joint_planes_kernel(double2 *dst, const double2 *src, int64
 }
 
 extern "C" int shc_engine_finish_sequence_startup(shc_engine *e) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   HIP_TRY(hipSetDevice(e->device));
   // Auto posing on its own clock (pose_frequency != -1) poses the body through the sequence calls (sequence_launch), and the PoseController lives on through
   // walker_->init() (:306): its phase counter, the posers' latches and Model::current_pose_ carry over, Leg::generateWorkspace searches at the pose of THAT loop
@@ -2937,16 +2663,11 @@ extern "C" int shc_engine_finish_sequence_startup(shc_engine *e) {
                                            std::to_string(worst) + " rad): one engine has one set of workspace / limit tables");
   }
   shc_tables t;
-  bool ok = false;
-  switch (e->NJ) {
-    case 3: ok = hostinit::generate_tables<3>(e->params, t, q.data(), own_clock ? &ws_pose : nullptr); break;
-    case 4: ok = hostinit::generate_tables<4>(e->params, t, q.data(), own_clock ? &ws_pose : nullptr); break;
-    default: ok = hostinit::generate_tables<5>(e->params, t, q.data(), own_clock ? &ws_pose : nullptr); break;
-  }
+  const bool ok = dispatch_nj(e->NJ, [&](auto nj) { return hostinit::generate_tables<decltype(nj)::value>(e->params, t, q.data(), own_clock ? &ws_pose : nullptr); });
   if (!ok) return fail(SHC_ERR_INVALID_ARG, "init chain failed for the configuration the sequence ended on");
   e->tables = t;
   e->span_dirty = true;
-  rebuild_cycle_params(e); // (a change still pending is served by the runningState() below: shc_engine_step's held cycle)
+  rebuild_cycle_params(e); // (shc_adjust.hpp, row "shc_engine_finish_sequence_startup")
   if ((rc = upload_consts(e)) != SHC_OK) return rc;
   // walker_->init() (:306): fresh LegSteppers / walk state; the joints stay where the sequence left them
   const int n_joint_planes = (2 * e->NJ + 1) / 2 + 1; // planes holding Q and QD (Fields: Q = 0, QD = NJ, TIP = 2 NJ)
@@ -2989,205 +2710,10 @@ extern "C" int shc_engine_finish_sequence_startup(shc_engine *e) {
   return shc_engine_synchronize(e);
 }
 
-extern "C" int64_t shc_sizeof_instance_state(void) { return (int64_t)sizeof(shc_instance_state); }
-
-// Snapshot records travel through a temporary device buffer (checkpoint / injection are not per-cycle operations).
-// Neither direction consumes an adjustParameter that waits for its loop: a record shows the legs' phases in the period they still count in (as the
-// reference's state between the two loops), an injected record's phases are mapped onto the new period inside the accepting loop.
-static int state_transfer(shc_engine *e, int64_t first, int64_t count, shc_instance_state *out, const shc_instance_state *in) {
-  if (!e || (!out && !in)) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
-  if (first < 0 || count < 0 || first + count > e->n) return fail(SHC_ERR_INVALID_ARG, "instance range out of bounds");
-  if (count == 0) return SHC_OK;
-  if (in) e->rt_flags |= RT_MANUAL_LIVE; // an injected state may carry any manual pose
-  if (in) // touchdown detection is one flag per engine: on as soon as any injected record has it (tip-state messages arrive for a whole robot)
-    for (int64_t i = 0; i < count; ++i)
-      if (in[i].touchdown_detection) e->rt_flags |= RT_TOUCHDOWN;
-  if (in && !(e->rt_flags & RT_EFFORT_LIVE)) { // a non-zero tip-force filter state decays over the following cycles: evaluate it
-    bool any = false;
-    for (int64_t i = 0; i < count && !any; ++i)
-      for (int l = 0; l < e->L; ++l)
-        for (int k = 0; k < 3; ++k) any |= in[i].leg[l].tip_force_calculated[k] != 0.0;
-    if (any) {
-      const int rc = effort_live(e);
-      if (rc != SHC_OK) return rc;
-    }
-  }
-  const int touchdown = (e->rt_flags & RT_TOUCHDOWN) ? 1 : 0;
-  CycleParams cp = e->cp; // (get_state_kernel derives swing / stance progress from the phase: in the step cycle the phase counts in)
-  if (e->step_remap_pending) {
-    const shc_step_cycle &s = e->remap_old_step;
-    cp.period = s.period, cp.swing_period = s.swing_period, cp.stance_period = s.stance_period;
-    cp.stance_end = s.stance_end, cp.swing_start = s.swing_start, cp.swing_end = s.swing_end, cp.stance_start = s.stance_start;
-  }
-  unsigned long_legs = 0;
-  for (int l = 0; l < e->L; ++l) long_legs |= e->params.leg_dof[l] > 3 ? 1u << l : 0u;
-  HIP_TRY(hipSetDevice(e->device));
-  shc_instance_state *d = nullptr;
-  const size_t bytes = size_t(count) * sizeof(shc_instance_state);
-  HIP_TRY(hipMalloc(&d, bytes));
-  hipError_t err = hipSuccess;
-  const dim3 grid((unsigned)((count + 63) / 64)), block(64);
-  if (in) err = hipMemcpyAsync(d, in, bytes, hipMemcpyHostToDevice, e->stream);
-  if (err == hipSuccess) {
-    switch (e->NJ) {
-      case 3: if (in) set_state_kernel<3><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, long_legs);
-              else get_state_kernel<3><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, touchdown, long_legs);
-              break;
-      case 4: if (in) set_state_kernel<4><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, long_legs);
-              else get_state_kernel<4><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, touchdown, long_legs);
-              break;
-      default: if (in) set_state_kernel<5><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, long_legs);
-               else get_state_kernel<5><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, touchdown, long_legs);
-               break;
-    }
-    err = hipGetLastError();
-  }
-  if (err == hipSuccess && out) err = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, e->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  (void)hipFree(d);
-  if (err != hipSuccess) return fail(SHC_ERR_HIP, std::string("state transfer: ") + hipGetErrorString(err));
-  return SHC_OK;
-}
-extern "C" int shc_engine_get_state(shc_engine *e, int64_t first, int64_t count, shc_instance_state *states) {
-  SHC_BUSY_GUARD(e);
-  if (!states) return fail(SHC_ERR_INVALID_ARG, "states is NULL");
-  return state_transfer(e, first, count, states, nullptr);
-}
-extern "C" int shc_engine_set_state(shc_engine *e, int64_t first, int64_t count, const shc_instance_state *states) {
-  SHC_BUSY_GUARD(e);
-  if (!states) return fail(SHC_ERR_INVALID_ARG, "states is NULL");
-  return state_transfer(e, first, count, nullptr, states);
-}
-
-// ---- auxiliary state: what only the calls AROUND the control cycle keep (shc_instance_state covers the cycle itself)
-struct AuxHeader {
-  uint32_t magic;   // 'SHCA'
-  uint16_t version; // layout version of this blob
-  uint8_t legs, dof;
-  uint32_t flags;   // 1: manual-leg record live, 2: external target records live, 4: sequence / planner record live,
-                    // 8: the LegPoser tips are state (plan calls under time-dependent posing since the last control cycle)
-  int32_t reset_mode; // PoseController::pose_reset_mode_ (RobotFields::I_RESET_MODE: written by the toggle kernel, read by the cycle)
-};
-constexpr uint32_t kAuxMagic = 0x41434853u;
-constexpr uint16_t kAuxVersion = 2; // 2: + the LegPoser tip positions (POSER_TIP) and flag 8
-static size_t aux_leg_doubles(int NJ) { // per leg: ExtFields record + leg fields [DES_TIP, COUNT) + the LegPoser tip position
-  const int tail = NJ == 3 ? Fields<3>::COUNT - Fields<3>::DES_TIP : (NJ == 4 ? Fields<4>::COUNT - Fields<4>::DES_TIP : Fields<5>::COUNT - Fields<5>::DES_TIP);
-  return size_t(ExtFields::COUNT) + size_t(tail) + 3;
-}
-static size_t aux_bytes(const shc_engine *e) {
-  return sizeof(AuxHeader) + sizeof(ManualRobot) + sizeof(SeqRobotState) + size_t(e->L) * aux_leg_doubles(e->NJ) * 8;
-}
-__global__ void aux_state_kernel(unsigned char *blobs, size_t stride, DevState st, SeqRobotState *seq, int L, int NJ, int des_tip_field, int n_leg_fields, int64_t first,
-                                 int64_t count, int to_engine, uint32_t live_flags, int poser_tip_field) {
-  const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t >= count) return;
-  const int64_t rob = first + t;
-  unsigned char *b = blobs + size_t(t) * stride;
-  AuxHeader *h = reinterpret_cast<AuxHeader *>(b);
-  ManualRobot *m = reinterpret_cast<ManualRobot *>(b + sizeof(AuxHeader));
-  SeqRobotState *q = reinterpret_cast<SeqRobotState *>(b + sizeof(AuxHeader) + sizeof(ManualRobot));
-  double *legs = reinterpret_cast<double *>(b + sizeof(AuxHeader) + sizeof(ManualRobot) + sizeof(SeqRobotState));
-  const int tail = n_leg_fields - des_tip_field;
-  const int per_leg = ExtFields::COUNT + tail + 3;
-  int32_t &reset_mode = st.robi[rob_index(rob, RobotFields::I_RESET_MODE, 64 / L, RobotFields::I_COUNT)];
-  if (!to_engine) {
-    h->magic = kAuxMagic, h->version = kAuxVersion, h->legs = uint8_t(L), h->dof = uint8_t(NJ), h->flags = live_flags, h->reset_mode = reset_mode;
-    if (st.manual) *m = st.manual[rob];
-    else memset(m, 0, sizeof(ManualRobot));
-    if (seq) *q = seq[rob];
-    else memset(q, 0, sizeof(SeqRobotState));
-  } else {
-    reset_mode = h->reset_mode;
-    if (st.manual) {
-      if (h->flags & 1) st.manual[rob] = *m;
-      else memset(&st.manual[rob], 0, sizeof(ManualRobot));
-    }
-    if (seq) {
-      if (h->flags & 4) seq[rob] = *q;
-      else memset(&seq[rob], 0, sizeof(SeqRobotState));
-    }
-  }
-  for (int leg = 0; leg < L; ++leg) {
-    const int64_t slot = slot_of(rob, leg, L);
-    double *row = legs + size_t(leg) * per_leg;
-    for (int f = 0; f < ExtFields::COUNT; ++f) {
-      if (!to_engine) row[f] = st.ext ? st.ext[leg_field_index(f, slot, st.n_slots)] : 0.0;
-      else if (st.ext) st.ext[leg_field_index(f, slot, st.n_slots)] = (h->flags & 2) ? row[f] : 0.0;
-    }
-    for (int f = 0; f < tail; ++f) {
-      double &x = st.legd[leg_field_index(des_tip_field + f, slot, st.n_slots)];
-      if (!to_engine) row[ExtFields::COUNT + f] = x;
-      else x = row[ExtFields::COUNT + f];
-    }
-    for (int f = 0; f < 3; ++f) { // LegPoser::current_tip_pose_.position_ (state while flag 8 holds, an output otherwise)
-      double &x = st.legd[leg_field_index(poser_tip_field + f, slot, st.n_slots)];
-      if (!to_engine) row[ExtFields::COUNT + tail + f] = x;
-      else if (h->flags & 8) x = row[ExtFields::COUNT + tail + f];
-    }
-  }
-}
-extern "C" int64_t shc_engine_aux_state_bytes(const shc_engine *e) { return e ? int64_t(aux_bytes(e)) : 0; }
-static int aux_state(shc_engine *e, int64_t first, int64_t count, void *blobs, int to_engine) {
-  if (!e || !blobs) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
-  if (first < 0 || count < 0 || first + count > e->n) return fail(SHC_ERR_INVALID_ARG, "instance range out of bounds");
-  if (count == 0) return SHC_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  const size_t stride = aux_bytes(e);
-  uint32_t want = 0;
-  if (to_engine) { // the engine grows the records the blobs carry
-    for (int64_t i = 0; i < count; ++i) {
-      const AuxHeader *h = reinterpret_cast<const AuxHeader *>(static_cast<const unsigned char *>(blobs) + size_t(i) * stride);
-      if (h->magic != kAuxMagic || h->version != kAuxVersion || h->legs != e->L || h->dof != e->NJ)
-        return fail(SHC_ERR_INVALID_ARG, "auxiliary state blob of another library version / morphology");
-      want |= h->flags;
-    }
-    int rc = SHC_OK;
-    if ((want & 1) && !e->st.manual) rc = ensure_manual(e, false);
-    if (rc == SHC_OK && (want & 4) && !e->d_seq) rc = ensure_seq(e);
-    double *ext_new = nullptr;
-    if (rc == SHC_OK && (want & 2) && !e->st.ext) { // (allocated and cleared completely before the engine sees it: a failure leaves nothing half-grown)
-      const size_t bytes = size_t(ExtFields::COUNT) * e->n_slots * 8;
-      if (hipMalloc(&ext_new, bytes) != hipSuccess) rc = fail(SHC_ERR_HIP, "hipMalloc(external target records)");
-      else if (hipMemsetAsync(ext_new, 0, bytes, e->stream) != hipSuccess) {
-        (void)hipFree(ext_new);
-        rc = fail(SHC_ERR_HIP, "hipMemset(external target records)");
-      }
-    }
-    if (rc != SHC_OK) return rc;
-    if (ext_new) e->st.ext = ext_new;
-    if (want & 1) e->rt_flags |= RT_MANUAL_LEGS | RT_MANUAL_LIVE;
-    if (want & 2) e->rt_flags |= RT_EXTERNAL;
-    // "The LegPoser tips of the last plan call are still current" is a fact about the whole engine (any control cycle clears it): a restore
-    // of the whole batch sets it from the blobs; a partial restore / migration of a few instances can only keep it when both sides agree -
-    // it never raises it for the instances it did not touch, and the per-blob flag stays authoritative for the restored ones.
-    if (first == 0 && count == e->n) e->plan_poser_tips_current = (want & 8) != 0;
-    else e->plan_poser_tips_current = e->plan_poser_tips_current && (want & 8) != 0;
-  }
-  unsigned char *d = nullptr;
-  HIP_TRY(hipMalloc(&d, stride * size_t(count)));
-  if (to_engine) HIP_TRY_OR(hipMemcpyAsync(d, blobs, stride * size_t(count), hipMemcpyHostToDevice, e->stream), (void)hipFree(d));
-  const uint32_t live = (e->st.manual && (e->rt_flags & RT_MANUAL_LEGS) ? 1u : 0u) | (e->st.ext ? 2u : 0u) | (e->d_seq ? 4u : 0u) |
-                        (e->plan_poser_tips_current ? 8u : 0u);
-  aux_state_kernel<<<dim3((unsigned)((count + 127) / 128)), dim3(128), 0, e->stream>>>(d, stride, e->st, e->d_seq, e->L, e->NJ, LEG_FIELD(e, DES_TIP), e->n_leg_fields,
-                                                                                   first, count, to_engine, live, LEG_FIELD(e, POSER_TIP));
-  HIP_TRY_OR(hipGetLastError(), (void)hipFree(d));
-  if (!to_engine) HIP_TRY_OR(hipMemcpyAsync(blobs, d, stride * size_t(count), hipMemcpyDeviceToHost, e->stream), (void)hipFree(d));
-  HIP_TRY_OR(hipStreamSynchronize(e->stream), (void)hipFree(d));
-  (void)hipFree(d);
-  return SHC_OK;
-}
-extern "C" int shc_engine_get_aux_state(shc_engine *e, int64_t first, int64_t count, void *blobs) {
-  SHC_BUSY_GUARD(e);
-  return aux_state(e, first, count, blobs, 0);
-}
-extern "C" int shc_engine_set_aux_state(shc_engine *e, int64_t first, int64_t count, const void *blobs) {
-  SHC_BUSY_GUARD(e);
-  return aux_state(e, first, count, const_cast<void *>(blobs), 1);
-}
+#include "shc_snapshot.hpp" // shc_engine_get_state / set_state, auxiliary state: kernels and host side
 
 extern "C" int shc_engine_get_body_state(shc_engine *e, double *pose, double *velocity, int32_t *walk_state, int on_device) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   int rc;
   if ((rc = gather_rob(e, pose, 7, RobotFields::CPOSE, on_device)) != SHC_OK) return rc;
   if ((rc = gather_rob(e, velocity, 3, RobotFields::VLIN, on_device)) != SHC_OK) return rc;

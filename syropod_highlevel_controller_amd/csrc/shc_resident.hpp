@@ -202,14 +202,13 @@ extern "C" int shc_engine_resident_begin(shc_engine *e, int ring_depth, int64_t 
   if (max_cycles < 1 || max_cycles > 0x7ffffffe) return fail(SHC_ERR_INVALID_ARG, "max_cycles must be 1..2^31-2");
   if (idle_timeout_ms < 0 || idle_timeout_ms > 600000) return fail(SHC_ERR_INVALID_ARG, "idle_timeout_ms must be 0..600000");
   if (e->starting_up) return fail(SHC_ERR_UNSUPPORTED, "resident mode starts from a running engine (finish the start-up first)");
-  // The resident kernel reads one parameter block for its whole life.  By design it is not given a second block and a switch after cycle 1 (that would
-  // change the kernel of the headline loop for a one-cycle case): the loop that still runs its posing part on the values before a
-  // shc_engine_adjust_parameter is a shc_engine_step.
-  if (e->pose_params_held)
+  // By design the resident kernel is not given a second parameter block and a switch after cycle 1 (that would change the kernel of the headline loop for a
+  // one-cycle case): shc_adjust.hpp, rows "resident_begin"
+  if (adjust_needs_stepped_cycle(e))
     return fail(SHC_ERR_UNSUPPORTED, "resident mode cannot start while an adjusted parameter waits for its cycle (the posing part of the next cycle runs on "
                                      "the old value): call shc_engine_step(e, 1) once first");
   {
-    const int rc_remap = flush_step_remap(e);
+    const int rc_remap = adjust_serve_now(e);
     if (rc_remap != SHC_OK) return rc_remap;
   }
   HIP_TRY(hipSetDevice(e->device));
@@ -222,7 +221,7 @@ extern "C" int shc_engine_resident_begin(shc_engine *e, int ring_depth, int64_t 
   {
     CycleLaunch a{e->st, e->d_consts, &e->cp, e->rt_flags, (e->features & SHC_FEAT_GENERIC_KERNEL) != 0, e->stream, 0, 64, 0, nullptr, &fit, 0};
 #define CALL(L_, NJ_) shc_launch_cycle_##L_##_##NJ_(a)
-    SHC_DISPATCH(e->L, e->NJ, CALL);
+    SHC_DISPATCH(e->L, e->NJ);
 #undef CALL
   }
   if (!fit.supported)
@@ -347,7 +346,7 @@ extern "C" int shc_engine_resident_begin(shc_engine *e, int ring_depth, int64_t 
   CycleLaunch a{e->st, e->d_consts, &e->cp, e->rt_flags, (e->features & SHC_FEAT_GENERIC_KERNEL) != 0, r->loop_stream,
                 two_wave ? unsigned((e->n_waves + 1) / 2 + 1) : unsigned(e->n_waves + 1), two_wave ? 256 : 64, 0, &A, nullptr, 0};
 #define CALL(L_, NJ_) shc_launch_cycle_##L_##_##NJ_(a)
-  SHC_DISPATCH(e->L, e->NJ, CALL);
+  SHC_DISPATCH(e->L, e->NJ);
 #undef CALL
   HIP_TRY(hipGetLastError());
   r->active = true;
@@ -746,8 +745,7 @@ static int step_k_serial(shc_engine *e, int K, const shc_cycle_inputs *in) {
 }
 
 extern "C" int shc_engine_step_k(shc_engine *e, int n_cycles, const shc_cycle_inputs *in) {
-  SHC_BUSY_ONLY(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER(e);
   if (n_cycles < 1 || n_cycles > 4096) return fail(SHC_ERR_INVALID_ARG, "shc_engine_step_k: 1 .. 4096 cycles per launch");
   if (e->starting_up) return fail(SHC_ERR_UNSUPPORTED, "shc_engine_step_k starts from a running engine (finish the start-up first)");
   unsigned mask = 0;
@@ -776,7 +774,7 @@ extern "C" int shc_engine_step_k(shc_engine *e, int n_cycles, const shc_cycle_in
   {
     CycleLaunch a{e->st, e->d_consts, &e->cp, e->rt_flags, (e->features & SHC_FEAT_GENERIC_KERNEL) != 0, e->stream, 0, 64, 0, nullptr, &fit, 0};
 #define CALL(L_, NJ_) shc_launch_cycle_##L_##_##NJ_(a)
-    SHC_DISPATCH(e->L, e->NJ, CALL);
+    SHC_DISPATCH(e->L, e->NJ);
 #undef CALL
   }
   if (size_t(e->NJ) * e->n_slots * 16 * size_t(n_cycles) >= (size_t(1) << 31))
@@ -786,10 +784,8 @@ extern "C" int shc_engine_step_k(shc_engine *e, int n_cycles, const shc_cycle_in
     if (rc != SHC_OK) return rc;
   }
   if (!fit.batch || (e->features & SHC_FEAT_STEP_K_SERIAL)) return step_k_serial(e, n_cycles, in);
-  // An adjustParameter waits for its loop (shc_engine_adjust_parameter): cycle 1 runs as shc_engine_step runs it - on the held parameter block, the phases
-  // mapped inside it - through the serial form (input row 0, ring slot 0); the batch kernel takes the other K - 1 cycles on the new block.
   int k0 = 0;
-  if (e->step_remap_pending || e->pose_params_held) {
+  if (adjust_pending(e)) { // shc_adjust.hpp, row "shc_engine_step_k, cycle 1": through the serial form (input row 0, ring slot 0), the batch kernel takes the other K - 1
     const int rc = step_k_serial(e, 1, in);
     if (rc != SHC_OK) return rc;
     if (n_cycles == 1) return SHC_OK;
@@ -817,13 +813,13 @@ extern "C" int shc_engine_step_k(shc_engine *e, int n_cycles, const shc_cycle_in
   // Workgroups as shc_engine_step picks them; from kSplitWaves waves on the launch goes out as two halves on the two split streams, and - as there -
   // the halves are NOT joined between launches (one half's tail runs under the other half's full rounds, launch after launch): each half is ordered
   // after the engine's stream (where the caller's input rows were written) and after its own previous launch; the engine's stream is ordered after
-  // both at the next call that needs it (join_side: every SHC_BUSY_GUARD entry point, shc_engine_get_step_k_joint_state among them).
+  // both at the next call that needs it (join_side: every SHC_ENTER_JOINED entry point, shc_engine_get_step_k_joint_state among them).
   const int block = e->n_waves < 1536 ? 64 : 128;
   const int64_t wpb = block / 64;
   CycleLaunch a{e->st, e->d_consts, &e->cp, e->rt_flags, (e->features & SHC_FEAT_GENERIC_KERNEL) != 0, e->stream, unsigned((e->n_waves + wpb - 1) / wpb), block, 0, &A, nullptr, 0};
 #define CALL(L_, NJ_) shc_launch_cycle_##L_##_##NJ_(a)
   if (!split) {
-    SHC_DISPATCH(e->L, e->NJ, CALL);
+    SHC_DISPATCH(e->L, e->NJ);
     HIP_TRY(hipGetLastError());
   } else {
     if (!e->half_stream[0]) {
@@ -840,7 +836,7 @@ extern "C" int shc_engine_step_k(shc_engine *e, int n_cycles, const shc_cycle_in
       A.batch_wave0 = h ? half : 0;
       a.stream = e->half_stream[h];
       a.grid = unsigned(((h ? e->n_waves - half : half) + wpb - 1) / wpb);
-      SHC_DISPATCH(e->L, e->NJ, CALL);
+      SHC_DISPATCH(e->L, e->NJ);
       HIP_TRY(hipGetLastError());
     }
     e->main_dirty = false;
@@ -854,8 +850,7 @@ extern "C" int shc_engine_step_k(shc_engine *e, int n_cycles, const shc_cycle_in
 
 // q / qd of cycle k (0 .. K - 1) of the latest shc_engine_step_k, from its output ring (stream-ordered after the launch).
 extern "C" int shc_engine_get_step_k_joint_state(shc_engine *e, int k, double *q, double *qd, int on_device) {
-  SHC_BUSY_GUARD(e);
-  if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
+  SHC_ENTER_JOINED(e);
   if (!e->k_out || k < 0 || k >= e->k_out_cycles) return fail(SHC_ERR_INVALID_ARG, "shc_engine_get_step_k_joint_state: cycle 0 .. K - 1 of the latest shc_engine_step_k");
   HIP_TRY(hipSetDevice(e->device));
   const double *slot = e->k_out + size_t(k) * size_t(e->NJ) * e->n_slots * 2;

@@ -1,5 +1,5 @@
 // shc_snapshot.hpp — shc_engine_get_state / shc_engine_set_state: the engine's SoA planes <-> shc_instance_state records
-// (include/shc_batch.h).  Checkpoint / restore and state injection; not on the per-cycle path.
+// (include/shc_batch.h), and the auxiliary state blobs.  Checkpoint / restore and state injection; not on the per-cycle path.
 //
 // The record speaks the reference's member names (LegStepper / LegPoser / WalkController / PoseController members, cited in
 // the header); the engine's packed words and direction vectors are converted here:
@@ -216,3 +216,189 @@ __global__ void set_state_kernel(const shc_instance_state *in, DevState st, Cycl
 }
 
 } // namespace shc
+
+// ---- host side (included by shc_engine.hip below the engine's helpers)
+extern "C" int64_t shc_sizeof_instance_state(void) { return (int64_t)sizeof(shc_instance_state); }
+
+// Snapshot records travel through a temporary device buffer (checkpoint / injection are not per-cycle operations).
+// Neither direction consumes an adjustParameter that waits for its loop: a record shows the legs' phases in the period they still count in (as the
+// reference's state between the two loops), an injected record's phases are mapped onto the new period inside the accepting loop.
+static int state_transfer(shc_engine *e, int64_t first, int64_t count, shc_instance_state *out, const shc_instance_state *in) {
+    if (first < 0 || count < 0 || first + count > e->n) return fail(SHC_ERR_INVALID_ARG, "instance range out of bounds");
+  if (count == 0) return SHC_OK;
+  if (in) e->rt_flags |= RT_MANUAL_LIVE; // an injected state may carry any manual pose
+  if (in) // touchdown detection is one flag per engine: on as soon as any injected record has it (tip-state messages arrive for a whole robot)
+    for (int64_t i = 0; i < count; ++i)
+      if (in[i].touchdown_detection) e->rt_flags |= RT_TOUCHDOWN;
+  if (in && !(e->rt_flags & RT_EFFORT_LIVE)) { // a non-zero tip-force filter state decays over the following cycles: evaluate it
+    bool any = false;
+    for (int64_t i = 0; i < count && !any; ++i)
+      for (int l = 0; l < e->L; ++l)
+        for (int k = 0; k < 3; ++k) any |= in[i].leg[l].tip_force_calculated[k] != 0.0;
+    if (any) {
+      const int rc = effort_live(e);
+      if (rc != SHC_OK) return rc;
+    }
+  }
+  const int touchdown = (e->rt_flags & RT_TOUCHDOWN) ? 1 : 0;
+  CycleParams cp = e->cp; // (get_state_kernel derives swing / stance progress from the phase: in the step cycle the phase counts in)
+  set_step_cycle(cp, phase_step_cycle(e));
+  unsigned long_legs = 0;
+  for (int l = 0; l < e->L; ++l) long_legs |= e->params.leg_dof[l] > 3 ? 1u << l : 0u;
+  HIP_TRY(hipSetDevice(e->device));
+  shc_instance_state *d = nullptr;
+  const size_t bytes = size_t(count) * sizeof(shc_instance_state);
+  HIP_TRY(hipMalloc(&d, bytes));
+  hipError_t err = hipSuccess;
+  const dim3 grid((unsigned)((count + 63) / 64)), block(64);
+  if (in) err = hipMemcpyAsync(d, in, bytes, hipMemcpyHostToDevice, e->stream);
+  if (err == hipSuccess) {
+    dispatch_nj(e->NJ, [&](auto nj) {
+      constexpr int NJ_ = decltype(nj)::value;
+      if (in) set_state_kernel<NJ_><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, long_legs);
+      else get_state_kernel<NJ_><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, touchdown, long_legs);
+    });
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess && out) err = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, e->stream);
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  (void)hipFree(d);
+  if (err != hipSuccess) return fail(SHC_ERR_HIP, std::string("state transfer: ") + hipGetErrorString(err));
+  return SHC_OK;
+}
+extern "C" int shc_engine_get_state(shc_engine *e, int64_t first, int64_t count, shc_instance_state *states) {
+  SHC_ENTER_JOINED(e);
+  if (!states) return fail(SHC_ERR_INVALID_ARG, "states is NULL");
+  return state_transfer(e, first, count, states, nullptr);
+}
+extern "C" int shc_engine_set_state(shc_engine *e, int64_t first, int64_t count, const shc_instance_state *states) {
+  SHC_ENTER_JOINED(e);
+  if (!states) return fail(SHC_ERR_INVALID_ARG, "states is NULL");
+  return state_transfer(e, first, count, nullptr, states);
+}
+
+// ---- auxiliary state: what only the calls AROUND the control cycle keep (shc_instance_state covers the cycle itself)
+struct AuxHeader {
+  uint32_t magic;   // 'SHCA'
+  uint16_t version; // layout version of this blob
+  uint8_t legs, dof;
+  uint32_t flags;   // 1: manual-leg record live, 2: external target records live, 4: sequence / planner record live,
+                    // 8: the LegPoser tips are state (plan calls under time-dependent posing since the last control cycle)
+  int32_t reset_mode; // PoseController::pose_reset_mode_ (RobotFields::I_RESET_MODE: written by the toggle kernel, read by the cycle)
+};
+constexpr uint32_t kAuxMagic = 0x41434853u;
+constexpr uint16_t kAuxVersion = 2; // 2: + the LegPoser tip positions (POSER_TIP) and flag 8
+static size_t aux_leg_doubles(int NJ) { // per leg: ExtFields record + leg fields [DES_TIP, COUNT) + the LegPoser tip position
+  const int tail = dispatch_nj(NJ, [](auto nj) { return Fields<decltype(nj)::value>::COUNT - Fields<decltype(nj)::value>::DES_TIP; });
+  return size_t(ExtFields::COUNT) + size_t(tail) + 3;
+}
+static size_t aux_bytes(const shc_engine *e) {
+  return sizeof(AuxHeader) + sizeof(ManualRobot) + sizeof(SeqRobotState) + size_t(e->L) * aux_leg_doubles(e->NJ) * 8;
+}
+__global__ void aux_state_kernel(unsigned char *blobs, size_t stride, DevState st, SeqRobotState *seq, int L, int NJ, int des_tip_field, int n_leg_fields, int64_t first,
+                                 int64_t count, int to_engine, uint32_t live_flags, int poser_tip_field) {
+  const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (t >= count) return;
+  const int64_t rob = first + t;
+  unsigned char *b = blobs + size_t(t) * stride;
+  AuxHeader *h = reinterpret_cast<AuxHeader *>(b);
+  ManualRobot *m = reinterpret_cast<ManualRobot *>(b + sizeof(AuxHeader));
+  SeqRobotState *q = reinterpret_cast<SeqRobotState *>(b + sizeof(AuxHeader) + sizeof(ManualRobot));
+  double *legs = reinterpret_cast<double *>(b + sizeof(AuxHeader) + sizeof(ManualRobot) + sizeof(SeqRobotState));
+  const int tail = n_leg_fields - des_tip_field;
+  const int per_leg = ExtFields::COUNT + tail + 3;
+  int32_t &reset_mode = st.robi[rob_index(rob, RobotFields::I_RESET_MODE, 64 / L, RobotFields::I_COUNT)];
+  if (!to_engine) {
+    h->magic = kAuxMagic, h->version = kAuxVersion, h->legs = uint8_t(L), h->dof = uint8_t(NJ), h->flags = live_flags, h->reset_mode = reset_mode;
+    if (st.manual) *m = st.manual[rob];
+    else memset(m, 0, sizeof(ManualRobot));
+    if (seq) *q = seq[rob];
+    else memset(q, 0, sizeof(SeqRobotState));
+  } else {
+    reset_mode = h->reset_mode;
+    if (st.manual) {
+      if (h->flags & 1) st.manual[rob] = *m;
+      else memset(&st.manual[rob], 0, sizeof(ManualRobot));
+    }
+    if (seq) {
+      if (h->flags & 4) seq[rob] = *q;
+      else memset(&seq[rob], 0, sizeof(SeqRobotState));
+    }
+  }
+  for (int leg = 0; leg < L; ++leg) {
+    const int64_t slot = slot_of(rob, leg, L);
+    double *row = legs + size_t(leg) * per_leg;
+    for (int f = 0; f < ExtFields::COUNT; ++f) {
+      if (!to_engine) row[f] = st.ext ? st.ext[leg_field_index(f, slot, st.n_slots)] : 0.0;
+      else if (st.ext) st.ext[leg_field_index(f, slot, st.n_slots)] = (h->flags & 2) ? row[f] : 0.0;
+    }
+    for (int f = 0; f < tail; ++f) {
+      double &x = st.legd[leg_field_index(des_tip_field + f, slot, st.n_slots)];
+      if (!to_engine) row[ExtFields::COUNT + f] = x;
+      else x = row[ExtFields::COUNT + f];
+    }
+    for (int f = 0; f < 3; ++f) { // LegPoser::current_tip_pose_.position_ (state while flag 8 holds, an output otherwise)
+      double &x = st.legd[leg_field_index(poser_tip_field + f, slot, st.n_slots)];
+      if (!to_engine) row[ExtFields::COUNT + tail + f] = x;
+      else if (h->flags & 8) x = row[ExtFields::COUNT + tail + f];
+    }
+  }
+}
+extern "C" int64_t shc_engine_aux_state_bytes(const shc_engine *e) { return e ? int64_t(aux_bytes(e)) : 0; }
+static int aux_state(shc_engine *e, int64_t first, int64_t count, void *blobs, int to_engine) {
+  if (!blobs) return fail(SHC_ERR_INVALID_ARG, "blobs is NULL");
+  if (first < 0 || count < 0 || first + count > e->n) return fail(SHC_ERR_INVALID_ARG, "instance range out of bounds");
+  if (count == 0) return SHC_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t stride = aux_bytes(e);
+  uint32_t want = 0;
+  if (to_engine) { // the engine grows the records the blobs carry
+    for (int64_t i = 0; i < count; ++i) {
+      const AuxHeader *h = reinterpret_cast<const AuxHeader *>(static_cast<const unsigned char *>(blobs) + size_t(i) * stride);
+      if (h->magic != kAuxMagic || h->version != kAuxVersion || h->legs != e->L || h->dof != e->NJ)
+        return fail(SHC_ERR_INVALID_ARG, "auxiliary state blob of another library version / morphology");
+      want |= h->flags;
+    }
+    int rc = SHC_OK;
+    if ((want & 1) && !e->st.manual) rc = ensure_manual(e, false);
+    if (rc == SHC_OK && (want & 4) && !e->d_seq) rc = ensure_seq(e);
+    double *ext_new = nullptr;
+    if (rc == SHC_OK && (want & 2) && !e->st.ext) { // (allocated and cleared completely before the engine sees it: a failure leaves nothing half-grown)
+      const size_t bytes = size_t(ExtFields::COUNT) * e->n_slots * 8;
+      if (hipMalloc(&ext_new, bytes) != hipSuccess) rc = fail(SHC_ERR_HIP, "hipMalloc(external target records)");
+      else if (hipMemsetAsync(ext_new, 0, bytes, e->stream) != hipSuccess) {
+        (void)hipFree(ext_new);
+        rc = fail(SHC_ERR_HIP, "hipMemset(external target records)");
+      }
+    }
+    if (rc != SHC_OK) return rc;
+    if (ext_new) e->st.ext = ext_new;
+    if (want & 1) e->rt_flags |= RT_MANUAL_LEGS | RT_MANUAL_LIVE;
+    if (want & 2) e->rt_flags |= RT_EXTERNAL;
+    // "The LegPoser tips of the last plan call are still current" is a fact about the whole engine (any control cycle clears it): a restore
+    // of the whole batch sets it from the blobs; a partial restore / migration of a few instances can only keep it when both sides agree -
+    // it never raises it for the instances it did not touch, and the per-blob flag stays authoritative for the restored ones.
+    if (first == 0 && count == e->n) e->plan_poser_tips_current = (want & 8) != 0;
+    else e->plan_poser_tips_current = e->plan_poser_tips_current && (want & 8) != 0;
+  }
+  unsigned char *d = nullptr;
+  HIP_TRY(hipMalloc(&d, stride * size_t(count)));
+  if (to_engine) HIP_TRY_OR(hipMemcpyAsync(d, blobs, stride * size_t(count), hipMemcpyHostToDevice, e->stream), (void)hipFree(d));
+  const uint32_t live = (e->st.manual && (e->rt_flags & RT_MANUAL_LEGS) ? 1u : 0u) | (e->st.ext ? 2u : 0u) | (e->d_seq ? 4u : 0u) |
+                        (e->plan_poser_tips_current ? 8u : 0u);
+  aux_state_kernel<<<dim3((unsigned)((count + 127) / 128)), dim3(128), 0, e->stream>>>(d, stride, e->st, e->d_seq, e->L, e->NJ, LEG_FIELD(e, DES_TIP), e->n_leg_fields,
+                                                                                   first, count, to_engine, live, LEG_FIELD(e, POSER_TIP));
+  HIP_TRY_OR(hipGetLastError(), (void)hipFree(d));
+  if (!to_engine) HIP_TRY_OR(hipMemcpyAsync(blobs, d, stride * size_t(count), hipMemcpyDeviceToHost, e->stream), (void)hipFree(d));
+  HIP_TRY_OR(hipStreamSynchronize(e->stream), (void)hipFree(d));
+  (void)hipFree(d);
+  return SHC_OK;
+}
+extern "C" int shc_engine_get_aux_state(shc_engine *e, int64_t first, int64_t count, void *blobs) {
+  SHC_ENTER_JOINED(e);
+  return aux_state(e, first, count, blobs, 0);
+}
+extern "C" int shc_engine_set_aux_state(shc_engine *e, int64_t first, int64_t count, const void *blobs) {
+  SHC_ENTER_JOINED(e);
+  return aux_state(e, first, count, const_cast<void *>(blobs), 1);
+}
