@@ -523,6 +523,13 @@ typedef struct shc_leg_state_msg {
 } shc_leg_state_msg;
 /* Fills legs[0 .. leg_count) for `instance`.  Synchronises the engine's stream. */
 int shc_engine_read_leg_state_msg(shc_engine *e, int64_t instance, shc_leg_state_msg *legs);
+/* publishLegState for instances [first, first + count) in one device pass: msgs[(i - first) * legs + l], the record layout of
+ * shc_leg_state_msg - 64 doubles, no padding: a dense [count][legs][64] double array - every field as documented above; the joint
+ * slots a robot does not use are zero.  on_device = 1: msgs is a device buffer (16-byte aligned), the call is ordered on the engine's
+ * stream and does not synchronise the host; on_device = 0: msgs is host memory, the call synchronises the stream.  Refreshes the
+ * derived model / poser tips as shc_engine_get_leg_state does and changes no other state.  count = 0 is a no-op.
+ * SHC_ERR_INVALID_ARG for a NULL msgs or a range outside [0, n); SHC_ERR_BUSY in resident mode. */
+int shc_engine_get_leg_state_msgs(shc_engine *e, int64_t first, int64_t count, shc_leg_state_msg *msgs, int on_device);
 
 /*
  * The other ROS messages of the path, batched: payloads in, payloads out; the node adds names,
@@ -847,6 +854,9 @@ int shc_fleet_step(shc_fleet *f, int n_cycles);
 int shc_fleet_synchronize(shc_fleet *f);
 int shc_fleet_get_joint_state(shc_fleet *f, double *q, double *qd /* [n][max_legs][max_dof], either may be NULL */);
 int shc_fleet_get_walk_state(shc_fleet *f, int32_t *walk_state /* [n] */);
+/* publishLegState of every robot of the fleet, in the caller's instance order: msgs[i * max_legs + l] (host memory); the records of
+ * legs a robot does not have are all zero.  Synchronises every part's stream. */
+int shc_fleet_get_leg_state_msgs(shc_fleet *f, shc_leg_state_msg *msgs);
 /* The exchange step of a sharded batch: every device ends up with the desired joint positions of ALL instances
  * ([n][max_legs][max_dof], caller's order, NaN padded) in its own HBM, copied device to device (hipMemcpyPeerAsync: xGMI on an
  * MI355X node).  device_buffers[d] (may be NULL) receives device_ids[d]'s buffer; the buffers belong to the fleet. */

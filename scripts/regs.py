@@ -1,11 +1,20 @@
 """Development aid: per-specialisation register / scratch / LDS use from hipcc's -Rpass-analysis=kernel-resource-usage
-output (scripts/build_dev.sh writes it to /tmp/shc_res.txt)."""
+output (scripts/build_dev.sh writes it to /tmp/shc_res.txt).  Usage: regs.py [report [kernel name]]: the cycle kernels by default, or the
+kernels whose name contains `kernel name` (e.g. leg_state_msgs_kernel: legs, dof, VGPR, SGPR, LDS, scratch)."""
 import re
 import sys
 
 t = open(sys.argv[1] if len(sys.argv) > 1 else "/tmp/shc_res.txt").read()
 for b in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
     name = b.split()[0]
+    if len(sys.argv) > 2:
+        if sys.argv[2] not in name:
+            continue
+        m = re.search(r"ILi(\d)ELi(\d)E", name)
+        g = lambda k: re.search(k + r": (\d+)", b).group(1)
+        print("legs %s dof %s" % (m.groups() if m else ("?", "?")), name.split("I")[0][4:], "VGPR", g("VGPRs"), "SGPR", g("TotalSGPRs"), "LDS", g(r"LDS Size \[bytes/block\]"),
+              "scratch", g(r"ScratchSize \[bytes/lane\]"), "waves/SIMD", g(r"Occupancy \[waves/SIMD\]"))
+        continue
     if "shc_cycle_kernel" not in name:
         continue
     m = re.search(r"ILi(\d)ELi(\d)ELj(\d+)E", name)

@@ -1527,59 +1527,7 @@ static int derive_tips(shc_engine *e) {
   return SHC_OK;
 }
 
-// PoseController::auto_pose_ of the cycle whose master phase and (post-update) poser latches are given: the sum the cycle
-// kernel forms (AutoPoser::updatePose, pose_controller.cpp:1338-1439), re-derived on the host for LegState.auto_pose.
-static Pose host_auto_pose(const shc_params &p, const shc_tables &t, int master_phase, int flags, Quat imu) {
-  Pose auto_pose = pose_identity();
-  const int len = t.pose_phase_length, nrm = t.pose_normaliser;
-  for (int i = 0; i < p.n_auto_posers && i < kMaxAutoPosers; ++i) {
-    const bool allow = ((flags >> (4 * i)) & 8) != 0;
-    int phase = master_phase, sp = p.pose_phase_starts[i] * nrm, ep = p.pose_phase_ends[i] * nrm;
-    if (sp > ep) {
-      ep += len;
-      if (phase < sp) phase += len;
-    }
-    if (!(phase >= sp && phase < ep && allow)) continue;
-    const int iteration = phase - sp + 1, num = ep - sp;
-    const bool first_half = iteration <= num / 2;
-    const double delta_t = 1.0 / (num / 2.0);
-    const int offset = int(first_half ? 0 : num / 2.0);
-    const double tt = (iteration - offset) * delta_t, u = 1.0 - tt;
-    const double wgt = first_half ? (4.0 * tt * tt * tt * u + tt * tt * tt * tt) : (u * u * u * u + 4.0 * tt * u * u * u);
-    V3 pos;
-    if (p.gravity_amplitudes[i] != 0.0) { // Model::estimateGravity (model.cpp:156-165)
-      const V3 e = quat_to_euler(imu, false);
-      V3 gv{0, 0, kGravity};
-      gv = rotate(angle_axis_y(-e.y), gv);
-      gv = rotate(angle_axis_x(-e.x), gv);
-      pos = normalized(gv) * (p.gravity_amplitudes[i] * wgt);
-    } else {
-      pos = V3{p.x_amplitudes[i] * wgt, p.y_amplitudes[i] * wgt, p.z_amplitudes[i] * wgt};
-    }
-    const V3 rot{p.roll_amplitudes[i] * wgt, p.pitch_amplitudes[i] * wgt, p.yaw_amplitudes[i] * wgt};
-    auto_pose = add_pose(auto_pose, Pose{pos, euler_to_quat(rot, false)});
-  }
-  return auto_pose;
-}
-// LegPoser::updateAutoPose's negation (pose_controller.cpp:1740-1776) for a leg whose negate flag is set
-static Pose host_leg_auto_pose(const shc_params &p, const shc_tables &t, int leg, int master_phase, bool negate, const Pose &auto_pose) {
-  if (!negate) return auto_pose;
-  const int len = t.pose_phase_length, nrm = t.pose_normaliser;
-  int sp = p.pose_negation_phase_starts[leg] * nrm, ep = p.pose_negation_phase_ends[leg] * nrm, np = master_phase;
-  if (sp == 0) sp = len;
-  if (ep == 0) ep = len;
-  if (sp > ep) {
-    ep += len;
-    if (np < sp) np += len;
-  }
-  const int iteration = np - sp + 1, num = ep - sp;
-  const bool first_half = iteration <= num / 2;
-  double ci = 1.0;
-  const double ratio = p.negation_transition_ratio[leg];
-  if (ratio > 0.0) ci = first_half ? fmin(1.0, iteration / (num * ratio)) : fmin(1.0, (num - iteration) / (num * ratio));
-  ci = smooth_step(ci);
-  return remove_pose(auto_pose, interpolate_pose(pose_identity(), ci, auto_pose));
-}
+#include "shc_leg_msgs.hpp" // the derived LegState fields (one host + device implementation) and shc_engine_get_leg_state_msgs
 
 template <int NJ>
 static Pose host_fk_tip_pose(const shc_params &p, int leg, const double *q) {
@@ -1604,16 +1552,13 @@ extern "C" int shc_engine_read_leg_state_msg(shc_engine *e, int64_t instance, sh
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(h.data(), e->d_stage, h.size() * 8, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
-  const shc_step_cycle &step = e->tables.step;
   const double *rb = &h[size_t(L) * per_leg];
   const double vx = rb[0], vy = rb[1], vw = rb[2];
-  const double swing_time = (double(step.swing_period) / step.period) / step.frequency;   // state_controller.cpp:863
-  const double stance_time = (double(step.stance_period) / step.period) / step.frequency; // :864
+  const LegMsgArgs args = leg_msg_args(e->params, e->tables); // (shc_leg_msgs.hpp: the arithmetic the batched kernel runs)
   // PoseController::auto_pose_ of the last cycle (auto posing runs only where IMU posing does not, pose_controller.cpp:836-846)
-  const bool auto_live = e->params.auto_posing && !e->params.imu_posing && e->tables.pose_phase_length > 0;
-  int master_phase = int(rb[5]);
-  if (auto_live && e->params.pose_frequency != -1.0) master_phase = mod_i(master_phase - 1, e->tables.pose_phase_length); // the counter has advanced
-  const Pose auto_pose = auto_live ? host_auto_pose(e->params, e->tables, master_phase, int(rb[4]), Quat{rb[6], rb[7], rb[8], rb[9]}) : pose_identity();
+  const bool auto_live = args.auto_live != 0;
+  const int master_phase = leg_msg_master_phase(args, int(rb[5])); // the counter has advanced
+  const Pose auto_pose = auto_live ? leg_msg_auto_pose(args, master_phase, int(rb[4]), Quat{rb[6], rb[7], rb[8], rb[9]}) : pose_identity();
   for (int l = 0; l < L; ++l) {
     const double *o = &h[size_t(l) * per_leg];
     shc_leg_state_msg &m = legs[l];
@@ -1638,29 +1583,13 @@ extern "C" int shc_engine_read_leg_state_msg(shc_engine *e, int64_t instance, sh
       m.actual_tip_pose[3] = tp.r.w, m.actual_tip_pose[4] = tp.r.x, m.actual_tip_pose[5] = tp.r.y, m.actual_tip_pose[6] = tp.r.z;
     }
     m.virtual_stiffness = o[18 + 2 * NJ];
-    // LegStepper::swing_progress_ / stance_progress_ as iteratePhase left them (walk_controller.cpp:871-897)
+    // LegStepper::swing_progress_ / stance_progress_ as iteratePhase left them, time_to_swing_end :866-873, calculateOdometry :875
     const int word = int(o[19 + 2 * NJ]);
-    const int pm = (word >> LW_PM_SHIFT) & 3, phase = (word >> LW_PHASE_SHIFT) & LW_PHASE_MASK;
-    m.swing_progress = m.stance_progress = -1.0; // walk_controller.h:498-499
-    if (pm == PM_SWING) {
-      m.swing_progress = clampd(double(phase - step.swing_start + 1) / double(step.swing_end - step.swing_start), 0.0, 1.0);
-    } else if (pm == PM_STANCE) {
-      m.stance_progress = clampd(double(mod_i(phase + (step.period - step.stance_start), step.period) + 1) /
-                                     double(mod_i(step.stance_end - step.stance_start, step.period)),
-                                 0.0, 1.0);
-    } else if (pm == PM_STOP) {
-      m.stance_progress = 0.0;
-    }
-    m.time_to_swing_end = m.stance_progress >= 0.0 ? stance_time * (1.0 - m.stance_progress) + swing_time
-                                                   : swing_time * (1.0 - m.swing_progress); // :866-873
-    const double t = m.time_to_swing_end; // WalkController::calculateOdometry (walk_controller.cpp:783-791)
-    m.pose_delta[0] = vx * t;
-    m.pose_delta[1] = vy * t;
-    m.pose_delta[2] = 0.0 * t;
-    m.pose_delta[3] = cos(0.5 * (vw * t));
-    m.pose_delta[6] = sin(0.5 * (vw * t));
+    const LegMsgProgress pr = leg_msg_progress(args, word, vx, vy, vw);
+    m.stance_progress = pr.stance_progress, m.swing_progress = pr.swing_progress, m.time_to_swing_end = pr.time_to_swing_end;
+    for (int k = 0; k < 7; ++k) m.pose_delta[k] = pr.pose_delta[k];
     // (model_tip_velocity stays 0: see the header.)  LegPoser::auto_pose_ :877-880
-    const Pose la = auto_live ? host_leg_auto_pose(e->params, e->tables, l, master_phase, (word & LW_NEG) != 0, auto_pose) : pose_identity();
+    const Pose la = auto_live ? leg_msg_leg_auto_pose(args, l, master_phase, (word & LW_NEG) != 0, auto_pose) : pose_identity();
     m.auto_pose[0] = la.p.x, m.auto_pose[1] = la.p.y, m.auto_pose[2] = la.p.z;
     m.auto_pose[3] = la.r.w, m.auto_pose[4] = la.r.x, m.auto_pose[5] = la.r.y, m.auto_pose[6] = la.r.z;
   }

@@ -270,6 +270,21 @@ extern "C" int shc_fleet_get_joint_state(shc_fleet *f, double *q, double *qd) {
   }
   return SHC_OK;
 }
+// publishLegState of every robot: msgs[i * max_legs + l] in the caller's instance order; the records of legs a robot does not have are all
+// zero.  Every part is read on its own device and stream (shc_engine_get_leg_state_msgs), then placed at its instances' ids.
+extern "C" int shc_fleet_get_leg_state_msgs(shc_fleet *f, shc_leg_state_msg *msgs) {
+  if (!f || !msgs) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
+  memset(msgs, 0, size_t(f->n) * f->max_legs * sizeof(shc_leg_state_msg));
+  std::vector<shc_leg_state_msg> rows;
+  for (auto &p : f->parts) {
+    const int L = f->params[p.morph].leg_count;
+    rows.resize(p.ids.size() * size_t(L));
+    const int rc = shc_engine_get_leg_state_msgs(p.engine, 0, int64_t(p.ids.size()), rows.data(), 0);
+    if (rc != SHC_OK) return rc;
+    for (size_t k = 0; k < p.ids.size(); ++k) std::copy(rows.begin() + k * L, rows.begin() + (k + 1) * L, msgs + size_t(p.ids[k]) * f->max_legs);
+  }
+  return SHC_OK;
+}
 extern "C" int shc_fleet_get_walk_state(shc_fleet *f, int32_t *walk_state) {
   if (!f || !walk_state) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
   for (auto &p : f->parts) {

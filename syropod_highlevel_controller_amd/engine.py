@@ -50,8 +50,25 @@ EXPORTED_SYMBOLS = [
     "shc_engine_resident_get_joint_state", "shc_engine_resident_get_joint_state_async", "shc_engine_resident_status", "shc_engine_resident_end", "shc_engine_join",
     "shc_engine_aux_state_bytes", "shc_engine_get_aux_state", "shc_engine_set_aux_state",
     "shc_engine_step_k", "shc_engine_get_step_k_joint_state", "shc_engine_adjust_parameter",
+    "shc_engine_get_leg_state_msgs", "shc_fleet_get_leg_state_msgs",
     "shc_peer_alloc", "shc_peer_open", "shc_peer_close", "shc_peer_scatter",
 ]
+
+
+def _struct_dtype(struct) -> np.dtype:
+    """The numpy structured dtype of a ctypes structure of doubles / double arrays: names, offsets and item size follow the structure's own
+    field list, so a field added to the C struct's mirror is a field of the arrays too."""
+    names, formats, offsets = [], [], []
+    for name, typ in struct._fields_:
+        k = C.sizeof(typ) // C.sizeof(C.c_double)
+        assert typ is C.c_double or (issubclass(typ, C.Array) and typ._type_ is C.c_double), name
+        names.append(name)
+        formats.append(np.float64 if typ is C.c_double else (np.float64, (k,)))
+        offsets.append(getattr(struct, name).offset)
+    return np.dtype({"names": names, "formats": formats, "offsets": offsets, "itemsize": C.sizeof(struct)})
+
+
+LEG_STATE_MSG_DTYPE = _struct_dtype(LegStateMsg)  # what BatchEngine.leg_state_msgs / MixedFleet.leg_state_msgs return
 
 
 class CycleInputs(C.Structure):
@@ -320,6 +337,8 @@ def lib():
         L.shc_engine_get_body_state.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int]
         L.shc_engine_get_odometry.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.shc_engine_read_leg_state_msg.argtypes = [C.c_void_p, C.c_int64, C.POINTER(LegStateMsg)]
+        L.shc_engine_get_leg_state_msgs.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int]
+        L.shc_fleet_get_leg_state_msgs.argtypes = [C.c_void_p, C.c_void_p]
         L.shc_stream_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
         L.shc_stream_destroy.argtypes = [C.c_int, C.c_void_p]
         L.shc_engine_change_gait.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_int64)]
@@ -693,6 +712,18 @@ class BatchEngine:
         arr = (LegStateMsg * self.legs)()
         _check(self.L.shc_engine_read_leg_state_msg(self.h, int(instance), arr), "read_leg_state_msg")
         return list(arr)
+
+    def leg_state_msgs(self, first: int = 0, count: Optional[int] = None, out: Optional[int] = None):
+        """publishLegState for instances [first, first + count) in one device pass (shc_engine_get_leg_state_msgs): a structured array of
+        shape (count, legs) with the fields of LegStateMsg (LEG_STATE_MSG_DTYPE).  out = a device pointer (integer, 16-byte aligned, room for
+        count * legs records of 512 B): the records are written there, ordered on the engine's stream without a host wait; returns None."""
+        count = self.n - first if count is None else count
+        if out is not None:
+            _check(self.L.shc_engine_get_leg_state_msgs(self.h, int(first), int(count), C.c_void_p(int(out)), 1), "get_leg_state_msgs")
+            return None
+        msgs = np.zeros((max(int(count), 0), self.legs), dtype=LEG_STATE_MSG_DTYPE)
+        _check(self.L.shc_engine_get_leg_state_msgs(self.h, int(first), int(count), msgs.ctypes.data_as(C.c_void_p), 0), "get_leg_state_msgs")
+        return msgs
 
     def get_state(self, first: int = 0, count: Optional[int] = None):
         """Full controller state of instances [first, first + count) as a ctypes array of InstanceState."""

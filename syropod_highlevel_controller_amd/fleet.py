@@ -88,6 +88,13 @@ class MixedFleet:
         _engine._check(self.L.shc_fleet_get_walk_state(self.h, self._p(ws)), "shc_fleet_get_walk_state")
         return ws
 
+    def leg_state_msgs(self):
+        """publishLegState of every robot in the caller's instance order: a structured array of shape (n, max_legs) with the fields of
+        LegStateMsg; the records of legs a robot does not have are all zero."""
+        msgs = np.zeros((self.n, self.max_legs), dtype=_engine.LEG_STATE_MSG_DTYPE)
+        _engine._check(self.L.shc_fleet_get_leg_state_msgs(self.h, self._p(msgs)), "shc_fleet_get_leg_state_msgs")
+        return msgs
+
     def all_gather_joints(self):
         """Device pointers (one per device slot) of the gathered [n][max_legs][max_dof] joint buffers."""
         bufs = (C.c_void_p * self.n_devices)()
