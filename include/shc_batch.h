@@ -532,6 +532,41 @@ int shc_engine_read_leg_state_msg(shc_engine *e, int64_t instance, shc_leg_state
 int shc_engine_get_leg_state_msgs(shc_engine *e, int64_t first, int64_t count, shc_leg_state_msg *msgs, int on_device);
 
 /*
+ * StateController::publishFrameTransforms (state_controller.cpp:963-1047), batched: the numeric payload of every TransformStamped the node
+ * broadcasts per loop - odom_ideal -> base_link, base_link -> walk_plane, base_link -> every joint and every tip of every leg.  The node adds
+ * stamps, frame ids and child names (joint->id_name_, tip->id_name_).  tf LOOKUPS (generateExternalTargetTransforms :703-773) stay with the
+ * caller (shc_engine_set_external_transform).  Every pose is (x, y, z, qw, qx, qy, qz); the records are doubles without padding.
+ */
+#define SHC_FRAME_JOINTS 5 /* joint frames per leg record: the longest leg the engine has kernels for (leg_dof 3..5) */
+enum {
+  SHC_FRAME_BASE_LINK = 0,  /* the leg frames as publishFrameTransforms sends them: children of base_link */
+  SHC_FRAME_ODOM_IDEAL = 1  /* every joint / tip frame composed with odom_to_base_link (odom_to_base_link.addPose(child), pose.h:167-173):
+                             * world poses for consumers that do not run a tf tree */
+};
+typedef struct shc_leg_frames { /* one per leg: 42 doubles, 336 bytes */
+  double joint[SHC_FRAME_JOINTS][7]; /* joint j: position = Joint::getPoseRobotFrame().position_ (:1015-1022; model.h:594-608: the chain's DH
+                                      * product up to the joint, pose.h:135-146); rotation = joint_robot_frame.rotation_ *
+                                      * AngleAxisd(desired_position_, UnitZ()) (:1023-1028).  The frames of the DESIRED joint positions (the
+                                      * chain applyFK() left behind).  Slots past the leg's own joint count are all zero */
+  double tip[7];                     /* Tip::getPoseRobotFrame() (:1032-1045; model.h:684-688) of the leg's own chain */
+} shc_leg_frames;
+typedef struct shc_body_frames { /* one per robot: 20 doubles, 160 bytes */
+  double odom_to_base_link[7];       /* getOdometryIdeal().addPose(getCurrentPose()) (:965-967, :984-990; pose.h:167-173) */
+  double base_link_to_walk_plane[7]; /* ~getCurrentPose() (:995-1005; pose.h:112-115) */
+  double pose_euler[3];              /* quaternionToEulerAngles(current_pose.rotation_): the angular part of publishPose (:911-923;
+                                      * standard_includes.h:248-291) */
+  double desired_velocity[3];        /* (vx, vy, omega) of publishVelocity (:897-907) */
+} shc_body_frames;
+/* The frames of instances [first, first + count) in one device pass: legs[(i - first) * leg_count + l], body[i - first]; either may be NULL
+ * (not both).  frame = SHC_FRAME_BASE_LINK or SHC_FRAME_ODOM_IDEAL selects the parent of the leg frames; the body records are the same for
+ * both.  on_device = 1: legs / body are device buffers (16-byte aligned), the call is ordered on the engine's stream and does not synchronise
+ * the host; on_device = 0: host memory, the call synchronises the stream.  Changes no engine state.  count = 0 is a no-op.
+ * SHC_ERR_INVALID_ARG for a range outside [0, n), both pointers NULL or an unknown frame; SHC_ERR_UNSUPPORTED without SHC_FEAT_ODOMETRY when
+ * body records or SHC_FRAME_ODOM_IDEAL are asked for; SHC_ERR_BUSY in resident mode. */
+int shc_engine_get_frame_transforms(shc_engine *e, int64_t first, int64_t count, int frame, shc_leg_frames *legs /* [count][legs] */,
+                                    shc_body_frames *body /* [count] */, int on_device);
+
+/*
  * The other ROS messages of the path, batched: payloads in, payloads out; the node adds names,
  * stamps and frame ids.
  */
@@ -857,6 +892,9 @@ int shc_fleet_get_walk_state(shc_fleet *f, int32_t *walk_state /* [n] */);
 /* publishLegState of every robot of the fleet, in the caller's instance order: msgs[i * max_legs + l] (host memory); the records of
  * legs a robot does not have are all zero.  Synchronises every part's stream. */
 int shc_fleet_get_leg_state_msgs(shc_fleet *f, shc_leg_state_msg *msgs);
+/* publishFrameTransforms of every robot of the fleet, in the caller's instance order (host memory): legs[i * max_legs + l], the records of
+ * legs a robot does not have all zero, and body[i]; either may be NULL (not both).  Synchronises every part's stream. */
+int shc_fleet_get_frame_transforms(shc_fleet *f, int frame, shc_leg_frames *legs /* [n][max_legs] */, shc_body_frames *body /* [n] */);
 /* The exchange step of a sharded batch: every device ends up with the desired joint positions of ALL instances
  * ([n][max_legs][max_dof], caller's order, NaN padded) in its own HBM, copied device to device (hipMemcpyPeerAsync: xGMI on an
  * MI355X node).  device_buffers[d] (may be NULL) receives device_ids[d]'s buffer; the buffers belong to the fleet. */

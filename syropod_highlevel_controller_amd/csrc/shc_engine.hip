@@ -1528,6 +1528,7 @@ static int derive_tips(shc_engine *e) {
 }
 
 #include "shc_leg_msgs.hpp" // the derived LegState fields (one host + device implementation) and shc_engine_get_leg_state_msgs
+#include "shc_frames.hpp"   // publishFrameTransforms: every joint / tip frame and the body frames, shc_engine_get_frame_transforms
 
 template <int NJ>
 static Pose host_fk_tip_pose(const shc_params &p, int leg, const double *q) {

@@ -285,6 +285,26 @@ extern "C" int shc_fleet_get_leg_state_msgs(shc_fleet *f, shc_leg_state_msg *msg
   }
   return SHC_OK;
 }
+// publishFrameTransforms of every robot: legs[i * max_legs + l] and body[i] in the caller's instance order (either may be NULL); the leg
+// records of legs a robot does not have are all zero.  Every part is read on its own device and stream (shc_engine_get_frame_transforms).
+extern "C" int shc_fleet_get_frame_transforms(shc_fleet *f, int frame, shc_leg_frames *legs, shc_body_frames *body) {
+  if (!f || (!legs && !body)) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
+  if (legs) memset(legs, 0, size_t(f->n) * f->max_legs * sizeof(shc_leg_frames));
+  std::vector<shc_leg_frames> rows;
+  std::vector<shc_body_frames> brows;
+  for (auto &p : f->parts) {
+    const int L = f->params[p.morph].leg_count;
+    if (legs) rows.resize(p.ids.size() * size_t(L));
+    if (body) brows.resize(p.ids.size());
+    const int rc = shc_engine_get_frame_transforms(p.engine, 0, int64_t(p.ids.size()), frame, legs ? rows.data() : nullptr, body ? brows.data() : nullptr, 0);
+    if (rc != SHC_OK) return rc;
+    for (size_t k = 0; k < p.ids.size(); ++k) {
+      if (legs) std::copy(rows.begin() + k * L, rows.begin() + (k + 1) * L, legs + size_t(p.ids[k]) * f->max_legs);
+      if (body) body[p.ids[k]] = brows[k];
+    }
+  }
+  return SHC_OK;
+}
 extern "C" int shc_fleet_get_walk_state(shc_fleet *f, int32_t *walk_state) {
   if (!f || !walk_state) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
   for (auto &p : f->parts) {

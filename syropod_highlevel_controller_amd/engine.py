@@ -15,7 +15,7 @@ from typing import Optional
 
 import numpy as np
 
-from .params import FEAT_DEFAULT, InstanceState, LegStateMsg, Params, Tables
+from .params import FEAT_DEFAULT, FRAME_IDS, BodyFrames, InstanceState, LegFrames, LegStateMsg, Params, Tables
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("SHC_LIB") or os.path.join(_HERE, "libshc_batch.so")
@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "shc_engine_aux_state_bytes", "shc_engine_get_aux_state", "shc_engine_set_aux_state",
     "shc_engine_step_k", "shc_engine_get_step_k_joint_state", "shc_engine_adjust_parameter",
     "shc_engine_get_leg_state_msgs", "shc_fleet_get_leg_state_msgs",
+    "shc_engine_get_frame_transforms", "shc_fleet_get_frame_transforms",
     "shc_peer_alloc", "shc_peer_open", "shc_peer_close", "shc_peer_scatter",
 ]
 
@@ -60,15 +61,19 @@ def _struct_dtype(struct) -> np.dtype:
     field list, so a field added to the C struct's mirror is a field of the arrays too."""
     names, formats, offsets = [], [], []
     for name, typ in struct._fields_:
-        k = C.sizeof(typ) // C.sizeof(C.c_double)
-        assert typ is C.c_double or (issubclass(typ, C.Array) and typ._type_ is C.c_double), name
+        shape, base = [], typ
+        while base is not C.c_double:   # double, double[k] or double[j][k]
+            assert issubclass(base, C.Array), name
+            shape.append(base._length_)
+            base = base._type_
         names.append(name)
-        formats.append(np.float64 if typ is C.c_double else (np.float64, (k,)))
+        formats.append((np.float64, tuple(shape)) if shape else np.float64)
         offsets.append(getattr(struct, name).offset)
     return np.dtype({"names": names, "formats": formats, "offsets": offsets, "itemsize": C.sizeof(struct)})
 
 
 LEG_STATE_MSG_DTYPE = _struct_dtype(LegStateMsg)  # what BatchEngine.leg_state_msgs / MixedFleet.leg_state_msgs return
+LEG_FRAMES_DTYPE, BODY_FRAMES_DTYPE = _struct_dtype(LegFrames), _struct_dtype(BodyFrames)  # ... and what frame_transforms returns
 
 
 class CycleInputs(C.Structure):
@@ -339,6 +344,8 @@ def lib():
         L.shc_engine_read_leg_state_msg.argtypes = [C.c_void_p, C.c_int64, C.POINTER(LegStateMsg)]
         L.shc_engine_get_leg_state_msgs.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int]
         L.shc_fleet_get_leg_state_msgs.argtypes = [C.c_void_p, C.c_void_p]
+        L.shc_engine_get_frame_transforms.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.shc_fleet_get_frame_transforms.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.shc_stream_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
         L.shc_stream_destroy.argtypes = [C.c_int, C.c_void_p]
         L.shc_engine_change_gait.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_int64)]
@@ -724,6 +731,27 @@ class BatchEngine:
         msgs = np.zeros((max(int(count), 0), self.legs), dtype=LEG_STATE_MSG_DTYPE)
         _check(self.L.shc_engine_get_leg_state_msgs(self.h, int(first), int(count), msgs.ctypes.data_as(C.c_void_p), 0), "get_leg_state_msgs")
         return msgs
+
+    def frame_transforms(self, first: int = 0, count: Optional[int] = None, frame="base_link", legs: bool = True, body: bool = True,
+                         out_legs: Optional[int] = None, out_body: Optional[int] = None):
+        """publishFrameTransforms for instances [first, first + count) in one device pass (shc_engine_get_frame_transforms): (legs, body),
+        structured arrays of shape (count, legs) with the fields of LegFrames (LEG_FRAMES_DTYPE: joint (5, 7), tip (7,)) and of shape (count,)
+        with the fields of BodyFrames (BODY_FRAMES_DTYPE); the one not asked for (legs / body = False) is None.  frame: "base_link" (what the
+        node broadcasts) or "odom_ideal" (every joint / tip frame composed with odom_to_base_link), or the SHC_FRAME_* integer.  out_legs /
+        out_body = device pointers (integers, 16-byte aligned, room for count * legs records of 336 B / count records of 160 B): the records
+        are written there, ordered on the engine's stream without a host wait; returns None."""
+        count = self.n - first if count is None else count
+        frame = FRAME_IDS[frame] if isinstance(frame, str) else int(frame)
+        fn = self.L.shc_engine_get_frame_transforms
+        if out_legs is not None or out_body is not None:
+            ptr = lambda p: None if p is None else C.c_void_p(int(p))
+            _check(fn(self.h, int(first), int(count), frame, ptr(out_legs), ptr(out_body), 1), "get_frame_transforms")
+            return None
+        lf = np.zeros((max(int(count), 0), self.legs), dtype=LEG_FRAMES_DTYPE) if legs else None
+        bf = np.zeros(max(int(count), 0), dtype=BODY_FRAMES_DTYPE) if body else None
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        _check(fn(self.h, int(first), int(count), frame, ptr(lf), ptr(bf), 0), "get_frame_transforms")
+        return lf, bf
 
     def get_state(self, first: int = 0, count: Optional[int] = None):
         """Full controller state of instances [first, first + count) as a ctypes array of InstanceState."""

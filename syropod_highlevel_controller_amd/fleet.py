@@ -95,6 +95,17 @@ class MixedFleet:
         _engine._check(self.L.shc_fleet_get_leg_state_msgs(self.h, self._p(msgs)), "shc_fleet_get_leg_state_msgs")
         return msgs
 
+    def frame_transforms(self, frame="base_link", legs: bool = True, body: bool = True):
+        """publishFrameTransforms of every robot in the caller's instance order: (legs, body), structured arrays of shape (n, max_legs) with
+        the fields of LegFrames - the records of legs a robot does not have all zero - and of shape (n,) with the fields of BodyFrames; the one
+        not asked for is None.  frame: "base_link" or "odom_ideal" (BatchEngine.frame_transforms)."""
+        frame = _engine.FRAME_IDS[frame] if isinstance(frame, str) else int(frame)
+        lf = np.zeros((self.n, self.max_legs), dtype=_engine.LEG_FRAMES_DTYPE) if legs else None
+        bf = np.zeros(self.n, dtype=_engine.BODY_FRAMES_DTYPE) if body else None
+        _engine._check(self.L.shc_fleet_get_frame_transforms(self.h, frame, None if lf is None else self._p(lf), None if bf is None else self._p(bf)),
+                       "shc_fleet_get_frame_transforms")
+        return lf, bf
+
     def all_gather_joints(self):
         """Device pointers (one per device slot) of the gathered [n][max_legs][max_dof] joint buffers."""
         bufs = (C.c_void_p * self.n_devices)()

@@ -42,6 +42,22 @@ class LegStateMsg(C.Structure):
                 ("admittance_delta", C.c_double * 3), ("virtual_stiffness", C.c_double)]
 
 
+SHC_FRAME_JOINTS = 5  # joint frames per shc_leg_frames record (include/shc_batch.h)
+FRAME_BASE_LINK, FRAME_ODOM_IDEAL = 0, 1  # SHC_FRAME_*: the parent of the leg frames shc_engine_get_frame_transforms reports
+FRAME_IDS = {"base_link": FRAME_BASE_LINK, "odom_ideal": FRAME_ODOM_IDEAL}
+
+
+class LegFrames(C.Structure):
+    """shc_leg_frames of include/shc_batch.h (publishFrameTransforms: base_link -> every joint and the tip of one leg; x y z qw qx qy qz)."""
+    _fields_ = [("joint", (C.c_double * 7) * SHC_FRAME_JOINTS), ("tip", C.c_double * 7)]
+
+
+class BodyFrames(C.Structure):
+    """shc_body_frames of include/shc_batch.h (publishFrameTransforms' two body transforms + the rest of publishPose / publishVelocity)."""
+    _fields_ = [("odom_to_base_link", C.c_double * 7), ("base_link_to_walk_plane", C.c_double * 7), ("pose_euler", C.c_double * 3),
+                ("desired_velocity", C.c_double * 3)]
+
+
 class ExternalTarget(C.Structure):
     """shc_external_target of include/shc_batch.h (struct ExternalTarget, walk_controller.h:38-46)."""
     _fields_ = [("pose", C.c_double * 7), ("transform", C.c_double * 7), ("swing_clearance", C.c_double),
