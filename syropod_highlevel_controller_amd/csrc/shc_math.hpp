@@ -87,8 +87,31 @@ SHC_HD double rad2deg(double r) { return (r / (2.0 * kPi)) * 360.0; } // :69
 SHC_HD double deg2rad(double d) { return d / 360.0 * 2.0 * kPi; }     // :64
 
 // sin and cos of a joint angle (|x| well below 2^20 * pi/2: DH offsets + joint limits are a few radians).
-// Cody-Waite reduction by pi/2 in two parts + the fdlibm kernel polynomials: < 1 ulp, ~45 FP64 instructions, no
-// large-argument path (ocml's sincos carries a Payne-Hanek branch and costs ~2x as many issue slots).
+// Cody-Waite reduction by pi/2 in two parts + the fdlibm kernel polynomials, ~45 FP64 instructions, no large-argument
+// path (ocml's sincos carries a Payne-Hanek branch and costs ~2x as many issue slots).
+// Accuracy: |error| <= |n| * 2^-87 + 1 ulp of the result, n = rint(x * 2 / pi).  Derivation: fn * pio2_1 is exact (33 bits
+// times < 2^20) and so is r; pi/2 is represented by pio2_1 + pio2_1t, off by at most half an ulp of pio2_1t = 2^-87 (in
+// fact by 3.5e-27), so the reduced argument y + yt is off by at most |n| * 2^-87 as long as it carries r - fn * pio2_1t
+// exactly: w = fn * pio2_1t is a rounded product (its own error of up to |n| * pio2_1t * 2^-53 would double the bound),
+// so that error is recovered with one fma and goes into the tail, and the block keeps fp-contraction off - fused into
+// fma(-fn, pio2_1t, r), y is no longer r - w and (r - y) - w stops being y's rounding error.  The kernel polynomials add
+// < 1 ulp of the result.  That is "< 1 ulp" for all but the arguments next to a multiple of pi/2, where the result is small
+// and the absolute term is what is left - fdlibm's third reduction part is not carried: cos of the double nearest pi/2 is
+// 6.1e-17 with an error of 3.5e-27, 3e5 ulp of itself and 1e-11 ulp of a joint angle.  REDUCE = false: n = 0, < 1 ulp.
+SHC_HD double pio2_reduce(double x, double *y, double *yt) { // -> fn; x - fn * pi/2 = y + yt
+#pragma clang fp contract(off)
+  const double inv_pio2 = 6.36619772367581382433e-01;
+  const double pio2_1 = 1.57079632673412561417e+00;  // first 33 bits of pi/2
+  const double pio2_1t = 6.07710050650619224932e-11; // pi/2 - pio2_1
+  const double fn = rint(x * inv_pio2);
+  const double r = fma(-fn, pio2_1, x);
+  const double w = fn * pio2_1t;
+  const double we = fma(fn, pio2_1t, -w); // fn * pio2_1t = w + we exactly
+  const double yy = r - w;
+  *y = yy;
+  *yt = ((r - yy) - w) - we; // tail of the reduced argument
+  return fn;
+}
 template <bool REDUCE = true>
 SHC_HD void sincos_joint(double x, double *sn, double *cs) {
   if (!REDUCE) { // caller guarantees |x| <= pi/4: the reduction below would return n = 0, y = x, tail 0
@@ -104,15 +127,8 @@ SHC_HD void sincos_joint(double x, double *sn, double *cs) {
     *cs = w1 + (((1.0 - w1) - hz) + z * rc);
     return;
   }
-  const double inv_pio2 = 6.36619772367581382433e-01;
-  const double pio2_1 = 1.57079632673412561417e+00;  // first 33 bits of pi/2
-  const double pio2_1t = 6.07710050650619224932e-11; // pi/2 - pio2_1
-  double fn = rint(x * inv_pio2);
-  double r = fma(-fn, pio2_1, x);
-  double w = fn * pio2_1t;
-  double y = r - w;
-  double yt = (r - y) - w; // tail of the reduced argument
-  int n = int(fn);
+  double y, yt;
+  int n = int(pio2_reduce(x, &y, &yt));
   double z = y * y;
   // __kernel_sin
   const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
@@ -201,7 +217,7 @@ SHC_HD V3 quat_to_euler(Quat q, bool intrinsic) {
 #ifdef SHC_POSE_R5 // (development A/B: the round-5 form)
     sincos(r0, &s1, &c1);
 #else
-    sincos_joint(r0, &s1, &c1); // |r0| <= pi: the joint-angle sin / cos (< 1 ulp, a third of ocml's sincos with its large-argument path)
+    sincos_joint(r0, &s1, &c1); // |r0| <= pi: the joint-angle sin / cos (a third of ocml's sincos with its large-argument path)
 #endif
     r2 = atan2(s1 * m20 - c1 * m10, c1 * m11 - s1 * m21);
     r0 = -r0;
@@ -220,7 +236,7 @@ SHC_HD V3 quat_to_euler(Quat q, bool intrinsic) {
 #ifdef SHC_POSE_R5 // (development A/B: the round-5 form)
     sincos(r0, &s1, &c1);
 #else
-    sincos_joint(r0, &s1, &c1); // |r0| <= pi: the joint-angle sin / cos (< 1 ulp, a third of ocml's sincos with its large-argument path)
+    sincos_joint(r0, &s1, &c1); // |r0| <= pi: the joint-angle sin / cos (a third of ocml's sincos with its large-argument path)
 #endif
     r2 = atan2(s1 * m02 - c1 * m12, c1 * m11 - s1 * m01);
   }

@@ -107,6 +107,18 @@ _FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-va
           "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"] + os.environ.get("SHC_EXTRA_FLAGS", "").split()  # (development builds)
 
 
+def compile_with_product_flags(src: str, out: str, extra=()) -> str:
+    """Compile one HIP source into the shared library `out` with exactly the flags the shipped kernels are built with (optimisation
+    level, fp-contraction default, scheduler options), so that a probe which includes the product's headers exercises the arithmetic
+    the engine runs (tests/math_probe.hip).  Include paths inside `src` are relative to the source, as in the product's own units."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc] + _FLAGS + list(extra) + ["-shared", "-o", out, src]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"hipcc failed: {' '.join(cmd)}\n{r.stderr[-4000:]}")
+    return out
+
+
 def _translation_units():
     """(object name, source, extra defines): the host side + small kernels, and the fused cycle kernels of each morphology - two objects each:
     the launch forms (part 0) and the loop forms (part 1: resident, batch), so that a build has twice as many units to spread over the cores.
