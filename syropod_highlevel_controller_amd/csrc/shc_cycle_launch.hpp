@@ -104,9 +104,9 @@ struct ResidentFit {
   int batch;              // the batch form (shc_engine_step_k's kernel) exists for it; without one step_k runs the K cycles as single launches
 };
 
-// One per (legs, joints); defined by shc_cycle_inst.hip.  Returns false when that morphology has no kernels in this build.
+// One per (legs, joints); defined by shc_cycle_inst.hip.  Returns false when the selected feature word has no kernel in this build (nothing was launched).
 #define SHC_FOR_EACH_MORPHOLOGY(X) X(3, 3) X(4, 3) X(4, 4) X(4, 5) X(5, 3) X(6, 3) X(6, 4) X(6, 5) X(7, 3) X(8, 3) X(8, 4) X(8, 5)
-#define SHC_DECLARE_LAUNCHER(L_, NJ_) void shc_launch_cycle_##L_##_##NJ_(const CycleLaunch &a);
+#define SHC_DECLARE_LAUNCHER(L_, NJ_) bool shc_launch_cycle_##L_##_##NJ_(const CycleLaunch &a);
 SHC_FOR_EACH_MORPHOLOGY(SHC_DECLARE_LAUNCHER)
 #undef SHC_DECLARE_LAUNCHER
 

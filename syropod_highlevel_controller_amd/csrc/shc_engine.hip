@@ -311,15 +311,33 @@ static void rebuild_cycle_params(shc_engine *e);
   } while (0)
 #define SHC_ENTER_JOINED(e) SHC_ENTER_JOINED_UNLESS(e, false)
 
-// The kernel specialisation of the engine's morphology: CALL(legs, joints), a macro the caller defines around the dispatch, runs for the entry of
-// SHC_FOR_EACH_MORPHOLOGY (shc_cycle_launch.hpp: the one list of the morphologies this build has kernels for) that matches.
-#define SHC_DISPATCH_CASE(L_, NJ_) if (shc_l_ == L_ && shc_nj_ == NJ_) { CALL(L_, NJ_); } else
-#define SHC_DISPATCH(L, NJ)                                                                   \
-  do {                                                                                        \
-    const int shc_l_ = (L), shc_nj_ = (NJ);                                                   \
-    SHC_FOR_EACH_MORPHOLOGY(SHC_DISPATCH_CASE)                                                \
-    return fail(SHC_ERR_UNSUPPORTED, "no kernel specialisation for this (legs, dof)");        \
-  } while (0)
+// The kernel specialisation of the engine's morphology: fn(std::integral_constant<int, legs>, std::integral_constant<int, joints>) -> int runs for the
+// entry of SHC_FOR_EACH_MORPHOLOGY (shc_cycle_launch.hpp: the one list of the morphologies this build has kernels for) that matches.
+static int no_specialisation() { return fail(SHC_ERR_UNSUPPORTED, "no kernel specialisation for this (legs, dof)"); }
+template <class Fn>
+static int dispatch_morphology(const shc_engine *e, Fn &&fn) {
+#define SHC_MORPHOLOGY_CASE(L_, NJ_) \
+  if (e->L == L_ && e->NJ == NJ_) return fn(std::integral_constant<int, L_>{}, std::integral_constant<int, NJ_>{});
+  SHC_FOR_EACH_MORPHOLOGY(SHC_MORPHOLOGY_CASE)
+#undef SHC_MORPHOLOGY_CASE
+  return no_specialisation();
+}
+// Everything a launch of the cycle kernel takes from the engine as it is; the caller names what is its own (grid, block, stream, cycles, loop form)
+static CycleLaunch cycle_launch(const shc_engine *e) {
+  CycleLaunch a{};
+  a.st = e->st, a.consts = e->d_consts, a.cp = &e->cp, a.rt_flags = e->rt_flags, a.stream = e->stream;
+  a.generic = (e->features & SHC_FEAT_GENERIC_KERNEL) != 0;
+  return a;
+}
+// ... and the launch, on the engine's morphology (shc_cycle_inst.hip picks the specialisation: shc_cycle_select.hpp)
+static int launch_cycle_for(const shc_engine *e, const CycleLaunch &a) {
+#define SHC_LAUNCHER_CASE(L_, NJ_) \
+  if (e->L == L_ && e->NJ == NJ_)  \
+    return shc_launch_cycle_##L_##_##NJ_(a) ? SHC_OK : fail(SHC_ERR_UNSUPPORTED, "the kernel selection named a specialisation this build has no kernel for");
+  SHC_FOR_EACH_MORPHOLOGY(SHC_LAUNCHER_CASE)
+#undef SHC_LAUNCHER_CASE
+  return no_specialisation();
+}
 // ... and of the joint count alone (validate_params: 3 .. 5): fn(std::integral_constant<int, joints>)
 template <class Fn>
 static auto dispatch_nj(int NJ, Fn &&fn) {
@@ -697,17 +715,15 @@ static int upload_consts(shc_engine *e) {
     const int rc = dispatch_nj(e->NJ, [&](auto nj) { return build_span_table<decltype(nj)::value>(e); });
     if (rc != SHC_OK) return rc;
   }
-#define CALL(L_, NJ_)                                                                                   \
-  {                                                                                                     \
-    SharedConsts<L_, NJ_> c;                                                                            \
-    build_shared_consts<L_, NJ_>(e->params, e->tables, e->cp, c);                                              \
-    if (!e->d_consts) HIP_TRY(hipMalloc(&e->d_consts, sizeof c));                                       \
-    HIP_TRY(hipMemcpyAsync(e->d_consts, &c, sizeof c, hipMemcpyHostToDevice, e->stream));               \
-    HIP_TRY(hipStreamSynchronize(e->stream));                                                           \
-  }
-  SHC_DISPATCH(e->L, e->NJ);
-#undef CALL
-  return SHC_OK;
+  return dispatch_morphology(e, [&](auto l, auto nj) -> int {
+    constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
+    SharedConsts<L, NJ> c;
+    build_shared_consts<L, NJ>(e->params, e->tables, e->cp, c);
+    if (!e->d_consts) HIP_TRY(hipMalloc(&e->d_consts, sizeof c));
+    HIP_TRY(hipMemcpyAsync(e->d_consts, &c, sizeof c, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return SHC_OK;
+  });
 }
 
 template <int NJ>
@@ -1020,10 +1036,27 @@ static int split_inputs_end(shc_engine *e) {
   }
   return SHC_OK;
 }
-static int64_t split_first_instance_of_second_half(const shc_engine *e) { // as shc_engine_step cuts the batch
-  const int64_t waves_per_block = e->n_waves < 1536 ? 1 : 2;
-  const int64_t half = ((e->n_waves / 2 + waves_per_block - 1) / waves_per_block) * waves_per_block;
-  const int64_t r = half * (64 / e->L);
+// How a launch of the cycle kernel cuts the batch - for shc_engine_step, shc_engine_step_k and the inputs scattered between split steps alike.
+// One wave per workgroup while the batch has about as many waves as the chip has SIMDs (1 024): the dispatcher then spreads
+// them one per SIMD (two-wave groups put pairs on the same SIMDs: 12.9 instead of 9.4 us at 768 waves, 12.2 instead of 10.2 at
+// 1 024; equal at 1 536).  Above that, 128-thread groups
+// (two waves share one LDS copy of the tables): measured against 64 and 256 threads up to 131 072 instances they are the
+// fastest or within noise (-2 ... 3 % on 65 536 hexapods).
+struct LaunchGeometry {
+  int block;               // threads per workgroup
+  int64_t waves_per_block;
+  int64_t half;            // split steps: the first wave of the second half (whole workgroups)
+  int64_t whole_blocks(int64_t waves) const { return ((waves + waves_per_block - 1) / waves_per_block) * waves_per_block; } // waves, rounded up to whole workgroups
+  unsigned grid(int64_t waves) const { return (unsigned)(whole_blocks(waves) / waves_per_block); }
+};
+static LaunchGeometry launch_geometry(const shc_engine *e) {
+  LaunchGeometry g{e->n_waves < 1536 ? 64 : 128, 0, 0};
+  g.waves_per_block = g.block / 64;
+  g.half = g.whole_blocks(e->n_waves / 2);
+  return g;
+}
+static int64_t split_first_instance_of_second_half(const shc_engine *e) {
+  const int64_t r = launch_geometry(e).half * (64 / e->L);
   return r < e->n ? r : e->n;
 }
 
@@ -1134,11 +1167,13 @@ extern "C" int shc_engine_set_tip_force(shc_engine *e, const double *tip_force, 
   e->rt_flags |= RT_TOUCHDOWN; // LegStepper::setTouchdownDetection(true) (state_controller.cpp:1642)
   if (e->params.rough_terrain_mode) { // the step plane is only read in rough terrain mode (walk_controller.cpp:1065, :1110)
     const int64_t threads = e->n * e->L;
-#define CALL(L_, NJ_)                                                                                                           \
-  touchdown_detection_kernel<L_, NJ_><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(                      \
-      e->st, (const SharedConsts<L_, NJ_> *)e->d_consts, e->params.touchdown_threshold, e->params.liftoff_threshold)
-    SHC_DISPATCH(e->L, e->NJ);
-#undef CALL
+    rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
+      constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
+      touchdown_detection_kernel<L, NJ><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(
+          e->st, (const SharedConsts<L, NJ> *)e->d_consts, e->params.touchdown_threshold, e->params.liftoff_threshold);
+      return SHC_OK;
+    });
+    if (rc != SHC_OK) return rc;
     HIP_TRY(hipGetLastError());
   }
   return SHC_OK;
@@ -1256,6 +1291,16 @@ static int split_streams(int device, hipStream_t out[2]) {
   out[0] = pool[device][0], out[1] = pool[device][1];
   return SHC_OK;
 }
+// ... and an engine takes them, with the events that order them against its own stream, the first time it launches a split step
+static int ensure_split_streams(shc_engine *e) {
+  if (e->half_stream[0]) return SHC_OK;
+  const int rc = split_streams(e->device, e->half_stream);
+  if (rc != SHC_OK) return rc;
+  HIP_TRY(hipEventCreateWithFlags(&e->ev_main, hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&e->ev_half[0], hipEventDisableTiming));
+  HIP_TRY(hipEventCreateWithFlags(&e->ev_half[1], hipEventDisableTiming));
+  return SHC_OK;
+}
 // Order the engine's stream after everything earlier split steps launched on the split streams (no host wait).
 static int join_side(shc_engine *e) {
   e->main_dirty = true;
@@ -1304,34 +1349,19 @@ extern "C" int shc_engine_step(shc_engine *e, int n_cycles) {
 // n control cycles in one launch (generic: on the runtime-flag kernel)
 static int launch_cycles(shc_engine *e, int n_cycles, bool generic) {
   if (!(e->rt_flags & (RT_SKIP_MARKED | RT_POSE_MARKED))) e->plan_poser_tips_current = false; // PoseController::updateStance rewrites every LegPoser's tip pose
-  // One wave per workgroup while the batch has about as many waves as the chip has SIMDs (1 024): the dispatcher then spreads
-  // them one per SIMD (two-wave groups put pairs on the same SIMDs: 12.9 instead of 9.4 us at 768 waves, 12.2 instead of 10.2 at
-  // 1 024; equal at 1 536).  Above that, 128-thread groups
-  // (two waves share one LDS copy of the tables): measured against 64 and 256 threads up to 131 072 instances they are the
-  // fastest or within noise (-2 ... 3 % on 65 536 hexapods).
-  const int block = e->n_waves < 1536 ? 64 : 128;
-  const int64_t waves_per_block = block / 64;
+  const LaunchGeometry g = launch_geometry(e);
   const bool split = e->n_waves >= kSplitWaves && !(e->features & SHC_FEAT_SINGLE_STREAM) && !(e->rt_flags & (RT_SKIP_MARKED | RT_POSE_MARKED));
+  CycleLaunch a = cycle_launch(e);
+  a.generic = generic, a.block = g.block, a.n_cycles = n_cycles, a.half_steps = e->half_steps;
+  int rc;
   if (!split) {
-    const int rc = join_side(e);
-    if (rc != SHC_OK) return rc;
-  }
-  const int64_t half = split ? ((e->n_waves / 2 + waves_per_block - 1) / waves_per_block) * waves_per_block : e->n_waves;
-  CycleLaunch a{e->st, e->d_consts, &e->cp, e->rt_flags, generic, e->stream,
-                (unsigned)((half + waves_per_block - 1) / waves_per_block), block, n_cycles, nullptr, nullptr, 0, e->half_steps};
-#define CALL(L_, NJ_) shc_launch_cycle_##L_##_##NJ_(a)
-  if (!split) {
-    SHC_DISPATCH(e->L, e->NJ);
+    if ((rc = join_side(e)) != SHC_OK) return rc;
+    a.grid = g.grid(e->n_waves);
+    if ((rc = launch_cycle_for(e, a)) != SHC_OK) return rc;
     HIP_TRY(hipGetLastError());
     return SHC_OK;
   }
-  if (!e->half_stream[0]) {
-    const int rc = split_streams(e->device, e->half_stream);
-    if (rc != SHC_OK) return rc;
-    HIP_TRY(hipEventCreateWithFlags(&e->ev_main, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&e->ev_half[0], hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&e->ev_half[1], hipEventDisableTiming));
-  }
+  if ((rc = ensure_split_streams(e)) != SHC_OK) return rc;
   const bool resync = e->main_dirty; // inputs or state were touched on the engine's stream since the last split step: both halves follow them
   if (resync) {
     HIP_TRY(hipEventRecord(e->ev_main, e->stream));
@@ -1340,29 +1370,29 @@ static int launch_cycles(shc_engine *e, int n_cycles, bool generic) {
     e->main_dirty = false;
   }
   a.stream = e->half_stream[0];
+  a.grid = g.grid(g.half);
   if (resync) {
     // Two halves that start together end together - their tails and ramp-ups coincide and nothing overlaps (measured: a join
     // every tenth step costs the whole gain).  After a join the halves are therefore STAGGERED: the first half of this one step
     // goes out as two launches and the second half starts when the first of them is through, i.e. a quarter of a step late;
     // both halves take the same time from then on, so the stagger stays until the next join.
-    const int64_t quarter = ((half / 2 + waves_per_block - 1) / waves_per_block) * waves_per_block; // (a quarter or three quarters of a half instead: the same step time within 1 %, profiles/r04_probe_build_variants.txt)
-    a.grid = (unsigned)(quarter / waves_per_block);
-    SHC_DISPATCH(e->L, e->NJ);
+    const int64_t quarter = g.whole_blocks(g.half / 2); // (a quarter or three quarters of a half instead: the same step time within 1 %, profiles/r04_probe_build_variants.txt)
+    a.grid = g.grid(quarter);
+    if ((rc = launch_cycle_for(e, a)) != SHC_OK) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(e->ev_half[0], e->half_stream[0]));
     HIP_TRY(hipStreamWaitEvent(e->half_stream[1], e->ev_half[0], 0));
     a.wave0 = quarter;
-    a.grid = (unsigned)((half - quarter + waves_per_block - 1) / waves_per_block);
+    a.grid = g.grid(g.half - quarter);
   }
-  SHC_DISPATCH(e->L, e->NJ);
+  if ((rc = launch_cycle_for(e, a)) != SHC_OK) return rc;
   HIP_TRY(hipGetLastError());
   a.stream = e->half_stream[1];
-  a.wave0 = half;
-  a.grid = (unsigned)((e->n_waves - half + waves_per_block - 1) / waves_per_block);
-  SHC_DISPATCH(e->L, e->NJ);
+  a.wave0 = g.half;
+  a.grid = g.grid(e->n_waves - g.half);
+  if ((rc = launch_cycle_for(e, a)) != SHC_OK) return rc;
   HIP_TRY(hipGetLastError());
   e->side_busy = true;
-#undef CALL
   return SHC_OK;
 }
 
@@ -1518,11 +1548,13 @@ static int derive_tips(shc_engine *e) {
   const int64_t threads = e->n * e->L;
   const int derive_poser = !(e->cp.auto_posing && !e->cp.imu_posing); // the auto-pose path stores its per-leg poser tip
   const int keep_marked = e->plan_poser_tips_current && (e->params.imu_posing || e->params.auto_posing || e->params.inclination_posing);
-#define CALL(L_, NJ_)                                                                                             \
-  derive_tips_kernel<L_, NJ_><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(                \
-      e->st, (const SharedConsts<L_, NJ_> *)e->d_consts, derive_poser, keep_marked)
-  SHC_DISPATCH(e->L, e->NJ);
-#undef CALL
+  const int rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
+    constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
+    derive_tips_kernel<L, NJ><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(e->st, (const SharedConsts<L, NJ> *)e->d_consts, derive_poser,
+                                                                                                keep_marked);
+    return SHC_OK;
+  });
+  if (rc != SHC_OK) return rc;
   HIP_TRY(hipGetLastError());
   return SHC_OK;
 }
@@ -1685,10 +1717,12 @@ extern "C" int shc_engine_set_tip_states_msg(shc_engine *e, const double *wrench
     const double *d;
     if ((rc = to_device(e, step_plane, size_t(e->n) * e->L * 3, on_device, &d)) != SHC_OK) return rc;
     const int64_t threads = e->n * e->L;
-#define CALL(L_, NJ_) \
-  step_plane_range_kernel<L_, NJ_><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(e->st, (const SharedConsts<L_, NJ_> *)e->d_consts, d)
-    SHC_DISPATCH(e->L, e->NJ);
-#undef CALL
+    rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
+      constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
+      step_plane_range_kernel<L, NJ><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(e->st, (const SharedConsts<L, NJ> *)e->d_consts, d);
+      return SHC_OK;
+    });
+    if (rc != SHC_OK) return rc;
     HIP_TRY(hipGetLastError());
     if (!on_device) HIP_TRY(hipStreamSynchronize(e->stream));
   }
@@ -1938,17 +1972,11 @@ struct LegCall {
   }
   dim3 grid() const { return dim3((unsigned)((rows + 63) / 64)); }
 };
-template <class Fn>
-static int leg_dispatch(shc_engine *e, Fn &&fn) {
-#define CALL(L_, NJ_) fn(std::integral_constant<int, L_>{}, std::integral_constant<int, NJ_>{})
-  SHC_DISPATCH(e->L, e->NJ);
-#undef CALL
-  return SHC_OK;
-}
 #define LEG_KERNEL(KERNEL, ...)                                                                                              \
-  leg_dispatch(e, [&](auto l_, auto nj_) {                                                                                   \
+  dispatch_morphology(e, [&](auto l_, auto nj_) -> int {                                                                        \
     constexpr int L_ = decltype(l_)::value, NJ_ = decltype(nj_)::value;                                                      \
     if (c.rows) KERNEL<L_, NJ_><<<c.grid(), dim3(64), 0, e->stream>>>(e->st, (const SharedConsts<L_, NJ_> *)e->d_consts, c.sel, __VA_ARGS__); \
+    return SHC_OK;                                                                                                           \
   })
 
 extern "C" int shc_leg_set_desired_tip_pose(shc_engine *e, int64_t first, int64_t count, int leg, const double *tip_pose, int apply_delta,
@@ -2261,11 +2289,13 @@ static int sequence_launch(shc_engine *e, int which /* 0 / 1: executeSequence(ST
     }
     P.posed = 1;
   }
-#define CALL(L_, NJ_)                                                                                                                        \
-  if (which == 2) step_to_new_stance_kernel<L_, NJ_><<<grid, block, 0, e->stream>>>(e->st, (const SharedConsts<L_, NJ_> *)e->d_consts, e->d_seq, P, d_progress); \
-  else execute_sequence_kernel<L_, NJ_><<<grid, block, 0, e->stream>>>(e->st, (const SharedConsts<L_, NJ_> *)e->d_consts, e->d_seq, which, P, d_progress)
-  SHC_DISPATCH(e->L, e->NJ);
-#undef CALL
+  rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
+    constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
+    if (which == 2) step_to_new_stance_kernel<L, NJ><<<grid, block, 0, e->stream>>>(e->st, (const SharedConsts<L, NJ> *)e->d_consts, e->d_seq, P, d_progress);
+    else execute_sequence_kernel<L, NJ><<<grid, block, 0, e->stream>>>(e->st, (const SharedConsts<L, NJ> *)e->d_consts, e->d_seq, which, P, d_progress);
+    return SHC_OK;
+  });
+  if (rc != SHC_OK) return rc;
   HIP_TRY(hipGetLastError());
   if (own_clock) {
     sequence_mark_kernel<<<grid, block, 0, e->stream>>>(e->st.manual, e->d_seq, e->n, which, 0);
@@ -2320,20 +2350,22 @@ extern "C" int shc_engine_toggle_leg_state(shc_engine *e, const int32_t *leg_sel
   const SeqParams P = seq_params(e);
   const double virtual_stiffness = posing_params(e).virtual_stiffness; // (as seq_params)
   const dim3 grid((unsigned)((e->n + 63) / 64)), block(64);
-  int phase = LOOP_WHOLE;
-#define CALL(L_, NJ_)                                                                                                                              \
-  leg_state_toggle_kernel<L_, NJ_><<<grid, block, 0, e->stream>>>(e->st, (const SharedConsts<L_, NJ_> *)e->d_consts, d_sel, P, virtual_stiffness,       \
-                                                                  e->params.swing_stiffness_scaler, e->params.load_stiffness_scaler,                \
-                                                                  e->params.admittance_control && e->params.dynamic_stiffness, d_res, d_cycle, phase)
-  if (posing_needs_pose_pass(e)) { // mark the robots that stand with a request, run the posing part of their loop in the cycle kernel
-    phase = LOOP_MARK;
-    SHC_DISPATCH(e->L, e->NJ);
+  const auto toggle = [&](int phase) {
+    return dispatch_morphology(e, [&](auto l, auto nj) -> int {
+      constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
+      leg_state_toggle_kernel<L, NJ><<<grid, block, 0, e->stream>>>(e->st, (const SharedConsts<L, NJ> *)e->d_consts, d_sel, P, virtual_stiffness,
+                                                                    e->params.swing_stiffness_scaler, e->params.load_stiffness_scaler,
+                                                                    e->params.admittance_control && e->params.dynamic_stiffness, d_res, d_cycle, phase);
+      return SHC_OK;
+    });
+  };
+  const bool posed = posing_needs_pose_pass(e);
+  if (posed) { // mark the robots that stand with a request, run the posing part of their loop in the cycle kernel
+    if ((rc = toggle(LOOP_MARK)) != SHC_OK) return rc;
     HIP_TRY(hipGetLastError());
     if ((rc = pose_pass(e)) != SHC_OK) return rc;
-    phase = LOOP_AFTER_POSE;
   }
-  SHC_DISPATCH(e->L, e->NJ);
-#undef CALL
+  if ((rc = toggle(posed ? LOOP_AFTER_POSE : LOOP_WHOLE)) != SHC_OK) return rc;
   HIP_TRY(hipGetLastError());
   int32_t cycle = 0;
   if (result) HIP_TRY(hipMemcpyAsync(result, d_res, size_t(e->n) * 4, hipMemcpyDeviceToHost, e->stream));
@@ -2445,19 +2477,21 @@ extern "C" int shc_engine_execute_plan(shc_engine *e, int32_t *progress, int32_t
   const SeqParams P = seq_params(e);
   const int reset_poser_tips = e->plan_poser_tips_current ? 0 : 1;
   const dim3 grid((unsigned)((e->n + 63) / 64)), block(64);
-  int phase = LOOP_WHOLE;
-#define CALL(L_, NJ_)                                                                                                                             \
-  execute_plan_kernel<L_, NJ_><<<grid, block, 0, e->stream>>>(e->st, (const SharedConsts<L_, NJ_> *)e->d_consts, e->d_seq, P, reset_poser_tips, d_progress, \
-                                                              d_step, d_walking, phase)
-  if (posing_needs_pose_pass(e)) { // mark the robots that stand, run the posing part of their loop in the cycle kernel
-    phase = LOOP_MARK;
-    SHC_DISPATCH(e->L, e->NJ);
+  const auto plan = [&](int phase) {
+    return dispatch_morphology(e, [&](auto l, auto nj) -> int {
+      constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
+      execute_plan_kernel<L, NJ><<<grid, block, 0, e->stream>>>(e->st, (const SharedConsts<L, NJ> *)e->d_consts, e->d_seq, P, reset_poser_tips, d_progress, d_step,
+                                                                d_walking, phase);
+      return SHC_OK;
+    });
+  };
+  const bool posed = posing_needs_pose_pass(e);
+  if (posed) { // mark the robots that stand, run the posing part of their loop in the cycle kernel
+    if ((rc = plan(LOOP_MARK)) != SHC_OK) return rc;
     HIP_TRY(hipGetLastError());
     if ((rc = pose_pass(e)) != SHC_OK) return rc;
-    phase = LOOP_AFTER_POSE;
   }
-  SHC_DISPATCH(e->L, e->NJ);
-#undef CALL
+  if ((rc = plan(posed ? LOOP_AFTER_POSE : LOOP_WHOLE)) != SHC_OK) return rc;
   HIP_TRY(hipGetLastError());
   e->plan_poser_tips_current = true;
   int32_t walking = 0;

@@ -181,15 +181,12 @@ extern "C" int shc_engine_get_frame_transforms(shc_engine *e, int64_t first, int
   double2 *d_body = body ? reinterpret_cast<double2 *>(on_device ? reinterpret_cast<char *>(body) : d + leg_bytes) : nullptr;
   const int rpw = 64 / e->L;
   const unsigned grid = (unsigned)((first + count - 1) / rpw - first / rpw + 1);
-  auto launch = [&]() -> int {
-#define CALL(L_, NJ_)                                                                                                     \
-  frame_transforms_kernel<L_, NJ_><<<dim3(grid), dim3(64), 0, e->stream>>>(d_legs, d_body, e->st, (const SharedConsts<L_, NJ_> *)e->d_consts, \
-                                                                           world, e->cp.odometry ? 1 : 0, first, count)
-    SHC_DISPATCH(e->L, e->NJ);
-#undef CALL
+  const int rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
+    constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
+    frame_transforms_kernel<L, NJ><<<dim3(grid), dim3(64), 0, e->stream>>>(d_legs, d_body, e->st, (const SharedConsts<L, NJ> *)e->d_consts, world,
+                                                                          e->cp.odometry ? 1 : 0, first, count);
     return SHC_OK;
-  };
-  const int rc = launch();
+  });
   hipError_t err = rc == SHC_OK ? hipGetLastError() : hipSuccess;
   if (!on_device) {
     if (rc == SHC_OK && err == hipSuccess && legs) err = hipMemcpyAsync(legs, d, leg_bytes, hipMemcpyDeviceToHost, e->stream);

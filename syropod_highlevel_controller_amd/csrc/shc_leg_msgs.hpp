@@ -292,15 +292,11 @@ extern "C" int shc_engine_get_leg_state_msgs(shc_engine *e, int64_t first, int64
   const LegMsgArgs args = leg_msg_args(e->params, e->tables);
   const int rpw = 64 / e->L;
   const unsigned grid = (unsigned)((first + count - 1) / rpw - first / rpw + 1);
-  auto launch = [&]() -> int {
-#define CALL(L_, NJ_)                                                                                                  \
-  leg_state_msgs_kernel<L_, NJ_><<<dim3(grid), dim3(64), 0, e->stream>>>(reinterpret_cast<double2 *>(d), e->st,        \
-                                                                         (const SharedConsts<L_, NJ_> *)e->d_consts, args, first, count)
-    SHC_DISPATCH(e->L, e->NJ);
-#undef CALL
+  rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
+    constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
+    leg_state_msgs_kernel<L, NJ><<<dim3(grid), dim3(64), 0, e->stream>>>(reinterpret_cast<double2 *>(d), e->st, (const SharedConsts<L, NJ> *)e->d_consts, args, first, count);
     return SHC_OK;
-  };
-  rc = launch();
+  });
   hipError_t err = rc == SHC_OK ? hipGetLastError() : hipSuccess;
   if (!on_device) {
     if (rc == SHC_OK && err == hipSuccess) err = hipMemcpyAsync(msgs, d, bytes, hipMemcpyDeviceToHost, e->stream);

@@ -195,6 +195,14 @@ extern "C" int shc_engine_resident_bind_inputs(shc_engine *e, int set, const shc
   return SHC_OK;
 }
 
+// Which loop forms the kernel specialisation of the engine's configuration has, and how densely its resident kernel fits (nothing is launched)
+static int resident_fit(const shc_engine *e, ResidentFit &fit) {
+  fit = ResidentFit{0, 0, 0, 0};
+  CycleLaunch a = cycle_launch(e);
+  a.fit = &fit;
+  return launch_cycle_for(e, a);
+}
+
 extern "C" int shc_engine_resident_begin(shc_engine *e, int ring_depth, int64_t max_cycles, int idle_timeout_ms) {
   if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
   if (e->res && e->res->active) return fail(SHC_ERR_BUSY, "resident mode is already active");
@@ -217,12 +225,10 @@ extern "C" int shc_engine_resident_begin(shc_engine *e, int ring_depth, int64_t 
     if (rc != SHC_OK) return rc;
   }
   // does this configuration have a resident kernel, and does the whole batch fit the chip at once (+ the relay block)?
-  ResidentFit fit{0, 0, 0, 0};
+  ResidentFit fit;
   {
-    CycleLaunch a{e->st, e->d_consts, &e->cp, e->rt_flags, (e->features & SHC_FEAT_GENERIC_KERNEL) != 0, e->stream, 0, 64, 0, nullptr, &fit, 0};
-#define CALL(L_, NJ_) shc_launch_cycle_##L_##_##NJ_(a)
-    SHC_DISPATCH(e->L, e->NJ);
-#undef CALL
+    const int rc = resident_fit(e, fit);
+    if (rc != SHC_OK) return rc;
   }
   if (!fit.supported)
     return fail(SHC_ERR_UNSUPPORTED, (e->rt_flags & RT_MANUAL_LEGS)
@@ -343,11 +349,13 @@ extern "C" int shc_engine_resident_begin(shc_engine *e, int ring_depth, int64_t 
   r->two_wave = two_wave;
   HIP_TRY(hipEventRecord(r->loop_ev, e->stream)); // everything the engine's stream holds (state, the buffers set up above) comes first
   HIP_TRY(hipStreamWaitEvent(r->loop_stream, r->loop_ev, 0));
-  CycleLaunch a{e->st, e->d_consts, &e->cp, e->rt_flags, (e->features & SHC_FEAT_GENERIC_KERNEL) != 0, r->loop_stream,
-                two_wave ? unsigned((e->n_waves + 1) / 2 + 1) : unsigned(e->n_waves + 1), two_wave ? 256 : 64, 0, &A, nullptr, 0};
-#define CALL(L_, NJ_) shc_launch_cycle_##L_##_##NJ_(a)
-  SHC_DISPATCH(e->L, e->NJ);
-#undef CALL
+  CycleLaunch a = cycle_launch(e);
+  a.stream = r->loop_stream, a.resident = &A;
+  a.grid = two_wave ? unsigned((e->n_waves + 1) / 2 + 1) : unsigned(e->n_waves + 1), a.block = two_wave ? 256 : 64;
+  {
+    const int rc = launch_cycle_for(e, a);
+    if (rc != SHC_OK) return rc;
+  }
   HIP_TRY(hipGetLastError());
   r->active = true;
   return SHC_OK;
@@ -770,12 +778,10 @@ extern "C" int shc_engine_step_k(shc_engine *e, int n_cycles, const shc_cycle_in
     const int rc = effort_live(e);
     if (rc != SHC_OK) return rc;
   }
-  ResidentFit fit{0, 0, 0, 0};
+  ResidentFit fit;
   {
-    CycleLaunch a{e->st, e->d_consts, &e->cp, e->rt_flags, (e->features & SHC_FEAT_GENERIC_KERNEL) != 0, e->stream, 0, 64, 0, nullptr, &fit, 0};
-#define CALL(L_, NJ_) shc_launch_cycle_##L_##_##NJ_(a)
-    SHC_DISPATCH(e->L, e->NJ);
-#undef CALL
+    const int rc = resident_fit(e, fit);
+    if (rc != SHC_OK) return rc;
   }
   if (size_t(e->NJ) * e->n_slots * 16 * size_t(n_cycles) >= (size_t(1) << 31))
     return fail(SHC_ERR_INVALID_ARG, "shc_engine_step_k: cycles x batch - the output ring must stay below 2 GiB (fewer cycles per launch)");
@@ -814,35 +820,28 @@ extern "C" int shc_engine_step_k(shc_engine *e, int n_cycles, const shc_cycle_in
   // the halves are NOT joined between launches (one half's tail runs under the other half's full rounds, launch after launch): each half is ordered
   // after the engine's stream (where the caller's input rows were written) and after its own previous launch; the engine's stream is ordered after
   // both at the next call that needs it (join_side: every SHC_ENTER_JOINED entry point, shc_engine_get_step_k_joint_state among them).
-  const int block = e->n_waves < 1536 ? 64 : 128;
-  const int64_t wpb = block / 64;
-  CycleLaunch a{e->st, e->d_consts, &e->cp, e->rt_flags, (e->features & SHC_FEAT_GENERIC_KERNEL) != 0, e->stream, unsigned((e->n_waves + wpb - 1) / wpb), block, 0, &A, nullptr, 0};
-#define CALL(L_, NJ_) shc_launch_cycle_##L_##_##NJ_(a)
+  const LaunchGeometry g = launch_geometry(e);
+  CycleLaunch a = cycle_launch(e);
+  a.block = g.block, a.resident = &A;
+  int rc;
   if (!split) {
-    SHC_DISPATCH(e->L, e->NJ);
+    a.grid = g.grid(e->n_waves);
+    if ((rc = launch_cycle_for(e, a)) != SHC_OK) return rc;
     HIP_TRY(hipGetLastError());
   } else {
-    if (!e->half_stream[0]) {
-      const int rc = split_streams(e->device, e->half_stream);
-      if (rc != SHC_OK) return rc;
-      HIP_TRY(hipEventCreateWithFlags(&e->ev_main, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&e->ev_half[0], hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&e->ev_half[1], hipEventDisableTiming));
-    }
+    if ((rc = ensure_split_streams(e)) != SHC_OK) return rc;
     HIP_TRY(hipEventRecord(e->ev_main, e->stream));
-    const int64_t half = ((e->n_waves / 2 + wpb - 1) / wpb) * wpb;
     for (int h = 0; h < 2; ++h) {
       HIP_TRY(hipStreamWaitEvent(e->half_stream[h], e->ev_main, 0));
-      A.batch_wave0 = h ? half : 0;
+      A.batch_wave0 = h ? g.half : 0;
       a.stream = e->half_stream[h];
-      a.grid = unsigned(((h ? e->n_waves - half : half) + wpb - 1) / wpb);
-      SHC_DISPATCH(e->L, e->NJ);
+      a.grid = g.grid(h ? e->n_waves - g.half : g.half);
+      if ((rc = launch_cycle_for(e, a)) != SHC_OK) return rc;
       HIP_TRY(hipGetLastError());
     }
     e->main_dirty = false;
     e->side_busy = true;
   }
-#undef CALL
   e->k_out_cycles = n_cycles;
   if (mask & (1u << RG_FORCE)) e->rt_flags |= RT_TOUCHDOWN; // as shc_engine_set_tip_force (state_controller.cpp:1642)
   return SHC_OK;
