@@ -862,6 +862,45 @@ int shc_engine_get_state(shc_engine *e, int64_t first, int64_t count, shc_instan
 int shc_engine_set_state(shc_engine *e, int64_t first, int64_t count, const shc_instance_state *states);
 
 /*
+ * Device checkpoints: the state of every instance kept in device memory, and an indexed restore from it - reset any subset of the batch to a
+ * known state, or clone one instance onto many, while the others keep walking.  Everything runs on the engine's stream.
+ * The host route above defines the result: after a restore with source[i] = j, shc_engine_get_state(i) and shc_engine_get_aux_state(i) return
+ * what they would return had the caller read instance j's records at capture time and written them to i with shc_engine_set_state /
+ * shc_engine_set_aux_state at restore time, and every later cycle is that engine's bit for bit.  Held inputs (velocity, IMU, forces, efforts)
+ * are inputs: a restored instance keeps the command it is being given now.  The engine-wide facts the host route derives from injected records
+ * (manual pose live, touchdown detection, manual legs, external targets, joint efforts live, "the LegPoser tips of the last plan call are
+ * current") are taken from the checkpoint as captured; nothing is read back from the device.
+ * A checkpoint belongs to the engine that made it (another engine's: SHC_ERR_INVALID_ARG) and to the gait and parameters it was captured
+ * under: after shc_engine_change_gait or shc_engine_adjust_parameter, and while an adjusted parameter waits for its loop, a restore is
+ * SHC_ERR_UNSUPPORTED and changes nothing - step, then shc_engine_checkpoint_update.  shc_engine_destroy releases the device memory of the
+ * engine's checkpoints; their handles stay valid only for shc_checkpoint_destroy (every other use: SHC_ERR_INVALID_ARG).
+ * Split steps are joined first; SHC_ERR_BUSY in resident mode.  Fleets (shc_fleet_*) and migration between engines stay on the host route.
+ */
+typedef struct shc_checkpoint shc_checkpoint;
+/* Allocates the checkpoint's device arrays (the size of the engine's state planes and records), then captures as shc_engine_checkpoint_update. */
+int shc_engine_checkpoint_create(shc_engine *e, shc_checkpoint **out);
+/* Captures the engine's state as of this point of its stream into the same storage: device-to-device copies on the engine's stream, no host
+ * wait, no allocation - unless the engine has grown a record array since (first leg toggle, first external request, first sequence call):
+ * then the checkpoint grows with it, once. */
+int shc_engine_checkpoint_update(shc_engine *e, shc_checkpoint *ck);
+/* Waits for the engine's stream (a capture or restore may be in flight), then frees the checkpoint.  NULL: SHC_ERR_INVALID_ARG. */
+int shc_checkpoint_destroy(shc_checkpoint *ck);
+/* Instance i <- the checkpoint's instance source[i], one kernel launch.  source[i] < 0 or >= n: instance i is left exactly as it is.
+ * source: [n] int64, HOST (on_device = 0; validated first: an entry >= n is SHC_ERR_INVALID_ARG and nothing is changed; synchronises the
+ * engine's stream) or DEVICE (on_device = 1; read on the engine's stream - the caller's writes to it must be ordered before this call on
+ * that stream - no host wait, no allocation; an entry >= n leaves its instance alone).  NULL = the identity (restore everything).
+ * A map is not a list of pairs: it cannot name one destination twice.  Reset from a device-side mask is where(done, arange(n), -1).
+ * Only NULL or a host map without negative entries counts as a restore of the whole batch for "the LegPoser tips are current"
+ * (see shc_engine_set_aux_state: a partial restore never raises it). */
+int shc_engine_restore_instances(shc_engine *e, const shc_checkpoint *ck, const int64_t *source, int on_device);
+/* Device bytes the checkpoint holds (0 for NULL, and once its engine has been destroyed). */
+int64_t shc_checkpoint_bytes(const shc_checkpoint *ck);
+/* Development: the class of leg field `field` of joints-per-leg `nj` (is_robot = 0) or of robot field `field` (is_robot = 1) in the
+ * checkpoint's classification - 0 state, 1 input (not restored), 2 output, 3 LDS-only (not restored) - or -1 for an index outside the
+ * field list or not classified exactly once.  No device needed. */
+int shc_debug_checkpoint_field_class(int nj, int is_robot, int field);
+
+/*
  * Fleets: mixed morphologies (BASELINE.json configs[4]) and several GPUs of one node (configs[3]) behind one handle, for hosts
  * that drive all devices from ONE process (a one-process-per-GPU host creates one engine per rank and exchanges with RCCL, see
  * bench.py).  morph_id[i] in [0, n_morphologies) assigns instance i to params[morph_id[i]] (NULL = all 0).  Instances are binned

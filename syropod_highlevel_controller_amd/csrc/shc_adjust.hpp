@@ -19,6 +19,8 @@
 //   get_state / set_state                         phase_step_cycle             read only: a record shows the phases in the cycle they still count in
 //   seq_params, toggle_leg_state                  posing_params                read only: the loop-level kernels of the serving loop read the old values
 //   rebuild_cycle_params                          adjust_overlay               the launch-uniform block of the serving cycle
+//   change_gait, adjust_parameter                 adjust_bump                  new tables / parameters are installed or queued: older device checkpoints are stale
+//   checkpoint capture / restore                  adjust_generation            read only: a restore needs the generation of its capture and nothing pending
 //
 // Every transition ends with adjust_settle: join the split streams, rebuild the parameter block, upload the constants.
 //
@@ -31,6 +33,7 @@ struct PendingAdjust {
   bool params_held;       // the posing part of the next cycle still runs on the values a just-adjusted parameter had
   shc_step_cycle old_step; // step_remap: the step cycle the legs' phases still count in
   shc_params held;        // params_held: the parameters as they were before the change
+  uint64_t generation;    // counts every installed or queued change of tables / parameters, and every served one: what a device checkpoint was captured under
 };
 
 #else // ------------------------------------------------------------------------------------------ operations (struct shc_engine is complete)
@@ -63,9 +66,13 @@ static int adjust_settle(shc_engine *e, int rc) {
   rebuild_cycle_params(e);
   return rc == SHC_OK ? upload_consts(e) : rc;
 }
+// The generation of tables / parameters a device checkpoint (shc_checkpoint.hpp) is captured under.
+static void adjust_bump(shc_engine *e) { ++e->adjust.generation; }
+static uint64_t adjust_generation(const shc_engine *e) { return e->adjust.generation; }
 // Nothing waits any more; returns whether the phases were still to be mapped.
 static bool adjust_take(shc_engine *e) {
   const bool remap = e->adjust.step_remap;
+  if (adjust_pending(e)) adjust_bump(e); // (a checkpoint captured while the change waited shows the state before its serving loop)
   e->adjust.step_remap = e->adjust.params_held = false;
   return remap;
 }
@@ -154,6 +161,7 @@ static int adjust_step_frequency(shc_engine *e, double value, int64_t *pending) 
   np.step_frequency = value;
   const shc_step_cycle ns = hostinit::generate_step_cycle(np);
   if (ns.period <= 0 || ns.period > LW_PHASE_MASK) return fail(SHC_ERR_INVALID_ARG, "step_frequency gives a degenerate step cycle");
+  adjust_bump(e);
   p.step_frequency = value; // p->current_value = new_parameter_value_ (:454): the sequence / transition timings read it from now on, accepted or not
   shc_tables tn = e->tables;
   tn.step = ns;
@@ -233,6 +241,7 @@ extern "C" int shc_engine_adjust_parameter(shc_engine *e, int which, double valu
     case SHC_PARAM_FORCE_GAIN: p.force_gain = value; break;              // admittance input (admittance_controller.cpp:32), tip-force estimate (model.cpp:705), LegState tip force
     default: return fail(SHC_ERR_INVALID_ARG, "unknown adjustable parameter (SHC_PARAM_*)");
   }
+  adjust_bump(e);
   // The eight parameters the control cycle reads as they are (params_.*.current_value): a new launch-uniform block, in force from the next cycle; no table is
   // regenerated and no state is touched.
   // ... except where the POSING part of the loop reads them (updateStiffness / updateAdmittance run before runningState, state_controller.cpp:170-180): the

@@ -285,10 +285,12 @@ struct shc_engine {
   int k_out_cycles = 0;
   bool side_busy = false;               // launches are outstanding on the split streams that the engine's stream has not been ordered after
   bool main_dirty = true;               // work other than steps was enqueued on the engine's stream since the last split step
+  struct shc_checkpoint *checkpoints = nullptr; // the registry of this engine's device checkpoints (shc_checkpoint.hpp): released with the engine
 };
 struct Resident;
 static bool resident_active(const shc_engine *e);
 static void resident_shutdown(shc_engine *e); // stop a running resident loop and free its buffers (shc_engine_destroy)
+static void release_checkpoints(shc_engine *e); // free the device arrays of the engine's checkpoints and orphan their handles (shc_engine_destroy)
 // While the resident kernel owns the engine's stream and state, every other entry point that would touch them is refused.
 static int join_side(shc_engine *e);
 static void rebuild_cycle_params(shc_engine *e);
@@ -959,6 +961,7 @@ extern "C" int shc_engine_destroy(shc_engine *e) {
   for (hipStream_t hs : e->half_stream) // (the halves of split steps: nothing may still be running on the buffers freed below)
     if (hs) (void)hipStreamSynchronize(hs);
   (void)hipStreamSynchronize(e->stream);
+  release_checkpoints(e);
   (void)hipFree(e->st.legd);
   (void)hipFree(e->st.legi);
   (void)hipFree(e->st.robd);
@@ -1512,6 +1515,7 @@ extern "C" int shc_engine_change_gait(shc_engine *e, const shc_params *ng, int64
   e->params = p;
   e->tables = t;
   e->span_dirty = true;
+  adjust_bump(e); // new tables: a device checkpoint of the old gait counts its phases in another step cycle
   adjust_drop(e); // shc_adjust.hpp, row "change_gait with every robot STOPPED"
   build_cycle_params(e->params, e->tables, e->features, e->rt_flags, e->cp);
   if ((rc = upload_consts(e)) != SHC_OK) return rc;
@@ -2675,6 +2679,7 @@ extern "C" int shc_engine_finish_sequence_startup(shc_engine *e) {
 }
 
 #include "shc_snapshot.hpp" // shc_engine_get_state / set_state, auxiliary state: kernels and host side
+#include "shc_checkpoint.hpp" // device checkpoints and the indexed restore (shc_engine_checkpoint_*, shc_engine_restore_instances)
 
 extern "C" int shc_engine_get_body_state(shc_engine *e, double *pose, double *velocity, int32_t *walk_state, int on_device) {
   SHC_ENTER_JOINED(e);

@@ -345,6 +345,10 @@ __global__ void aux_state_kernel(unsigned char *blobs, size_t stride, DevState s
   }
 }
 extern "C" int64_t shc_engine_aux_state_bytes(const shc_engine *e) { return e ? int64_t(aux_bytes(e)) : 0; }
+// AuxHeader::flags of the blobs this engine writes now: the lazily allocated records it holds, and whether the LegPoser tips are state
+static uint32_t aux_live_flags(const shc_engine *e) {
+  return (e->st.manual && (e->rt_flags & RT_MANUAL_LEGS) ? 1u : 0u) | (e->st.ext ? 2u : 0u) | (e->d_seq ? 4u : 0u) | (e->plan_poser_tips_current ? 8u : 0u);
+}
 static int aux_state(shc_engine *e, int64_t first, int64_t count, void *blobs, int to_engine) {
   if (!blobs) return fail(SHC_ERR_INVALID_ARG, "blobs is NULL");
   if (first < 0 || count < 0 || first + count > e->n) return fail(SHC_ERR_INVALID_ARG, "instance range out of bounds");
@@ -384,8 +388,7 @@ static int aux_state(shc_engine *e, int64_t first, int64_t count, void *blobs, i
   unsigned char *d = nullptr;
   HIP_TRY(hipMalloc(&d, stride * size_t(count)));
   if (to_engine) HIP_TRY_OR(hipMemcpyAsync(d, blobs, stride * size_t(count), hipMemcpyHostToDevice, e->stream), (void)hipFree(d));
-  const uint32_t live = (e->st.manual && (e->rt_flags & RT_MANUAL_LEGS) ? 1u : 0u) | (e->st.ext ? 2u : 0u) | (e->d_seq ? 4u : 0u) |
-                        (e->plan_poser_tips_current ? 8u : 0u);
+  const uint32_t live = aux_live_flags(e);
   aux_state_kernel<<<dim3((unsigned)((count + 127) / 128)), dim3(128), 0, e->stream>>>(d, stride, e->st, e->d_seq, e->L, e->NJ, LEG_FIELD(e, DES_TIP), e->n_leg_fields,
                                                                                    first, count, to_engine, live, LEG_FIELD(e, POSER_TIP));
   HIP_TRY_OR(hipGetLastError(), (void)hipFree(d));

@@ -52,6 +52,8 @@ EXPORTED_SYMBOLS = [
     "shc_engine_step_k", "shc_engine_get_step_k_joint_state", "shc_engine_adjust_parameter",
     "shc_engine_get_leg_state_msgs", "shc_fleet_get_leg_state_msgs",
     "shc_engine_get_frame_transforms", "shc_fleet_get_frame_transforms",
+    "shc_engine_checkpoint_create", "shc_engine_checkpoint_update", "shc_checkpoint_destroy", "shc_engine_restore_instances", "shc_checkpoint_bytes",
+    "shc_debug_checkpoint_field_class",
     "shc_peer_alloc", "shc_peer_open", "shc_peer_close", "shc_peer_scatter",
 ]
 
@@ -336,6 +338,13 @@ def lib():
         L.shc_engine_aux_state_bytes.restype = C.c_int64
         L.shc_engine_get_aux_state.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
         L.shc_engine_set_aux_state.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+        L.shc_engine_checkpoint_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.shc_engine_checkpoint_update.argtypes = [C.c_void_p, C.c_void_p]
+        L.shc_checkpoint_destroy.argtypes = [C.c_void_p]
+        L.shc_engine_restore_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.shc_checkpoint_bytes.argtypes = [C.c_void_p]
+        L.shc_checkpoint_bytes.restype = C.c_int64
+        L.shc_debug_checkpoint_field_class.argtypes = [C.c_int, C.c_int, C.c_int]
         L.shc_engine_resident_begin.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int]
         L.shc_engine_resident_post.argtypes = [C.c_void_p, C.POINTER(CycleInputs), C.POINTER(C.c_int64)]
         L.shc_engine_resident_bind_inputs.argtypes = [C.c_void_p, C.c_int, C.POINTER(CycleInputs)]
@@ -450,6 +459,42 @@ def generate_tables_batch(params_list, device: int = 0):
     status = (C.c_int32 * n)()
     _check(lib().shc_generate_tables_batch(arr, n, out, status, device), "shc_generate_tables_batch")
     return list(out), np.array(status[:], dtype=np.int32)
+
+
+class Checkpoint:
+    """The state of every robot of an engine, kept in device memory (shc_engine_checkpoint_create): what ``BatchEngine.restore`` resets or clones
+    robots from.  A context manager; ``close()`` after the engine's ``close()`` is a no-op for the caller."""
+
+    def __init__(self, engine: "BatchEngine"):
+        self.engine, self.L, self.h = engine, engine.L, None
+        h = C.c_void_p()
+        _check(self.L.shc_engine_checkpoint_create(engine.h, C.byref(h)), "checkpoint_create")
+        self.h = h
+
+    def update(self):
+        """Capture the engine's state again into the same device storage: stream-ordered copies, no host wait."""
+        _check(self.L.shc_engine_checkpoint_update(self.engine.h, self.h), "checkpoint_update")
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.L.shc_checkpoint_bytes(self.h)) if self.h else 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.shc_checkpoint_destroy(self.h)   # (a handle whose engine is gone holds nothing on the device: this frees the handle itself)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class BatchEngine:
@@ -787,6 +832,29 @@ class BatchEngine:
         per = int(self.L.shc_engine_aux_state_bytes(self.h))
         assert len(blobs) % per == 0
         _check(self.L.shc_engine_set_aux_state(self.h, first, len(blobs) // per, C.c_char_p(blobs)), "set_aux_state")
+
+    def checkpoint(self) -> Checkpoint:
+        """A device-resident checkpoint of every robot's state as of now (on the engine's stream)."""
+        return Checkpoint(self)
+
+    def restore(self, ck: Checkpoint, source=None):
+        """Robot i <- the checkpoint's robot ``source[i]``; an entry < 0 leaves robot i alone.  ``source``: a host int64 array of length n (an entry
+        >= n raises), an object with ``__cuda_array_interface__`` (a contiguous int64 array of length n on the engine's device, e.g. a torch tensor:
+        read on the engine's stream without a host wait - the writes to it must be ordered before this call on that stream; an entry >= n leaves its
+        robot alone), or None for every robot.  Reset from a mask: ``torch.where(done, torch.arange(n), -1)``."""
+        if source is None:
+            ptr, on_device = None, 0
+        elif hasattr(source, "__cuda_array_interface__"):
+            cai = source.__cuda_array_interface__
+            if cai["typestr"] != "<i8" or tuple(cai["shape"]) != (self.n,) or cai.get("strides") not in (None, (8,)):
+                raise ValueError(f"a device source map must be a contiguous int64 array of length {self.n}")
+            ptr, on_device = C.c_void_p(cai["data"][0]), 1
+        else:
+            a = np.ascontiguousarray(source, dtype=np.int64)
+            if a.shape != (self.n,):
+                raise ValueError(f"a source map has one entry per robot: expected shape ({self.n},), got {a.shape}")
+            ptr, on_device = a.ctypes.data_as(C.c_void_p), 0
+        _check(self.L.shc_engine_restore_instances(self.h, ck.h, ptr, on_device), "restore_instances")
 
     # -- per-leg Leg methods (model.h:448-492), batched: instances [first, first + count), leg = -1 for every leg
     def _rows(self, first, count, leg):
