@@ -901,6 +901,62 @@ int64_t shc_checkpoint_bytes(const shc_checkpoint *ck);
 int shc_debug_checkpoint_field_class(int nj, int is_robot, int field);
 
 /*
+ * Health scan: what the reference reports as throttled ROS_WARN lines of ONE robot - "IK Clamping Event/s" (Leg::updateJointPositions,
+ * model.cpp:811-853), "Inverse kinematics deviation!" (Leg::applyIK, :914-929) and the limit proximity the two return (:843-849, :903, :940) -
+ * as one record per robot, and the robots that meet a caller's criteria as a restore map and an ascending list: step -> scan -> restore
+ * (shc_engine_restore_instances, on_device = 1) without a host round trip.  Everything is a function of the stored state; joints are a
+ * leg's own (a leg shorter than the robot's longest has no others).
+ */
+enum {
+  SHC_HEALTH_IK_DEVIATION = 1,   /* a leg carries the 5 mm deviation warning of its last applyIK (model.cpp:916-929): leg_status bit 2 of
+                                    shc_engine_get_leg_state, shc_leg_snapshot.ik_failed */
+  SHC_HEALTH_POSITION_LIMIT = 2, /* a joint of non-zero range stands with desired_position_ <= min or >= max: what a position clamp leaves
+                                    behind (model.cpp:827-841) */
+  SHC_HEALTH_SPEED_LIMIT = 4,    /* max_speed_ratio >= 1: what a velocity clamp leaves behind (model.cpp:812-821) */
+  SHC_HEALTH_NEAR_LIMIT = 8,     /* min_limit_proximity < criteria.near_limit_proximity */
+  SHC_HEALTH_TIP_DEVIATION = 16, /* max_tip_deviation > criteria.tip_deviation */
+  SHC_HEALTH_NONFINITE = 32      /* a joint angle or rate, walker / poser / model tip, admittance delta or component of
+                                    Model::current_pose_ is NaN or +-Inf; the three doubles of such a record are unspecified */
+};
+typedef struct shc_health_criteria {
+  uint32_t select;             /* SHC_HEALTH_* bits: a robot is selected when flags & select != 0 */
+  uint32_t reserved;           /* 0 */
+  double near_limit_proximity; /* threshold of SHC_HEALTH_NEAR_LIMIT, in the units of Leg::updateJointPositions' return value (1 = mid-range, 0 = on a limit) */
+  double tip_deviation;        /* threshold of SHC_HEALTH_TIP_DEVIATION, metres (the reference warns above IK_TOLERANCE = 0.005, model.h:17) */
+} shc_health_criteria;
+typedef struct shc_robot_health { /* 32 bytes, no padding */
+  double min_limit_proximity; /* Leg::updateJointPositions' return value (model.cpp:843-849) evaluated on the stored desired_position_: the minimum over
+                                 legs and joints of min(|min - q|, |max - q|) / ((max - min) / 2); a zero-range joint contributes 1.0 (:848) */
+  double max_tip_deviation;   /* the maximum over legs and axes of |current_tip_pose_ - desired_tip_pose_| (model.cpp:918) with desired_tip_pose_ =
+                                 poser tip + admittance_delta_ (setDesiredTipPose, :660-661; no delta for MANUAL / WALKING_TO_MANUAL legs, :656): the
+                                 model_tip, poser_tip and admittance rows of shc_engine_get_leg_state */
+  double max_speed_ratio;     /* the maximum over legs and joints of |desired_velocity_| / max_angular_speed_ (model.cpp:814) */
+  uint32_t flags;             /* SHC_HEALTH_* */
+  uint32_t leg_masks;         /* byte 0: legs with the IK deviation bit, 1: on a position limit, 2: on the speed limit, 3: non-finite; bit l = leg l */
+} shc_robot_health;
+/* Instances [first, first + count) in one device pass.  Any output may be NULL (not all four):
+ *   health       [count]  the records
+ *   restore_map  [n]      i for a selected robot of the range, -1 for every other i of [0, n): the source map of
+ *                         shc_engine_restore_instances(.., on_device = 1)
+ *   selected     [count]  the selected instance ids in ascending order; entries past the count are left untouched
+ *   n_selected   [1]      their number
+ * criteria is HOST memory; NULL = select 0, thresholds unused (NEAR_LIMIT / TIP_DEVIATION are never raised).
+ * on_device = 1: the outputs are device buffers (health 16-byte aligned, the int64 buffers 8-byte aligned), the call is ordered on the engine's
+ * stream and does not wait on the host; on_device = 0: host memory, the call synchronises the stream.  Split steps are joined first.  Refreshes
+ * the derived model / poser tips as shc_engine_get_leg_state does and changes no other state.  count = 0 writes *n_selected = 0 and a
+ * restore_map of -1.  The pass keeps one small count buffer per engine, allocated by the engine's first scan (like
+ * shc_engine_checkpoint_create, that call allocates device memory; later device-form calls do not) and freed by shc_engine_destroy.
+ * SHC_ERR_INVALID_ARG for a range outside [0, n), all outputs NULL, reserved != 0, select bits outside the six, misaligned device buffers;
+ * SHC_ERR_BUSY in resident mode. */
+int shc_engine_scan_health(shc_engine *e, int64_t first, int64_t count, const shc_health_criteria *criteria, shc_robot_health *health /* [count] */,
+                           int64_t *restore_map /* [n] */, int64_t *selected /* [count] */, int64_t *n_selected /* [1] */, int on_device);
+/* Development: the record of ONE robot of parameters `params` from host arrays in the layouts of the getters - q, qd [legs][longest leg's DOF],
+ * poser_tip, model_tip, admittance [legs][3], leg_status [legs] (bit 2 = IK deviation), pose7 = Model::current_pose_ (x,y,z,qw,qx,qy,qz) - through the
+ * functions the scan kernel runs (the walker tip and the manual leg states are not part of it: finite, WALKING).  criteria may be NULL.  No device needed. */
+int shc_debug_robot_health(const shc_params *params, const shc_health_criteria *criteria, const double *q, const double *qd, const double *poser_tip,
+                           const double *model_tip, const double *admittance, const int32_t *leg_status, const double *pose7, shc_robot_health *out);
+
+/*
  * Fleets: mixed morphologies (BASELINE.json configs[4]) and several GPUs of one node (configs[3]) behind one handle, for hosts
  * that drive all devices from ONE process (a one-process-per-GPU host creates one engine per rank and exchanges with RCCL, see
  * bench.py).  morph_id[i] in [0, n_morphologies) assigns instance i to params[morph_id[i]] (NULL = all 0).  Instances are binned
@@ -934,6 +990,9 @@ int shc_fleet_get_leg_state_msgs(shc_fleet *f, shc_leg_state_msg *msgs);
 /* publishFrameTransforms of every robot of the fleet, in the caller's instance order (host memory): legs[i * max_legs + l], the records of
  * legs a robot does not have all zero, and body[i]; either may be NULL (not both).  Synchronises every part's stream. */
 int shc_fleet_get_frame_transforms(shc_fleet *f, int frame, shc_leg_frames *legs /* [n][max_legs] */, shc_body_frames *body /* [n] */);
+/* shc_engine_scan_health of every robot of the fleet: the records in the caller's instance order (host memory; criteria may be NULL).  Records only -
+ * restore maps and selected lists are per engine, as device checkpoints are (shc_fleet_part).  Synchronises every part's stream. */
+int shc_fleet_scan_health(shc_fleet *f, const shc_health_criteria *criteria, shc_robot_health *health /* [n] */);
 /* The exchange step of a sharded batch: every device ends up with the desired joint positions of ALL instances
  * ([n][max_legs][max_dof], caller's order, NaN padded) in its own HBM, copied device to device (hipMemcpyPeerAsync: xGMI on an
  * MI355X node).  device_buffers[d] (may be NULL) receives device_ids[d]'s buffer; the buffers belong to the fleet. */

@@ -286,6 +286,7 @@ struct shc_engine {
   bool side_busy = false;               // launches are outstanding on the split streams that the engine's stream has not been ordered after
   bool main_dirty = true;               // work other than steps was enqueued on the engine's stream since the last split step
   struct shc_checkpoint *checkpoints = nullptr; // the registry of this engine's device checkpoints (shc_checkpoint.hpp): released with the engine
+  void *d_health = nullptr;             // shc_engine_scan_health: per-wavefront selection masks and the levels of their counts (shc_health.hpp), allocated by the first scan
 };
 struct Resident;
 static bool resident_active(const shc_engine *e);
@@ -973,6 +974,7 @@ extern "C" int shc_engine_destroy(shc_engine *e) {
   (void)hipFree(e->d_stage);
   (void)hipFree(e->d_span);
   (void)hipFree(e->k_out);
+  (void)hipFree(e->d_health);
   if (e->half_stream[0]) { // (the streams belong to the process-wide pair)
     (void)hipEventDestroy(e->ev_main);
     (void)hipEventDestroy(e->ev_half[0]);
@@ -1565,6 +1567,7 @@ static int derive_tips(shc_engine *e) {
 
 #include "shc_leg_msgs.hpp" // the derived LegState fields (one host + device implementation) and shc_engine_get_leg_state_msgs
 #include "shc_frames.hpp"   // publishFrameTransforms: every joint / tip frame and the body frames, shc_engine_get_frame_transforms
+#include "shc_health.hpp"   // the reference's IK / clamping warnings per robot, a restore map and the selected robots: shc_engine_scan_health
 
 template <int NJ>
 static Pose host_fk_tip_pose(const shc_params &p, int leg, const double *q) {

@@ -305,6 +305,18 @@ extern "C" int shc_fleet_get_frame_transforms(shc_fleet *f, int frame, shc_leg_f
   }
   return SHC_OK;
 }
+// shc_engine_scan_health of every part: the records in the caller's instance order
+extern "C" int shc_fleet_scan_health(shc_fleet *f, const shc_health_criteria *criteria, shc_robot_health *health) {
+  if (!f || !health) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
+  std::vector<shc_robot_health> rows;
+  for (auto &p : f->parts) {
+    rows.resize(p.ids.size());
+    const int rc = shc_engine_scan_health(p.engine, 0, int64_t(p.ids.size()), criteria, rows.data(), nullptr, nullptr, nullptr, 0);
+    if (rc != SHC_OK) return rc;
+    for (size_t k = 0; k < p.ids.size(); ++k) health[p.ids[k]] = rows[k];
+  }
+  return SHC_OK;
+}
 extern "C" int shc_fleet_get_walk_state(shc_fleet *f, int32_t *walk_state) {
   if (!f || !walk_state) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
   for (auto &p : f->parts) {

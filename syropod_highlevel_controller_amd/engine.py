@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = [
     "shc_engine_get_frame_transforms", "shc_fleet_get_frame_transforms",
     "shc_engine_checkpoint_create", "shc_engine_checkpoint_update", "shc_checkpoint_destroy", "shc_engine_restore_instances", "shc_checkpoint_bytes",
     "shc_debug_checkpoint_field_class",
+    "shc_engine_scan_health", "shc_fleet_scan_health", "shc_debug_robot_health",
     "shc_peer_alloc", "shc_peer_open", "shc_peer_close", "shc_peer_scatter",
 ]
 
@@ -76,6 +77,27 @@ def _struct_dtype(struct) -> np.dtype:
 
 LEG_STATE_MSG_DTYPE = _struct_dtype(LegStateMsg)  # what BatchEngine.leg_state_msgs / MixedFleet.leg_state_msgs return
 LEG_FRAMES_DTYPE, BODY_FRAMES_DTYPE = _struct_dtype(LegFrames), _struct_dtype(BodyFrames)  # ... and what frame_transforms returns
+
+
+# shc_engine_scan_health (include/shc_batch.h): the SHC_HEALTH_* bits of shc_robot_health.flags / shc_health_criteria.select
+HEALTH_IK_DEVIATION, HEALTH_POSITION_LIMIT, HEALTH_SPEED_LIMIT, HEALTH_NEAR_LIMIT, HEALTH_TIP_DEVIATION, HEALTH_NONFINITE = 1, 2, 4, 8, 16, 32
+HEALTH_ALL = 63
+
+
+class HealthCriteria(C.Structure):
+    """shc_health_criteria: which flags select a robot, and the thresholds of NEAR_LIMIT / TIP_DEVIATION."""
+    _fields_ = [("select", C.c_uint32), ("reserved", C.c_uint32), ("near_limit_proximity", C.c_double), ("tip_deviation", C.c_double)]
+
+
+class RobotHealth(C.Structure):
+    """shc_robot_health: 32 bytes, no padding."""
+    _fields_ = [("min_limit_proximity", C.c_double), ("max_tip_deviation", C.c_double), ("max_speed_ratio", C.c_double), ("flags", C.c_uint32),
+                ("leg_masks", C.c_uint32)]
+
+
+# what BatchEngine.scan_health / MixedFleet.scan_health return; leg_masks: byte 0 IK deviation, 1 position limit, 2 speed limit, 3 non-finite, bit l = leg l
+ROBOT_HEALTH_DTYPE = np.dtype({"names": [k for k, _ in RobotHealth._fields_], "formats": [np.float64, np.float64, np.float64, np.uint32, np.uint32],
+                               "offsets": [getattr(RobotHealth, k).offset for k, _ in RobotHealth._fields_], "itemsize": C.sizeof(RobotHealth)})
 
 
 class CycleInputs(C.Structure):
@@ -345,6 +367,9 @@ def lib():
         L.shc_checkpoint_bytes.argtypes = [C.c_void_p]
         L.shc_checkpoint_bytes.restype = C.c_int64
         L.shc_debug_checkpoint_field_class.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.shc_engine_scan_health.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(HealthCriteria)] + [C.c_void_p] * 4 + [C.c_int]
+        L.shc_fleet_scan_health.argtypes = [C.c_void_p, C.POINTER(HealthCriteria), C.c_void_p]
+        L.shc_debug_robot_health.argtypes = [C.POINTER(Params), C.POINTER(HealthCriteria)] + [C.c_void_p] * 7 + [C.POINTER(RobotHealth)]
         L.shc_engine_resident_begin.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int]
         L.shc_engine_resident_post.argtypes = [C.c_void_p, C.POINTER(CycleInputs), C.POINTER(C.c_int64)]
         L.shc_engine_resident_bind_inputs.argtypes = [C.c_void_p, C.c_int, C.POINTER(CycleInputs)]
@@ -855,6 +880,53 @@ class BatchEngine:
                 raise ValueError(f"a source map has one entry per robot: expected shape ({self.n},), got {a.shape}")
             ptr, on_device = a.ctypes.data_as(C.c_void_p), 0
         _check(self.L.shc_engine_restore_instances(self.h, ck.h, ptr, on_device), "restore_instances")
+
+    def _device_out(self, obj, typestr: str, items: int, itemsize: int, what: str) -> Optional[C.c_void_p]:
+        """A device output of scan_health: an integer device pointer (taken as it is) or an object with ``__cuda_array_interface__`` - a contiguous
+        array of at least `items` elements of `typestr` (or, for records, of any type with as many bytes)."""
+        if obj is None:
+            return None
+        if not hasattr(obj, "__cuda_array_interface__"):
+            return C.c_void_p(int(obj))
+        cai = obj.__cuda_array_interface__
+        size = int(np.prod(cai["shape"], dtype=np.int64))
+        width = int(cai["typestr"][2:])
+        if cai.get("strides") is not None and size > 0:
+            dense, ok = width, True
+            for extent, stride in zip(reversed(cai["shape"]), reversed(cai["strides"])):
+                ok, dense = ok and (extent == 1 or stride == dense), dense * extent
+            if not ok:
+                raise ValueError(f"{what}: a device buffer must be contiguous")
+        if typestr is not None and cai["typestr"] != typestr:
+            raise ValueError(f"{what}: a device buffer of type {typestr} is expected, got {cai['typestr']}")
+        if size * width < items * itemsize:
+            raise ValueError(f"{what}: the device buffer holds {size * width} bytes, {items * itemsize} are needed")
+        return C.c_void_p(cai["data"][0])
+
+    def scan_health(self, select: int = 0, near_limit_proximity: float = 0.0, tip_deviation: float = 0.0, first: int = 0, count: Optional[int] = None,
+                    out_health=None, out_restore_map=None, out_selected=None, out_n_selected=None):
+        """The reference's IK warnings per robot in one device pass (shc_engine_scan_health): for instances [first, first + count) a record each
+        (ROBOT_HEALTH_DTYPE: min_limit_proximity, max_tip_deviation, max_speed_ratio, flags = HEALTH_* bits, leg_masks), and the robots whose
+        flags meet ``select``.  Without out_* arguments: (records, ascending int64 array of the selected instance ids), on the host.  With any
+        out_*: the device form - out_health (count records of 32 B, 16-byte aligned), out_restore_map (int64[n]: i for a selected robot of the
+        range, -1 elsewhere - what ``restore`` takes), out_selected (int64[count]; entries past the count stay as they are) and out_n_selected
+        (int64[1]) are device pointers (integers) or objects with ``__cuda_array_interface__``; they are written on the engine's stream without
+        a host wait; returns None."""
+        count = self.n - first if count is None else count
+        crit = HealthCriteria(int(select), 0, float(near_limit_proximity), float(tip_deviation))
+        fn = self.L.shc_engine_scan_health
+        if any(o is not None for o in (out_health, out_restore_map, out_selected, out_n_selected)):
+            rows = max(int(count), 0)
+            _check(fn(self.h, int(first), int(count), C.byref(crit), self._device_out(out_health, None, rows, 32, "out_health"),
+                      self._device_out(out_restore_map, "<i8", self.n, 8, "out_restore_map"), self._device_out(out_selected, "<i8", rows, 8, "out_selected"),
+                      self._device_out(out_n_selected, "<i8", 1, 8, "out_n_selected"), 1), "scan_health")
+            return None
+        health = np.zeros(max(int(count), 0), dtype=ROBOT_HEALTH_DTYPE)
+        selected = np.zeros(max(int(count), 0), dtype=np.int64)
+        n_sel = C.c_int64(0)
+        _check(fn(self.h, int(first), int(count), C.byref(crit), health.ctypes.data_as(C.c_void_p), None, selected.ctypes.data_as(C.c_void_p),
+                  C.cast(C.byref(n_sel), C.c_void_p), 0), "scan_health")
+        return health, selected[:n_sel.value].copy()
 
     # -- per-leg Leg methods (model.h:448-492), batched: instances [first, first + count), leg = -1 for every leg
     def _rows(self, first, count, leg):

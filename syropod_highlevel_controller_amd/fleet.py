@@ -106,6 +106,14 @@ class MixedFleet:
                        "shc_fleet_get_frame_transforms")
         return lf, bf
 
+    def scan_health(self, select: int = 0, near_limit_proximity: float = 0.0, tip_deviation: float = 0.0):
+        """BatchEngine.scan_health's records for every robot in the caller's instance order (ROBOT_HEALTH_DTYPE, shape (n,)).  Records only:
+        restore maps and selected lists are per engine (parts()), as device checkpoints are."""
+        crit = _engine.HealthCriteria(int(select), 0, float(near_limit_proximity), float(tip_deviation))
+        health = np.zeros(self.n, dtype=_engine.ROBOT_HEALTH_DTYPE)
+        _engine._check(self.L.shc_fleet_scan_health(self.h, C.byref(crit), self._p(health)), "shc_fleet_scan_health")
+        return health
+
     def all_gather_joints(self):
         """Device pointers (one per device slot) of the gathered [n][max_legs][max_dof] joint buffers."""
         bufs = (C.c_void_p * self.n_devices)()
