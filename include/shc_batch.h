@@ -874,7 +874,8 @@ int shc_engine_set_state(shc_engine *e, int64_t first, int64_t count, const shc_
  * under: after shc_engine_change_gait or shc_engine_adjust_parameter, and while an adjusted parameter waits for its loop, a restore is
  * SHC_ERR_UNSUPPORTED and changes nothing - step, then shc_engine_checkpoint_update.  shc_engine_destroy releases the device memory of the
  * engine's checkpoints; their handles stay valid only for shc_checkpoint_destroy (every other use: SHC_ERR_INVALID_ARG).
- * Split steps are joined first; SHC_ERR_BUSY in resident mode.  Fleets (shc_fleet_*) and migration between engines stay on the host route.
+ * Split steps are joined first; SHC_ERR_BUSY in resident mode.  Fleets have the same calls in the caller's instance order
+ * (shc_fleet_checkpoint_*, shc_fleet_restore_instances, shc_fleet_scan_and_restore below); migration between engines stays on the host route.
  */
 typedef struct shc_checkpoint shc_checkpoint;
 /* Allocates the checkpoint's device arrays (the size of the engine's state planes and records), then captures as shc_engine_checkpoint_update. */
@@ -991,8 +992,55 @@ int shc_fleet_get_leg_state_msgs(shc_fleet *f, shc_leg_state_msg *msgs);
  * legs a robot does not have all zero, and body[i]; either may be NULL (not both).  Synchronises every part's stream. */
 int shc_fleet_get_frame_transforms(shc_fleet *f, int frame, shc_leg_frames *legs /* [n][max_legs] */, shc_body_frames *body /* [n] */);
 /* shc_engine_scan_health of every robot of the fleet: the records in the caller's instance order (host memory; criteria may be NULL).  Records only -
- * restore maps and selected lists are per engine, as device checkpoints are (shc_fleet_part).  Synchronises every part's stream. */
+ * shc_fleet_scan_and_restore below resets the selected robots in the same pass; selected lists are per engine (shc_fleet_part).  Synchronises
+ * every part's stream. */
 int shc_fleet_scan_health(shc_fleet *f, const shc_health_criteria *criteria, shc_robot_health *health /* [n] */);
+/*
+ * Fleet checkpoints: the device checkpoints of every part behind one handle, and maps in the CALLER's instance order.  A fleet checkpoint is one
+ * shc_checkpoint per part, made, captured and restored through the shc_engine_* calls above on the part's own stream: everything said there
+ * about what a restore moves, about held inputs and about the engine-wide facts holds part by part.  The fleet's FIRST shc_fleet_checkpoint_create
+ * also allocates what the calls below work with - per part a small block on its device (its caller ids, its restore map, health records, a count)
+ * and, when one device holds every part, the tables caller id -> (part, id within the part) on that device - and uploads it synchronously; no
+ * later call allocates anything but a new checkpoint's own arrays.
+ * A handle belongs to its fleet: with another fleet, or once its fleet has been destroyed, every use but shc_fleet_checkpoint_destroy is
+ * SHC_ERR_INVALID_ARG.  shc_fleet_destroy releases the device memory of the fleet's checkpoints, as shc_engine_destroy does for an engine's.
+ * Errors of the parts pass through unchanged - SHC_ERR_UNSUPPORTED after shc_engine_change_gait / shc_engine_adjust_parameter on a part (step,
+ * then shc_fleet_checkpoint_update), SHC_ERR_BUSY while a part is in resident mode - and every part is asked before the first launch: when one
+ * part refuses, no part has changed, whichever robots the call named.
+ */
+typedef struct shc_fleet_checkpoint shc_fleet_checkpoint;
+int shc_fleet_checkpoint_create(shc_fleet *f, shc_fleet_checkpoint **out);
+/* shc_engine_checkpoint_update of every part, on its stream: no host wait. */
+int shc_fleet_checkpoint_update(shc_fleet *f, shc_fleet_checkpoint *ck);
+/* shc_checkpoint_destroy of every part's checkpoint (waits for the part's stream while the fleet lives), then frees the handle.  NULL: SHC_ERR_INVALID_ARG. */
+int shc_fleet_checkpoint_destroy(shc_fleet_checkpoint *ck);
+/* Device bytes the parts' checkpoints hold (0 for NULL, and once the fleet has been destroyed). */
+int64_t shc_fleet_checkpoint_bytes(const shc_fleet_checkpoint *ck);
+/* Instance i <- the checkpoint's instance source[i], both in the caller's order; source[i] < 0 leaves instance i exactly as it is; NULL = the
+ * identity (restore everything, either form).  The result is the engine route's: instance i's slot of its part reads back
+ * (shc_engine_get_state / shc_engine_get_aux_state) as after the part's own shc_engine_restore_instances with the translated map.
+ * A source must be of its destination's part.  Another morphology is another layout; another part of the same morphology (another device's
+ * shard of the bin) would need a peer copy of checkpoint rows, which is not implemented.
+ * HOST map (on_device = 0): validated as a whole first - an entry >= n or of another morphology is SHC_ERR_INVALID_ARG, an entry of another
+ * part of the same morphology SHC_ERR_UNSUPPORTED, and nothing has changed - then split into the parts' maps on the host and restored with
+ * one launch per part that has a non-negative entry (the engine's host form: that part's stream is synchronised); a part the map does not
+ * name is not touched and its stream is not waited for.
+ * DEVICE map (on_device = 1): [n] int64 on the device that holds EVERY part of the fleet; a fleet that spans devices answers
+ * SHC_ERR_UNSUPPORTED (use the host form).  Each part translates its slice on its own stream directly before its restore: no host wait, no
+ * allocation.  The parts' streams are the fleet's own and nothing orders them behind a stream of the caller's: the caller's writes to `source`
+ * must be COMPLETE before the call (synchronise the stream that wrote it), and the buffer must stay untouched until the parts have read it
+ * (shc_fleet_synchronize, or any later synchronising call).  An entry that is out of range, of another morphology or of another part leaves
+ * its destination alone, as an entry >= n does in the engine's device form. */
+int shc_fleet_restore_instances(shc_fleet *f, const shc_fleet_checkpoint *ck, const int64_t *source /* [n], CALLER's instance ids */, int on_device);
+/* step -> scan -> restore for a fleet, no map crossing the host: on every part's stream shc_engine_scan_health(.., restore_map = the part's own map
+ * buffer, on_device = 1), then shc_engine_restore_instances(.., that buffer, on_device = 1) - the robots that meet `criteria` are reset to the
+ * checkpoint, the others keep walking.  criteria = NULL (or select = 0) selects nobody: a scan and nothing else.  health ([n], HOST, caller's order,
+ * may be NULL) receives the records as shc_fleet_scan_health fills them - the records BEFORE the restore; n_restored (HOST, may be NULL) the sum
+ * of the parts' selected counts.  Asking for either synchronises every part's stream; with both NULL the call returns without waiting.
+ * The scan refreshes the derived model / poser tips as shc_engine_scan_health does - from the state BEFORE the restore: a restored robot's
+ * are refreshed by the next getter or scan, as after shc_engine_restore_instances. */
+int shc_fleet_scan_and_restore(shc_fleet *f, const shc_fleet_checkpoint *ck, const shc_health_criteria *criteria,
+                               shc_robot_health *health /* [n] host, caller order, may be NULL */, int64_t *n_restored /* host, may be NULL */);
 /* The exchange step of a sharded batch: every device ends up with the desired joint positions of ALL instances
  * ([n][max_legs][max_dof], caller's order, NaN padded) in its own HBM, copied device to device (hipMemcpyPeerAsync: xGMI on an
  * MI355X node).  device_buffers[d] (may be NULL) receives device_ids[d]'s buffer; the buffers belong to the fleet. */

@@ -24,6 +24,8 @@ struct FleetPart {
   hipEvent_t g_ready = nullptr;       // recorded on `stream` once g_joints is complete
   std::vector<double *> r_joints;     // per device slot (other devices only): the landing buffer of the peer copy ...
   std::vector<int64_t *> r_ids;       // ... and the ids over there
+  // fleet checkpoints (shc_fleet_checkpoint.hpp): one block on the part's device, allocated by the first shc_fleet_checkpoint_create and kept
+  char *ck_block = nullptr;           // [health records][restore map][ids][selected count], FleetCkBlock gives the offsets
 };
 
 struct shc_fleet {
@@ -36,10 +38,19 @@ struct shc_fleet {
   std::vector<hipStream_t> gather_stream; // per device: incoming peer copies + their placement
   std::vector<double> host_a, host_b;
   std::vector<int32_t> host_i;
+  // fleet checkpoints (shc_fleet_checkpoint.hpp)
+  struct shc_fleet_checkpoint *checkpoints = nullptr; // the registry of this fleet's checkpoint handles: orphaned with the fleet
+  std::vector<int32_t> ck_part_of;   // caller's id -> its part ...
+  std::vector<int64_t> ck_local_of;  // ... and its instance id inside that part
+  char *ck_tables = nullptr;         // the two tables on the device, when one device holds every part: local_of [n] int64, then part_of [n] int32
+  bool ck_ready = false;
 };
+static void fleet_release_checkpoints(shc_fleet *f); // orphan the fleet's checkpoint handles (shc_fleet_destroy)
 
 static void fleet_free(shc_fleet *f) {
   if (!f) return;
+  fleet_release_checkpoints(f); // (the parts' engines release the device arrays of their own checkpoints below)
+  const int ck_device = f->parts.empty() ? 0 : f->parts[0].device;
   for (auto &p : f->parts) {
     if (p.engine) shc_engine_destroy(p.engine);
     if (p.stream) {
@@ -51,12 +62,17 @@ static void fleet_free(shc_fleet *f) {
     (void)hipSetDevice(p.device);
     (void)hipFree(p.g_joints);
     (void)hipFree(p.g_ids);
+    (void)hipFree(p.ck_block);
     if (p.g_ready) (void)hipEventDestroy(p.g_ready);
     for (size_t d = 0; d < p.r_joints.size(); ++d) {
       (void)hipSetDevice(f->devices[d]);
       (void)hipFree(p.r_joints[d]);
       (void)hipFree(p.r_ids[d]);
     }
+  }
+  if (f->ck_tables) { // (every part's stream has drained: shc_engine_destroy waits for it)
+    (void)hipSetDevice(ck_device);
+    (void)hipFree(f->ck_tables);
   }
   for (size_t d = 0; d < f->gather.size(); ++d) {
     (void)hipSetDevice(f->devices[d]);
@@ -419,6 +435,8 @@ extern "C" int shc_fleet_all_gather_joints(shc_fleet *f, double **device_buffers
     for (int d = 0; d < nd; ++d) device_buffers[d] = f->gather[d];
   return SHC_OK;
 }
+
+#include "shc_fleet_checkpoint.hpp" // shc_fleet_checkpoint_*, shc_fleet_restore_instances, shc_fleet_scan_and_restore
 
 // ================================================================================================ one process per GPU: the exchange over peer copies
 // The all-gather of the final joint buffer (BASELINE.json north_star) without a collective library, for the one-process-per-GPU host (bench.py

@@ -55,6 +55,8 @@ EXPORTED_SYMBOLS = [
     "shc_engine_checkpoint_create", "shc_engine_checkpoint_update", "shc_checkpoint_destroy", "shc_engine_restore_instances", "shc_checkpoint_bytes",
     "shc_debug_checkpoint_field_class",
     "shc_engine_scan_health", "shc_fleet_scan_health", "shc_debug_robot_health",
+    "shc_fleet_checkpoint_create", "shc_fleet_checkpoint_update", "shc_fleet_checkpoint_destroy", "shc_fleet_checkpoint_bytes",
+    "shc_fleet_restore_instances", "shc_fleet_scan_and_restore",
     "shc_peer_alloc", "shc_peer_open", "shc_peer_close", "shc_peer_scatter",
 ]
 
@@ -370,6 +372,13 @@ def lib():
         L.shc_engine_scan_health.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(HealthCriteria)] + [C.c_void_p] * 4 + [C.c_int]
         L.shc_fleet_scan_health.argtypes = [C.c_void_p, C.POINTER(HealthCriteria), C.c_void_p]
         L.shc_debug_robot_health.argtypes = [C.POINTER(Params), C.POINTER(HealthCriteria)] + [C.c_void_p] * 7 + [C.POINTER(RobotHealth)]
+        L.shc_fleet_checkpoint_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.shc_fleet_checkpoint_update.argtypes = [C.c_void_p, C.c_void_p]
+        L.shc_fleet_checkpoint_destroy.argtypes = [C.c_void_p]
+        L.shc_fleet_checkpoint_bytes.argtypes = [C.c_void_p]
+        L.shc_fleet_checkpoint_bytes.restype = C.c_int64
+        L.shc_fleet_restore_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.shc_fleet_scan_and_restore.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(HealthCriteria), C.c_void_p, C.POINTER(C.c_int64)]
         L.shc_engine_resident_begin.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int]
         L.shc_engine_resident_post.argtypes = [C.c_void_p, C.POINTER(CycleInputs), C.POINTER(C.c_int64)]
         L.shc_engine_resident_bind_inputs.argtypes = [C.c_void_p, C.c_int, C.POINTER(CycleInputs)]
@@ -484,6 +493,22 @@ def generate_tables_batch(params_list, device: int = 0):
     status = (C.c_int32 * n)()
     _check(lib().shc_generate_tables_batch(arr, n, out, status, device), "shc_generate_tables_batch")
     return list(out), np.array(status[:], dtype=np.int32)
+
+
+def _source_map(source, n: int):
+    """The source map of a restore as (pointer, on_device, the array that owns a host pointer): None, a host int64 array of length n, or an object
+    with ``__cuda_array_interface__`` (a contiguous int64 array of length n on the device)."""
+    if source is None:
+        return None, 0, None
+    if hasattr(source, "__cuda_array_interface__"):
+        cai = source.__cuda_array_interface__
+        if cai["typestr"] != "<i8" or tuple(cai["shape"]) != (n,) or cai.get("strides") not in (None, (8,)):
+            raise ValueError(f"a device source map must be a contiguous int64 array of length {n}")
+        return C.c_void_p(cai["data"][0]), 1, None
+    a = np.ascontiguousarray(source, dtype=np.int64)
+    if a.shape != (n,):
+        raise ValueError(f"a source map has one entry per robot: expected shape ({n},), got {a.shape}")
+    return a.ctypes.data_as(C.c_void_p), 0, a
 
 
 class Checkpoint:
@@ -867,18 +892,7 @@ class BatchEngine:
         >= n raises), an object with ``__cuda_array_interface__`` (a contiguous int64 array of length n on the engine's device, e.g. a torch tensor:
         read on the engine's stream without a host wait - the writes to it must be ordered before this call on that stream; an entry >= n leaves its
         robot alone), or None for every robot.  Reset from a mask: ``torch.where(done, torch.arange(n), -1)``."""
-        if source is None:
-            ptr, on_device = None, 0
-        elif hasattr(source, "__cuda_array_interface__"):
-            cai = source.__cuda_array_interface__
-            if cai["typestr"] != "<i8" or tuple(cai["shape"]) != (self.n,) or cai.get("strides") not in (None, (8,)):
-                raise ValueError(f"a device source map must be a contiguous int64 array of length {self.n}")
-            ptr, on_device = C.c_void_p(cai["data"][0]), 1
-        else:
-            a = np.ascontiguousarray(source, dtype=np.int64)
-            if a.shape != (self.n,):
-                raise ValueError(f"a source map has one entry per robot: expected shape ({self.n},), got {a.shape}")
-            ptr, on_device = a.ctypes.data_as(C.c_void_p), 0
+        ptr, on_device, _keep = _source_map(source, self.n)
         _check(self.L.shc_engine_restore_instances(self.h, ck.h, ptr, on_device), "restore_instances")
 
     def _device_out(self, obj, typestr: str, items: int, itemsize: int, what: str) -> Optional[C.c_void_p]:

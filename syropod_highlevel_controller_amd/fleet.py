@@ -15,11 +15,52 @@ from . import engine as _engine
 from .params import Params
 
 
+class FleetCheckpoint:
+    """The state of every robot of a fleet, kept in device memory part by part (shc_fleet_checkpoint_create): what ``MixedFleet.restore`` and
+    ``MixedFleet.scan_and_restore`` reset or clone robots from.  A context manager; closed with its fleet (``close()`` afterwards is a no-op
+    for the caller).  Mirrors ``engine.Checkpoint``."""
+
+    def __init__(self, fleet: "MixedFleet"):
+        self.fleet, self.L, self.h = fleet, fleet.L, None
+        h = C.c_void_p()
+        _engine._check(self.L.shc_fleet_checkpoint_create(fleet.h, C.byref(h)), "shc_fleet_checkpoint_create")
+        self.h = h
+        fleet._checkpoints.append(self)
+
+    def update(self):
+        """Capture every part's state again into the same device storage: copies on each part's stream, no host wait."""
+        _engine._check(self.L.shc_fleet_checkpoint_update(self.fleet.h, self.h), "shc_fleet_checkpoint_update")
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.L.shc_fleet_checkpoint_bytes(self.h)) if self.h else 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.shc_fleet_checkpoint_destroy(self.h)
+            self.h = None
+            if self in self.fleet._checkpoints:
+                self.fleet._checkpoints.remove(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class MixedFleet:
     def __init__(self, morphologies: Sequence[Params], morph_id, devices: Sequence[int] = (0,)):
         """morphologies[k] describes bin k; morph_id[i] in [0, len(morphologies)) assigns instance i to a bin; every bin is
         sharded over `devices` (repeating a device id gives several shards on that device)."""
         self.L = _engine.lib()
+        self._checkpoints = []
         if self.L.shc_device_count() < 1:
             raise _engine.ShcError("no HIP device visible: the batched engine has no CPU fallback")
         self.morph_id = np.ascontiguousarray(morph_id, dtype=np.int32)
@@ -36,6 +77,8 @@ class MixedFleet:
         self.max_legs, self.max_dof = a.value, b.value
 
     def close(self):
+        for ck in list(getattr(self, "_checkpoints", [])):
+            ck.close()
         if getattr(self, "h", None):
             self.L.shc_fleet_destroy(self.h)
             self.h = None
@@ -108,11 +151,36 @@ class MixedFleet:
 
     def scan_health(self, select: int = 0, near_limit_proximity: float = 0.0, tip_deviation: float = 0.0):
         """BatchEngine.scan_health's records for every robot in the caller's instance order (ROBOT_HEALTH_DTYPE, shape (n,)).  Records only:
-        restore maps and selected lists are per engine (parts()), as device checkpoints are."""
+        ``scan_and_restore`` resets the selected robots in the same pass; selected lists are per engine (parts())."""
         crit = _engine.HealthCriteria(int(select), 0, float(near_limit_proximity), float(tip_deviation))
         health = np.zeros(self.n, dtype=_engine.ROBOT_HEALTH_DTYPE)
         _engine._check(self.L.shc_fleet_scan_health(self.h, C.byref(crit), self._p(health)), "shc_fleet_scan_health")
         return health
+
+    def checkpoint(self) -> FleetCheckpoint:
+        """A device-resident checkpoint of every robot's state as of now (on each part's stream).  The fleet's first one also uploads the tables
+        between the caller's order and the parts' (shc_fleet_checkpoint_create)."""
+        return FleetCheckpoint(self)
+
+    def restore(self, ck: FleetCheckpoint, source=None):
+        """Robot i <- the checkpoint's robot ``source[i]``, both in the caller's order; an entry < 0 leaves robot i alone; None = every robot.
+        ``source``: a host int64 array or list of length n - validated first: an entry >= n, of another morphology or of another part raises and
+        nothing changes - or an object with ``__cuda_array_interface__`` (a contiguous int64 array of length n on the fleet's one device, e.g. a
+        torch tensor): no host wait, an entry that is out of range or of another morphology / part leaves its robot alone.  The parts run on
+        streams of their own: finish the writes to a device map first (``torch.cuda.current_stream().synchronize()``)."""
+        ptr, on_device, _keep = _engine._source_map(source, self.n)
+        _engine._check(self.L.shc_fleet_restore_instances(self.h, ck.h, ptr, on_device), "shc_fleet_restore_instances")
+
+    def scan_and_restore(self, ck: FleetCheckpoint, select: int, near_limit_proximity: float = 0.0, tip_deviation: float = 0.0, health: bool = False):
+        """step -> scan -> restore without a map crossing the host (shc_fleet_scan_and_restore): the robots whose flags meet ``select``
+        (engine.HEALTH_* bits) are reset to the checkpoint on their part's stream, the others keep walking.  Returns the number of robots restored,
+        or with ``health=True`` (n_restored, records): scan_health()'s records as they were BEFORE the restore.  select = 0 is a scan only."""
+        crit = _engine.HealthCriteria(int(select), 0, float(near_limit_proximity), float(tip_deviation))
+        records = np.zeros(self.n, dtype=_engine.ROBOT_HEALTH_DTYPE) if health else None
+        n_restored = C.c_int64(0)
+        _engine._check(self.L.shc_fleet_scan_and_restore(self.h, ck.h, C.byref(crit), None if records is None else self._p(records), C.byref(n_restored)),
+                       "shc_fleet_scan_and_restore")
+        return (n_restored.value, records) if health else n_restored.value
 
     def all_gather_joints(self):
         """Device pointers (one per device slot) of the gathered [n][max_legs][max_dof] joint buffers."""
