@@ -964,7 +964,8 @@ int shc_debug_robot_health(const shc_params *params, const shc_health_criteria *
  * by morphology - the cycle kernel keeps one morphology's tables in LDS and maps one leg to one lane - and every bin is split
  * into contiguous shards over device_ids[0 .. n_devices) (NULL / 0 = device 0); each (bin, device) part is an engine on its own
  * HIP stream.  Nothing is exchanged while stepping.  All arrays are HOST arrays in the CALLER's instance order; per-leg arrays
- * are padded to [n][max_legs][max_k] (shc_fleet_shape), outputs are NaN where a morphology has no such leg / joint.
+ * are padded to [n][max_legs][max_k] (shc_fleet_shape), outputs are NaN where a morphology has no such leg / joint.  The same calls
+ * with DEVICE arrays, for a caller that lives on the GPU: shc_fleet_set_inputs_device / shc_fleet_get_outputs_device below.
  */
 typedef struct shc_fleet shc_fleet;
 int shc_fleet_create(const shc_params *params, int n_morphologies, const int32_t *morph_id, int64_t n_instances, const int *device_ids,
@@ -1041,6 +1042,64 @@ int shc_fleet_restore_instances(shc_fleet *f, const shc_fleet_checkpoint *ck, co
  * are refreshed by the next getter or scan, as after shc_engine_restore_instances. */
 int shc_fleet_scan_and_restore(shc_fleet *f, const shc_fleet_checkpoint *ck, const shc_health_criteria *criteria,
                                shc_robot_health *health /* [n] host, caller order, may be NULL */, int64_t *n_restored /* host, may be NULL */);
+/*
+ * Fleet device I/O: the setters and getters above with DEVICE arrays in the CALLER's instance order, for a simulator or learner whose commands
+ * and observations never leave the GPU.  Nothing crosses the host: per part and direction one kernel on the part's own stream permutes between
+ * the caller's padded order and the part's dense order, and the engine's own device forms (shc_engine_set_*(.., on_device = 1), shc_engine_get_*
+ * (.., on_device = 1)) stand between that and the state.
+ * shc_fleet_set_inputs_device leaves every robot's state, and every engine-side fact a setter touches (touchdown detection and its step planes
+ * in rough terrain mode, the first-effort switch, the manual-posing switch, quaternion normalisation), exactly as shc_fleet_set_velocity /
+ * _set_imu / _set_pose_input / _set_tip_force / _set_joint_effort with host copies of the same arrays do.  A NULL member holds that input.
+ * shc_fleet_get_outputs_device writes, member by member, the bytes shc_fleet_get_joint_state / _get_walk_state / _get_leg_state_msgs /
+ * _get_frame_transforms / _scan_health write to host arrays, padding included (the NaN of q / qd, all-zero records of legs a robot does not
+ * have): every entry of every requested buffer is written by every call.  The derived model / poser tips are refreshed as those getters do.
+ * Staging (per part: its rows of all inputs, or of one joint array, or one chunk of records) and the parts' caller ids on the device are
+ * allocated by the fleet's first device I/O call and kept; no later call allocates.  Record outputs (leg messages, frames, health) walk each
+ * part in chunks of shc_fleet_set_io_chunk robots (0 = the default, 8 192), so staging does not grow with the records of the whole fleet;
+ * changing the chunk waits for the parts and lets the next call allocate again.  shc_fleet_io_bytes: the device bytes held - the staging, and the parts' ids from
+ * the moment any of their three users (device I/O, checkpoints, the exchange step) has uploaded them; 0 before that.
+ * Every part is asked before the first launch: SHC_ERR_BUSY while a part is in resident mode, and nothing has changed.  A fleet that spans
+ * devices answers SHC_ERR_UNSUPPORTED to the four device entry points (the caller's arrays live on one device, as the device map of
+ * shc_fleet_restore_instances; the host forms remain).  SHC_ERR_INVALID_ARG: NULL fleet or struct, every output NULL, reserved != 0, an unknown
+ * frame, a record buffer that is not 16-byte aligned (as the engine forms require), criteria the scan refuses.  SHC_ERR_UNSUPPORTED passes
+ * through from a part without SHC_FEAT_ODOMETRY when body_frames or SHC_FRAME_ODOM_IDEAL is asked for.  pose_reset_mode stays on the part
+ * route (shc_fleet_part, shc_engine_set_pose_reset_mode).
+ * STREAMS.  The parts' streams are the fleet's own.  Without the two ordering calls the rule is the one of shc_fleet_restore_instances' device
+ * map: the caller's writes to the input arrays must be COMPLETE before the call, the arrays must stay untouched until the parts have read them
+ * (shc_fleet_synchronize), and the outputs are complete after shc_fleet_synchronize.  With them no host wait is needed:
+ *   shc_fleet_order_after_stream(f, s)   every part's stream waits for what is queued on `s` now (inputs written by kernels on s);
+ *   shc_fleet_order_stream_after(f, s)   `s` waits for what is queued on every part's stream now; parts with split steps in flight are joined
+ *                                        first (shc_engine_join).
+ * i.e. order_after_stream(s) -> set inputs -> step -> get outputs -> order_stream_after(s) -> the caller's kernels on s.  Both are events only,
+ * one per part and direction, created at first use with timing disabled.  stream = NULL is the default stream.
+ */
+typedef struct shc_fleet_inputs {              /* DEVICE arrays, CALLER's instance order; NULL member = that input is held */
+  const double *linear_xy;                     /* [n][2] */
+  const double *angular;                       /* [n] */
+  const double *imu_orientation_wxyz;          /* [n][4], normalised on entry as shc_engine_set_imu does */
+  const double *imu_angular_velocity;          /* [n][3] */
+  const double *pose_translation_velocity;     /* [n][3] */
+  const double *pose_rotation_velocity;        /* [n][3] */
+  const double *tip_force;                     /* [n][max_legs][3];       entries beyond a robot's legs are ignored */
+  const double *joint_effort;                  /* [n][max_legs][max_dof]; entries beyond a bin's (legs, dof) are ignored */
+} shc_fleet_inputs;
+int shc_fleet_set_inputs_device(shc_fleet *f, const shc_fleet_inputs *in);
+typedef struct shc_fleet_outputs {             /* DEVICE buffers, CALLER's instance order; NULL member = not asked for (not all NULL) */
+  double *q, *qd;                              /* [n][max_legs][max_dof]: exactly the array shc_fleet_get_joint_state fills, NaN padding included */
+  int32_t *walk_state;                         /* [n] */
+  shc_leg_state_msg *leg_state_msgs;           /* [n][max_legs]; records of legs a robot does not have all zero */
+  shc_leg_frames *leg_frames;                  /* [n][max_legs]; same rule */
+  shc_body_frames *body_frames;                /* [n] */
+  int32_t frame;                               /* SHC_FRAME_* for leg_frames */
+  int32_t reserved;                            /* 0 */
+  shc_robot_health *health;                    /* [n] */
+  const shc_health_criteria *criteria;         /* HOST, may be NULL: as shc_fleet_scan_health */
+} shc_fleet_outputs;
+int shc_fleet_get_outputs_device(shc_fleet *f, const shc_fleet_outputs *out);
+int shc_fleet_order_after_stream(shc_fleet *f, void *stream);
+int shc_fleet_order_stream_after(shc_fleet *f, void *stream);
+int shc_fleet_set_io_chunk(shc_fleet *f, int64_t robots);      /* staging granularity of the record outputs, robots per part; 0 = default */
+int64_t shc_fleet_io_bytes(const shc_fleet *f);                /* device bytes the I/O path holds (ids, staging); 0 before first use */
 /* The exchange step of a sharded batch: every device ends up with the desired joint positions of ALL instances
  * ([n][max_legs][max_dof], caller's order, NaN padded) in its own HBM, copied device to device (hipMemcpyPeerAsync: xGMI on an
  * MI355X node).  device_buffers[d] (may be NULL) receives device_ids[d]'s buffer; the buffers belong to the fleet. */

@@ -18,14 +18,18 @@ struct FleetPart {
   int morph = 0, device = 0, device_slot = 0;
   hipStream_t stream = nullptr;
   std::vector<int64_t> ids; // caller's instance ids, ascending
+  int64_t *d_ids = nullptr;           // ... and on the part's device (fleet_part_ids): the one copy the exchange step, the checkpoints and the device I/O read
   // the exchange step's buffers, allocated by the first shc_fleet_all_gather_joints and kept
   double *g_joints = nullptr;         // this part's joints [rows][L][D] on its own device
-  int64_t *g_ids = nullptr;           // its ids on its own device
   hipEvent_t g_ready = nullptr;       // recorded on `stream` once g_joints is complete
   std::vector<double *> r_joints;     // per device slot (other devices only): the landing buffer of the peer copy ...
   std::vector<int64_t *> r_ids;       // ... and the ids over there
   // fleet checkpoints (shc_fleet_checkpoint.hpp): one block on the part's device, allocated by the first shc_fleet_checkpoint_create and kept
-  char *ck_block = nullptr;           // [health records][restore map][ids][selected count], FleetCkBlock gives the offsets
+  char *ck_block = nullptr;           // [health records][restore map][selected count], FleetCkBlock gives the offsets
+  // device I/O (shc_fleet_io.hpp): staging and the two ordering events, made by the first device I/O call and kept
+  char *io_stage = nullptr;
+  size_t io_stage_bytes = 0;
+  hipEvent_t io_after = nullptr, io_before = nullptr; // the part's stream after the caller's / the caller's stream after the part's
 };
 
 struct shc_fleet {
@@ -44,6 +48,9 @@ struct shc_fleet {
   std::vector<int64_t> ck_local_of;  // ... and its instance id inside that part
   char *ck_tables = nullptr;         // the two tables on the device, when one device holds every part: local_of [n] int64, then part_of [n] int32
   bool ck_ready = false;
+  // device I/O (shc_fleet_io.hpp)
+  int64_t io_chunk = 0; // robots per part and staging pass of the record outputs; 0 = the default
+  bool io_ready = false;
 };
 static void fleet_release_checkpoints(shc_fleet *f); // orphan the fleet's checkpoint handles (shc_fleet_destroy)
 
@@ -61,8 +68,11 @@ static void fleet_free(shc_fleet *f) {
   for (auto &p : f->parts) {
     (void)hipSetDevice(p.device);
     (void)hipFree(p.g_joints);
-    (void)hipFree(p.g_ids);
+    (void)hipFree(p.d_ids);
     (void)hipFree(p.ck_block);
+    (void)hipFree(p.io_stage);
+    if (p.io_after) (void)hipEventDestroy(p.io_after);
+    if (p.io_before) (void)hipEventDestroy(p.io_before);
     if (p.g_ready) (void)hipEventDestroy(p.g_ready);
     for (size_t d = 0; d < p.r_joints.size(); ++d) {
       (void)hipSetDevice(f->devices[d]);
@@ -182,6 +192,15 @@ extern "C" int shc_fleet_part(const shc_fleet *f, int k, shc_engine **engine, in
 extern "C" int shc_fleet_part_instances(const shc_fleet *f, int k, int64_t *ids) {
   if (!f || !ids || k < 0 || k >= int(f->parts.size())) return fail(SHC_ERR_INVALID_ARG, "part index out of range / ids NULL");
   std::copy(f->parts[k].ids.begin(), f->parts[k].ids.end(), ids);
+  return SHC_OK;
+}
+
+// The part's caller ids on its own device, uploaded (synchronously) by the first user and kept.
+static int fleet_part_ids(FleetPart &p) {
+  if (p.d_ids) return SHC_OK;
+  HIP_TRY(hipSetDevice(p.device));
+  HIP_TRY(hipMalloc(&p.d_ids, p.ids.size() * 8));
+  HIP_TRY(hipMemcpy(p.d_ids, p.ids.data(), p.ids.size() * 8, hipMemcpyHostToDevice));
   return SHC_OK;
 }
 
@@ -381,9 +400,8 @@ extern "C" int shc_fleet_all_gather_joints(shc_fleet *f, double **device_buffers
     const size_t rows = p.ids.size(), elems = rows * pp.leg_count * max_dof(pp);
     HIP_TRY(hipSetDevice(p.device));
     HIP_TRY(hipMalloc(&p.g_joints, elems * 8));
-    HIP_TRY(hipMalloc(&p.g_ids, rows * 8));
     HIP_TRY(hipEventCreateWithFlags(&p.g_ready, hipEventDisableTiming));
-    HIP_TRY(hipMemcpy(p.g_ids, p.ids.data(), rows * 8, hipMemcpyHostToDevice));
+    if (const int rc = fleet_part_ids(p); rc != SHC_OK) return rc;
     p.r_joints.assign(nd, nullptr);
     p.r_ids.assign(nd, nullptr);
     for (int d = 0; d < nd; ++d) {
@@ -404,7 +422,7 @@ extern "C" int shc_fleet_all_gather_joints(shc_fleet *f, double **device_buffers
     HIP_TRY(hipEventRecord(p.g_ready, p.stream));
     for (int d = 0; d < nd; ++d)
       if (f->devices[d] == p.device) { // (also covers several device slots naming one device)
-        fleet_place_joints_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, p.stream>>>(f->gather[d], p.g_joints, p.g_ids, rows, L, D, f->max_legs,
+        fleet_place_joints_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, p.stream>>>(f->gather[d], p.g_joints, p.d_ids, rows, L, D, f->max_legs,
                                                                                                    f->max_dof);
         HIP_TRY(hipGetLastError());
       }
@@ -437,6 +455,7 @@ extern "C" int shc_fleet_all_gather_joints(shc_fleet *f, double **device_buffers
 }
 
 #include "shc_fleet_checkpoint.hpp" // shc_fleet_checkpoint_*, shc_fleet_restore_instances, shc_fleet_scan_and_restore
+#include "shc_fleet_io.hpp" // shc_fleet_set_inputs_device, shc_fleet_get_outputs_device, the two ordering calls
 
 // ================================================================================================ one process per GPU: the exchange over peer copies
 // The all-gather of the final joint buffer (BASELINE.json north_star) without a collective library, for the one-process-per-GPU host (bench.py

@@ -11,15 +11,14 @@
 
 // the block a part keeps on its own device (FleetPart::ck_block), every piece at a multiple of 16 bytes
 struct FleetCkBlock {
-  size_t health, map, ids, count, bytes; // [rows] shc_robot_health, [rows] int64 restore map, [rows] int64 caller's ids, [1] int64 selected count
+  size_t health, map, count, bytes; // [rows] shc_robot_health, [rows] int64 restore map, [1] int64 selected count (the caller's ids: FleetPart::d_ids)
 };
 static FleetCkBlock fleet_ck_block(size_t rows) {
   const size_t r16 = (rows * 8 + 15) & ~size_t(15);
   FleetCkBlock b;
   b.health = 0;
   b.map = rows * sizeof(shc_robot_health);
-  b.ids = b.map + r16;
-  b.count = b.ids + r16;
+  b.count = b.map + r16;
   b.bytes = b.count + 16;
   return b;
 }
@@ -72,11 +71,10 @@ static int fleet_ck_prepare(shc_fleet *f) {
   bool one_device = true;
   for (auto &p : f->parts) {
     one_device = one_device && p.device == f->parts[0].device;
+    if (const int rc = fleet_part_ids(p); rc != SHC_OK) return rc;
     if (p.ck_block) continue;
-    const FleetCkBlock b = fleet_ck_block(p.ids.size());
     HIP_TRY(hipSetDevice(p.device));
-    HIP_TRY(hipMalloc(&p.ck_block, b.bytes));
-    HIP_TRY(hipMemcpy(p.ck_block + b.ids, p.ids.data(), p.ids.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMalloc(&p.ck_block, fleet_ck_block(p.ids.size()).bytes));
   }
   if (one_device && !f->ck_tables) {
     const size_t n = size_t(f->n);
@@ -181,7 +179,7 @@ extern "C" int shc_fleet_restore_instances(shc_fleet *f, const shc_fleet_checkpo
       const FleetCkBlock b = fleet_ck_block(size_t(rows));
       int64_t *map = reinterpret_cast<int64_t *>(p.ck_block + b.map);
       const unsigned grid = unsigned(std::min<int64_t>((rows + 255) / 256, 2048));
-      fleet_translate_map_kernel<<<dim3(grid), dim3(256), 0, p.engine->stream>>>(map, source, reinterpret_cast<const int64_t *>(p.ck_block + b.ids), part_of, local_of, rows,
+      fleet_translate_map_kernel<<<dim3(grid), dim3(256), 0, p.engine->stream>>>(map, source, p.d_ids, part_of, local_of, rows,
                                                                                  f->n, int32_t(k));
       HIP_TRY(hipGetLastError());
       if ((rc = shc_engine_restore_instances(p.engine, ck->parts[k], map, 1)) != SHC_OK) return rc;

@@ -1,0 +1,295 @@
+// shc_fleet_io.hpp — fleet device I/O: shc_fleet_set_inputs_device, shc_fleet_get_outputs_device, shc_fleet_order_after_stream,
+// shc_fleet_order_stream_after, shc_fleet_set_io_chunk, shc_fleet_io_bytes.  Included by shc_fleet.hpp.
+//
+// The host forms (shc_fleet_set_* / shc_fleet_get_*) permute rows between the caller's padded order and a part's dense order on the host and
+// cross it once per part and call.  Here both sides are device arrays and the permutation is a kernel on the part's own stream: PACK gathers
+// the rows of a part out of the caller's input arrays into the part's staging, PLACE scatters a part's rows out of staging into the caller's
+// buffers.  Between staging and the state stand the engines' own device forms (shc_engine_set_*(.., on_device = 1), shc_engine_get_*(..,
+// on_device = 1)), so every side effect of a setter or getter - RT_TOUCHDOWN and touchdown detection, the first-effort switch, RT_MANUAL_LIVE,
+// quaternion normalisation, the derived-tip refresh, inputs riding the two half streams of split steps - is the engine's, written once.
+//
+// One staging buffer per part, allocated by the fleet's first device I/O call and kept.  Every use of it is ordered on the part's stream: the
+// engine getters join split steps before they write it, and a setter that scatters on the half streams orders the part's stream behind those
+// reads (split_inputs_end), so the next pack cannot overwrite rows a half has not read yet.  Its size is the largest of
+//   inputs:   rows x (16 + 3 L + L D) doubles   (all eight groups of one call, packed by one launch),
+//   joints:   rows x L x D doubles              (shc_engine_get_joint_state has no range: q, then qd, through the same rows),
+//   records:  chunk x L x 512 bytes             (leg messages; leg frames + body frames of the same chunk need less, health 32 bytes a robot),
+// with rows, L, D the part's own and chunk = min(rows, shc_fleet_set_io_chunk).  Record outputs walk the part in chunks through the engine
+// calls' (first, count).  Default chunk: 8 192 robots - 32 MiB of octopod leg messages, which the place kernel reads back out of the 256 MiB
+// last-level cache while six parts run side by side, and 64 chunks (two launches each) for a part of 2^19 robots.  A choice from that
+// trade-off; the record outputs have not been timed (DESIGN 4.6 has the figures of the joint route).
+#pragma once
+
+static_assert(sizeof(shc_fleet_inputs) == 64 && sizeof(shc_fleet_outputs) == 72 && offsetof(shc_fleet_outputs, frame) == 48 && offsetof(shc_fleet_outputs, health) == 56,
+              "shc_fleet_inputs is eight pointers; shc_fleet_outputs six pointers, two int32, two pointers");
+constexpr int64_t kFleetIoDefaultChunk = 8192;
+constexpr int kFleetIoGroups = 8;
+
+// PACK: one launch per part.  Group g is an input array of the caller, [n][src_robot] doubles, of which a part's robot takes legs x k entries:
+// entry (l, j) of part row r is src[ids[r] * src_robot + l * src_leg + j] and lands at stage[dst + r * legs * k + l * k + j].  The group is
+// blockIdx.y, so its description is wave-uniform (scalar loads of the kernel arguments), the stores of a group are one contiguous run, and -
+// ids ascending - the loads walk the caller's array forwards, skipping the rows of other parts and the padding.
+// Both kernels number their threads word by word in 64 bits, but divide in 32: a workgroup's first word is split into (row, column) once,
+// wave-uniformly, and a thread adds its lane to the column - at most one row length plus 255, far inside 32 bits.
+struct FleetPackGroup {
+  const double *src;
+  int64_t dst;       // doubles from the start of staging
+  int32_t legs, k;   // per robot of the part
+  int32_t src_robot; // doubles per robot in the caller's array
+  int32_t src_leg;   // doubles per leg there (per-robot inputs: legs = 1)
+};
+struct FleetPackArgs {
+  FleetPackGroup g[kFleetIoGroups];
+  int32_t n_groups;
+};
+__global__ void fleet_pack_inputs_kernel(double *__restrict__ stage, const int64_t *__restrict__ ids, int64_t rows, FleetPackArgs a) {
+  const FleetPackGroup &g = a.g[blockIdx.y];
+  const uint32_t w = uint32_t(g.legs * g.k), gk = uint32_t(g.k);
+  const int64_t total = rows * w, stride = int64_t(gridDim.x) * blockDim.x;
+  for (int64_t t0 = int64_t(blockIdx.x) * blockDim.x; t0 < total; t0 += stride) {
+    const int64_t r0 = t0 / w; // uniform over the workgroup
+    const uint32_t u = uint32_t(t0 - r0 * w) + threadIdx.x, dr = u / w, c = u - dr * w, l = c / gk, j = c - l * gk;
+    const int64_t r = r0 + dr;
+    if (r < rows) stage[g.dst + r * w + c] = g.src[ids[r] * g.src_robot + int64_t(l) * g.src_leg + j];
+  }
+}
+
+// PLACE: `count` rows of a part ([count][legs][k] words, dense, in staging) into the caller's buffer ([n][dst_legs][dst_k] words) at the rows
+// ids[0 .. count).  One thread per word of a DESTINATION row, so that the stores of a robot are one contiguous run and every word of the row is
+// written: a thread of a leg or joint the part's morphology lacks stores `pad` (the NaN of the joint arrays, zero for records).  Words are 8
+// bytes (doubles, the 64 / 42 / 20 doubles of the leg message, leg frame and body frame records, the four words of a health record) or 4 (walk
+// state).  Records are placed whole: legs = 1 .. L of k = dst_k words each.
+template <class Word>
+__global__ void fleet_place_kernel(Word *__restrict__ dst, const Word *__restrict__ part, const int64_t *__restrict__ ids, int64_t count, int legs, int k,
+                                   int dst_legs, int dst_k, Word pad) {
+  const uint32_t row = uint32_t(dst_legs * dst_k), dk = uint32_t(dst_k);
+  const int64_t total = count * row, stride = int64_t(gridDim.x) * blockDim.x;
+  for (int64_t t0 = int64_t(blockIdx.x) * blockDim.x; t0 < total; t0 += stride) {
+    const int64_t r0 = t0 / row; // uniform over the workgroup
+    const uint32_t u = uint32_t(t0 - r0 * row) + threadIdx.x, dr = u / row, c = u - dr * row, l = c / dk, j = c - l * dk;
+    const int64_t r = r0 + dr;
+    if (r >= count) continue;
+    Word v = pad;
+    if (l < uint32_t(legs) && j < uint32_t(k)) v = part[(r * legs + l) * k + j];
+    dst[ids[r] * row + c] = v;
+  }
+}
+// one word per thread: at most 2 048 workgroups, the rest by the grid stride
+static unsigned fleet_io_grid(int64_t threads) { return unsigned(std::max<int64_t>(1, std::min<int64_t>((threads + 255) / 256, 2048))); }
+
+template <class Word>
+static int fleet_place(const FleetPart &p, Word *dst, int64_t first, int64_t count, int legs, int k, int dst_legs, int dst_k, Word pad) {
+  fleet_place_kernel<Word><<<dim3(fleet_io_grid(count * dst_legs * dst_k)), dim3(256), 0, p.engine->stream>>>(dst, reinterpret_cast<const Word *>(p.io_stage), p.d_ids + first,
+                                                                                                          count, legs, k, dst_legs, dst_k, pad);
+  HIP_TRY(hipGetLastError());
+  return SHC_OK;
+}
+
+static int64_t fleet_io_chunk_of(const shc_fleet *f, const FleetPart &p) {
+  return std::min<int64_t>(int64_t(p.ids.size()), f->io_chunk > 0 ? f->io_chunk : kFleetIoDefaultChunk);
+}
+static size_t fleet_io_stage_bytes(const shc_fleet *f, const FleetPart &p) {
+  const shc_params &pp = f->params[p.morph];
+  const size_t rows = p.ids.size(), L = size_t(pp.leg_count), D = size_t(max_dof(pp));
+  const size_t inputs = rows * (16 + 3 * L + L * D) * 8, joints = rows * L * D * 8;
+  const size_t records = size_t(fleet_io_chunk_of(f, p)) * L * sizeof(shc_leg_state_msg);
+  static_assert(sizeof(shc_leg_frames) + sizeof(shc_body_frames) <= sizeof(shc_leg_state_msg), "a chunk of leg messages is the largest record output");
+  return (std::max(inputs, std::max(joints, records)) + 15) & ~size_t(15);
+}
+
+// What all four device entry points ask before they do anything: one device, nobody in resident mode.
+static int fleet_io_ready(const shc_fleet *f) {
+  for (const auto &p : f->parts) {
+    if (p.device != f->parts[0].device)
+      return fail(SHC_ERR_UNSUPPORTED, "device I/O needs one device that holds every part of the fleet (the caller's arrays live on one): use the host forms");
+    if (resident_active(p.engine))
+      return fail(SHC_ERR_BUSY, "a part of the fleet is in resident mode: only shc_engine_resident_* calls are valid until shc_engine_resident_end");
+  }
+  return SHC_OK;
+}
+// The first device I/O call of a fleet (and the first after shc_fleet_set_io_chunk): ids, staging and events of every part.  Allocates and
+// uploads synchronously; later calls find everything in place.
+static int fleet_io_prepare(shc_fleet *f) {
+  if (f->io_ready) return SHC_OK;
+  for (auto &p : f->parts) {
+    int rc = fleet_part_ids(p);
+    if (rc != SHC_OK) return rc;
+    HIP_TRY(hipSetDevice(p.device));
+    if (!p.io_stage) {
+      const size_t bytes = fleet_io_stage_bytes(f, p);
+      HIP_TRY(hipMalloc(&p.io_stage, bytes));
+      p.io_stage_bytes = bytes;
+    }
+    if (!p.io_after) HIP_TRY(hipEventCreateWithFlags(&p.io_after, hipEventDisableTiming));
+    if (!p.io_before) HIP_TRY(hipEventCreateWithFlags(&p.io_before, hipEventDisableTiming));
+  }
+  f->io_ready = true;
+  return SHC_OK;
+}
+
+extern "C" int shc_fleet_set_io_chunk(shc_fleet *f, int64_t robots) {
+  if (!f || robots < 0) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL or a negative chunk");
+  if (robots == f->io_chunk) return SHC_OK;
+  for (auto &p : f->parts) { // staging is sized by the chunk: drain the part, release it, and let the next device I/O call allocate it again
+    if (!p.io_stage) continue;
+    HIP_TRY(hipSetDevice(p.device));
+    if (p.engine->side_busy) HIP_TRY(hipDeviceSynchronize()); // (a half stream may still read staged inputs)
+    HIP_TRY(hipStreamSynchronize(p.engine->stream));
+    HIP_TRY(hipFree(p.io_stage));
+    p.io_stage = nullptr, p.io_stage_bytes = 0;
+  }
+  f->io_chunk = robots;
+  f->io_ready = false;
+  return SHC_OK;
+}
+extern "C" int64_t shc_fleet_io_bytes(const shc_fleet *f) {
+  int64_t bytes = 0;
+  if (f)
+    for (const auto &p : f->parts)
+      bytes += int64_t(p.io_stage_bytes) + (p.d_ids ? int64_t(p.ids.size()) * 8 : 0); // (the ids stay when shc_fleet_set_io_chunk releases the staging)
+  return bytes;
+}
+
+extern "C" int shc_fleet_order_after_stream(shc_fleet *f, void *stream) {
+  if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
+  int rc = fleet_io_ready(f);
+  if (rc == SHC_OK) rc = fleet_io_prepare(f);
+  if (rc != SHC_OK) return rc;
+  HIP_TRY(hipSetDevice(f->parts[0].device));
+  for (auto &p : f->parts) { // (inputs that ride the half streams of split steps follow the part's stream: split_inputs_begin)
+    HIP_TRY(hipEventRecord(p.io_after, hipStream_t(stream)));
+    HIP_TRY(hipStreamWaitEvent(p.engine->stream, p.io_after, 0));
+  }
+  return SHC_OK;
+}
+extern "C" int shc_fleet_order_stream_after(shc_fleet *f, void *stream) {
+  if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
+  int rc = fleet_io_ready(f);
+  if (rc == SHC_OK) rc = fleet_io_prepare(f);
+  if (rc != SHC_OK) return rc;
+  HIP_TRY(hipSetDevice(f->parts[0].device));
+  for (auto &p : f->parts) {
+    if ((rc = shc_engine_join(p.engine)) != SHC_OK) return rc; // split steps in flight: the part's stream follows both halves first
+    HIP_TRY(hipEventRecord(p.io_before, p.engine->stream));
+    HIP_TRY(hipStreamWaitEvent(hipStream_t(stream), p.io_before, 0));
+  }
+  return SHC_OK;
+}
+
+extern "C" int shc_fleet_set_inputs_device(shc_fleet *f, const shc_fleet_inputs *in) {
+  if (!f || !in) return fail(SHC_ERR_INVALID_ARG, "fleet or inputs NULL");
+  int rc = fleet_io_ready(f);
+  if (rc == SHC_OK) rc = fleet_io_prepare(f);
+  if (rc != SHC_OK) return rc;
+  // the caller's arrays in the order of the staged groups: [pointer, entries per robot there]; the per-leg groups are the last two
+  const double *src[kFleetIoGroups] = {in->linear_xy, in->angular, in->imu_orientation_wxyz, in->imu_angular_velocity, in->pose_translation_velocity,
+                                       in->pose_rotation_velocity, in->tip_force, in->joint_effort};
+  const int width[kFleetIoGroups - 2] = {2, 1, 4, 3, 3, 3};
+  for (auto &p : f->parts) {
+    const shc_params &pp = f->params[p.morph];
+    const int L = pp.leg_count, D = max_dof(pp);
+    const int64_t rows = int64_t(p.ids.size());
+    double *stage = reinterpret_cast<double *>(p.io_stage);
+    const double *staged[kFleetIoGroups] = {};
+    FleetPackArgs a{};
+    int64_t at = 0, widest = 0;
+    for (int g = 0; g < kFleetIoGroups; ++g) {
+      if (!src[g]) continue;
+      FleetPackGroup &pg = a.g[a.n_groups++];
+      pg.src = src[g], pg.dst = at;
+      if (g < kFleetIoGroups - 2) {
+        pg.legs = 1, pg.k = width[g], pg.src_robot = width[g], pg.src_leg = 0;
+      } else {
+        const int max_k = g == kFleetIoGroups - 1 ? f->max_dof : 3;
+        pg.legs = L, pg.k = g == kFleetIoGroups - 1 ? D : 3, pg.src_robot = f->max_legs * max_k, pg.src_leg = max_k;
+      }
+      staged[g] = stage + at;
+      at += rows * pg.legs * pg.k;
+      widest = std::max<int64_t>(widest, rows * pg.legs * pg.k);
+    }
+    if (a.n_groups == 0) return SHC_OK; // every input is held
+    HIP_TRY(hipSetDevice(p.device));
+    fleet_pack_inputs_kernel<<<dim3(fleet_io_grid(widest), unsigned(a.n_groups)), dim3(256), 0, p.engine->stream>>>(stage, p.d_ids, rows, a);
+    HIP_TRY(hipGetLastError());
+    // a setter none of whose members is given is not called: with nothing to set it would still enter the engine, and some of them join split steps
+    if ((staged[0] || staged[1]) && (rc = shc_engine_set_velocity(p.engine, staged[0], staged[1], 1)) != SHC_OK) return rc;
+    if ((staged[2] || staged[3]) && (rc = shc_engine_set_imu(p.engine, staged[2], staged[3], 1)) != SHC_OK) return rc;
+    if ((staged[4] || staged[5]) && (rc = shc_engine_set_pose_input(p.engine, staged[4], staged[5], 1)) != SHC_OK) return rc;
+    if (staged[6] && (rc = shc_engine_set_tip_force(p.engine, staged[6], 1)) != SHC_OK) return rc;
+    if (staged[7] && (rc = shc_engine_set_joint_effort(p.engine, staged[7], 1)) != SHC_OK) return rc;
+  }
+  return SHC_OK;
+}
+
+extern "C" int shc_fleet_get_outputs_device(shc_fleet *f, const shc_fleet_outputs *out) {
+  if (!f || !out) return fail(SHC_ERR_INVALID_ARG, "fleet or outputs NULL");
+  const bool frames = out->leg_frames || out->body_frames;
+  if (!out->q && !out->qd && !out->walk_state && !out->leg_state_msgs && !frames && !out->health) return fail(SHC_ERR_INVALID_ARG, "every output is NULL");
+  if (out->reserved != 0) return fail(SHC_ERR_INVALID_ARG, "shc_fleet_outputs.reserved must be 0");
+  if (frames && out->frame != SHC_FRAME_BASE_LINK && out->frame != SHC_FRAME_ODOM_IDEAL) return fail(SHC_ERR_INVALID_ARG, "unknown frame");
+  if ((reinterpret_cast<uintptr_t>(out->leg_state_msgs) | reinterpret_cast<uintptr_t>(out->leg_frames) | reinterpret_cast<uintptr_t>(out->body_frames) |
+       reinterpret_cast<uintptr_t>(out->health)) & 15)
+    return fail(SHC_ERR_INVALID_ARG, "record buffers must be 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(out->q) | reinterpret_cast<uintptr_t>(out->qd)) & 7 || reinterpret_cast<uintptr_t>(out->walk_state) & 3)
+    return fail(SHC_ERR_INVALID_ARG, "q / qd must be 8-byte aligned, walk_state 4-byte aligned");
+  if (out->health) { // (what shc_engine_scan_health would refuse, before the first part has run)
+    const shc_health_criteria crit = health_criteria(out->criteria);
+    if (crit.reserved != 0) return fail(SHC_ERR_INVALID_ARG, "shc_health_criteria.reserved must be 0");
+    if (crit.select & ~kHealthAllFlags) return fail(SHC_ERR_INVALID_ARG, "shc_health_criteria.select has bits outside SHC_HEALTH_*");
+  }
+  int rc = fleet_io_ready(f);
+  if (rc != SHC_OK) return rc;
+  if (out->body_frames || (out->leg_frames && out->frame == SHC_FRAME_ODOM_IDEAL))
+    for (const auto &p : f->parts)
+      if (!p.engine->cp.odometry) return fail(SHC_ERR_UNSUPPORTED, "SHC_FEAT_ODOMETRY is off on a part: odom_to_base_link needs the ideal odometry");
+  if ((rc = fleet_io_prepare(f)) != SHC_OK) return rc;
+
+  uint64_t nan_word; // the bit pattern shc_fleet_get_joint_state fills the padding with
+  const double nan_value = std::nan("");
+  memcpy(&nan_word, &nan_value, 8);
+  constexpr int kMsgWords = int(sizeof(shc_leg_state_msg) / 8), kLegWords = int(sizeof(shc_leg_frames) / 8), kBodyWords = int(sizeof(shc_body_frames) / 8),
+                kHealthWords = int(sizeof(shc_robot_health) / 8);
+  for (auto &p : f->parts) {
+    const shc_params &pp = f->params[p.morph];
+    const int L = pp.leg_count, D = max_dof(pp);
+    const int64_t rows = int64_t(p.ids.size()), chunk = fleet_io_chunk_of(f, p);
+    HIP_TRY(hipSetDevice(p.device));
+    for (int which = 0; which < 2; ++which) { // the same staged rows for q, then for qd
+      double *dst = which == 0 ? out->q : out->qd, *stage = reinterpret_cast<double *>(p.io_stage);
+      if (!dst) continue;
+      if ((rc = shc_engine_get_joint_state(p.engine, which == 0 ? stage : nullptr, which == 0 ? nullptr : stage, 1)) != SHC_OK) return rc;
+      if ((rc = fleet_place<uint64_t>(p, reinterpret_cast<uint64_t *>(dst), 0, rows, L, D, f->max_legs, f->max_dof, nan_word)) != SHC_OK) return rc;
+    }
+    if (out->walk_state) {
+      if ((rc = shc_engine_get_body_state(p.engine, nullptr, nullptr, reinterpret_cast<int32_t *>(p.io_stage), 1)) != SHC_OK) return rc;
+      if ((rc = fleet_place<int32_t>(p, out->walk_state, 0, rows, 1, 1, 1, 1, 0)) != SHC_OK) return rc;
+    }
+    for (int64_t first = 0; first < rows; first += chunk) {
+      const int64_t count = std::min(chunk, rows - first);
+      if (out->leg_state_msgs) {
+        if ((rc = shc_engine_get_leg_state_msgs(p.engine, first, count, reinterpret_cast<shc_leg_state_msg *>(p.io_stage), 1)) != SHC_OK) return rc;
+        if ((rc = fleet_place<uint64_t>(p, reinterpret_cast<uint64_t *>(out->leg_state_msgs), first, count, L, kMsgWords, f->max_legs, kMsgWords, 0)) != SHC_OK) return rc;
+      }
+      if (frames) { // one engine pass for both; the body records sit behind the chunk's leg records
+        char *body = p.io_stage + size_t(count) * L * sizeof(shc_leg_frames);
+        rc = shc_engine_get_frame_transforms(p.engine, first, count, out->frame, out->leg_frames ? reinterpret_cast<shc_leg_frames *>(p.io_stage) : nullptr,
+                                             out->body_frames ? reinterpret_cast<shc_body_frames *>(body) : nullptr, 1);
+        if (rc != SHC_OK) return rc;
+        if (out->leg_frames &&
+            (rc = fleet_place<uint64_t>(p, reinterpret_cast<uint64_t *>(out->leg_frames), first, count, L, kLegWords, f->max_legs, kLegWords, 0)) != SHC_OK)
+          return rc;
+        if (out->body_frames) {
+          fleet_place_kernel<uint64_t><<<dim3(fleet_io_grid(count * kBodyWords)), dim3(256), 0, p.engine->stream>>>(
+              reinterpret_cast<uint64_t *>(out->body_frames), reinterpret_cast<const uint64_t *>(body), p.d_ids + first, count, 1, kBodyWords, 1, kBodyWords, 0);
+          HIP_TRY(hipGetLastError());
+        }
+      }
+      if (out->health) {
+        rc = shc_engine_scan_health(p.engine, first, count, out->criteria, reinterpret_cast<shc_robot_health *>(p.io_stage), nullptr, nullptr, nullptr, 1);
+        if (rc != SHC_OK) return rc;
+        if ((rc = fleet_place<uint64_t>(p, reinterpret_cast<uint64_t *>(out->health), first, count, 1, kHealthWords, 1, kHealthWords, 0)) != SHC_OK) return rc;
+      }
+    }
+  }
+  return SHC_OK;
+}

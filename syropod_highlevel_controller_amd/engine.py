@@ -57,6 +57,8 @@ EXPORTED_SYMBOLS = [
     "shc_engine_scan_health", "shc_fleet_scan_health", "shc_debug_robot_health",
     "shc_fleet_checkpoint_create", "shc_fleet_checkpoint_update", "shc_fleet_checkpoint_destroy", "shc_fleet_checkpoint_bytes",
     "shc_fleet_restore_instances", "shc_fleet_scan_and_restore",
+    "shc_fleet_set_inputs_device", "shc_fleet_get_outputs_device", "shc_fleet_order_after_stream", "shc_fleet_order_stream_after",
+    "shc_fleet_set_io_chunk", "shc_fleet_io_bytes",
     "shc_peer_alloc", "shc_peer_open", "shc_peer_close", "shc_peer_scatter",
 ]
 
@@ -107,6 +109,22 @@ class CycleInputs(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("linear_xy", "angular", "imu_orientation_wxyz", "imu_angular_velocity", "pose_translation_velocity",
                                            "pose_rotation_velocity", "pose_reset_mode", "tip_force", "joint_effort")] + [("on_device", C.c_int32), ("publish", C.c_int32),
                                                                                                                   ("direct", C.c_int32), ("reserved_", C.c_int32)]
+
+
+FLEET_INPUTS = ("linear_xy", "angular", "imu_orientation_wxyz", "imu_angular_velocity", "pose_translation_velocity", "pose_rotation_velocity", "tip_force",
+                "joint_effort")
+
+
+class FleetInputs(C.Structure):
+    """shc_fleet_inputs: device arrays in the caller's instance order; NULL = that input is held."""
+    _fields_ = [(k, C.c_void_p) for k in FLEET_INPUTS]
+
+
+class FleetOutputs(C.Structure):
+    """shc_fleet_outputs: device buffers in the caller's instance order; NULL = not asked for.  criteria is a host pointer."""
+    _fields_ = [(k, C.c_void_p) for k in ("q", "qd", "walk_state", "leg_state_msgs", "leg_frames", "body_frames")] + [("frame", C.c_int32), ("reserved", C.c_int32),
+                                                                                                                 ("health", C.c_void_p),
+                                                                                                                 ("criteria", C.POINTER(HealthCriteria))]
 
 
 class ShcError(RuntimeError):
@@ -379,6 +397,13 @@ def lib():
         L.shc_fleet_checkpoint_bytes.restype = C.c_int64
         L.shc_fleet_restore_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.shc_fleet_scan_and_restore.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(HealthCriteria), C.c_void_p, C.POINTER(C.c_int64)]
+        L.shc_fleet_set_inputs_device.argtypes = [C.c_void_p, C.POINTER(FleetInputs)]
+        L.shc_fleet_get_outputs_device.argtypes = [C.c_void_p, C.POINTER(FleetOutputs)]
+        L.shc_fleet_order_after_stream.argtypes = [C.c_void_p, C.c_void_p]
+        L.shc_fleet_order_stream_after.argtypes = [C.c_void_p, C.c_void_p]
+        L.shc_fleet_set_io_chunk.argtypes = [C.c_void_p, C.c_int64]
+        L.shc_fleet_io_bytes.argtypes = [C.c_void_p]
+        L.shc_fleet_io_bytes.restype = C.c_int64
         L.shc_engine_resident_begin.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int]
         L.shc_engine_resident_post.argtypes = [C.c_void_p, C.POINTER(CycleInputs), C.POINTER(C.c_int64)]
         L.shc_engine_resident_bind_inputs.argtypes = [C.c_void_p, C.c_int, C.POINTER(CycleInputs)]
@@ -509,6 +534,37 @@ def _source_map(source, n: int):
     if a.shape != (n,):
         raise ValueError(f"a source map has one entry per robot: expected shape ({n},), got {a.shape}")
     return a.ctypes.data_as(C.c_void_p), 0, a
+
+
+def _device_array(obj, typestr: str, shape, what: str) -> C.c_void_p:
+    """The pointer of a device array of exactly this type and shape: an object with ``__cuda_array_interface__`` (e.g. a torch tensor), contiguous."""
+    if not hasattr(obj, "__cuda_array_interface__"):
+        raise ValueError(f"{what}: a device array (an object with __cuda_array_interface__) of shape {tuple(shape)} and type {typestr} is expected")
+    cai = obj.__cuda_array_interface__
+    dense, strides = int(typestr[2:]), []
+    for extent in reversed(shape):
+        strides.insert(0, dense)
+        dense *= extent
+    if cai["typestr"] != typestr or tuple(cai["shape"]) != tuple(shape) or cai.get("strides") not in (None, tuple(strides)):
+        raise ValueError(f"{what}: a contiguous device array of shape {tuple(shape)} and type {typestr} is expected, "
+                         f"got shape {tuple(cai['shape'])}, type {cai['typestr']}, strides {cai.get('strides')}")
+    return C.c_void_p(cai["data"][0])
+
+
+def _device_records(obj, nbytes: int, what: str) -> C.c_void_p:
+    """The pointer of a device buffer for records: a contiguous array of any element type (uint8, float64, ...) with exactly `nbytes` bytes."""
+    if not hasattr(obj, "__cuda_array_interface__"):
+        raise ValueError(f"{what}: a device buffer (an object with __cuda_array_interface__) of {nbytes} bytes is expected")
+    cai = obj.__cuda_array_interface__
+    width, shape = int(cai["typestr"][2:]), tuple(cai["shape"])
+    dense, ok = width, True
+    if cai.get("strides") is not None:
+        for extent, stride in zip(reversed(shape), reversed(cai["strides"])):
+            ok, dense = ok and (extent == 1 or stride == dense), dense * extent
+    size = int(np.prod(shape, dtype=np.int64)) * width
+    if not ok or size != nbytes:
+        raise ValueError(f"{what}: a contiguous device buffer of {nbytes} bytes is expected, got shape {shape} of {cai['typestr']} ({size} bytes)")
+    return C.c_void_p(cai["data"][0])
 
 
 class Checkpoint:

@@ -2,7 +2,8 @@
 
 The binning (one engine and one HIP stream per (morphology bin, device)), the contiguous sharding over devices and the
 device-to-device all-gather of the joint buffer live in the library (csrc/shc_fleet.hpp); this class only converts numpy
-arrays.  Inputs arrive and outputs leave indexed by the caller's instance id, whatever the interleaving pattern.
+arrays.  Inputs arrive and outputs leave indexed by the caller's instance id, whatever the interleaving pattern - as host
+arrays, or (set_inputs / outputs, csrc/shc_fleet_io.hpp) as device arrays that never cross the host.
 """
 from __future__ import annotations
 
@@ -104,9 +105,28 @@ class MixedFleet:
     def _p(a):
         return None if a is None else a.ctypes.data_as(C.c_void_p)
 
-    def set_velocity(self, linear_xy, angular):
-        a, b = np.ascontiguousarray(linear_xy, dtype=np.float64), np.ascontiguousarray(angular, dtype=np.float64)
+    def set_velocity(self, linear_xy=None, angular=None):
+        """linear_xy [n][2], angular [n]; None holds that input."""
+        a, b = _engine._host(linear_xy), _engine._host(angular)
         _engine._check(self.L.shc_fleet_set_velocity(self.h, self._p(a), self._p(b)), "shc_fleet_set_velocity")
+
+    def set_imu(self, orientation_wxyz=None, angular_velocity=None):
+        """orientation_wxyz [n][4] (normalised on entry), angular_velocity [n][3]; None holds that input."""
+        a, b = _engine._host(orientation_wxyz), _engine._host(angular_velocity)
+        assert (a is None or a.shape == (self.n, 4)) and (b is None or b.shape == (self.n, 3))
+        _engine._check(self.L.shc_fleet_set_imu(self.h, self._p(a), self._p(b)), "shc_fleet_set_imu")
+
+    def set_pose_input(self, translation_velocity=None, rotation_velocity=None):
+        """Manual posing velocities, [n][3] each; None holds that input."""
+        a, b = _engine._host(translation_velocity), _engine._host(rotation_velocity)
+        assert (a is None or a.shape == (self.n, 3)) and (b is None or b.shape == (self.n, 3))
+        _engine._check(self.L.shc_fleet_set_pose_input(self.h, self._p(a), self._p(b)), "shc_fleet_set_pose_input")
+
+    def set_tip_force(self, force_padded):
+        """force_padded [n][max_legs][3]; entries beyond a robot's legs are ignored."""
+        a = np.ascontiguousarray(force_padded, dtype=np.float64)
+        assert a.shape == (self.n, self.max_legs, 3)
+        _engine._check(self.L.shc_fleet_set_tip_force(self.h, self._p(a)), "shc_fleet_set_tip_force")
 
     def set_joint_effort(self, effort_padded):
         """effort_padded [n][max_legs][max_dof]; entries beyond a bin's (legs, dof) are ignored."""
@@ -156,6 +176,77 @@ class MixedFleet:
         health = np.zeros(self.n, dtype=_engine.ROBOT_HEALTH_DTYPE)
         _engine._check(self.L.shc_fleet_scan_health(self.h, C.byref(crit), self._p(health)), "shc_fleet_scan_health")
         return health
+
+    # -- device I/O: the setters and getters above with device arrays (shc_fleet_set_inputs_device / shc_fleet_get_outputs_device)
+    def _input_shapes(self):
+        n = self.n
+        return {"linear_xy": (n, 2), "angular": (n,), "imu_orientation_wxyz": (n, 4), "imu_angular_velocity": (n, 3), "pose_translation_velocity": (n, 3),
+                "pose_rotation_velocity": (n, 3), "tip_force": (n, self.max_legs, 3), "joint_effort": (n, self.max_legs, self.max_dof)}
+
+    def set_inputs(self, **arrays):
+        """The five setters in one call, from contiguous float64 DEVICE arrays in the caller's instance order (objects with
+        ``__cuda_array_interface__``, e.g. torch tensors): linear_xy (n, 2), angular (n,), imu_orientation_wxyz (n, 4), imu_angular_velocity (n, 3),
+        pose_translation_velocity (n, 3), pose_rotation_velocity (n, 3), tip_force (n, max_legs, 3), joint_effort (n, max_legs, max_dof).  An
+        argument left out (or None) holds that input.  No host wait: the parts read the arrays on streams of their own - ``order_after(stream)``
+        first when a stream is still writing them, or finish the writes (``stream.synchronize()``), and keep them untouched until the parts have
+        read them (``order_before`` + stream order, or ``synchronize()``)."""
+        shapes, st = self._input_shapes(), _engine.FleetInputs()
+        for name, a in arrays.items():
+            if name not in shapes:
+                raise TypeError(f"set_inputs: unknown input {name!r} (one of {', '.join(shapes)})")
+            if a is not None:
+                setattr(st, name, _engine._device_array(a, "<f8", shapes[name], name))
+        _engine._check(self.L.shc_fleet_set_inputs_device(self.h, C.byref(st)), "shc_fleet_set_inputs_device")
+
+    def outputs(self, q=None, qd=None, walk_state=None, leg_state_msgs=None, leg_frames=None, body_frames=None, health=None, frame="base_link",
+                select: int = 0, near_limit_proximity: float = 0.0, tip_deviation: float = 0.0):
+        """joints(), walk_state(), leg_state_msgs(), frame_transforms(frame) and scan_health(select, ...) into DEVICE buffers of the caller's, in
+        the caller's instance order and byte for byte what those return (NaN padding of q / qd, all-zero records of missing legs): q, qd float64
+        (n, max_legs, max_dof); walk_state int32 (n,); leg_state_msgs, leg_frames, body_frames, health: contiguous buffers of any element type
+        (uint8, float64, ...) with n * max_legs * 512, n * max_legs * 336, n * 160 and n * 32 bytes, 16-byte aligned.  Only the buffers given are
+        written, every entry of them; at least one must be given.  No host wait: complete after ``synchronize()``, or for work queued on a stream
+        after ``order_before(stream)``."""
+        n, row = self.n, (self.n, self.max_legs, self.max_dof)
+        st = _engine.FleetOutputs()
+        if q is not None:
+            st.q = _engine._device_array(q, "<f8", row, "q")
+        if qd is not None:
+            st.qd = _engine._device_array(qd, "<f8", row, "qd")
+        if walk_state is not None:
+            st.walk_state = _engine._device_array(walk_state, "<i4", (n,), "walk_state")
+        for name, buf, nbytes in (("leg_state_msgs", leg_state_msgs, n * self.max_legs * _engine.LEG_STATE_MSG_DTYPE.itemsize),
+                                  ("leg_frames", leg_frames, n * self.max_legs * _engine.LEG_FRAMES_DTYPE.itemsize),
+                                  ("body_frames", body_frames, n * _engine.BODY_FRAMES_DTYPE.itemsize),
+                                  ("health", health, n * _engine.ROBOT_HEALTH_DTYPE.itemsize)):
+            if buf is not None:
+                setattr(st, name, _engine._device_records(buf, nbytes, name))
+        st.frame = _engine.FRAME_IDS[frame] if isinstance(frame, str) else int(frame)
+        crit = _engine.HealthCriteria(int(select), 0, float(near_limit_proximity), float(tip_deviation))
+        st.criteria = C.pointer(crit)
+        _engine._check(self.L.shc_fleet_get_outputs_device(self.h, C.byref(st)), "shc_fleet_get_outputs_device")
+
+    @staticmethod
+    def _stream_handle(stream):
+        return C.c_void_p(int(getattr(stream, "cuda_stream", stream) or 0))
+
+    def order_after(self, stream):
+        """Every part's stream waits for what is queued on ``stream`` now (a raw stream handle or an object with ``.cuda_stream``; 0 / None: the
+        default stream): inputs written by kernels on ``stream`` are complete before a following ``set_inputs`` reads them.  No host wait."""
+        _engine._check(self.L.shc_fleet_order_after_stream(self.h, self._stream_handle(stream)), "shc_fleet_order_after_stream")
+
+    def order_before(self, stream):
+        """``stream`` waits for what is queued on every part's stream now (split steps are joined first): work queued on ``stream`` afterwards
+        sees the results of the preceding ``outputs`` and may overwrite the arrays given to ``set_inputs``.  No host wait."""
+        _engine._check(self.L.shc_fleet_order_stream_after(self.h, self._stream_handle(stream)), "shc_fleet_order_stream_after")
+
+    def set_io_chunk(self, robots: int = 0):
+        """Robots per part and staging pass of the record outputs (0 = the default)."""
+        _engine._check(self.L.shc_fleet_set_io_chunk(self.h, int(robots)), "shc_fleet_set_io_chunk")
+
+    @property
+    def io_nbytes(self) -> int:
+        """Device bytes the device I/O path holds (ids, staging): 0 before its first use."""
+        return int(self.L.shc_fleet_io_bytes(self.h)) if self.h else 0
 
     def checkpoint(self) -> FleetCheckpoint:
         """A device-resident checkpoint of every robot's state as of now (on each part's stream).  The fleet's first one also uploads the tables
