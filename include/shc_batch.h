@@ -1100,6 +1100,42 @@ int shc_fleet_order_after_stream(shc_fleet *f, void *stream);
 int shc_fleet_order_stream_after(shc_fleet *f, void *stream);
 int shc_fleet_set_io_chunk(shc_fleet *f, int64_t robots);      /* staging granularity of the record outputs, robots per part; 0 = default */
 int64_t shc_fleet_io_bytes(const shc_fleet *f);                /* device bytes the I/O path holds (ids, staging); 0 before first use */
+/*
+ * Fleet step_k: shc_engine_step_k for a mixed fleet - K cycles per launch, cycle k with row k of K-deep DEVICE arrays in the CALLER's instance
+ * order.  `rows` is a shc_fleet_inputs whose non-NULL members hold K rows, each padded exactly as for shc_fleet_set_inputs_device: linear_xy
+ * [K][n][2], angular [K][n], imu_orientation_wxyz [K][n][4], imu_angular_velocity [K][n][3], tip_force [K][n][max_legs][3], joint_effort
+ * [K][n][max_legs][max_dof].  A NULL member - or rows = NULL: every member - is held at what the parts have; the velocity pair and the IMU pair
+ * are given together, as the engine requires; the two pose members must be NULL (SHC_ERR_UNSUPPORTED: set them beforehand, they are held for the
+ * K cycles).
+ * DEFINITION.  After the call every robot's state record, auxiliary blob and held inputs, and the q / qd of each of the K cycles, are byte for
+ * byte what
+ *   for k in 0 .. K - 1 { shc_fleet_set_inputs_device(row k); shc_fleet_step(f, 1); shc_fleet_get_outputs_device(q, qd) }
+ * leaves and reads.  Per part and call one kernel gathers the part's rows of all K cycles into K-deep staging and one shc_engine_step_k runs them;
+ * what that call documents is the part's own behaviour and passes through unchanged: the serial form for configurations without a batch kernel,
+ * the first cycle through the serial form while an adjusted parameter is pending, touchdown detection on fresh tip forces inside the loop, the
+ * first-effort switch, the last row becoming the held input.
+ * shc_fleet_get_step_k_joints_device: q / qd of cycles [first_cycle, first_cycle + n_cycles) of the latest shc_fleet_step_k into DEVICE buffers
+ * [n_cycles][n][max_legs][max_dof] (8-byte aligned; either may be NULL, not both) in the caller's order, NaN - the bit pattern
+ * shc_fleet_get_joint_state writes - where a morphology has no such leg / joint.  Every entry of every requested buffer is written by every call:
+ * per part and buffer one kernel reads the part's output ring where it lies.  Stream-ordered on the parts' streams (split launches are joined
+ * first), no host wait.
+ * STAGING.  The K-deep staging is a buffer of its own per part, sized K x the part's rows x the groups given; it is allocated by the first call
+ * that needs it, grows when a call needs more (that call waits for the part), is kept, and is counted by shc_fleet_io_bytes: a later call with
+ * the same or a smaller K and the same groups allocates nothing.  It does not depend on shc_fleet_set_io_chunk and stays across it.
+ * STREAMS.  As for device I/O: order_after_stream(s) -> shc_fleet_step_k -> shc_fleet_get_step_k_joints_device -> order_stream_after(s).  The
+ * caller's K-deep arrays are read by the gather kernel alone, on each part's stream, before the part's launch: they are free once that has run -
+ * after order_stream_after(s) for work queued on s, or after shc_fleet_synchronize.  shc_engine_step_k's stricter rule (its arrays stay valid
+ * until the engine is joined) applies to the fleet's own staging, not to the caller; a part whose launches run split on its two internal streams
+ * is joined before the next call overwrites the staging.
+ * REFUSALS.  Every part is asked before the first launch; when one refuses - the answers listed here - nothing has changed.  (A runtime error
+ * of a part's own launch, SHC_ERR_HIP, can leave the parts before it stepped; the latest K then stays what it was.)  SHC_ERR_INVALID_ARG: NULL fleet; n_cycles
+ * outside 1 .. 4096; half a pair; q and qd both NULL; a cycle range outside the latest call's K, or no call yet (or a part stepped through its own
+ * shc_engine_step_k since); a misaligned buffer; a part whose output ring (the engine's bound) or whose K-deep staging would reach 2 GiB.
+ * SHC_ERR_UNSUPPORTED: a fleet that spans devices (as the other device entry points), pose members, a part still starting up.  SHC_ERR_BUSY: a
+ * part in resident mode.
+ */
+int shc_fleet_step_k(shc_fleet *f, int n_cycles, const shc_fleet_inputs *rows /* may be NULL: every input held */);
+int shc_fleet_get_step_k_joints_device(shc_fleet *f, int first_cycle, int n_cycles, double *q, double *qd /* either may be NULL, not both */);
 /* The exchange step of a sharded batch: every device ends up with the desired joint positions of ALL instances
  * ([n][max_legs][max_dof], caller's order, NaN padded) in its own HBM, copied device to device (hipMemcpyPeerAsync: xGMI on an
  * MI355X node).  device_buffers[d] (may be NULL) receives device_ids[d]'s buffer; the buffers belong to the fleet. */

@@ -73,13 +73,15 @@ __global__ void scatter_leg_kernel(const double *src, double *legd, int64_t n_sl
   int64_t slot = slot_of(rob, leg, L);
   for (int k = 0; k < K; ++k) legd[leg_field_index(f0 + k, slot, n_slots)] = src[t * K + k];
 }
+// element index of leg field f of (robot, leg) in the leg state planes - and in a slot of the step_k output ring, which keeps the planes of Q and QD in
+// the same layout: the one address both gather_leg_kernel and the fleet's ring place (shc_fleet_step_k.hpp) read joints at
+__device__ __forceinline__ int64_t leg_state_index(int f, int64_t rob, int leg, int L, int64_t n_slots) { return leg_field_index(f, slot_of(rob, leg, L), n_slots); }
 __global__ void gather_leg_kernel(double *dst, const double *legd, int64_t n_slots, int64_t n, int L, int K, int f0) {
   int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (t >= n * L) return;
   int64_t rob = t / L;
   int leg = int(t - rob * L);
-  int64_t slot = slot_of(rob, leg, L);
-  for (int k = 0; k < K; ++k) dst[t * K + k] = legd[leg_field_index(f0 + k, slot, n_slots)];
+  for (int k = 0; k < K; ++k) dst[t * K + k] = legd[leg_state_index(f0 + k, rob, leg, L, n_slots)];
 }
 // LegState tips derived from the stored state (see store_leg): model tip = FK(q) in the robot frame (Leg::applyFK,
 // model.cpp:975), poser tip = Model::current_pose_^-1 * walker tip (PoseController::updateStance, pose_controller.cpp:122-131).

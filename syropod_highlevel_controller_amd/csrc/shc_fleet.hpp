@@ -30,6 +30,9 @@ struct FleetPart {
   char *io_stage = nullptr;
   size_t io_stage_bytes = 0;
   hipEvent_t io_after = nullptr, io_before = nullptr; // the part's stream after the caller's / the caller's stream after the part's
+  // shc_fleet_step_k (shc_fleet_step_k.hpp): the part's rows of the K-deep input arrays, dense [K][rows][..] group by group; grows on demand, kept
+  char *k_stage = nullptr;
+  size_t k_stage_bytes = 0;
 };
 
 struct shc_fleet {
@@ -51,6 +54,7 @@ struct shc_fleet {
   // device I/O (shc_fleet_io.hpp)
   int64_t io_chunk = 0; // robots per part and staging pass of the record outputs; 0 = the default
   bool io_ready = false;
+  int k_cycles = 0;     // K of the latest shc_fleet_step_k (0: none yet): what shc_fleet_get_step_k_joints_device may be asked for
 };
 static void fleet_release_checkpoints(shc_fleet *f); // orphan the fleet's checkpoint handles (shc_fleet_destroy)
 
@@ -71,6 +75,7 @@ static void fleet_free(shc_fleet *f) {
     (void)hipFree(p.d_ids);
     (void)hipFree(p.ck_block);
     (void)hipFree(p.io_stage);
+    (void)hipFree(p.k_stage);
     if (p.io_after) (void)hipEventDestroy(p.io_after);
     if (p.io_before) (void)hipEventDestroy(p.io_before);
     if (p.g_ready) (void)hipEventDestroy(p.g_ready);
@@ -456,6 +461,7 @@ extern "C" int shc_fleet_all_gather_joints(shc_fleet *f, double **device_buffers
 
 #include "shc_fleet_checkpoint.hpp" // shc_fleet_checkpoint_*, shc_fleet_restore_instances, shc_fleet_scan_and_restore
 #include "shc_fleet_io.hpp" // shc_fleet_set_inputs_device, shc_fleet_get_outputs_device, the two ordering calls
+#include "shc_fleet_step_k.hpp" // shc_fleet_step_k, shc_fleet_get_step_k_joints_device: K cycles per launch from K-deep device arrays
 
 // ================================================================================================ one process per GPU: the exchange over peer copies
 // The all-gather of the final joint buffer (BASELINE.json north_star) without a collective library, for the one-process-per-GPU host (bench.py

@@ -1,5 +1,6 @@
 // shc_fleet_io.hpp — fleet device I/O: shc_fleet_set_inputs_device, shc_fleet_get_outputs_device, shc_fleet_order_after_stream,
-// shc_fleet_order_stream_after, shc_fleet_set_io_chunk, shc_fleet_io_bytes.  Included by shc_fleet.hpp.
+// shc_fleet_order_stream_after, shc_fleet_set_io_chunk, shc_fleet_io_bytes.  Included by shc_fleet.hpp.  (K cycles per launch from K-deep
+// device arrays - shc_fleet_step_k, shc_fleet_get_step_k_joints_device - is shc_fleet_step_k.hpp, built on what is here.)
 //
 // The host forms (shc_fleet_set_* / shc_fleet_get_*) permute rows between the caller's padded order and a part's dense order on the host and
 // cross it once per part and call.  Here both sides are device arrays and the permutation is a kernel on the part's own stream: PACK gathers
@@ -42,16 +43,21 @@ struct FleetPackArgs {
   FleetPackGroup g[kFleetIoGroups];
   int32_t n_groups;
 };
-__global__ void fleet_pack_inputs_kernel(double *__restrict__ stage, const int64_t *__restrict__ ids, int64_t rows, FleetPackArgs a) {
-  const FleetPackGroup &g = a.g[blockIdx.y];
+// (the rows of one group: `dst` the group's staged rows, `src` the caller's array - both of ONE cycle; shc_fleet_step_k.hpp packs K of them in one launch)
+__device__ __forceinline__ void fleet_pack_rows(double *__restrict__ dst, const double *__restrict__ src, const int64_t *__restrict__ ids, int64_t rows,
+                                                const FleetPackGroup &g) {
   const uint32_t w = uint32_t(g.legs * g.k), gk = uint32_t(g.k);
   const int64_t total = rows * w, stride = int64_t(gridDim.x) * blockDim.x;
   for (int64_t t0 = int64_t(blockIdx.x) * blockDim.x; t0 < total; t0 += stride) {
     const int64_t r0 = t0 / w; // uniform over the workgroup
     const uint32_t u = uint32_t(t0 - r0 * w) + threadIdx.x, dr = u / w, c = u - dr * w, l = c / gk, j = c - l * gk;
     const int64_t r = r0 + dr;
-    if (r < rows) stage[g.dst + r * w + c] = g.src[ids[r] * g.src_robot + int64_t(l) * g.src_leg + j];
+    if (r < rows) dst[r * w + c] = src[ids[r] * g.src_robot + int64_t(l) * g.src_leg + j];
   }
+}
+__global__ void fleet_pack_inputs_kernel(double *__restrict__ stage, const int64_t *__restrict__ ids, int64_t rows, FleetPackArgs a) {
+  const FleetPackGroup &g = a.g[blockIdx.y];
+  fleet_pack_rows(stage + g.dst, g.src, ids, rows, g);
 }
 
 // PLACE: `count` rows of a part ([count][legs][k] words, dense, in staging) into the caller's buffer ([n][dst_legs][dst_k] words) at the rows
@@ -131,7 +137,7 @@ extern "C" int shc_fleet_set_io_chunk(shc_fleet *f, int64_t robots) {
   if (!f || robots < 0) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL or a negative chunk");
   if (robots == f->io_chunk) return SHC_OK;
   for (auto &p : f->parts) { // staging is sized by the chunk: drain the part, release it, and let the next device I/O call allocate it again
-    if (!p.io_stage) continue;
+    if (!p.io_stage) continue; // (the K-deep staging of shc_fleet_step_k does not depend on the chunk: it stays)
     HIP_TRY(hipSetDevice(p.device));
     if (p.engine->side_busy) HIP_TRY(hipDeviceSynchronize()); // (a half stream may still read staged inputs)
     HIP_TRY(hipStreamSynchronize(p.engine->stream));
@@ -146,7 +152,7 @@ extern "C" int64_t shc_fleet_io_bytes(const shc_fleet *f) {
   int64_t bytes = 0;
   if (f)
     for (const auto &p : f->parts)
-      bytes += int64_t(p.io_stage_bytes) + (p.d_ids ? int64_t(p.ids.size()) * 8 : 0); // (the ids stay when shc_fleet_set_io_chunk releases the staging)
+      bytes += int64_t(p.io_stage_bytes) + int64_t(p.k_stage_bytes) + (p.d_ids ? int64_t(p.ids.size()) * 8 : 0); // (the ids stay when shc_fleet_set_io_chunk releases the staging)
   return bytes;
 }
 

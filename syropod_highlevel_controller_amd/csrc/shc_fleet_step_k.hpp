@@ -1,0 +1,188 @@
+// shc_fleet_step_k.hpp — K cycles per launch for a mixed fleet, from K-deep device arrays in the caller's order: shc_fleet_step_k,
+// shc_fleet_get_step_k_joints_device.  Included by shc_fleet.hpp behind shc_fleet_io.hpp, whose pack groups, grid rule, readiness checks, ids and
+// ordering events it uses.
+//
+// The cycle-by-cycle device route (shc_fleet_set_inputs_device, shc_fleet_step(1), shc_fleet_get_outputs_device) pays per part and CYCLE one pack
+// launch, the engine's setters, the step, two engine gathers and two place launches.  Here a part and CALL pays one pack launch, one
+// shc_engine_step_k and one place launch per requested array:
+//   K-deep PACK   fleet_pack_inputs_kernel with a cycle dimension (blockIdx.z).  Group g of the caller is [K][n][src_robot] doubles; the part's
+//                 rows of cycle k land at k_stage[g.dst + k * rows * legs * k_width ..], so that each staged group is the dense [K][rows][..]
+//                 array shc_engine_step_k reads with its own kstride (rows x width).  Bytes are copied as they are: the engine normalises.
+//   ring PLACE    reads the part's step_k output ring where it lies ([K][NJ planes][n_slots] double2, the leg state's own layout: leg_state_index)
+//                 and writes whole rows of the caller's [cycle][n][max_legs][max_dof] buffer at ids[r], NaN where the morphology has no such leg
+//                 or joint.  No dense copy in between: shc_engine_get_step_k_joint_state + fleet_place would move every joint twice and launch
+//                 2 x cycles x parts times.
+// Everything between the two - the batch kernel or the serial form, a pending adjusted parameter's first cycle, touchdown detection on fresh tip
+// forces, the first-effort switch, the last row staying as the held input - is shc_engine_step_k's, unchanged.
+//
+// K-deep staging: one buffer per part next to io_stage, K x rows x (the widths of the groups GIVEN: 2, 1, 4, 3, 3 L, L D) doubles, allocated by the
+// first call that needs it, grown (never shrunk) by a call that needs more, counted by shc_fleet_io_bytes, released with the fleet.  A call with
+// the same or a smaller K and the same groups allocates nothing.  The part's launch reads it - on the two half streams when the part steps split
+// (alone on its device, 4 096 wavefronts or more), which only a join orders behind the part's stream.  So before a pack overwrites it, a part
+// with split launches in flight is joined (shc_engine_join: events, no host wait); before it is freed to grow, the part is joined and its stream
+// drained, as step_k_out_ring does for the ring.  The caller's arrays are read by the pack alone, on the part's stream.
+#pragma once
+
+// A part's output ring (the engine's own bound, asked here before any part has launched) and its K-deep staging both stay below 2 GiB.
+constexpr size_t kFleetStepKMaxBytes = size_t(1) << 31;
+
+__global__ void fleet_pack_inputs_k_kernel(double *__restrict__ stage, const int64_t *__restrict__ ids, int64_t rows, int64_t n, FleetPackArgs a) {
+  const FleetPackGroup &g = a.g[blockIdx.y]; // group and cycle are wave-uniform: kernel arguments and block indices only
+  const int64_t cycle = blockIdx.z;
+  fleet_pack_rows(stage + g.dst + cycle * rows * (g.legs * g.k), g.src + cycle * n * g.src_robot, ids, rows, g);
+}
+
+// PLACE out of the ring.  `ring` is the slot of the first requested cycle; cycle c (blockIdx.y, wave-uniform) lies c * cycle_words further and goes
+// to dst + c * n * row.  One thread per word of a DESTINATION row, as fleet_place_kernel: a robot's stores are one contiguous run and every word
+// of the row is written.  f0: the leg field of joint 0 (Q or QD).  Words are copied as 64-bit patterns.
+__global__ void fleet_place_ring_kernel(uint64_t *__restrict__ dst, const uint64_t *__restrict__ ring, const int64_t *__restrict__ ids, int64_t rows, int64_t n,
+                                        int64_t n_slots, int64_t cycle_words, int legs, int k, int f0, int dst_legs, int dst_k, uint64_t pad) {
+  const uint32_t row = uint32_t(dst_legs * dst_k), dk = uint32_t(dst_k);
+  const uint64_t *__restrict__ slot = ring + int64_t(blockIdx.y) * cycle_words;
+  uint64_t *__restrict__ out = dst + int64_t(blockIdx.y) * n * row;
+  const int64_t total = rows * row, stride = int64_t(gridDim.x) * blockDim.x;
+  for (int64_t t0 = int64_t(blockIdx.x) * blockDim.x; t0 < total; t0 += stride) {
+    const int64_t r0 = t0 / row; // uniform over the workgroup
+    const uint32_t u = uint32_t(t0 - r0 * row) + threadIdx.x, dr = u / row, c = u - dr * row, l = c / dk, j = c - l * dk;
+    const int64_t r = r0 + dr;
+    if (r >= rows) continue;
+    uint64_t v = pad;
+    if (l < uint32_t(legs) && j < uint32_t(k)) v = slot[leg_state_index(f0 + int(j), r, int(l), legs, n_slots)];
+    out[ids[r] * row + c] = v;
+  }
+}
+// workgroups along x of a launch that has `cycles` of them along another grid dimension: the 2 048 of fleet_io_grid shared among the cycles
+static unsigned fleet_step_k_grid(int64_t threads, int cycles) {
+  return unsigned(std::max<int64_t>(1, std::min<int64_t>((threads + 255) / 256, 2048 / cycles)));
+}
+
+// the K-deep groups given, in staging order: the caller's array, which member of shc_cycle_inputs it becomes, and its shape on both sides
+enum { FSK_LIN, FSK_ANG, FSK_IMUQ, FSK_IMUW, FSK_FORCE, FSK_EFFORT, FSK_COUNT };
+struct FleetStepKGroup {
+  const double *src;
+  int member, legs, k, src_robot, src_leg;
+};
+static int fleet_step_k_groups(const shc_fleet *f, const FleetPart &p, const shc_fleet_inputs *rows, FleetStepKGroup (&g)[FSK_COUNT]) {
+  const shc_params &pp = f->params[p.morph];
+  const int L = pp.leg_count, D = max_dof(pp);
+  int n = 0;
+  if (!rows) return 0;
+  if (rows->linear_xy) g[n++] = {rows->linear_xy, FSK_LIN, 1, 2, 2, 0};
+  if (rows->angular) g[n++] = {rows->angular, FSK_ANG, 1, 1, 1, 0};
+  if (rows->imu_orientation_wxyz) g[n++] = {rows->imu_orientation_wxyz, FSK_IMUQ, 1, 4, 4, 0};
+  if (rows->imu_angular_velocity) g[n++] = {rows->imu_angular_velocity, FSK_IMUW, 1, 3, 3, 0};
+  if (rows->tip_force) g[n++] = {rows->tip_force, FSK_FORCE, L, 3, f->max_legs * 3, 3};
+  if (rows->joint_effort) g[n++] = {rows->joint_effort, FSK_EFFORT, L, D, f->max_legs * f->max_dof, f->max_dof};
+  return n;
+}
+static size_t fleet_step_k_stage_bytes(const shc_fleet *f, const FleetPart &p, int K, const shc_fleet_inputs *rows) {
+  FleetStepKGroup g[FSK_COUNT];
+  const int n = fleet_step_k_groups(f, p, rows, g);
+  size_t width = 0;
+  for (int i = 0; i < n; ++i) width += size_t(g[i].legs) * g[i].k;
+  return size_t(K) * p.ids.size() * width * 8;
+}
+
+extern "C" int shc_fleet_step_k(shc_fleet *f, int n_cycles, const shc_fleet_inputs *rows) {
+  if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
+  if (n_cycles < 1 || n_cycles > 4096) return fail(SHC_ERR_INVALID_ARG, "shc_fleet_step_k: 1 .. 4096 cycles per launch");
+  if (rows) {
+    if ((rows->linear_xy == nullptr) != (rows->angular == nullptr)) return fail(SHC_ERR_INVALID_ARG, "linear_xy and angular are given together");
+    if ((rows->imu_orientation_wxyz == nullptr) != (rows->imu_angular_velocity == nullptr)) return fail(SHC_ERR_INVALID_ARG, "the two IMU arrays are given together");
+    if (rows->pose_translation_velocity || rows->pose_rotation_velocity)
+      return fail(SHC_ERR_UNSUPPORTED, "shc_fleet_step_k carries velocity, IMU, tip force and joint effort; give pose inputs / reset modes with their setters before the call (held for the K cycles)");
+  }
+  int rc = fleet_io_ready(f);
+  if (rc != SHC_OK) return rc;
+  // every part is asked before the first launch (and before anything is allocated): what its shc_engine_step_k would refuse
+  for (const auto &p : f->parts) {
+    const shc_engine *e = p.engine;
+    if (e->starting_up) return fail(SHC_ERR_UNSUPPORTED, "shc_fleet_step_k: a part of the fleet is still starting up (finish the start-up first)");
+    if (size_t(e->NJ) * e->n_slots * 16 * size_t(n_cycles) >= kFleetStepKMaxBytes)
+      return fail(SHC_ERR_INVALID_ARG, "shc_fleet_step_k: cycles x a part's batch - the part's output ring must stay below 2 GiB (fewer cycles per launch)");
+    if (fleet_step_k_stage_bytes(f, p, n_cycles, rows) >= kFleetStepKMaxBytes)
+      return fail(SHC_ERR_INVALID_ARG, "shc_fleet_step_k: cycles x a part's rows of the inputs given - the part's K-deep staging must stay below 2 GiB (fewer cycles per launch)");
+    ResidentFit fit;
+    if ((rc = resident_fit(e, fit)) != SHC_OK) return rc;
+  }
+  if ((rc = fleet_io_prepare(f)) != SHC_OK) return rc;
+  for (auto &p : f->parts) { // staging that is too small: drained (the part's launches may still read it), released, allocated again
+    const size_t need = fleet_step_k_stage_bytes(f, p, n_cycles, rows);
+    if (need <= p.k_stage_bytes) continue;
+    HIP_TRY(hipSetDevice(p.device));
+    if (p.k_stage) {
+      if ((rc = shc_engine_join(p.engine)) != SHC_OK) return rc;
+      HIP_TRY(hipStreamSynchronize(p.engine->stream));
+      HIP_TRY(hipFree(p.k_stage));
+      p.k_stage = nullptr, p.k_stage_bytes = 0;
+    }
+    HIP_TRY(hipMalloc(&p.k_stage, need));
+    p.k_stage_bytes = need;
+  }
+  for (auto &p : f->parts) {
+    const int64_t n_rows = int64_t(p.ids.size());
+    FleetStepKGroup groups[FSK_COUNT];
+    const int n_groups = fleet_step_k_groups(f, p, rows, groups);
+    if (n_groups == 0) { // every input is held
+      if ((rc = shc_engine_step_k(p.engine, n_cycles, nullptr)) != SHC_OK) return rc;
+      continue;
+    }
+    double *stage = reinterpret_cast<double *>(p.k_stage);
+    const double *where[FSK_COUNT] = {};
+    FleetPackArgs a{};
+    int64_t at = 0, widest = 0;
+    for (int i = 0; i < n_groups; ++i) {
+      const FleetStepKGroup &g = groups[i];
+      FleetPackGroup &pg = a.g[a.n_groups++];
+      pg.src = g.src, pg.dst = at, pg.legs = g.legs, pg.k = g.k, pg.src_robot = g.src_robot, pg.src_leg = g.src_leg;
+      where[g.member] = stage + at;
+      at += int64_t(n_cycles) * n_rows * g.legs * g.k;
+      widest = std::max<int64_t>(widest, n_rows * g.legs * g.k);
+    }
+    HIP_TRY(hipSetDevice(p.device));
+    // the halves of an earlier split shc_engine_step_k may still be reading the rows this pack is about to overwrite: the part's stream follows them first
+    if (p.engine->side_busy && (rc = shc_engine_join(p.engine)) != SHC_OK) return rc;
+    fleet_pack_inputs_k_kernel<<<dim3(fleet_step_k_grid(widest, n_cycles), unsigned(a.n_groups), unsigned(n_cycles)), dim3(256), 0, p.engine->stream>>>(
+        stage, p.d_ids, n_rows, f->n, a);
+    HIP_TRY(hipGetLastError());
+    shc_cycle_inputs staged{};
+    staged.linear_xy = where[FSK_LIN], staged.angular = where[FSK_ANG], staged.imu_orientation_wxyz = where[FSK_IMUQ], staged.imu_angular_velocity = where[FSK_IMUW];
+    staged.tip_force = where[FSK_FORCE], staged.joint_effort = where[FSK_EFFORT], staged.on_device = 1;
+    if ((rc = shc_engine_step_k(p.engine, n_cycles, &staged)) != SHC_OK) return rc;
+  }
+  f->k_cycles = n_cycles;
+  return SHC_OK;
+}
+
+extern "C" int shc_fleet_get_step_k_joints_device(shc_fleet *f, int first_cycle, int n_cycles, double *q, double *qd) {
+  if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
+  if (!q && !qd) return fail(SHC_ERR_INVALID_ARG, "q and qd are both NULL");
+  if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(qd)) & 7) return fail(SHC_ERR_INVALID_ARG, "q / qd must be 8-byte aligned");
+  int rc = fleet_io_ready(f);
+  if (rc != SHC_OK) return rc;
+  const char *range = "shc_fleet_get_step_k_joints_device: cycles [first_cycle, first_cycle + n_cycles) of the K of the latest shc_fleet_step_k";
+  if (f->k_cycles < 1 || first_cycle < 0 || n_cycles < 1 || first_cycle > f->k_cycles - n_cycles) return fail(SHC_ERR_INVALID_ARG, range);
+  for (const auto &p : f->parts) // (a part stepped on its own since, through shc_fleet_part: its ring holds another launch)
+    if (!p.engine->k_out || p.engine->k_out_cycles != f->k_cycles) return fail(SHC_ERR_INVALID_ARG, range);
+  if ((rc = fleet_io_prepare(f)) != SHC_OK) return rc;
+
+  uint64_t nan_word; // the bit pattern shc_fleet_get_joint_state fills the padding with
+  const double nan_value = std::nan("");
+  memcpy(&nan_word, &nan_value, 8);
+  for (auto &p : f->parts) {
+    shc_engine *e = p.engine;
+    const int64_t n_rows = int64_t(p.ids.size()), cycle_words = int64_t(e->NJ) * e->n_slots * 2;
+    if ((rc = shc_engine_join(e)) != SHC_OK) return rc; // split launches: the part's stream follows both halves before it reads their ring
+    HIP_TRY(hipSetDevice(p.device));
+    const uint64_t *ring = reinterpret_cast<const uint64_t *>(e->k_out) + int64_t(first_cycle) * cycle_words;
+    for (int which = 0; which < 2; ++which) {
+      double *dst = which == 0 ? q : qd;
+      if (!dst) continue;
+      fleet_place_ring_kernel<<<dim3(fleet_step_k_grid(n_rows * f->max_legs * f->max_dof, n_cycles), unsigned(n_cycles)), dim3(256), 0, e->stream>>>(
+          reinterpret_cast<uint64_t *>(dst), ring, p.d_ids, n_rows, f->n, e->n_slots, cycle_words, e->L, e->NJ, which == 0 ? LEG_FIELD(e, Q) : LEG_FIELD(e, QD),
+          f->max_legs, f->max_dof, nan_word);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  return SHC_OK;
+}

@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = [
     "shc_fleet_restore_instances", "shc_fleet_scan_and_restore",
     "shc_fleet_set_inputs_device", "shc_fleet_get_outputs_device", "shc_fleet_order_after_stream", "shc_fleet_order_stream_after",
     "shc_fleet_set_io_chunk", "shc_fleet_io_bytes",
+    "shc_fleet_step_k", "shc_fleet_get_step_k_joints_device",
     "shc_peer_alloc", "shc_peer_open", "shc_peer_close", "shc_peer_scatter",
 ]
 
@@ -404,6 +405,8 @@ def lib():
         L.shc_fleet_set_io_chunk.argtypes = [C.c_void_p, C.c_int64]
         L.shc_fleet_io_bytes.argtypes = [C.c_void_p]
         L.shc_fleet_io_bytes.restype = C.c_int64
+        L.shc_fleet_step_k.argtypes = [C.c_void_p, C.c_int, C.POINTER(FleetInputs)]
+        L.shc_fleet_get_step_k_joints_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.shc_engine_resident_begin.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int]
         L.shc_engine_resident_post.argtypes = [C.c_void_p, C.POINTER(CycleInputs), C.POINTER(C.c_int64)]
         L.shc_engine_resident_bind_inputs.argtypes = [C.c_void_p, C.c_int, C.POINTER(CycleInputs)]

@@ -3,7 +3,8 @@
 The binning (one engine and one HIP stream per (morphology bin, device)), the contiguous sharding over devices and the
 device-to-device all-gather of the joint buffer live in the library (csrc/shc_fleet.hpp); this class only converts numpy
 arrays.  Inputs arrive and outputs leave indexed by the caller's instance id, whatever the interleaving pattern - as host
-arrays, or (set_inputs / outputs, csrc/shc_fleet_io.hpp) as device arrays that never cross the host.
+arrays, or (set_inputs / outputs, csrc/shc_fleet_io.hpp; step_k / step_k_joints, csrc/shc_fleet_step_k.hpp: K cycles per launch) as device
+arrays that never cross the host.
 """
 from __future__ import annotations
 
@@ -224,6 +225,37 @@ class MixedFleet:
         crit = _engine.HealthCriteria(int(select), 0, float(near_limit_proximity), float(tip_deviation))
         st.criteria = C.pointer(crit)
         _engine._check(self.L.shc_fleet_get_outputs_device(self.h, C.byref(st)), "shc_fleet_get_outputs_device")
+
+    def step_k(self, n_cycles: int, **arrays):
+        """K = ``n_cycles`` cycles in one launch per part (shc_fleet_step_k), cycle k with row k of K-deep DEVICE arrays: the names of
+        ``set_inputs`` with a leading dimension K - linear_xy (K, n, 2), angular (K, n), imu_orientation_wxyz (K, n, 4), imu_angular_velocity
+        (K, n, 3), tip_force (K, n, max_legs, 3), joint_effort (K, n, max_legs, max_dof).  An argument left out (or None) holds that input for
+        the K cycles; the two pose inputs are refused (set them beforehand: they are held).  The state, the held inputs and every cycle's
+        joints are what K rounds of ``set_inputs(row k)``, ``step(1)``, ``outputs(q, qd)`` give.  No host wait, and the stream rules of
+        ``set_inputs``; the arrays are free once the parts have read them (``order_before`` + stream order, or ``synchronize()``)."""
+        K = int(n_cycles)
+        shapes, st = self._input_shapes(), _engine.FleetInputs()
+        for name, a in arrays.items():
+            if name not in shapes:
+                raise TypeError(f"step_k: unknown input {name!r} (one of {', '.join(shapes)})")
+            if a is not None:
+                setattr(st, name, _engine._device_array(a, "<f8", (K,) + shapes[name], name))
+        _engine._check(self.L.shc_fleet_step_k(self.h, K, C.byref(st)), "shc_fleet_step_k")
+
+    def step_k_joints(self, first: int = 0, count=None, q=None, qd=None):
+        """q / qd of cycles [first, first + count) of the latest ``step_k`` into DEVICE buffers of the caller's, float64 (count, n, max_legs,
+        max_dof) in the caller's instance order, NaN padded as ``joints()``.  count None: as many cycles as the buffers given have rows (the
+        library refuses a range past the latest K).  Only the buffers given are
+        written, every entry of them; at least one must be given.  No host wait: complete after ``synchronize()``, or for work queued on a
+        stream after ``order_before(stream)``."""
+        given = [b for b in (q, qd) if b is not None]
+        if count is None and given:
+            cai = getattr(given[0], "__cuda_array_interface__", None)
+            count = cai["shape"][0] if cai and len(cai["shape"]) == 4 else 0
+        shape = (int(count or 0), self.n, self.max_legs, self.max_dof)
+        pq = None if q is None else _engine._device_array(q, "<f8", shape, "q")
+        pqd = None if qd is None else _engine._device_array(qd, "<f8", shape, "qd")
+        _engine._check(self.L.shc_fleet_get_step_k_joints_device(self.h, int(first), int(count), pq, pqd), "shc_fleet_get_step_k_joints_device")
 
     @staticmethod
     def _stream_handle(stream):
