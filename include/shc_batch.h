@@ -1136,6 +1136,63 @@ int64_t shc_fleet_io_bytes(const shc_fleet *f);                /* device bytes t
  */
 int shc_fleet_step_k(shc_fleet *f, int n_cycles, const shc_fleet_inputs *rows /* may be NULL: every input held */);
 int shc_fleet_get_step_k_joints_device(shc_fleet *f, int first_cycle, int n_cycles, double *q, double *qd /* either may be NULL, not both */);
+/*
+ * Observation pass: chosen fields of every robot as one dense [rows][D] array of float64 or float32, for a learner that wants 40 - 120 numbers
+ * per robot and not the whole records of the getters above.  One kernel per engine (per part of a fleet) evaluates only the fields asked for,
+ * converts them to the element type and writes each robot's row where the caller's array wants it; nothing is staged.
+ * ROW.  The fields of a spec follow each other in the order of `fields`.  A per-leg field of `width` columns per leg takes legs x width columns,
+ * leg-major (leg l, component k at l * width + k; width = spec.dof for the joint fields); a per-robot field takes its width.  shc_obs_width is the
+ * number of columns D, shc_obs_column the column of one component; neither needs a device.
+ * DEFINITION.  Column c of robot i's row holds the double the getter named beside the field writes for that robot, leg and component - unchanged
+ * for SHC_OBS_F64, static_cast<float> (round to nearest even) for SHC_OBS_F32.  `pad`, converted in the same way once on the host, is written
+ * wherever the robot's morphology has no such leg or no such joint (leg >= its legs, joint >= its longest leg's DOF; the joints a shorter leg of a
+ * mixed-DOF robot lacks hold what shc_engine_get_joint_state holds there).  Columns [width, row_stride) of a row are not touched.
+ * SHC_OBS_MODEL_TIP / SHC_OBS_POSER_TIP are the values the derived-tip refresh of shc_engine_get_leg_state_msgs produces, derived inside the
+ * pass from the same stored state by the same device functions, and only when one of the two is asked for; the pass WRITES NOTHING into an
+ * engine: every robot's state record and auxiliary blob are byte for byte what they were.  SHC_OBS_ADMITTANCE_DELTA is zero with admittance
+ * control off, as in shc_leg_state_msg.
+ * shc_engine_get_observations: instances [first, first + count) into rows 0 .. count - 1 of `out` (host array, or device array with on_device =
+ * 1, aligned to the element size).  on_device, stream ordering, the join of split steps and count = 0 (a no-op) are those of
+ * shc_engine_get_leg_state_msgs.
+ * shc_fleet_get_observations_device: every robot of the fleet into row i = its CALLER's instance id of the device array `out` ([n][row_stride]).
+ * One kernel per part on the part's own stream reads the part's state and writes the caller's rows through the part's caller ids (the ids device
+ * I/O keeps on the device): no staging, no allocation after the fleet's first device I/O call, shc_fleet_io_bytes unchanged.  The STREAMS rules
+ * of device I/O and shc_fleet_order_after_stream / shc_fleet_order_stream_after apply as written there.
+ * REFUSALS (nothing is launched; a fleet asks every part before the first launch).  SHC_ERR_INVALID_ARG: NULL handle, spec or out; n_fields
+ * outside 1 .. SHC_OBS_MAX_FIELDS; an unknown or repeated field; an unknown dtype; reserved != 0; legs / dof below the engine's (legs, longest leg's
+ * DOF) or the fleet's shc_fleet_shape, or above SHC_MAX_LEGS / SHC_MAX_JOINTS; row_stride non-zero and below the width; a range outside [0, n); a
+ * buffer not aligned to the element size.  SHC_ERR_UNSUPPORTED: SHC_OBS_ODOM_TO_BASE_LINK on an engine or part without SHC_FEAT_ODOMETRY;
+ * SHC_OBS_VIRTUAL_STIFFNESS with admittance control off (as shc_engine_get_virtual_stiffness); a fleet that spans devices.  SHC_ERR_BUSY: resident mode.
+ */
+enum { /* per-leg fields: `width` columns per leg, leg-major, for `legs` legs */
+  SHC_OBS_Q, SHC_OBS_QD,            /* width dof: shc_engine_get_joint_state / shc_fleet_get_joint_state              */
+  SHC_OBS_JOINT_EFFORT,             /* width dof: shc_leg_state_msg.joint_efforts                                     */
+  SHC_OBS_WALKER_TIP, SHC_OBS_TARGET_TIP, SHC_OBS_POSER_TIP, SHC_OBS_MODEL_TIP,   /* 3: the *_tip_position members     */
+  SHC_OBS_TIP_FORCE, SHC_OBS_ADMITTANCE_DELTA,                                      /* 3: tip_force (x force_gain), admittance_delta */
+  SHC_OBS_VIRTUAL_STIFFNESS, SHC_OBS_STANCE_PROGRESS, SHC_OBS_SWING_PROGRESS, SHC_OBS_TIME_TO_SWING_END, /* 1 each: the shc_leg_state_msg members */
+  SHC_OBS_STEP_STATE,               /* 1: bits 0-1 of shc_engine_get_leg_state's leg_status, as a number               */
+  /* per-robot fields */
+  SHC_OBS_BODY_POSE,                /* 7: shc_engine_get_body_state pose                                               */
+  SHC_OBS_DESIRED_VELOCITY,         /* 3: shc_body_frames.desired_velocity                                             */
+  SHC_OBS_POSE_EULER,               /* 3: shc_body_frames.pose_euler                                                   */
+  SHC_OBS_ODOM_TO_BASE_LINK,        /* 7: shc_body_frames.odom_to_base_link (needs SHC_FEAT_ODOMETRY)                  */
+  SHC_OBS_WALK_STATE,               /* 1: walk_state as a number                                                       */
+  SHC_OBS_FIELD_COUNT
+};
+enum { SHC_OBS_F64 = 0, SHC_OBS_F32 = 1 };
+#define SHC_OBS_MAX_FIELDS 32
+typedef struct shc_obs_spec {
+  int32_t n_fields, fields[SHC_OBS_MAX_FIELDS]; /* column order = this order; a field may appear once                 */
+  int32_t dtype;                                /* SHC_OBS_F64 / SHC_OBS_F32                                           */
+  int32_t legs, dof;                            /* row geometry; engine: >= its legs / longest leg's dof; fleet: >= shc_fleet_shape */
+  int32_t reserved;                             /* 0 */
+  int64_t row_stride;                           /* elements between rows; 0 = dense (= shc_obs_width); >= width otherwise */
+  double pad;                                   /* written where a robot has no such leg or a leg no such joint        */
+} shc_obs_spec;
+int64_t shc_obs_width(const shc_obs_spec *spec);                       /* columns of a row; < 0 for an invalid spec; no device needed */
+int shc_obs_column(const shc_obs_spec *spec, int field, int leg, int k); /* column of component k of `field` (leg ignored for robot fields); -1 if absent */
+int shc_engine_get_observations(shc_engine *e, int64_t first, int64_t count, const shc_obs_spec *spec, void *out, int on_device);
+int shc_fleet_get_observations_device(shc_fleet *f, const shc_obs_spec *spec, void *out /* [n][row_stride], caller's order */);
 /* The exchange step of a sharded batch: every device ends up with the desired joint positions of ALL instances
  * ([n][max_legs][max_dof], caller's order, NaN padded) in its own HBM, copied device to device (hipMemcpyPeerAsync: xGMI on an
  * MI355X node).  device_buffers[d] (may be NULL) receives device_ids[d]'s buffer; the buffers belong to the fleet. */

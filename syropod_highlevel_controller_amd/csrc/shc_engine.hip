@@ -85,6 +85,21 @@ __global__ void gather_leg_kernel(double *dst, const double *legd, int64_t n_slo
 }
 // LegState tips derived from the stored state (see store_leg): model tip = FK(q) in the robot frame (Leg::applyFK,
 // model.cpp:975), poser tip = Model::current_pose_^-1 * walker tip (PoseController::updateStance, pose_controller.cpp:122-131).
+// The three functions are the one implementation: derive_tips_kernel stores what they return, observe_kernel (shc_observe.hpp) uses it in place.
+template <int NJ>
+__device__ __forceinline__ V3 derived_model_tip(const LegConst<NJ> &lc, const double (&q)[NJ]) {
+  Chain<NJ> ch;
+  fk_chain<NJ>(lc, q, ch);
+  return tip_robot_frame(lc, ch.pe);
+}
+__device__ __forceinline__ V3 derived_poser_tip(const double (&c)[7], V3 walker_tip) {
+  return inverse_transform_vector(Pose{V3{c[0], c[1], c[2]}, Quat{c[3], c[4], c[5], c[6]}}, walker_tip);
+}
+// keep_marked: the last loop of the marked robots was a plan call under time-dependent posing - their LegPoser tips are state (the
+// pose has moved on since the updateStance that produced them, see execute_plan_kernel LOOP_MARK)
+__device__ __forceinline__ bool poser_tip_is_derived(const DevState &st, int64_t rob, int derive_poser, int keep_marked) {
+  return derive_poser && !(keep_marked && st.manual != nullptr && st.manual[rob].skip_cycle != 0);
+}
 template <int L, int NJ>
 __global__ void derive_tips_kernel(DevState st, const SharedConsts<L, NJ> *gc, int derive_poser, int keep_marked) {
   using FD = Fields<NJ>;
@@ -97,21 +112,17 @@ __global__ void derive_tips_kernel(DevState st, const SharedConsts<L, NJ> *gc, i
   const LegConst<NJ> &lc = gc->leg[leg];
   double q[NJ];
   for (int j = 0; j < NJ; ++j) q[j] = st.legd[leg_field_index(FD::Q + j, slot, st.n_slots)];
-  Chain<NJ> ch;
-  fk_chain<NJ>(lc, q, ch);
-  V3 tip = tip_robot_frame(lc, ch.pe);
+  V3 tip = derived_model_tip<NJ>(lc, q);
   st.legd[leg_field_index(FD::MODEL_TIP, slot, st.n_slots)] = tip.x;
   st.legd[leg_field_index(FD::MODEL_TIP + 1, slot, st.n_slots)] = tip.y;
   st.legd[leg_field_index(FD::MODEL_TIP + 2, slot, st.n_slots)] = tip.z;
-  // keep_marked: the last loop of the marked robots was a plan call under time-dependent posing - their LegPoser tips are state (the
-  // pose has moved on since the updateStance that produced them, see execute_plan_kernel LOOP_MARK)
-  if (derive_poser && !(keep_marked && st.manual != nullptr && st.manual[rob].skip_cycle != 0)) {
+  if (poser_tip_is_derived(st, rob, derive_poser, keep_marked)) {
     constexpr int rpw = 64 / L;
     double c[7];
     for (int k = 0; k < 7; ++k) c[k] = st.robd[rob_index(rob, R::CPOSE + k, rpw, R::COUNT)];
     V3 w{st.legd[leg_field_index(FD::TIP, slot, st.n_slots)], st.legd[leg_field_index(FD::TIP + 1, slot, st.n_slots)],
          st.legd[leg_field_index(FD::TIP + 2, slot, st.n_slots)]};
-    V3 pt = inverse_transform_vector(Pose{V3{c[0], c[1], c[2]}, Quat{c[3], c[4], c[5], c[6]}}, w);
+    V3 pt = derived_poser_tip(c, w);
     st.legd[leg_field_index(FD::POSER_TIP, slot, st.n_slots)] = pt.x;
     st.legd[leg_field_index(FD::POSER_TIP + 1, slot, st.n_slots)] = pt.y;
     st.legd[leg_field_index(FD::POSER_TIP + 2, slot, st.n_slots)] = pt.z;
@@ -170,14 +181,17 @@ __global__ void read_instance_kernel(double *dst, DevState st, int L, int64_t ro
     for (int k = 0; k < 4; ++k) o[6 + k] = st.robd[rob_index(rob, R::IMUQ + k, rpw, R::COUNT)];
   }
 }
+// leg_status of shc_engine_get_leg_state from the leg word: bits 0-1 the step state, bit 2 the IK failure, the phase from bit 8
+__device__ __forceinline__ int leg_status_of(int w) {
+  int phase = (w >> LW_PHASE_SHIFT) & LW_PHASE_MASK;
+  return (w & 3) | ((w & LW_IKFAIL) ? 4 : 0) | (phase << 8);
+}
 __global__ void gather_leg_status_kernel(int32_t *dst, const int32_t *legi, int64_t n, int L) {
   int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (t >= n * L) return;
   int64_t rob = t / L;
   int leg = int(t - rob * L);
-  int w = legi[slot_of(rob, leg, L)];
-  int phase = (w >> LW_PHASE_SHIFT) & LW_PHASE_MASK;
-  dst[t] = (w & 3) | ((w & LW_IKFAIL) ? 4 : 0) | (phase << 8);
+  dst[t] = leg_status_of(legi[slot_of(rob, leg, L)]);
 }
 // AoS [n][K] -> robot fields
 
@@ -220,10 +234,11 @@ __global__ void fill_robi_kernel(int32_t *robi, int rpw, int64_t n, int f, int32
   int64_t r = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (r < n) robi[rob_index(r, f, rpw, RobotFields::I_COUNT)] = v;
 }
+__device__ __forceinline__ int walk_state_of(const int32_t *robi, int64_t r, int rpw) { return robi[rob_index(r, RobotFields::I_WORD, rpw, RobotFields::I_COUNT)] & 3; }
 __global__ void gather_walk_state_kernel(int32_t *dst, const int32_t *robi, int rpw, int64_t n) {
   int64_t r = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (r >= n) return;
-  dst[r] = robi[rob_index(r, RobotFields::I_WORD, rpw, RobotFields::I_COUNT)] & 3;
+  dst[r] = walk_state_of(robi, r, rpw);
 }
 // replicate the post-start-up state of one robot into every slot
 __global__ void init_state_kernel(DevState st, const double *leg_template /*[L][nf]*/, const int32_t *legw_template /*[L]*/,
@@ -1551,11 +1566,15 @@ extern "C" int shc_engine_get_virtual_stiffness(shc_engine *e, double *stiffness
   return gather_leg(e, stiffness, 1, LEG_FIELD(e, ADM_DELTA) + 3, on_device);
 }
 
+// The two launch-uniform facts of the derivation (derive_tips_kernel, observe_kernel)
+static int derive_poser_tips(const shc_engine *e) { return !(e->cp.auto_posing && !e->cp.imu_posing); } // the auto-pose path stores its per-leg poser tip
+static int keep_marked_poser_tips(const shc_engine *e) {
+  return e->plan_poser_tips_current && (e->params.imu_posing || e->params.auto_posing || e->params.inclination_posing);
+}
 static int derive_tips(shc_engine *e) {
   HIP_TRY(hipSetDevice(e->device));
   const int64_t threads = e->n * e->L;
-  const int derive_poser = !(e->cp.auto_posing && !e->cp.imu_posing); // the auto-pose path stores its per-leg poser tip
-  const int keep_marked = e->plan_poser_tips_current && (e->params.imu_posing || e->params.auto_posing || e->params.inclination_posing);
+  const int derive_poser = derive_poser_tips(e), keep_marked = keep_marked_poser_tips(e);
   const int rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
     constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
     derive_tips_kernel<L, NJ><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(e->st, (const SharedConsts<L, NJ> *)e->d_consts, derive_poser,
@@ -1570,6 +1589,7 @@ static int derive_tips(shc_engine *e) {
 #include "shc_leg_msgs.hpp" // the derived LegState fields (one host + device implementation) and shc_engine_get_leg_state_msgs
 #include "shc_frames.hpp"   // publishFrameTransforms: every joint / tip frame and the body frames, shc_engine_get_frame_transforms
 #include "shc_health.hpp"   // the reference's IK / clamping warnings per robot, a restore map and the selected robots: shc_engine_scan_health
+#include "shc_observe.hpp"  // chosen fields of every robot as one dense [rows][D] array: shc_engine_get_observations
 
 template <int NJ>
 static Pose host_fk_tip_pose(const shc_params &p, int leg, const double *q) {

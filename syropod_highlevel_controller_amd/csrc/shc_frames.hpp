@@ -82,18 +82,37 @@ SHC_HD void leg_frames_to_world(const Pose &odom_to_base_link, double (&rec)[kLe
 //   base_link_to_walk_plane = ~getCurrentPose()                                 (:995-1005; pose.h:112-115)
 //   pose_euler              = quaternionToEulerAngles(current_pose.rotation_)   (:919-921)
 //   desired_velocity        = (vx, vy, omega)                                   (:900-905)
+// (the members the observation pass evaluates on their own - shc_observe.hpp - are functions of their own)
+SHC_HD Pose body_odom_to_base_link(const Pose &odometry, const Pose &current) { return add_pose(odometry, current); }
+SHC_HD V3 body_pose_euler(const Pose &current) { return quat_to_euler(current.r, false); }
 SHC_HD Pose body_frames(const Pose &odometry, const Pose &current, V3 velocity, double (&rec)[kBodyFrameDoubles]) {
-  const Pose o2b = add_pose(odometry, current);
+  const Pose o2b = body_odom_to_base_link(odometry, current);
   put_pose(&rec[0], o2b);
   const Quat rc = conj(current.r);
   put_pose(&rec[7], Pose{rotate(rc, -current.p), rc});
-  const V3 e = quat_to_euler(current.r, false);
+  const V3 e = body_pose_euler(current);
   rec[14] = e.x, rec[15] = e.y, rec[16] = e.z;
   rec[17] = velocity.x, rec[18] = velocity.y, rec[19] = velocity.z;
   return o2b;
 }
 
 // ---- the batched form
+// The robot-level inputs of body_frames out of the wavefront's robot tile (frame_transforms_kernel, observe_kernel)
+__device__ __forceinline__ Pose frames_current_pose(const DevState &st, int64_t rob, int rpw) {
+  using R = RobotFields;
+  auto rd = [&](int f) { return st.robd[rob_index(rob, f, rpw, R::COUNT)]; };
+  return Pose{V3{rd(R::CPOSE), rd(R::CPOSE + 1), rd(R::CPOSE + 2)}, Quat{rd(R::CPOSE + 3), rd(R::CPOSE + 4), rd(R::CPOSE + 5), rd(R::CPOSE + 6)}};
+}
+__device__ __forceinline__ Pose frames_odometry(const DevState &st, int64_t rob, int rpw, int have_odom) {
+  using R = RobotFields;
+  auto rd = [&](int f) { return st.robd[rob_index(rob, f, rpw, R::COUNT)]; };
+  if (!have_odom) return pose_identity();
+  return Pose{V3{rd(R::ODOM), rd(R::ODOM + 1), 0.0}, Quat{rd(R::ODOM + 2), 0.0, 0.0, rd(R::ODOM + 3)}}; // stored as x, y, qw, qz
+}
+__device__ __forceinline__ V3 frames_desired_velocity(const DevState &st, int64_t rob, int rpw) {
+  using R = RobotFields;
+  return V3{st.robd[rob_index(rob, R::VLIN, rpw, R::COUNT)], st.robd[rob_index(rob, R::VLIN + 1, rpw, R::COUNT)], st.robd[rob_index(rob, R::VANG, rpw, R::COUNT)]};
+}
 // One leg per lane, floor(64 / L) robots per wavefront (the cycle's slot mapping: the joint-angle planes are read as contiguous double2 per
 // lane); one wavefront per workgroup.  Block b serves the robot group first / rpw + b, clipped to [first, first + count).
 //
@@ -109,7 +128,6 @@ __global__ __launch_bounds__(64) void frame_transforms_kernel(double2 *__restric
                                                               const SharedConsts<L, NJ> *__restrict__ gc, int world, int have_odom, int64_t first,
                                                               int64_t count) {
   using FD = Fields<NJ>;
-  using R = RobotFields;
   constexpr int rpw = 64 / L;
   constexpr int kLegChunks = kLegFrameDoubles / 2, kBodyChunks = kBodyFrameDoubles / 2;
   __shared__ double2 strip[64 * kLegChunks];
@@ -132,11 +150,7 @@ __global__ __launch_bounds__(64) void frame_transforms_kernel(double2 *__restric
   if (live) {
     Pose o2b = pose_identity();
     if (body_out != nullptr || world) { // every lane of a robot's group forms the robot's record for itself, as the cycle does
-      auto rd = [&](int f) { return st.robd[rob_index(rob, f, rpw, R::COUNT)]; };
-      const Pose current{V3{rd(R::CPOSE), rd(R::CPOSE + 1), rd(R::CPOSE + 2)}, Quat{rd(R::CPOSE + 3), rd(R::CPOSE + 4), rd(R::CPOSE + 5), rd(R::CPOSE + 6)}};
-      Pose odometry = pose_identity();
-      if (have_odom) odometry = Pose{V3{rd(R::ODOM), rd(R::ODOM + 1), 0.0}, Quat{rd(R::ODOM + 2), 0.0, 0.0, rd(R::ODOM + 3)}}; // stored as x, y, qw, qz
-      o2b = body_frames(odometry, current, V3{rd(R::VLIN), rd(R::VLIN + 1), rd(R::VANG)}, brec);
+      o2b = body_frames(frames_odometry(st, rob, rpw, have_odom), frames_current_pose(st, rob, rpw), frames_desired_velocity(st, rob, rpw), brec);
     }
     if (legs_out != nullptr) {
       double q[NJ]; // Joint::desired_position_: the chain applyFK() left behind

@@ -140,6 +140,9 @@ SHC_HD LegMsgProgress leg_msg_progress(const LegMsgArgs &a, int word, double vx,
   return r;
 }
 
+// LegState.tip_force: tip_force_calculated_ * force_gain (state_controller.cpp:883-885)
+SHC_HD double leg_msg_tip_force(const LegMsgArgs &a, double calculated) { return calculated * a.force_gain; }
+
 // ---- the batched form
 // Record layout in doubles (shc_leg_state_msg is 64 doubles, no padding: the kernel builds a record as double rec[64])
 struct LegMsgAt {
@@ -221,7 +224,7 @@ __global__ __launch_bounds__(64) void leg_state_msgs_kernel(double2 *__restrict_
       for (int k = 0; k < 3; ++k) rec[At::MODEL + k] = v[k];
       load_leg_fields<FD::TF, 3>(planes, st.n_slots, slot, v);
 #pragma unroll
-      for (int k = 0; k < 3; ++k) rec[At::FORCE + k] = v[k] * a.force_gain; // tip_force_calculated_ * force_gain (:883-885)
+      for (int k = 0; k < 3; ++k) rec[At::FORCE + k] = leg_msg_tip_force(a, v[k]);
     }
     if (a.admittance_control) {
       double v[4];

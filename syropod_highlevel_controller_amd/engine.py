@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = [
     "shc_fleet_set_inputs_device", "shc_fleet_get_outputs_device", "shc_fleet_order_after_stream", "shc_fleet_order_stream_after",
     "shc_fleet_set_io_chunk", "shc_fleet_io_bytes",
     "shc_fleet_step_k", "shc_fleet_get_step_k_joints_device",
+    "shc_obs_width", "shc_obs_column", "shc_engine_get_observations", "shc_fleet_get_observations_device",
     "shc_peer_alloc", "shc_peer_open", "shc_peer_close", "shc_peer_scatter",
 ]
 
@@ -126,6 +127,79 @@ class FleetOutputs(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("q", "qd", "walk_state", "leg_state_msgs", "leg_frames", "body_frames")] + [("frame", C.c_int32), ("reserved", C.c_int32),
                                                                                                                  ("health", C.c_void_p),
                                                                                                                  ("criteria", C.POINTER(HealthCriteria))]
+
+
+# The observation pass (include/shc_batch.h, "Observation pass"): SHC_OBS_* by name, in the order of the enum
+OBS_FIELD_NAMES = ("q", "qd", "joint_effort", "walker_tip", "target_tip", "poser_tip", "model_tip", "tip_force", "admittance_delta", "virtual_stiffness",
+                   "stance_progress", "swing_progress", "time_to_swing_end", "step_state",
+                   "body_pose", "desired_velocity", "pose_euler", "odom_to_base_link", "walk_state")
+OBS_FIELDS = {name: i for i, name in enumerate(OBS_FIELD_NAMES)}
+OBS_MAX_FIELDS = 32
+OBS_DTYPES = {"float64": 0, "float32": 1}  # SHC_OBS_F64 / SHC_OBS_F32
+_OBS_ROBOT_WIDTH = {"body_pose": 7, "desired_velocity": 3, "pose_euler": 3, "odom_to_base_link": 7, "walk_state": 1}
+_OBS_JOINT_FIELDS = ("q", "qd", "joint_effort")
+_OBS_LEG_WIDTH = {"walker_tip": 3, "target_tip": 3, "poser_tip": 3, "model_tip": 3, "tip_force": 3, "admittance_delta": 3, "virtual_stiffness": 1,
+                  "stance_progress": 1, "swing_progress": 1, "time_to_swing_end": 1, "step_state": 1}
+
+
+class ObsSpec(C.Structure):
+    """shc_obs_spec: which fields, in which order, as which element type, for which row geometry."""
+    _fields_ = [("n_fields", C.c_int32), ("fields", C.c_int32 * OBS_MAX_FIELDS), ("dtype", C.c_int32), ("legs", C.c_int32), ("dof", C.c_int32),
+                ("reserved", C.c_int32), ("row_stride", C.c_int64), ("pad", C.c_double)]
+
+
+def obs_spec(fields, legs: int, dof: int, dtype="float32", row_stride: int = 0, pad: float = 0.0) -> ObsSpec:
+    """The shc_obs_spec of a list of field names (OBS_FIELDS) or SHC_OBS_* integers.  Nothing is checked here: the library judges the spec."""
+    ids = [OBS_FIELDS[f] if isinstance(f, str) else int(f) for f in fields]
+    st = ObsSpec()
+    st.n_fields = len(ids)
+    for i, f in enumerate(ids[:OBS_MAX_FIELDS]):
+        st.fields[i] = f
+    st.dtype = OBS_DTYPES[np.dtype(dtype).name] if not isinstance(dtype, int) else dtype
+    st.legs, st.dof, st.row_stride, st.pad = int(legs), int(dof), int(row_stride), float(pad)
+    return st
+
+
+def observation_columns(fields, legs: int, dof: int):
+    """({name: slice}, width) of a row of observations(fields) for the row geometry (legs, dof): a per-leg field's slice reshapes to (legs, width
+    per leg), leg-major.  Computed here and checked against the library's own answer (shc_obs_width / shc_obs_column)."""
+    names = [f if isinstance(f, str) else OBS_FIELD_NAMES[int(f)] for f in fields]
+    cols, at = {}, 0
+    for name in names:
+        if name in cols:
+            raise ValueError(f"observation field {name!r} is named twice")
+        if name not in OBS_FIELDS:
+            raise ValueError(f"unknown observation field {name!r} (one of {', '.join(OBS_FIELD_NAMES)})")
+        w = _OBS_ROBOT_WIDTH[name] if name in _OBS_ROBOT_WIDTH else int(legs) * (int(dof) if name in _OBS_JOINT_FIELDS else _OBS_LEG_WIDTH[name])
+        cols[name] = slice(at, at + w)
+        at += w
+    L, spec = lib(), obs_spec(names, legs, dof)
+    width = int(L.shc_obs_width(C.byref(spec)))
+    if width < 0:
+        msg = L.shc_last_error()
+        raise ValueError(f"observation spec refused: {msg.decode() if msg else ''}")
+    for name, sl in cols.items():
+        per_leg = name not in _OBS_ROBOT_WIDTH
+        last = (int(legs) - 1, (sl.stop - sl.start) // int(legs) - 1) if per_leg else (0, sl.stop - sl.start - 1)
+        if width != at or L.shc_obs_column(C.byref(spec), OBS_FIELDS[name], 0, 0) != sl.start or L.shc_obs_column(C.byref(spec), OBS_FIELDS[name], *last) != sl.stop - 1:
+            raise ShcError(f"observation_columns and the library disagree on {name!r}")
+    return cols, at
+
+
+def _observation_target(out, what: str):
+    """(pointer, numpy dtype, rows, columns, row stride in elements) of a 2-D float32 / float64 device array whose rows are contiguous - a view
+    of some columns of a wider array included."""
+    cai = getattr(out, "__cuda_array_interface__", None)
+    if cai is None:
+        raise ValueError(f"{what}: a device array (an object with __cuda_array_interface__) is expected")
+    if cai["typestr"] not in ("<f4", "<f8") or len(cai["shape"]) != 2:
+        raise ValueError(f"{what}: a 2-D float32 or float64 device array is expected, got {cai['typestr']} {tuple(cai['shape'])}")
+    dt = np.dtype(cai["typestr"])
+    rows, columns = (int(x) for x in cai["shape"])
+    strides = cai.get("strides") or (columns * dt.itemsize, dt.itemsize)
+    if strides[1] != dt.itemsize or strides[0] % dt.itemsize or strides[0] < columns * dt.itemsize:
+        raise ValueError(f"{what}: the elements of a row must be contiguous and the rows a whole number of elements apart (strides {tuple(strides)})")
+    return C.c_void_p(cai["data"][0]), dt, rows, columns, strides[0] // dt.itemsize
 
 
 class ShcError(RuntimeError):
@@ -429,6 +503,11 @@ def lib():
         L.shc_fleet_get_leg_state_msgs.argtypes = [C.c_void_p, C.c_void_p]
         L.shc_engine_get_frame_transforms.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.shc_fleet_get_frame_transforms.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.shc_obs_width.restype = C.c_int64
+        L.shc_obs_width.argtypes = [C.POINTER(ObsSpec)]
+        L.shc_obs_column.argtypes = [C.POINTER(ObsSpec), C.c_int, C.c_int, C.c_int]
+        L.shc_engine_get_observations.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(ObsSpec), C.c_void_p, C.c_int]
+        L.shc_fleet_get_observations_device.argtypes = [C.c_void_p, C.POINTER(ObsSpec), C.c_void_p]
         L.shc_stream_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
         L.shc_stream_destroy.argtypes = [C.c_int, C.c_void_p]
         L.shc_engine_change_gait.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_int64)]
@@ -897,6 +976,33 @@ class BatchEngine:
         msgs = np.zeros((max(int(count), 0), self.legs), dtype=LEG_STATE_MSG_DTYPE)
         _check(self.L.shc_engine_get_leg_state_msgs(self.h, int(first), int(count), msgs.ctypes.data_as(C.c_void_p), 0), "get_leg_state_msgs")
         return msgs
+
+    def observations(self, fields, dtype="float32", out=None, first: int = 0, count: Optional[int] = None, pad: float = 0.0, legs: Optional[int] = None,
+                     dof: Optional[int] = None):
+        """Chosen fields (names of OBS_FIELDS, in column order) of instances [first, first + count) as one (count, D) array in one device pass
+        (shc_engine_get_observations); ``observation_columns(fields, legs, dof)`` names the columns.  Every value is the double the matching
+        getter returns (joints, leg_state_msgs, frame_transforms, get_body_state, leg_state), cast to ``dtype``; legs / dof (default: the engine's)
+        may be larger than the robot's, the columns of legs and joints it lacks then hold ``pad``.  Returns a host array - or, with out = a 2-D
+        float32 / float64 device array (``__cuda_array_interface__``; a view of some columns of a wider array will do) of count rows and at least
+        D columns, fills its first D columns on the engine's stream without a host wait and returns None: dtype then is the array's."""
+        count = self.n - first if count is None else count
+        legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
+        if out is not None:
+            ptr, dt, rows, columns, stride = _observation_target(out, "observations")
+            spec = obs_spec(fields, legs, dof, dt, stride, pad)
+            width = int(self.L.shc_obs_width(C.byref(spec)))
+            if rows != int(count) or (width >= 0 and columns < width):
+                raise ValueError(f"observations: out has shape ({rows}, {columns}), {int(count)} rows of at least {width} columns are expected")
+            _check(self.L.shc_engine_get_observations(self.h, int(first), int(count), C.byref(spec), ptr, 1), "get_observations")
+            return None
+        spec = obs_spec(fields, legs, dof, dtype, 0, pad)
+        width = int(self.L.shc_obs_width(C.byref(spec)))
+        if width < 0:
+            _check(SHC_ERR_INVALID_ARG, "get_observations")
+        obs = np.zeros((max(int(count), 0), width), dtype=np.dtype(dtype))
+        # (an empty array has no buffer to speak of: count = 0 is a no-op in the library, which still judges the arguments)
+        _check(self.L.shc_engine_get_observations(self.h, int(first), int(count), C.byref(spec), obs.ctypes.data_as(C.c_void_p), 0), "get_observations")
+        return obs
 
     def frame_transforms(self, first: int = 0, count: Optional[int] = None, frame="base_link", legs: bool = True, body: bool = True,
                          out_legs: Optional[int] = None, out_body: Optional[int] = None):

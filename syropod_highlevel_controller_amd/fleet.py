@@ -226,6 +226,21 @@ class MixedFleet:
         st.criteria = C.pointer(crit)
         _engine._check(self.L.shc_fleet_get_outputs_device(self.h, C.byref(st)), "shc_fleet_get_outputs_device")
 
+    def observations(self, out, fields, pad: float = 0.0):
+        """Chosen fields (names of ``engine.OBS_FIELDS``, in column order) of every robot into the DEVICE array ``out``, row i = the caller's
+        instance i, in one kernel per part with no staging (shc_fleet_get_observations_device).  out: any 2-D float32 / float64 object with
+        ``__cuda_array_interface__`` of n rows and at least D columns whose rows are contiguous - a view ``big[:, 5:5 + D]`` of a wider torch tensor
+        will do: element type, row stride and the offset pointer are taken from it, and only its first D columns are written.
+        ``engine.observation_columns(fields, max_legs, max_dof)`` names the columns; every value is the double the matching member of
+        ``outputs()`` / ``joints()`` holds, cast to out's type, and ``pad`` where a morphology has no such leg or joint.  No host wait: complete
+        after ``synchronize()``, or for work queued on a stream after ``order_before(stream)``."""
+        ptr, dt, rows, columns, stride = _engine._observation_target(out, "observations")
+        spec = _engine.obs_spec(fields, self.max_legs, self.max_dof, dt, stride, pad)
+        width = int(self.L.shc_obs_width(C.byref(spec)))
+        if rows != self.n or (width >= 0 and columns < width):
+            raise ValueError(f"observations: out has shape ({rows}, {columns}), {self.n} rows of at least {width} columns are expected")
+        _engine._check(self.L.shc_fleet_get_observations_device(self.h, C.byref(spec), ptr), "shc_fleet_get_observations_device")
+
     def step_k(self, n_cycles: int, **arrays):
         """K = ``n_cycles`` cycles in one launch per part (shc_fleet_step_k), cycle k with row k of K-deep DEVICE arrays: the names of
         ``set_inputs`` with a leading dimension K - linear_xy (K, n, 2), angular (K, n), imu_orientation_wxyz (K, n, 4), imu_angular_velocity
