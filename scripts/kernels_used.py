@@ -41,10 +41,11 @@ def main(argv):
         dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
         total, unused = collections.Counter(), []
         for d in dem:
-            m = re.match(r"void shc::(shc_\w+)<(\d+), (\d+), (\d+)u(?:, (\d))?>", d)
+            m = re.match(r"void shc::(shc_\w+)<(\d+), (\d+), (\d+)u(?:, (\d|true|false))?>", d)
             if not m or m.group(5) == "2":
                 continue
-            key = (KIND[m.group(1)], int(m.group(2)), int(m.group(3)), int(m.group(4)))
+            kind = "resident3" if m.group(5) == "true" else KIND[m.group(1)]   # (the three-role form of shc_resident2_kernel is logged under its own name)
+            key = (kind, int(m.group(2)), int(m.group(3)), int(m.group(4)))
             total[key[0]] += 1
             if key not in used:
                 unused.append(key)

@@ -12,8 +12,10 @@ for b in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
             continue
         m = re.search(r"ILi(\d)ELi(\d)E", name)
         g = lambda k: re.search(k + r": (\d+)", b).group(1)
-        print("legs %s dof %s" % (m.groups() if m else ("?", "?")), name.split("I")[0][4:], "VGPR", g("VGPRs"), "SGPR", g("TotalSGPRs"), "LDS", g(r"LDS Size \[bytes/block\]"),
-              "scratch", g(r"ScratchSize \[bytes/lane\]"), "waves/SIMD", g(r"Occupancy \[waves/SIMD\]"))
+        f = re.search(r"ILi\dELi\dELj(\d+)E(?:Lb([01])E)?", name)   # the loop forms: feature word, and the three-role flag of shc_resident2_kernel
+        form = ("features %-10s %s" % (f.group(1), "helper" if f.group(2) == "1" else "      "),) if f else ()
+        print("legs %s dof %s" % (m.groups() if m else ("?", "?")), name.split("I")[0][4:], *form, "VGPR", g("VGPRs"), "AGPR", g("AGPRs"), "SGPR", g("TotalSGPRs"),
+              "LDS", g(r"LDS Size \[bytes/block\]"), "scratch", g(r"ScratchSize \[bytes/lane\]"), "waves/SIMD", g(r"Occupancy \[waves/SIMD\]"))
         continue
     if "shc_cycle_kernel" not in name:
         continue

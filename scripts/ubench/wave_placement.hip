@@ -1,11 +1,13 @@
 // Where do the wavefronts of a small grid land?  For every wave: XCC, SE, CU, SIMD (s_getreg HW_ID / XCC_ID), for 64- and
 // 128-thread workgroups - the question behind the two-wave (front / back) resident kernel: do the two waves of a 128-thread
-// workgroup get two different SIMDs of their CU?
+// workgroup get two different SIMDs of their CU? - and for 256- and 384-thread workgroups (the resident pipelines: 2 robot groups x 2 or 3
+// roles): which SIMD does wave i of a workgroup get?  The three-role kernel orders its roles for "the first four waves on four SIMDs, waves i and i + 4 on the same one".
 // build: hipcc --offload-arch=gfx950 -O2 -o wave_placement wave_placement.hip ; run: ./wave_placement [workgroups]
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <map>
+#include <string>
 #include <vector>
 
 __global__ void probe(unsigned *out, int spin) {
@@ -24,7 +26,7 @@ __global__ void probe(unsigned *out, int spin) {
 
 int main(int argc, char **argv) {
   const int wgs = argc > 1 ? atoi(argv[1]) : 410;
-  for (int block : {64, 128}) {
+  for (int block : {64, 128, 256, 384}) {
     const int waves = wgs * block / 64;
     unsigned *d;
     hipMalloc(&d, waves * 8);
@@ -59,6 +61,30 @@ int main(int argc, char **argv) {
     for (auto &kv : hist_cu) printf("  %d waves: %d CUs", kv.first, kv.second);
     printf("\n");
     if (block == 128) printf("  pairs (wave 0, wave 1 of a workgroup): %d on the same CU, %d of them on the same SIMD\n", same_cu_pairs, same_simd_pairs);
+    if (block >= 256) { // the SIMDs of a workgroup's waves, in wave order: how many workgroups show each pattern, and how many sit on one CU
+      const int wpb = block / 64;
+      std::map<std::string, int> patterns;
+      int one_cu = 0, paired = 0;
+      for (int g = 0; g < wgs; ++g) {
+        std::string pat;
+        bool same = true, pairs = true; // pairs: waves 0 .. 3 on four different SIMDs, wave i >= 4 on the SIMD of wave i - 4
+        unsigned first_four = 0;
+        for (int i = 0; i < wpb; ++i) {
+          const unsigned hw = h[2 * (g * wpb + i)], hw0 = h[2 * g * wpb];
+          const unsigned simd = (hw >> 4) & 3;
+          pat += char('0' + simd);
+          same = same && ((hw ^ hw0) & 0xff00) == 0 && ((h[2 * (g * wpb + i) + 1] ^ h[2 * g * wpb + 1]) & 0xf) == 0;
+          if (i < 4) first_four |= 1u << simd;
+          else pairs = pairs && simd == ((h[2 * (g * wpb + i - 4)] >> 4) & 3);
+        }
+        patterns[pat]++;
+        one_cu += same;
+        paired += pairs && first_four == 0xf;
+      }
+      printf("  %d of %d workgroups on one CU; waves 0 .. 3 on four SIMDs and wave i >= 4 with wave i - 4 in %d of them; SIMD of waves 0 .. %d:", one_cu, wgs, paired, wpb - 1);
+      for (auto &kv : patterns) printf("  %s x %d", kv.first.c_str(), kv.second);
+      printf("\n");
+    }
     hipFree(d);
   }
   return 0;

@@ -48,6 +48,7 @@ static void launch_cycle(const CycleLaunch &a) {
     a.fit->supported = has_resident(F) ? 1 : 0;
     a.fit->batch = has_batch(F) ? 1 : 0;
     a.fit->two_wave = has_two_wave(F) ? 1 : 0;
+    a.fit->helper_wave = has_helper_wave(L, NJ, F) ? 1 : 0;
     a.fit->blocks_per_cu = 0;
     if constexpr (has_resident(F)) {
       int blocks = 0;
@@ -58,6 +59,13 @@ static void launch_cycle(const CycleLaunch &a) {
     if constexpr (has_batch(F)) {
       note_kernel("batch", L, NJ, F);
       shc_batch_kernel<L, NJ, F><<<dim3(a.grid), dim3(a.block), wave_bytes * (a.block / 64), a.stream>>>(a.st, (const SharedConsts<L, NJ> *)a.consts, *a.resident, a.rt_flags);
+    }
+  } else if (a.block == 384) {
+    if constexpr (has_helper_wave(L, NJ, F)) {
+      static_assert(has_two_wave(F), "the three-role form is a form of the two-wavefront pipeline");
+      note_kernel("resident3", L, NJ, F);
+      shc_resident2_kernel<L, NJ, F, true><<<dim3(a.grid), dim3(384), 2 * wave_bytes + sizeof(Resident3Lds<L, NJ>), a.stream>>>(
+          a.st, (const SharedConsts<L, NJ> *)a.consts, *a.resident, a.rt_flags);
     }
   } else if (a.block == 256) {
     if constexpr (has_two_wave(F)) {

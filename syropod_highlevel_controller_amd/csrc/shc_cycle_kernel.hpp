@@ -10,6 +10,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace shc {
 
 #ifndef SHC_WAVES_PER_SIMD
@@ -1080,13 +1082,26 @@ struct Resident2Lds { // dynamic LDS of one workgroup, after the two walker wave
   int ikfail[2][64];           // model -> walker at exit (IK-deviation flag lives in the leg word)
   unsigned long long ctrl[4][4]; // [iteration & 3]: kind, h0, h1, -
 };
+template <int L, int NJ>
+struct Resident3Lds : Resident2Lds<L, NJ> { // ... of the three-role form (below)
+  int leg_word[2][2][64];     // [pair][cycle parity][lane] walker -> helper: the packed leg words updateWalk left (the helper reduces them to pose_c's value itself)
+  unsigned back_seen[2];      // model -> walker at exit: input groups the model wavefront received
+};
 
-template <int L, int NJ, unsigned F>
-__global__ void __launch_bounds__(256, 1) shc_resident2_kernel(DevState st, const SharedConsts<L, NJ> *gc, ResidentArgs A, unsigned rt_flags) {
+// THREE roles per robot group (HELPER; has_helper_wave: default.yaml's posing set on 6 x 3, the specialisations whose model wavefront carries the pose AND the
+// odometry): the model wavefront's share that belongs to neither Model::updateModel nor the walker's recurrence - PoseController::updateCurrentPose of the walker's
+// next cycle, the odometry accumulator, the leader's duty - runs on a third wavefront, and so does the walker's reduction of its leg words for that pose.
+// 384-thread workgroups = 2 robot groups x (model, walker, helper), six wavefronts on the four SIMDs of a compute unit; the first four waves of a workgroup get
+// the four SIMDs and waves i and i + 4 share one (scripts/ubench/wave_placement.hip: every workgroup measured), so the order [M0, M1, W0, W1, H0, H1] leaves each
+// walker - the recurrence that bounds the cycle - alone on its SIMD and puts each helper behind a model wavefront (equal priorities: lowering the helper's with
+// s_setprio measured 0.5 % slower).  Hand-offs as before: the per-iteration barrier and the bounded PoseWait.
+template <int L, int NJ, unsigned F, bool HELPER = false>
+__global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(DevState st, const SharedConsts<L, NJ> *gc, ResidentArgs A, unsigned rt_flags) {
   using R = RobotFields;
   using FD = Fields<NJ>;
   using FT = Feat<F>;
   constexpr int RPW = 64 / L;
+  constexpr int kThreads = HELPER ? 384 : 256;
   if (blockIdx.x == 0) { // the relay workgroup: one wave per direction
     if (threadIdx.x < 64) resident_relay<PART_GATE>(A);
     else if (threadIdx.x < 128) resident_relay<PART_DONE>(A);
@@ -1095,12 +1110,14 @@ __global__ void __launch_bounds__(256, 1) shc_resident2_kernel(DevState st, cons
   __shared__ SharedConsts<L, NJ> C;
   extern __shared__ double wave_lds[];
   constexpr int kWaveDoubles = R::COUNT * RPW + PK_COUNT * 64 + (R::I_COUNT * RPW + 1) / 2;
-  Resident2Lds<L, NJ> &X = *reinterpret_cast<Resident2Lds<L, NJ> *>(wave_lds + 2 * kWaveDoubles);
+  using Lds = std::conditional_t<HELPER, Resident3Lds<L, NJ>, Resident2Lds<L, NJ>>;
+  Lds &X = *reinterpret_cast<Lds *>(wave_lds + 2 * kWaveDoubles);
   const bool manual_live = (rt_flags & RT_MANUAL_LIVE) != 0;
   const int lane = threadIdx.x & 63;
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int pair = wib & 1;
-  const bool walker = wib < 2, leader = wib == 2; // the model wavefront of pair 0 decides what the next iteration is: it has the time to spare
+  // the model wavefront of pair 0 decides what the next iteration is: it has the time to spare (HELPER: the helper of pair 0, in the order [M0, M1, W0, W1, H0, H1])
+  const bool walker = HELPER ? (wib >> 1) == 1 : wib < 2, helper = HELPER && wib >= 4, leader = wib == (HELPER ? 4 : 2);
   const int64_t wave = (int64_t(blockIdx.x) - 1) * 2 + pair;
   const bool active = wave < A.n_waves;
   const int64_t rob0 = wave * RPW;
@@ -1119,7 +1136,7 @@ __global__ void __launch_bounds__(256, 1) shc_resident2_kernel(DevState st, cons
   int32_t *gtile_i = st.robi + (active ? wave : 0) * (R::I_COUNT * RPW);
   const CycleParams &GP = gc->P;
   LegRegs<NJ> s;
-  // ---- prologue: tables (all four waves), robot tile (walker), the half of the leg state this wave owns
+  // ---- prologue: tables (every wave), robot tile (walker), the half of the leg state this wave owns (the helper: none)
   {
     using SC = SharedConsts<L, NJ>;
     constexpr int n16_all = sizeof(SC) / 16;
@@ -1127,7 +1144,7 @@ __global__ void __launch_bounds__(256, 1) shc_resident2_kernel(DevState st, cons
     const int n16 = FT::autop(GP) ? n16_all : n16_core;
     const double2 *src = reinterpret_cast<const double2 *>(gc);
     double2 *dst = reinterpret_cast<double2 *>(&C);
-    for (int i = threadIdx.x; i < n16; i += 256) dst[i] = src[i];
+    for (int i = threadIdx.x; i < n16; i += kThreads) dst[i] = src[i];
   }
   LegLoad<NJ> ll;
   if (active) {
@@ -1136,7 +1153,7 @@ __global__ void __launch_bounds__(256, 1) shc_resident2_kernel(DevState st, cons
       for (int i = lane; i < R::COUNT * RPW; i += 64) tile[i] = gtile[i];
       for (int i = lane; i < R::I_COUNT * RPW; i += 64) tile_i[i] = gtile_i[i];
       load_leg_finish<NJ, ROLE_FRONT>(s, pk, ll);
-    } else {
+    } else if (!helper) {
       load_leg_issue<NJ, F, ROLE_BACK>(ll, st, GP, slot);
       load_leg_finish<NJ, ROLE_BACK>(s, pk, ll);
     }
@@ -1158,7 +1175,7 @@ __global__ void __launch_bounds__(256, 1) shc_resident2_kernel(DevState st, cons
   LegOut out;
   out.poser_tip = out.model_tip = out.adm_delta = V3{0, 0, 0};
   s.tipx = V3{1, 0, 0};
-  if (active && !walker) { // Leg::applyFK of the previous cycle, as in cycle_wave
+  if (active && !walker && !helper) { // Leg::applyFK of the previous cycle, as in cycle_wave
 #pragma unroll
     for (int k = 0; k < NJ; ++k) sincos_joint(C.leg[leg].link_th[k] + s.q[k], &s.sn[k], &s.cs[k]);
     if (FT::adm(P) || LegRegs<NJ>::kKeepJacobian) {
@@ -1186,7 +1203,8 @@ __global__ void __launch_bounds__(256, 1) shc_resident2_kernel(DevState st, cons
         mb[7 * 64] = pp.x, mb[8 * 64] = pp.y, mb[9 * 64] = pp.z, mb[10 * 64] = pn.x, mb[11 * 64] = pn.y, mb[12 * 64] = pn.z;
       }
     }
-    X.pose_c[pair][cycle & 1][lane] = walk_plane_control_candidate<L, NJ>(s.word, C, P, swing_c_count_u); // (the model wavefront picks the group's leg)
+    if constexpr (HELPER) X.leg_word[pair][cycle & 1][lane] = s.word; // (the helper evaluates the candidates and picks the group's leg)
+    else X.pose_c[pair][cycle & 1][lane] = walk_plane_control_candidate<L, NJ>(s.word, C, P, swing_c_count_u); // (the model wavefront picks the group's leg)
   };
   if (POSE_SPLIT && walker && active) publish_for_pose(0, true); // (iteration 0 is a bubble: its closing barrier comes before any pose)
   const int64_t ns = st.n_slots;
@@ -1202,7 +1220,8 @@ __global__ void __launch_bounds__(256, 1) shc_resident2_kernel(DevState st, cons
   fb.uf = load_uni_flags(C.P); // (once: the parameter block does not change while the loop runs)
   OdomCache odom_cache;        // walker wavefront: (sin, cos) of the half yaw step while the desired angular velocities stay as they are
   Pose owpp_cache = pose_identity();
-  if (POSE_SPLIT && active && !walker) owpp_cache = rb.getpose(R::OWPP); // ... and the origin walk-plane pose (the walker wavefront filled the tile before the barrier)
+  const bool poser = HELPER ? helper : !walker; // the wavefront that runs the pose (and, where it is not the walker's, the odometry)
+  if (POSE_SPLIT && active && poser) owpp_cache = rb.getpose(R::OWPP); // ... and the origin walk-plane pose (the walker wavefront filled the tile before the barrier)
   // ... and WalkController::odometry_ideal_ itself: nothing inside the loop reads it, so the wavefront that advances it (ODOM_WALKER below) accumulates it in registers and
   // puts it back into the tile when the loop ends (4 LDS reads + 4 writes per cycle less on the longer of the two wavefronts).  Short chains
   // only: the 4- and 5-joint model wavefronts already keep part of their state in AGPRs, four more loop-carried doubles cost them more
@@ -1212,15 +1231,17 @@ __global__ void __launch_bounds__(256, 1) shc_resident2_kernel(DevState st, cons
   // without admittance / IMU posing (its IK step, FK and tip force are short: 5 120 against the walker's 5 330 clocks without the odometry), the walker
   // wavefront for everything else (admittance, IMU posing, 4- and 5-joint chains make the model wavefront the longer one by 400 - 700 clocks)
   constexpr bool ODOM_WALKER = NJ > 3 || (F & (F_ADM | F_IMU | F_INCL | F_AUTO | F_DYN)) != 0;
+  static_assert(!HELPER || (POSE_SPLIT && !ODOM_WALKER && ODOM_REGS), "the helper takes the pose and the odometry off the MODEL wavefront");
+  const bool odom_mine = ODOM_WALKER ? walker : poser;
   double odom[4] = {0.0, 0.0, 1.0, 0.0};
-  if (ODOM_REGS && FT::odom(P) && active && walker == ODOM_WALKER) {
+  if (ODOM_REGS && FT::odom(P) && active && odom_mine) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) odom[i] = rb.get(R::ODOM + i);
   }
 #ifdef SHC_RES2_TIMING
   long long tm_busy = 0, tm_total0 = __builtin_readcyclecounter(), tm_real = 0;
 #ifndef SHC_RES2_BUSY_ONLY
-  if (threadIdx.x < 64) shc_acc_lds[threadIdx.x] = 0;
+  if (threadIdx.x < 96) shc_acc_lds[threadIdx.x] = 0;
 #endif
 #endif
   // The two roles run SEPARATE loops - one barrier per iteration each, and the same number of iterations: what an iteration is comes from the
@@ -1247,6 +1268,90 @@ __global__ void __launch_bounds__(256, 1) shc_resident2_kernel(DevState st, cons
 #endif
   LegInRing<NJ> in_at; // model wavefront: where this lane's per-leg inputs in force lie (recomputed when a post moves them)
   int in_src_force = -1000, in_src_effort = -1000;
+  // The blocks of an iteration that belong to neither Model::updateModel nor the walker's recurrence, for the loop of the wavefront that runs them (the model
+  // wavefront; HELPER: the helper).  The leader's: what will iteration k + 1 be? ...
+  const auto leader_decide = [&](const int kind, int &nk, u64 &nh0v, u64 &nh1v) __attribute__((always_inline)) {
+    u64 gate;
+    if (kind == IT_BUBBLE) {
+      __builtin_amdgcn_s_sleep(2);
+      gate = uni64(ld_agent(&A.ctl->gate)); // nothing else to do: look again
+    } else {
+      gate = uni64(gate_pref); // read one iteration ago: at worst the loop learns of a release one iteration late
+    }
+    const unsigned db = unsigned(gate), sp = unsigned(gate >> 32);
+    const unsigned cn = c_front + (kind == IT_REAL ? 1u : 0u); // the cycle iteration k + 1 would start
+    nk = cn >= sp ? IT_EXIT : (cn < db ? IT_REAL : IT_BUBBLE);
+    if (nk == IT_BUBBLE) {
+      const u64 now = wall_clock64();
+      if (bubble_since == 0) bubble_since = now;
+      else if (now - bubble_since > emergency_ticks) nk = IT_EXIT, held.fault = true;
+    } else {
+      bubble_since = 0;
+    }
+    if (nk == IT_REAL) {
+      const u64 *hp = reinterpret_cast<const u64 *>(A.headers + (cn & (kResidentHeaders - 1)));
+      nh0v = ld_agent(hp);
+      nh1v = ld_agent(hp + 1);
+    }
+    // (out of a bubble the gate was read just now: the control words below wait for every load of this iteration, and one more trip to
+    //  memory on the way out of a bubble is a microsecond on the latency of every burst)
+    if (kind == IT_BUBBLE) gate_pref = gate;
+    else gate_pref = ld_agent(&A.ctl->gate);
+  };
+  // ... and its announcement (the header loads issued at the top of the iteration have long arrived)
+  const auto leader_announce = [&](const int nk, const u64 nh0v, const u64 nh1v) __attribute__((always_inline)) {
+    X.ctrl[(k + 1) & 3][0] = u64(nk);
+    X.ctrl[(k + 1) & 3][1] = nh0v;
+    X.ctrl[(k + 1) & 3][2] = nh1v;
+  };
+  // PoseController::updateCurrentPose of the cycle the walker is starting: first thing, the walker waits for it
+  const auto pose_of_cycle = [&](const u64 h0, const u64 h1) __attribute__((always_inline)) {
+    if constexpr (!POSE_SPLIT) return;
+    else {
+    resident_take_inputs<RPW, ROBOT_POSE, false>(A, c_front, h0, h1, wave, lane, tile, tile_i, dirty, held, st.n_robots);
+    SHC_TICK(30);
+    double pose_c = -1.0; // the candidate of the LAST leg (in id order) of this lane's robot that has one (pose_controller.cpp:1100-1108)
+    if constexpr (HELPER) { // from the leg words the walker left
+      const double c_own = walk_plane_control_candidate<L, NJ>(X.leg_word[pair][c_front & 1][lane], C, P, swing_c_count_u);
+#pragma unroll
+      for (int j = 0; j < L; ++j) {
+        const double cj = g.get(c_own, j);
+        pose_c = cj >= 0.0 ? cj : pose_c;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < L; ++j) {
+        const double cj = X.pose_c[pair][c_front & 1][g.base + j];
+        pose_c = cj >= 0.0 ? cj : pose_c;
+      }
+    }
+    int lw[L] = {}; // (not filled in: the walker wavefront has already reduced the leg words to the pose's control input)
+    const double *mb = &X.mailbox[pair][c_front & 1][0][lane];
+    const V3 plane_prev{mb[7 * 64], mb[8 * 64], mb[9 * 64]}, pnorm_prev{mb[10 * 64], mb[11 * 64], mb[12 * 64]};
+    int rword_unused = 0;
+    Pose ap = pose_identity(), la = pose_identity();
+#ifdef SHC_ABLATE
+    if (!(P.debug_skip & 2048))
+#endif
+    // (OWN_WORD with the control input handed over: cycle_pose reads nothing of `s` - the helper, which loads no leg state, passes its empty record)
+    (void)cycle_pose<L, NJ, F, true>(s, C, P, C.leg[leg], rb, g, leg, lw, rword_unused, 0, dirty, manual_live, ap, la, plane_prev, pnorm_prev, fb.uf.swing_c_count, 0,
+                                     &owpp_cache, &pose_c);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) *const_cast<volatile unsigned *>(&X.pose_done[pair]) = c_front + 1;
+    }
+  };
+  // odometry_ideal_ of the cycle whose walker half ran one iteration ago: the desired body velocity travelled with the poser tip (mailbox `mb`)
+  const auto odometry_of_cycle = [&](const double *mb) __attribute__((always_inline)) {
+    const V3 ov{mb[192], mb[256], mb[320]};
+    if (__any(mb[384] != 0.0)) { // (robots whose updateWalk returned early keep their odometry)
+      if (mb[384] != 0.0) {
+        if constexpr (ODOM_REGS) odometry_advance(odom[0], odom[1], odom[2], odom[3], P, ov.x, ov.y, ov.z, &odom_cache);
+        else odometry_step(rb, P, ov.x, ov.y, ov.z, &odom_cache);
+      }
+    }
+  };
+  constexpr int kWalkerThread = HELPER ? 128 : 0, kModelThread = HELPER ? 0 : 128; // (development stamps: the first thread of each role's wavefront of pair 0)
   if (walker) {
     // ---------------------------------------------------------------- walker wavefront: cycle_front of cycle c_front
     for (;;) {
@@ -1281,74 +1386,54 @@ __global__ void __launch_bounds__(256, 1) shc_resident2_kernel(DevState st, cons
       }
       SHC_TICK(23);
       if (kind == IT_EXIT) break;
-      SHC_R2_ITER_END(0, 19, 20, 21, 2, 3, 4, 5, 6, 7, 16, 8, 17, 15, 29, 22, 23);
+      SHC_R2_ITER_END(kWalkerThread, 19, 20, 21, 2, 3, 4, 5, 6, 7, 16, 8, 17, 15, 29, 22, 23);
       if (kind == IT_REAL) ++c_front;
       prev_real = kind == IT_REAL;
       __syncthreads();
       ++k;
     }
-  } else {
-    // ---------------------------------------------------------------- model wavefront: the pose of cycle c_front, cycle_back of cycle c_back
-    for (;;) {
+  } else if (helper) {
+    // ---------------------------------------------------------------- helper wavefront (HELPER): the pose of cycle c_front, the odometry of cycle c_back, the leader's duty
+    if constexpr (HELPER) for (;;) {
       SHC_R2_ITER_BEGIN();
       const int kind = __builtin_amdgcn_readfirstlane(int(X.ctrl[k & 3][0]));
       const u64 h0 = uni64(X.ctrl[k & 3][1]), h1 = uni64(X.ctrl[k & 3][2]);
       SHC_TICK(29);
       int nk = IT_EXIT;
       u64 nh0v = 0, nh1v = 0;
-      if (leader && kind != IT_EXIT) { // what will iteration k + 1 be?
-        u64 gate;
-        if (kind == IT_BUBBLE) {
-          __builtin_amdgcn_s_sleep(2);
-          gate = uni64(ld_agent(&A.ctl->gate)); // nothing else to do: look again
-        } else {
-          gate = uni64(gate_pref); // read one iteration ago: at worst the loop learns of a release one iteration late
+      if (leader && kind != IT_EXIT) leader_decide(kind, nk, nh0v, nh1v);
+      if (active) { // (the helper of an inactive pair only keeps the barriers)
+        SHC_TICK(24);
+        if (kind == IT_REAL) pose_of_cycle(h0, h1);
+        SHC_TICK(25);
+        if (prev_real) { // the cycle whose walker half ran one iteration ago
+          if (FT::odom(P)) odometry_of_cycle(&X.mailbox[pair][c_back & 1][0][lane]);
+          ++c_back;
         }
-        const unsigned db = unsigned(gate), sp = unsigned(gate >> 32);
-        const unsigned cn = c_front + (kind == IT_REAL ? 1u : 0u); // the cycle iteration k + 1 would start
-        nk = cn >= sp ? IT_EXIT : (cn < db ? IT_REAL : IT_BUBBLE);
-        if (nk == IT_BUBBLE) {
-          const u64 now = wall_clock64();
-          if (bubble_since == 0) bubble_since = now;
-          else if (now - bubble_since > emergency_ticks) nk = IT_EXIT, held.fault = true;
-        } else {
-          bubble_since = 0;
-        }
-        if (nk == IT_REAL) {
-          const u64 *hp = reinterpret_cast<const u64 *>(A.headers + (cn & (kResidentHeaders - 1)));
-          nh0v = ld_agent(hp);
-          nh1v = ld_agent(hp + 1);
-        }
-        // (out of a bubble the gate was read just now: the control words below wait for every load of this iteration, and one more trip to
-        //  memory on the way out of a bubble is a microsecond on the latency of every burst)
-        if (kind == IT_BUBBLE) gate_pref = gate;
-        else gate_pref = ld_agent(&A.ctl->gate);
+        SHC_TICK(26);
       }
+      if (leader && kind != IT_EXIT && lane == 0) leader_announce(nk, nh0v, nh1v);
+      SHC_TICK(14);
+      if (kind == IT_EXIT) break;
+      SHC_R2_ITER_END(256, 19, 29, 24, 30, 25, 26, 14);
+      if (kind == IT_REAL) ++c_front;
+      prev_real = kind == IT_REAL;
+      __syncthreads();
+      ++k;
+    }
+  } else {
+    // ---------------------------------------------------------------- model wavefront: (the pose of cycle c_front,) cycle_back of cycle c_back
+    for (;;) {
+      SHC_R2_ITER_BEGIN();
+      const int kind = __builtin_amdgcn_readfirstlane(int(X.ctrl[k & 3][0]));
+      const u64 h0 = uni64(X.ctrl[k & 3][1]), h1 = uni64(X.ctrl[k & 3][2]);
+      SHC_TICK(29);
+      [[maybe_unused]] int nk = IT_EXIT; // (the leader's: unused in the three-role form, where the helper of pair 0 leads)
+      [[maybe_unused]] u64 nh0v = 0, nh1v = 0;
+      if constexpr (!HELPER) if (leader && kind != IT_EXIT) leader_decide(kind, nk, nh0v, nh1v);
       if (active) {
         SHC_TICK(24);
-        if constexpr (POSE_SPLIT) if (kind == IT_REAL) { // PoseController::updateCurrentPose of the cycle the walker is starting: first thing, the walker waits for it
-          resident_take_inputs<RPW, ROBOT_POSE, false>(A, c_front, h0, h1, wave, lane, tile, tile_i, dirty, held, st.n_robots);
-          SHC_TICK(30);
-          double pose_c = -1.0; // the candidate of the LAST leg (in id order) of this lane's robot that has one (pose_controller.cpp:1100-1108)
-#pragma unroll
-          for (int j = 0; j < L; ++j) {
-            const double cj = X.pose_c[pair][c_front & 1][g.base + j];
-            pose_c = cj >= 0.0 ? cj : pose_c;
-          }
-          int lw[L] = {}; // (not filled in: the walker wavefront has already reduced the leg words to the pose's control input)
-          const double *mb = &X.mailbox[pair][c_front & 1][0][lane];
-          const V3 plane_prev{mb[7 * 64], mb[8 * 64], mb[9 * 64]}, pnorm_prev{mb[10 * 64], mb[11 * 64], mb[12 * 64]};
-          int rword_unused = 0;
-          Pose ap = pose_identity(), la = pose_identity();
-#ifdef SHC_ABLATE
-          if (!(P.debug_skip & 2048))
-#endif
-          (void)cycle_pose<L, NJ, F, true>(s, C, P, C.leg[leg], rb, g, leg, lw, rword_unused, 0, dirty, manual_live, ap, la, plane_prev, pnorm_prev, fb.uf.swing_c_count, 0,
-                                           &owpp_cache, &pose_c);
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-          __builtin_amdgcn_wave_barrier();
-          if (lane == 0) *const_cast<volatile unsigned *>(&X.pose_done[pair]) = c_front + 1;
-        }
+        if constexpr (POSE_SPLIT && !HELPER) if (kind == IT_REAL) pose_of_cycle(h0, h1);
         SHC_TICK(25);
         if (prev_real) { // the model half of the cycle whose walker half ran one iteration ago
           resident_take_inputs<RPW, ROBOT_NONE, true>(A, c_back, prev_h0, prev_h1, wave, lane, tile, tile_i, dirty, held, st.n_robots);
@@ -1361,15 +1446,7 @@ __global__ void __launch_bounds__(256, 1) shc_resident2_kernel(DevState st, cons
           SHC_TICK(31);
           const double *mb = &X.mailbox[pair][c_back & 1][0][lane];
           out.poser_tip = V3{mb[0], mb[64], mb[128]};
-          if constexpr (!ODOM_WALKER) if (FT::odom(P)) {
-            const V3 ov{mb[192], mb[256], mb[320]};
-            if (__any(mb[384] != 0.0)) { // (robots whose updateWalk returned early keep their odometry)
-              if (mb[384] != 0.0) {
-                if constexpr (ODOM_REGS) odometry_advance(odom[0], odom[1], odom[2], odom[3], P, ov.x, ov.y, ov.z, &odom_cache);
-                else odometry_step(rb, P, ov.x, ov.y, ov.z, &odom_cache);
-              }
-            }
-          }
+          if constexpr (!ODOM_WALKER && !HELPER) if (FT::odom(P)) odometry_of_cycle(mb);
           out.adm_delta = V3{0, 0, 0};
           if (FT::adm(P)) cycle_admittance<NJ>(s, out, P, in);
           s.word = 0;
@@ -1407,14 +1484,10 @@ __global__ void __launch_bounds__(256, 1) shc_resident2_kernel(DevState st, cons
           if (lane == 0) st_agent(A.progress + wave, u64(c_back));
         }
       }
-      if (leader && kind != IT_EXIT && lane == 0) { // (the header loads issued at the top of the iteration have long arrived)
-        X.ctrl[(k + 1) & 3][0] = u64(nk);
-        X.ctrl[(k + 1) & 3][1] = nh0v;
-        X.ctrl[(k + 1) & 3][2] = nh1v;
-      }
+      if constexpr (!HELPER) if (leader && kind != IT_EXIT && lane == 0) leader_announce(nk, nh0v, nh1v);
       SHC_TICK(14);
       if (kind == IT_EXIT) break;
-      SHC_R2_ITER_END(128, 19, 29, 24, 30, 25, 31, 26, 9, 10, 11, 12, 27, 13, 28, 14);
+      SHC_R2_ITER_END(kModelThread, 19, 29, 24, 30, 25, 31, 26, 9, 10, 11, 12, 27, 13, 28, 14);
       if (kind == IT_REAL) ++c_front;
       prev_real = kind == IT_REAL;
       prev_h0 = h0, prev_h1 = h1;
@@ -1427,19 +1500,17 @@ __global__ void __launch_bounds__(256, 1) shc_resident2_kernel(DevState st, cons
 #undef SHC_R2_PHASES
 #ifdef SHC_RES2_TIMING
   if (blockIdx.x == 1 && lane == 0 && pair == 0) { // development: clocks from iteration start to the barrier, REAL iterations in steady state
-    unsigned long long *dbg = reinterpret_cast<unsigned long long *>(A.ctl) + 8 + (walker ? 0 : 4);
+    // ResidentCtl::dbg: busy clocks of the walker [0, 4), the model [4, 8), the helper wavefront [72, 76); phase clocks [8, 40), [40, 72), [80, 112)
+    unsigned long long *rec = reinterpret_cast<unsigned long long *>(A.ctl) + 8, *dbg = rec + (walker ? 0 : helper ? 72 : 4);
     dbg[0] = tm_busy, dbg[1] = tm_real, dbg[2] = __builtin_readcyclecounter() - tm_total0, dbg[3] = k;
 #ifndef SHC_RES2_BUSY_ONLY
-    if (walker) {
-      for (int i = 0; i < 32; ++i) dbg[8 + i] = (unsigned long long)shc_acc_lds[i];
-    } else { // (dbg points 4 words into ResidentCtl::dbg for the model wavefront: its phase clocks go to dbg[40 .. 72) of the record)
-      for (int i = 0; i < 32; ++i) dbg[36 + i] = (unsigned long long)shc_acc_lds[32 + i];
-    }
+    const int from = int(threadIdx.x >> 7) * 32, to = walker ? 8 : helper ? 80 : 40; // (the stamps are kept per wavefront of pair 0: SHC_TICK)
+    for (int i = 0; i < 32; ++i) rec[to + i] = (unsigned long long)shc_acc_lds[from + i];
 #endif
   }
 #endif
   // ---- epilogue: the halves exchange what the other one stores, then each writes its half of the state back
-  if (active && ODOM_REGS && FT::odom(P) && walker == ODOM_WALKER) { // the odometry accumulated in registers back into the tile the walker wavefront stores
+  if (active && ODOM_REGS && FT::odom(P) && odom_mine) { // the odometry accumulated in registers back into the tile the walker wavefront stores
 #pragma unroll
     for (int i = 0; i < 4; ++i) rb.put(R::ODOM + i, odom[i]);
   }
@@ -1447,21 +1518,25 @@ __global__ void __launch_bounds__(256, 1) shc_resident2_kernel(DevState st, cons
     if (walker) {
       X.stiff[pair][lane] = s.stiff;
     } else {
-      X.ikfail[pair][lane] = s.word & LW_IKFAIL;
-      if (POSE_SPLIT) { // what the pose on this wavefront dirtied / received is written back by the walker, which owns the tile stores
-        unsigned d = 0;
+      if (!helper) X.ikfail[pair][lane] = s.word & LW_IKFAIL;
+      if constexpr (HELPER) if (!helper && lane == 0) X.back_seen[pair] = held.seen;
+      if (poser) {
+        if (POSE_SPLIT) { // what the pose on this wavefront dirtied / received is written back by the walker, which owns the tile stores
+          unsigned d = 0;
 #pragma unroll
-        for (unsigned b = 1; b <= DIRTY_LAST; b <<= 1)
-          if (__any((dirty & b) != 0)) d |= b;
-        if (lane == 0) X.model_dirty[pair] = d, X.model_seen[pair] = held.seen;
+          for (unsigned b = 1; b <= DIRTY_LAST; b <<= 1)
+            if (__any((dirty & b) != 0)) d |= b;
+          if (lane == 0) X.model_dirty[pair] = d, X.model_seen[pair] = held.seen;
+        }
+        if (lane == 0) X.model_fault[pair] = held.fault ? 1u : 0u; // (the leader's emergency bound)
       }
-      if (lane == 0) X.model_fault[pair] = held.fault ? 1u : 0u; // (the leader's emergency bound)
     }
   }
   __syncthreads();
-  if (!active) return;
+  if (!active || helper) return;
   if (walker) {
     if (POSE_SPLIT) dirty |= X.model_dirty[pair], held.seen |= X.model_seen[pair];
+    if constexpr (HELPER) held.seen |= X.back_seen[pair];
     if (X.model_fault[pair]) held.fault = true;
     if (c_front > 0) s.word = (s.word & ~LW_IKFAIL) | X.ikfail[pair][lane];
     {

@@ -44,6 +44,7 @@ struct Resident {
   bool stream_doorbell_pending = false;     // a doorbell value travels on in_stream behind the posts it releases
   unsigned groups_posted = 0;
   bool two_wave = false;                    // the two-wavefront (walker / model) pipeline is running
+  bool helper_wave = false;                 // ... in its three-role form (walker / model / helper)
   long long direct_last = -1;               // cycle of the latest direct post (the doorbell only moves once the relay has released it)
 };
 
@@ -197,7 +198,7 @@ extern "C" int shc_engine_resident_bind_inputs(shc_engine *e, int set, const shc
 
 // Which loop forms the kernel specialisation of the engine's configuration has, and how densely its resident kernel fits (nothing is launched)
 static int resident_fit(const shc_engine *e, ResidentFit &fit) {
-  fit = ResidentFit{0, 0, 0, 0};
+  fit = ResidentFit{};
   CycleLaunch a = cycle_launch(e);
   a.fit = &fit;
   return launch_cycle_for(e, a);
@@ -347,11 +348,14 @@ extern "C" int shc_engine_resident_begin(shc_engine *e, int ring_depth, int64_t 
   // - two robot groups - and the relay get a compute unit of their own; one wavefront per group above that.
   const bool two_wave = fit.two_wave && !(e->features & SHC_FEAT_RESIDENT_ONE_WAVE) && (e->n_waves + 1) / 2 + 1 <= prop.multiProcessorCount;
   r->two_wave = two_wave;
+  // ... in its three-role form where the specialisation has one (same workgroup count).  Development: SHC_RESIDENT_TWO_ROLE=1 keeps the two-role form (A/B in one build)
+  const char *two_role = getenv("SHC_RESIDENT_TWO_ROLE");
+  r->helper_wave = two_wave && fit.helper_wave && !(two_role && atoi(two_role) > 0);
   HIP_TRY(hipEventRecord(r->loop_ev, e->stream)); // everything the engine's stream holds (state, the buffers set up above) comes first
   HIP_TRY(hipStreamWaitEvent(r->loop_stream, r->loop_ev, 0));
   CycleLaunch a = cycle_launch(e);
   a.stream = r->loop_stream, a.resident = &A;
-  a.grid = two_wave ? unsigned((e->n_waves + 1) / 2 + 1) : unsigned(e->n_waves + 1), a.block = two_wave ? 256 : 64;
+  a.grid = two_wave ? unsigned((e->n_waves + 1) / 2 + 1) : unsigned(e->n_waves + 1), a.block = r->helper_wave ? 384 : two_wave ? 256 : 64;
   {
     const int rc = launch_cycle_for(e, a);
     if (rc != SHC_OK) return rc;
@@ -668,9 +672,11 @@ extern "C" int shc_engine_resident_end(shc_engine *e, int64_t *cycles_run) {
   if (err == hipSuccess) {
     ResidentCtl c;
     (void)hipMemcpy(&c, r->ctl, sizeof c, hipMemcpyDeviceToHost);
-    for (int w = 0; w < 2; ++w)
-      fprintf(stderr, "[res2 timing] %s: %.0f clocks busy per steady REAL iteration (%llu of them), loop %llu clocks, %llu iterations\n", w ? "model " : "walker",
-              c.dbg[4 * w + 1] ? double(c.dbg[4 * w]) / double(c.dbg[4 * w + 1]) : 0.0, c.dbg[4 * w + 1], c.dbg[4 * w + 2], c.dbg[4 * w + 3]);
+    for (int w = 0; w < (r->helper_wave ? 3 : 2); ++w) {
+      const unsigned long long *b = c.dbg + (w == 2 ? 72 : 4 * w); // (the helper's record lies behind the phase clocks of the other two)
+      fprintf(stderr, "[res2 timing] %s: %.0f clocks busy per steady REAL iteration (%llu of them), loop %llu clocks, %llu iterations\n", w == 0 ? "walker" : w == 1 ? "model " : "helper",
+              b[1] ? double(b[0]) / double(b[1]) : 0.0, b[1], b[2], b[3]);
+    }
 #ifndef SHC_RES2_BUSY_ONLY
     const int order[] = {20, 21, 2, 3, 4, 5, 6, 7, 16, 8, 17, 15, 29, 22, 23};
     const char *wname[] = {"control words (LDS) read", "inputs of the cycle taken", "cycle_front entry", "robot word / command read, stop predicates", "(pose elsewhere)", "getLimit",
@@ -686,7 +692,18 @@ extern "C" int shc_engine_resident_end(shc_engine *e, int64_t *cycles_run) {
                            "wait for the previous stores + progress word", "output-ring stores issued", "control words written (leader: waits for its loads)"};
     const double mits = c.dbg[5] ? double(c.dbg[5]) : 1.0;
     fprintf(stderr, "[res2 timing] model wavefront of pair 0 (the leader), mean clocks per phase:\n");
-    for (int i = 0; i < int(sizeof(morder) / sizeof(int)); ++i) fprintf(stderr, "[res2 timing]   model  t%-2d %-58s %7.0f\n", morder[i], mname[i], double(c.dbg[40 + morder[i]]) / mits);
+    for (int i = 0; i < int(sizeof(morder) / sizeof(int)); ++i) {
+      if (r->helper_wave && (morder[i] == 30 || morder[i] == 25)) continue; // (the three-role form: the pose's stamps are the helper's)
+      fprintf(stderr, "[res2 timing]   model  t%-2d %-58s %7.0f\n", morder[i], mname[i], double(c.dbg[40 + morder[i]]) / mits);
+    }
+    if (r->helper_wave) {
+      const int horder[] = {29, 24, 30, 25, 26, 14};
+      const char *hname[] = {"control words (LDS) read", "leader: gate, what the next iteration is, header prefetch issued", "pose inputs of the cycle taken",
+                             "leg words reduced, updateCurrentPose of the walker's cycle + flag", "odometry", "control words written (leader: waits for its loads)"};
+      const double hits = c.dbg[73] ? double(c.dbg[73]) : 1.0;
+      fprintf(stderr, "[res2 timing] helper wavefront of pair 0 (the leader), mean clocks per phase:\n");
+      for (int i = 0; i < int(sizeof(horder) / sizeof(int)); ++i) fprintf(stderr, "[res2 timing]   helper t%-2d %-58s %7.0f\n", horder[i], hname[i], double(c.dbg[80 + horder[i]]) / hits);
+    }
 #endif
   }
 #endif

@@ -219,7 +219,8 @@ def _sources():
 # -disable-machine-licm: MachineLICM hoists the materialisation of ~100 FP64 literals (polynomial coefficients of
 # sincos / atan2, tolerances) out of the n_cycles loop and pins them in VGPRs for the whole launch (256 VGPRs + scratch
 # spills); re-materialising them at use keeps the hexapod kernel free of scratch.
-# -amdgpu-sched-strategy=max-ilp: at one or two waves per SIMD the cycle is bound by dependent-issue latency (FP64
+# -amdgpu-sched-strategy=max-ilp: at one or two waves per SIMD (the resident loops: two or, in the three-role form of the hexapod loop - 384-thread workgroups,
+# walker / model / helper wavefront per robot group - three wavefronts per robot group, a helper sharing its SIMD with a model wavefront) the cycle is bound by dependent-issue latency (FP64
 # dependent ops issue every 8 clocks, LDS reads return after ~60); the ILP-first scheduler spends the spare VGPRs
 # (the occupancy target of 2 waves/SIMD allows 256) on overlapping independent chains.
 _FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value",
