@@ -1193,6 +1193,53 @@ int64_t shc_obs_width(const shc_obs_spec *spec);                       /* column
 int shc_obs_column(const shc_obs_spec *spec, int field, int leg, int k); /* column of component k of `field` (leg ignored for robot fields); -1 if absent */
 int shc_engine_get_observations(shc_engine *e, int64_t first, int64_t count, const shc_obs_spec *spec, void *out, int on_device);
 int shc_fleet_get_observations_device(shc_fleet *f, const shc_obs_spec *spec, void *out /* [n][row_stride], caller's order */);
+/*
+ * Action pass: the observation pass turned round.  Chosen input groups of every robot taken from one dense [n][A] array of float64 or float32 -
+ * what a policy emits - in one kernel per engine (per part of a fleet), which converts and scatters straight into the state; nothing is staged
+ * and the array is never written.
+ * ROW.  The rule of the observation pass: the fields of a spec follow each other in the order of `fields`; SHC_ACT_TIP_FORCE (width 3) and
+ * SHC_ACT_JOINT_EFFORT (width spec.dof) take legs x width columns, leg-major; the other fields take their width (2, 1, 4, 3, 3, 3 in the order
+ * of the enum).  The width of a row and the column of one component come from the two layout calls below; neither needs a device.
+ * DEFINITION.  After the engine call the engine is byte for byte what the existing device setters (on_device = 1) leave when they are given
+ * float64 arrays whose entries are static_cast<double> of the matching columns, and NULL for every group the spec does not name: every robot's
+ * state record, auxiliary blob and held inputs, and every host-side fact a setter touches - the IMU quaternion normalised in double after the
+ * conversion, the touchdown flag and (rough terrain mode) touchdown detection with its step planes, the switch to the tip-force estimate at the
+ * first joint effort (with its one stream synchronisation), the manual-pose flag, the entries of a shorter leg's joints on a mixed-DOF robot.
+ * One half of a pair may be named alone.  Columns of legs or joints the morphology lacks and columns [width, row_stride) are ignored.  The
+ * pose reset mode stays on its own setter; resident mode and the K-cycle launches take their inputs as before.
+ * The fleet form is defined the same way against shc_fleet_set_inputs_device: robot r of a part reads row ids[r] - its CALLER's instance id -
+ * of `actions` ([n][row_stride]) through the ids device I/O keeps on the device; one kernel per part on the part's own stream, no allocation
+ * after the fleet's first device I/O call, the staging footprint unchanged.
+ * STREAMS.  Those of the device setters: the engine's stream; while split steps are in flight the pass rides the two half streams, when every
+ * group of the spec could (tip force in rough terrain mode, or a joint effort before the switch, join first as their setters do).  on_device = 0
+ * copies the host rows into a temporary device buffer and synchronises.  The ordering calls of fleet device I/O apply as written there.
+ * REFUSALS (decided before anything changes; a fleet asks every part before the first launch).  SHC_ERR_INVALID_ARG: NULL handle, spec or
+ * array; n_fields outside 1 .. SHC_ACT_FIELD_COUNT; an unknown or repeated field; an unknown dtype; reserved != 0; legs / dof below the
+ * engine's (legs, longest leg's DOF) or the fleet's shape, or above SHC_MAX_LEGS / SHC_MAX_JOINTS; row_stride non-zero and below the width; an
+ * array not aligned to its element size.  SHC_ERR_BUSY: resident mode.  SHC_ERR_UNSUPPORTED: a fleet that spans devices.
+ */
+enum {
+  SHC_ACT_LINEAR_XY,                 /* 2: shc_engine_set_velocity linear_xy               */
+  SHC_ACT_ANGULAR,                   /* 1:                         angular                 */
+  SHC_ACT_IMU_ORIENTATION,           /* 4: shc_engine_set_imu orientation_wxyz             */
+  SHC_ACT_IMU_ANGULAR_VELOCITY,      /* 3:                    angular_velocity             */
+  SHC_ACT_POSE_TRANSLATION_VELOCITY, /* 3: shc_engine_set_pose_input translation_velocity  */
+  SHC_ACT_POSE_ROTATION_VELOCITY,    /* 3:                           rotation_velocity     */
+  SHC_ACT_TIP_FORCE,                 /* per leg, width 3:   shc_engine_set_tip_force       */
+  SHC_ACT_JOINT_EFFORT,              /* per leg, width dof: shc_engine_set_joint_effort    */
+  SHC_ACT_FIELD_COUNT
+};
+typedef struct shc_act_spec {        /* 64 bytes */
+  int32_t n_fields, fields[SHC_ACT_FIELD_COUNT]; /* column order = this order; a field may appear once               */
+  int32_t dtype;                                 /* SHC_OBS_F64 / SHC_OBS_F32                                         */
+  int32_t legs, dof;                             /* row geometry, as in shc_obs_spec                                  */
+  int32_t reserved;                              /* 0 */
+  int64_t row_stride;                            /* elements between rows; 0 = dense; >= the width otherwise          */
+} shc_act_spec;
+int64_t shc_act_width(const shc_act_spec *spec);                       /* columns of a row; < 0 for an invalid spec; no device needed */
+int shc_act_column(const shc_act_spec *spec, int field, int leg, int k); /* column of component k of `field` (leg ignored for robot fields); -1 if absent */
+int shc_engine_set_actions(shc_engine *e, const shc_act_spec *spec, const void *actions, int on_device);
+int shc_fleet_set_actions_device(shc_fleet *f, const shc_act_spec *spec, const void *actions /* [n][row_stride], caller's order */);
 /* The exchange step of a sharded batch: every device ends up with the desired joint positions of ALL instances
  * ([n][max_legs][max_dof], caller's order, NaN padded) in its own HBM, copied device to device (hipMemcpyPeerAsync: xGMI on an
  * MI355X node).  device_buffers[d] (may be NULL) receives device_ids[d]'s buffer; the buffers belong to the fleet. */

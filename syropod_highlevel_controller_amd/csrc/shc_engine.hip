@@ -1590,6 +1590,7 @@ static int derive_tips(shc_engine *e) {
 #include "shc_frames.hpp"   // publishFrameTransforms: every joint / tip frame and the body frames, shc_engine_get_frame_transforms
 #include "shc_health.hpp"   // the reference's IK / clamping warnings per robot, a restore map and the selected robots: shc_engine_scan_health
 #include "shc_observe.hpp"  // chosen fields of every robot as one dense [rows][D] array: shc_engine_get_observations
+#include "shc_actions.hpp"  // ... turned round: chosen input groups of every robot from one dense [n][A] array: shc_engine_set_actions
 
 template <int NJ>
 static Pose host_fk_tip_pose(const shc_params &p, int leg, const double *q) {

@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = [
     "shc_fleet_set_io_chunk", "shc_fleet_io_bytes",
     "shc_fleet_step_k", "shc_fleet_get_step_k_joints_device",
     "shc_obs_width", "shc_obs_column", "shc_engine_get_observations", "shc_fleet_get_observations_device",
+    "shc_act_width", "shc_act_column", "shc_engine_set_actions", "shc_fleet_set_actions_device",
     "shc_peer_alloc", "shc_peer_open", "shc_peer_close", "shc_peer_scatter",
 ]
 
@@ -200,6 +201,57 @@ def _observation_target(out, what: str):
     if strides[1] != dt.itemsize or strides[0] % dt.itemsize or strides[0] < columns * dt.itemsize:
         raise ValueError(f"{what}: the elements of a row must be contiguous and the rows a whole number of elements apart (strides {tuple(strides)})")
     return C.c_void_p(cai["data"][0]), dt, rows, columns, strides[0] // dt.itemsize
+
+
+# The action pass (include/shc_batch.h, "Action pass"): SHC_ACT_* by name, in the order of the enum
+ACT_FIELD_NAMES = ("linear_xy", "angular", "imu_orientation", "imu_angular_velocity", "pose_translation_velocity", "pose_rotation_velocity", "tip_force",
+                   "joint_effort")
+ACT_FIELDS = {name: i for i, name in enumerate(ACT_FIELD_NAMES)}
+_ACT_ROBOT_WIDTH = {"linear_xy": 2, "angular": 1, "imu_orientation": 4, "imu_angular_velocity": 3, "pose_translation_velocity": 3, "pose_rotation_velocity": 3}
+
+
+class ActSpec(C.Structure):
+    """shc_act_spec: which input groups, in which order, as which element type, for which row geometry."""
+    _fields_ = [("n_fields", C.c_int32), ("fields", C.c_int32 * len(ACT_FIELD_NAMES)), ("dtype", C.c_int32), ("legs", C.c_int32), ("dof", C.c_int32),
+                ("reserved", C.c_int32), ("row_stride", C.c_int64)]
+
+
+def act_spec(fields, legs: int, dof: int, dtype="float32", row_stride: int = 0) -> ActSpec:
+    """The shc_act_spec of a list of field names (ACT_FIELDS) or SHC_ACT_* integers.  Nothing is checked here: the library judges the spec."""
+    ids = [ACT_FIELDS[f] if isinstance(f, str) else int(f) for f in fields]
+    st = ActSpec()
+    st.n_fields = len(ids)
+    for i, f in enumerate(ids[:len(ACT_FIELD_NAMES)]):
+        st.fields[i] = f
+    st.dtype = OBS_DTYPES[np.dtype(dtype).name] if not isinstance(dtype, int) else dtype
+    st.legs, st.dof, st.row_stride = int(legs), int(dof), int(row_stride)
+    return st
+
+
+def action_columns(fields, legs: int, dof: int):
+    """({name: slice}, width) of a row of set_actions(fields) for the row geometry (legs, dof): the slice of tip_force reshapes to (legs, 3), that
+    of joint_effort to (legs, dof), leg-major.  Computed here and checked against the library's own answer (shc_act_width / shc_act_column)."""
+    names = [f if isinstance(f, str) else ACT_FIELD_NAMES[int(f)] for f in fields]
+    cols, at = {}, 0
+    for name in names:
+        if name in cols:
+            raise ValueError(f"action field {name!r} is named twice")
+        if name not in ACT_FIELDS:
+            raise ValueError(f"unknown action field {name!r} (one of {', '.join(ACT_FIELD_NAMES)})")
+        w = _ACT_ROBOT_WIDTH[name] if name in _ACT_ROBOT_WIDTH else int(legs) * (int(dof) if name == "joint_effort" else 3)
+        cols[name] = slice(at, at + w)
+        at += w
+    L, spec = lib(), act_spec(names, legs, dof)
+    width = int(L.shc_act_width(C.byref(spec)))
+    if width < 0:
+        msg = L.shc_last_error()
+        raise ValueError(f"action spec refused: {msg.decode() if msg else ''}")
+    for name, sl in cols.items():
+        per_leg = name not in _ACT_ROBOT_WIDTH
+        last = (int(legs) - 1, (sl.stop - sl.start) // int(legs) - 1) if per_leg else (0, sl.stop - sl.start - 1)
+        if width != at or L.shc_act_column(C.byref(spec), ACT_FIELDS[name], 0, 0) != sl.start or L.shc_act_column(C.byref(spec), ACT_FIELDS[name], *last) != sl.stop - 1:
+            raise ShcError(f"action_columns and the library disagree on {name!r}")
+    return cols, at
 
 
 class ShcError(RuntimeError):
@@ -509,6 +561,11 @@ def lib():
         L.shc_obs_column.argtypes = [C.POINTER(ObsSpec), C.c_int, C.c_int, C.c_int]
         L.shc_engine_get_observations.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(ObsSpec), C.c_void_p, C.c_int]
         L.shc_fleet_get_observations_device.argtypes = [C.c_void_p, C.POINTER(ObsSpec), C.c_void_p]
+        L.shc_act_width.restype = C.c_int64
+        L.shc_act_width.argtypes = [C.POINTER(ActSpec)]
+        L.shc_act_column.argtypes = [C.POINTER(ActSpec), C.c_int, C.c_int, C.c_int]
+        L.shc_engine_set_actions.argtypes = [C.c_void_p, C.POINTER(ActSpec), C.c_void_p, C.c_int]
+        L.shc_fleet_set_actions_device.argtypes = [C.c_void_p, C.POINTER(ActSpec), C.c_void_p]
         L.shc_stream_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
         L.shc_stream_destroy.argtypes = [C.c_int, C.c_void_p]
         L.shc_engine_change_gait.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_int64)]
@@ -764,6 +821,28 @@ class BatchEngine:
     def set_pose_reset_mode(self, mode):
         a = _host(mode, np.int32)
         _check(self.L.shc_engine_set_pose_reset_mode(self.h, _p(a), 0), "set_pose_reset_mode")
+
+    def set_actions(self, actions, fields, legs: Optional[int] = None, dof: Optional[int] = None):
+        """Chosen input groups (names of ACT_FIELDS, in column order) of every instance from one 2-D array of n rows in one device pass
+        (shc_engine_set_actions); ``action_columns(fields, legs, dof)`` names the columns.  The engine is left as the device setters leave it when
+        they are given the columns as float64 arrays; groups not named are held.  actions: a float32 / float64 device array
+        (``__cuda_array_interface__``; a view of some columns of a wider array will do) of at least the width in columns, read on the engine's
+        stream without a host wait and never written - or a numpy array, which is copied to the device and waited for.  legs / dof (default: the
+        engine's) may be larger than the robot's: the columns of legs and joints it lacks are ignored."""
+        legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
+        if isinstance(actions, np.ndarray):
+            if actions.ndim != 2 or actions.dtype not in (np.float32, np.float64):
+                raise ValueError(f"set_actions: a 2-D float32 or float64 array is expected, got {actions.dtype} {actions.shape}")
+            a = np.ascontiguousarray(actions)
+            ptr, dt, rows, columns, stride, on_device = a.ctypes.data_as(C.c_void_p), a.dtype, a.shape[0], a.shape[1], a.shape[1], 0
+        else:
+            ptr, dt, rows, columns, stride = _observation_target(actions, "set_actions")
+            on_device = 1
+        spec = act_spec(fields, legs, dof, dt, stride)
+        width = int(self.L.shc_act_width(C.byref(spec)))
+        if rows != self.n or (width >= 0 and columns < width):
+            raise ValueError(f"set_actions: actions has shape ({rows}, {columns}), {self.n} rows of at least {width} columns are expected")
+        _check(self.L.shc_engine_set_actions(self.h, C.byref(spec), ptr, on_device), "set_actions")
 
     # -- inputs (device pointers, e.g. torch tensors' data_ptr())
     def set_velocity_device(self, linear_ptr: Optional[int], angular_ptr: Optional[int]):

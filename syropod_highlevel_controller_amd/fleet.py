@@ -241,6 +241,20 @@ class MixedFleet:
             raise ValueError(f"observations: out has shape ({rows}, {columns}), {self.n} rows of at least {width} columns are expected")
         _engine._check(self.L.shc_fleet_get_observations_device(self.h, C.byref(spec), ptr), "shc_fleet_get_observations_device")
 
+    def set_actions(self, actions, fields):
+        """Chosen input groups (names of ``engine.ACT_FIELDS``, in column order) of every robot from the DEVICE array ``actions``, row i = the
+        caller's instance i, in one kernel per part with no staging (shc_fleet_set_actions_device).  actions: any 2-D float32 / float64 object with
+        ``__cuda_array_interface__`` of n rows and at least A columns whose rows are contiguous - a view ``big[:, 5:5 + A]`` of a wider torch tensor
+        will do; it is never written.  ``engine.action_columns(fields, max_legs, max_dof)`` names the columns; the fleet is left as ``set_inputs``
+        leaves it when given the columns as float64 arrays, groups not named are held, columns of legs and joints a morphology lacks are ignored.
+        No host wait, and the stream rules of ``set_inputs``."""
+        ptr, dt, rows, columns, stride = _engine._observation_target(actions, "set_actions")
+        spec = _engine.act_spec(fields, self.max_legs, self.max_dof, dt, stride)
+        width = int(self.L.shc_act_width(C.byref(spec)))
+        if rows != self.n or (width >= 0 and columns < width):
+            raise ValueError(f"set_actions: actions has shape ({rows}, {columns}), {self.n} rows of at least {width} columns are expected")
+        _engine._check(self.L.shc_fleet_set_actions_device(self.h, C.byref(spec), ptr), "shc_fleet_set_actions_device")
+
     def step_k(self, n_cycles: int, **arrays):
         """K = ``n_cycles`` cycles in one launch per part (shc_fleet_step_k), cycle k with row k of K-deep DEVICE arrays: the names of
         ``set_inputs`` with a leading dimension K - linear_xy (K, n, 2), angular (K, n), imu_orientation_wxyz (K, n, 4), imu_angular_velocity
