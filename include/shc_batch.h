@@ -1240,6 +1240,74 @@ int64_t shc_act_width(const shc_act_spec *spec);                       /* column
 int shc_act_column(const shc_act_spec *spec, int field, int leg, int k); /* column of component k of `field` (leg ignored for robot fields); -1 if absent */
 int shc_engine_set_actions(shc_engine *e, const shc_act_spec *spec, const void *actions, int on_device);
 int shc_fleet_set_actions_device(shc_fleet *f, const shc_act_spec *spec, const void *actions /* [n][row_stride], caller's order */);
+/*
+ * Foothold pass: the externally requested tip targets / default stance poses of rough terrain mode (shc_external_target above) of every robot
+ * taken from - or read back into - one dense [n][F] array of float64 or float32, in one kernel per engine (per part of a fleet).  What a
+ * foothold planner on the GPU emits never crosses the host; the three host calls above stay as they are.
+ * ROW.  The rule of the observation and action passes: the fields of a spec follow each other in the order of `fields`; every field is per
+ * leg and takes legs x width columns, leg-major (widths 3, 4, 7, 1, 1, 1 in the order of the enum).  The width of a row and the column of one
+ * component come from the two layout calls below; neither needs a device, and both take any selection of fields (what a mode asks of the
+ * fields is the set calls' to judge; the get calls read any selection).
+ * SET, mode SHC_FH_REQUEST (targetTipPoseCallback).  Every column is read as v = static_cast<double>(column).  For robot i and leg l < its
+ * legs let d be its SHC_FH_DEFINED column (d = 1 when the field is not named).  !(d >= 0) - negative or NaN - leaves the leg alone.
+ * Otherwise the engine ends byte for byte as shc_engine_set_external_target(e, which, i, 1, l, &row, ..) leaves it with row.defined = (d > 0),
+ * row.frame_is_odom_ideal = (column != 0) and the other members taken from the columns; a field the spec does not name has the callback's
+ * value: rotation all zero (UNDEFINED_ROTATION), transform the identity 0 0 0 1 0 0 0, clearance 0, frame 0.  SHC_FH_POSITION must be named.
+ * "Byte for byte" covers the state record, the auxiliary blob (the records and the sequence state), the lazy allocation of the records and
+ * of the sequence state, and the rules of the host call: a LegStepper takes a request only while its robot is not STOPPED, the TARGET of a
+ * robot that stands goes to its planner-mode LegPoser, a DEFAULT for it and any stepper request without rough_terrain_mode is dropped.  (One
+ * host-side fact is decided per call, not per leg: a REQUEST call marks the engine as carrying external requests even when every leg of its
+ * rows is left alone; no record changes by that.)
+ * SET, mode SHC_FH_REFRESH_TRANSFORM (generateExternalTargetTransforms).  SHC_FH_TRANSFORM must be named, SHC_FH_DEFINED may be (the same skip
+ * rule), nothing else: every selected leg ends as shc_engine_set_external_transform leaves it - only records that are currently defined take
+ * the new transform.
+ * Columns of legs the robot lacks and columns [width, row_stride) are ignored; the array is never written.
+ * IGNORED.  The number of dropped rows, as the host call counts them, is ADDED to *ignored (may be NULL): a host word, valid on return, with
+ * on_device = 0; with on_device = 1 and in the fleet form a device int64, 8-byte aligned, that the caller zeroes, ordered on the stream - all
+ * parts of a fleet add to the same word.
+ * GET.  For every leg a robot has the named columns hold what shc_engine_get_external_target(which) returns for it: SHC_FH_DEFINED and
+ * SHC_FH_FRAME_IS_ODOM_IDEAL 0 or 1, the clearance 0 for SHC_EXTERNAL_DEFAULT; unchanged for SHC_OBS_F64, static_cast<float> for SHC_OBS_F32.
+ * `pad`, converted once on the host, goes into every column of a leg the robot lacks; columns [width, row_stride) are not touched.  Nothing
+ * is written into the engine beyond the lazy allocations the host getter makes too.
+ * FLEET.  Robot r of a part reads or writes row ids[r] - its CALLER's instance id - of the [n][row_stride] device array; one kernel per part
+ * on the part's stream; part k ends as shc_engine_set_footholds leaves it on the gathered rows.  A part's first foothold call allocates its
+ * records (and the sequence state for targets); after that nothing is allocated or staged and shc_fleet_io_bytes does not change.  The
+ * readiness checks and the ordering calls of fleet device I/O apply as written there.
+ * STREAMS.  The engine calls join split steps first, as the host calls do, and run on the engine's stream.  With on_device = 1 there is no
+ * host wait, no allocation and no free but the first call's lazy ones; on_device = 0 stages the columns [0, width) of the host rows with one
+ * 2-D copy and synchronises.
+ * REFUSALS (decided before anything changes; a fleet asks every part before the first launch).  SHC_ERR_INVALID_ARG: NULL handle, spec or
+ * array; n_fields outside 1 .. SHC_FH_FIELD_COUNT; an unknown or repeated field; an unknown dtype, which or mode; reserved != 0; legs below the
+ * engine's legs or the fleet's shape, or above SHC_MAX_LEGS; row_stride non-zero and below the width; a mandatory field missing or a forbidden
+ * one named for the mode; an array not aligned to its element size or `ignored` not aligned to 8 bytes.  SHC_ERR_UNSUPPORTED:
+ * SHC_EXTERNAL_DEFAULT on an engine or part without rough_terrain_mode, as the host calls; a fleet that spans devices.  SHC_ERR_BUSY: resident mode.
+ */
+enum {
+  SHC_FH_POSITION,            /* 3: ExternalTarget::pose_ position                                  */
+  SHC_FH_ROTATION,            /* 4: pose_ rotation wxyz; all zero = UNDEFINED_ROTATION              */
+  SHC_FH_TRANSFORM,           /* 7: transform_ (x y z qw qx qy qz)                                  */
+  SHC_FH_SWING_CLEARANCE,     /* 1                                                                  */
+  SHC_FH_FRAME_IS_ODOM_IDEAL, /* 1: != 0 -> frame_id_ == "odom_ideal"                               */
+  SHC_FH_DEFINED,             /* 1: > 0 request, 0 withdraw, negative or NaN: leave the leg alone   */
+  SHC_FH_FIELD_COUNT
+};
+enum { SHC_FH_REQUEST = 0, SHC_FH_REFRESH_TRANSFORM = 1 };
+typedef struct shc_foothold_spec {   /* 64 bytes */
+  int32_t n_fields, fields[SHC_FH_FIELD_COUNT]; /* column order = this order; a field may appear once                */
+  int32_t dtype;                                /* SHC_OBS_F64 / SHC_OBS_F32                                          */
+  int32_t legs;                                 /* row geometry: >= the engine's legs / the fleet's shc_fleet_shape max_legs */
+  int32_t which;                                /* SHC_EXTERNAL_TARGET / _DEFAULT / _PLANNER_TARGET                   */
+  int32_t mode;                                 /* SHC_FH_REQUEST / SHC_FH_REFRESH_TRANSFORM (set only; 0 for get)    */
+  int32_t reserved;                             /* 0 */
+  int64_t row_stride;                           /* elements between rows; 0 = dense; >= the width otherwise           */
+  double pad;                                   /* get only: written where a robot has no such leg                    */
+} shc_foothold_spec;
+int64_t shc_foothold_width(const shc_foothold_spec *spec);                /* columns of a row; < 0 for an invalid spec; no device needed */
+int shc_foothold_column(const shc_foothold_spec *spec, int field, int leg, int k); /* column of component k of `field` of `leg`; -1 if absent */
+int shc_engine_set_footholds(shc_engine *e, const shc_foothold_spec *spec, const void *rows, int on_device, int64_t *ignored);
+int shc_engine_get_footholds(shc_engine *e, const shc_foothold_spec *spec, void *rows, int on_device);
+int shc_fleet_set_footholds_device(shc_fleet *f, const shc_foothold_spec *spec, const void *rows /* [n][row_stride], caller's order */, int64_t *ignored_device);
+int shc_fleet_get_footholds_device(shc_fleet *f, const shc_foothold_spec *spec, void *rows /* [n][row_stride], caller's order */);
 /* The exchange step of a sharded batch: every device ends up with the desired joint positions of ALL instances
  * ([n][max_legs][max_dof], caller's order, NaN padded) in its own HBM, copied device to device (hipMemcpyPeerAsync: xGMI on an
  * MI355X node).  device_buffers[d] (may be NULL) receives device_ids[d]'s buffer; the buffers belong to the fleet. */

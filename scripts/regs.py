@@ -1,6 +1,6 @@
 """Development aid: per-specialisation register / scratch / LDS use from hipcc's -Rpass-analysis=kernel-resource-usage
 output (scripts/build_dev.sh writes it to /tmp/shc_res.txt).  Usage: regs.py [report [kernel name]]: the cycle kernels by default, or the
-kernels whose name contains `kernel name` (e.g. leg_state_msgs_kernel: legs, dof, VGPR, SGPR, LDS, scratch)."""
+kernels whose name contains `kernel name` (e.g. leg_state_msgs_kernel: legs, dof, VGPR, SGPR, LDS, scratch; footholds_: legs, element type, ...)."""
 import re
 import sys
 
@@ -14,7 +14,9 @@ for b in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
         g = lambda k: re.search(k + r": (\d+)", b).group(1)
         f = re.search(r"ILi\dELi\dELj(\d+)E(?:Lb([01])E)?", name)   # the loop forms: feature word, and the three-role flag of shc_resident2_kernel
         form = ("features %-10s %s" % (f.group(1), "helper" if f.group(2) == "1" else "      "),) if f else ()
-        print("legs %s dof %s" % (m.groups() if m else ("?", "?")), name.split("I")[0][4:], *form, "VGPR", g("VGPRs"), "AGPR", g("AGPRs"), "SGPR", g("TotalSGPRs"),
+        one = re.search(r"ILi(\d)E([fd])E", name)   # kernels on the leg count and an element type only (footholds_set_kernel / footholds_get_kernel)
+        head = "legs %s dof %s" % m.groups() if m else "legs %s %s" % (one.group(1), {"f": "float32", "d": "float64"}[one.group(2)]) if one else "legs ? dof ?"
+        print(head, name.split("I")[0][4:], *form, "VGPR", g("VGPRs"), "AGPR", g("AGPRs"), "SGPR", g("TotalSGPRs"),
               "LDS", g(r"LDS Size \[bytes/block\]"), "scratch", g(r"ScratchSize \[bytes/lane\]"), "waves/SIMD", g(r"Occupancy \[waves/SIMD\]"))
         continue
     if "shc_cycle_kernel" not in name:

@@ -1920,6 +1920,8 @@ extern "C" int shc_engine_get_external_target(shc_engine *e, int which, int64_t 
   return SHC_OK;
 }
 
+#include "shc_footholds.hpp" // the three calls above for every robot from / into one dense [n][F] device array: shc_engine_set_footholds / _get_footholds
+
 extern "C" int shc_engine_get_joint_commands(shc_engine *e, double *position, double *velocity, double *effort, double *position_command, int on_device) {
   SHC_ENTER_JOINED(e);
   HIP_TRY(hipSetDevice(e->device));

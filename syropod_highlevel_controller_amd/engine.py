@@ -62,6 +62,8 @@ EXPORTED_SYMBOLS = [
     "shc_fleet_step_k", "shc_fleet_get_step_k_joints_device",
     "shc_obs_width", "shc_obs_column", "shc_engine_get_observations", "shc_fleet_get_observations_device",
     "shc_act_width", "shc_act_column", "shc_engine_set_actions", "shc_fleet_set_actions_device",
+    "shc_foothold_width", "shc_foothold_column", "shc_engine_set_footholds", "shc_engine_get_footholds", "shc_fleet_set_footholds_device",
+    "shc_fleet_get_footholds_device",
     "shc_peer_alloc", "shc_peer_open", "shc_peer_close", "shc_peer_scatter",
 ]
 
@@ -252,6 +254,80 @@ def action_columns(fields, legs: int, dof: int):
         if width != at or L.shc_act_column(C.byref(spec), ACT_FIELDS[name], 0, 0) != sl.start or L.shc_act_column(C.byref(spec), ACT_FIELDS[name], *last) != sl.stop - 1:
             raise ShcError(f"action_columns and the library disagree on {name!r}")
     return cols, at
+
+
+# The foothold pass (include/shc_batch.h, "Foothold pass"): SHC_FH_* by name, in the order of the enum; every field is per leg
+FH_FIELD_NAMES = ("position", "rotation", "transform", "swing_clearance", "frame_is_odom_ideal", "defined")
+FH_FIELDS = {name: i for i, name in enumerate(FH_FIELD_NAMES)}
+FH_MODES = {"request": 0, "refresh_transform": 1}  # SHC_FH_REQUEST / SHC_FH_REFRESH_TRANSFORM
+_FH_WIDTH = {"position": 3, "rotation": 4, "transform": 7, "swing_clearance": 1, "frame_is_odom_ideal": 1, "defined": 1}
+
+
+class FootholdSpec(C.Structure):
+    """shc_foothold_spec: which members of the requests, in which order, as which element type, for which row geometry, record and mode."""
+    _fields_ = [("n_fields", C.c_int32), ("fields", C.c_int32 * len(FH_FIELD_NAMES)), ("dtype", C.c_int32), ("legs", C.c_int32), ("which", C.c_int32),
+                ("mode", C.c_int32), ("reserved", C.c_int32), ("row_stride", C.c_int64), ("pad", C.c_double)]
+
+
+def foothold_spec(fields, legs: int, dtype="float32", which: int = 0, mode="request", row_stride: int = 0, pad: float = 0.0) -> FootholdSpec:
+    """The shc_foothold_spec of a list of field names (FH_FIELDS) or SHC_FH_* integers.  Nothing is checked here: the library judges the spec."""
+    ids = [FH_FIELDS[f] if isinstance(f, str) else int(f) for f in fields]
+    st = FootholdSpec()
+    st.n_fields = len(ids)
+    for i, f in enumerate(ids[:len(FH_FIELD_NAMES)]):
+        st.fields[i] = f
+    st.dtype = OBS_DTYPES[np.dtype(dtype).name] if not isinstance(dtype, int) else dtype
+    st.legs, st.which, st.mode = int(legs), int(which), FH_MODES[mode] if isinstance(mode, str) else int(mode)
+    st.row_stride, st.pad = int(row_stride), float(pad)
+    return st
+
+
+def foothold_columns(fields, legs: int):
+    """({name: slice}, width) of a row of set_footholds(fields) / footholds(fields) for a row geometry of ``legs`` legs: a field's slice reshapes
+    to (legs, width per leg), leg-major.  Computed here and checked against the library's own answer (shc_foothold_width / shc_foothold_column)."""
+    names = [f if isinstance(f, str) else FH_FIELD_NAMES[int(f)] for f in fields]
+    cols, at = {}, 0
+    for name in names:
+        if name in cols:
+            raise ValueError(f"foothold field {name!r} is named twice")
+        if name not in FH_FIELDS:
+            raise ValueError(f"unknown foothold field {name!r} (one of {', '.join(FH_FIELD_NAMES)})")
+        cols[name] = slice(at, at + int(legs) * _FH_WIDTH[name])
+        at += int(legs) * _FH_WIDTH[name]
+    L, spec = lib(), foothold_spec(names, legs)
+    width = int(L.shc_foothold_width(C.byref(spec)))
+    if width < 0:
+        msg = L.shc_last_error()
+        raise ValueError(f"foothold spec refused: {msg.decode() if msg else ''}")
+    for name, sl in cols.items():
+        if (width != at or L.shc_foothold_column(C.byref(spec), FH_FIELDS[name], 0, 0) != sl.start
+                or L.shc_foothold_column(C.byref(spec), FH_FIELDS[name], int(legs) - 1, _FH_WIDTH[name] - 1) != sl.stop - 1):
+            raise ShcError(f"foothold_columns and the library disagree on {name!r}")
+    return cols, at
+
+
+def _foothold_rows(rows, what: str):
+    """(pointer, numpy dtype, rows, columns, row stride in elements, on_device, the array that owns a host pointer) of a 2-D float32 / float64
+    array of foothold rows: a numpy array, or a device array (``__cuda_array_interface__``; a view of some columns of a wider one will do)."""
+    if isinstance(rows, np.ndarray):
+        if rows.ndim != 2 or rows.dtype not in (np.float32, np.float64):
+            raise ValueError(f"{what}: a 2-D float32 or float64 array is expected, got {rows.dtype} {rows.shape}")
+        size = rows.dtype.itemsize
+        if (rows.shape[1] > 1 and rows.strides[1] != size) or (rows.shape[0] > 1 and (rows.strides[0] % size or rows.strides[0] < rows.shape[1] * size)):
+            raise ValueError(f"{what}: the elements of a row must be contiguous and the rows a whole number of elements apart (strides {rows.strides})")
+        stride = rows.strides[0] // size if rows.shape[0] > 1 else rows.shape[1]
+        return rows.ctypes.data_as(C.c_void_p), rows.dtype, rows.shape[0], rows.shape[1], stride, 0, rows
+    return _observation_target(rows, what) + (1, None)
+
+
+def _foothold_ignored(ignored, what: str):
+    """The pointer of a device int64 the dropped rows are added to: None, or a one-element int64 device array."""
+    if ignored is None:
+        return None
+    cai = getattr(ignored, "__cuda_array_interface__", None)
+    if cai is None or cai["typestr"] != "<i8" or int(np.prod(cai["shape"], dtype=np.int64)) != 1:
+        raise ValueError(f"{what}: ignored must be a device int64 array of one element (an object with __cuda_array_interface__)")
+    return C.c_void_p(cai["data"][0])
 
 
 class ShcError(RuntimeError):
@@ -566,6 +642,13 @@ def lib():
         L.shc_act_column.argtypes = [C.POINTER(ActSpec), C.c_int, C.c_int, C.c_int]
         L.shc_engine_set_actions.argtypes = [C.c_void_p, C.POINTER(ActSpec), C.c_void_p, C.c_int]
         L.shc_fleet_set_actions_device.argtypes = [C.c_void_p, C.POINTER(ActSpec), C.c_void_p]
+        L.shc_foothold_width.restype = C.c_int64
+        L.shc_foothold_width.argtypes = [C.POINTER(FootholdSpec)]
+        L.shc_foothold_column.argtypes = [C.POINTER(FootholdSpec), C.c_int, C.c_int, C.c_int]
+        L.shc_engine_set_footholds.argtypes = [C.c_void_p, C.POINTER(FootholdSpec), C.c_void_p, C.c_int, C.c_void_p]
+        L.shc_engine_get_footholds.argtypes = [C.c_void_p, C.POINTER(FootholdSpec), C.c_void_p, C.c_int]
+        L.shc_fleet_set_footholds_device.argtypes = [C.c_void_p, C.POINTER(FootholdSpec), C.c_void_p, C.c_void_p]
+        L.shc_fleet_get_footholds_device.argtypes = [C.c_void_p, C.POINTER(FootholdSpec), C.c_void_p]
         L.shc_stream_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
         L.shc_stream_destroy.argtypes = [C.c_int, C.c_void_p]
         L.shc_engine_change_gait.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_int64)]
@@ -1324,6 +1407,52 @@ class BatchEngine:
         rows = (ExternalTarget * n_rows)()
         _check(self.L.shc_engine_get_external_target(self.h, which, first, count, leg, rows), "get_external_target")
         return rows
+
+    def set_footholds(self, rows, fields, which=0, mode="request", ignored=None, legs: Optional[int] = None):
+        """The requests of every leg of every instance from one 2-D array of n rows in one device pass (shc_engine_set_footholds): fields are
+        names of FH_FIELDS in column order, ``foothold_columns(fields, legs)`` names the columns.  Per leg the engine is left as
+        ``set_external_target`` (mode "request": "defined" > 0 requests, 0 withdraws, negative or NaN leaves the leg alone; members not named
+        take the callback's values) or ``set_external_transform`` (mode "refresh_transform") leaves it.  rows: a float32 / float64 device array
+        (``__cuda_array_interface__``; a view of some columns of a wider array will do), read on the engine's stream without a host wait and
+        never written; the dropped rows are then ADDED to ``ignored``, a one-element int64 device array the caller zeroes (or None), and None
+        is returned.  Or a numpy array, which is copied to the device and waited for: the number of dropped rows is returned.  legs (default:
+        the engine's) may be larger than the robot's: the columns of legs it lacks are ignored."""
+        legs = self.legs if legs is None else legs
+        ptr, dt, n_rows, columns, stride, on_device, _keep = _foothold_rows(rows, "set_footholds")
+        spec = foothold_spec(fields, legs, dt, which, mode, stride)
+        width = int(self.L.shc_foothold_width(C.byref(spec)))
+        if n_rows != self.n or (width >= 0 and columns < width):
+            raise ValueError(f"set_footholds: rows has shape ({n_rows}, {columns}), {self.n} rows of at least {width} columns are expected")
+        if on_device:
+            _check(self.L.shc_engine_set_footholds(self.h, C.byref(spec), ptr, 1, _foothold_ignored(ignored, "set_footholds")), "set_footholds")
+            return None
+        if ignored is not None:
+            raise ValueError("set_footholds: host rows return the count; ignored goes with device rows")
+        count = C.c_int64(0)
+        _check(self.L.shc_engine_set_footholds(self.h, C.byref(spec), ptr, 0, C.cast(C.byref(count), C.c_void_p)), "set_footholds")
+        return count.value
+
+    def footholds(self, out=None, fields=FH_FIELD_NAMES, which=0, pad: float = 0.0, dtype="float64", legs: Optional[int] = None):
+        """The requests as the steppers / posers hold them now, every leg of every instance as one (n, F) array in one device pass
+        (shc_engine_get_footholds): per leg the named columns hold what ``get_external_target(which)`` returns, "defined" and
+        "frame_is_odom_ideal" as 0 / 1; the columns of legs the robot lacks (legs > the engine's) hold ``pad``.  Returns a host array of
+        ``dtype`` - or, with out = a 2-D float32 / float64 device array of n rows and at least F columns, fills its first F columns on the
+        engine's stream without a host wait and returns None (out may also be a numpy array, filled and waited for)."""
+        legs = self.legs if legs is None else legs
+        if out is None:
+            width = int(self.L.shc_foothold_width(C.byref(foothold_spec(fields, legs, dtype, which))))
+            if width < 0:
+                _check(SHC_ERR_INVALID_ARG, "get_footholds")
+            host = np.zeros((self.n, width), dtype=np.dtype(dtype))
+            self.footholds(host, fields, which, pad, legs=legs)
+            return host
+        ptr, dt, n_rows, columns, stride, on_device, _keep = _foothold_rows(out, "footholds")
+        spec = foothold_spec(fields, legs, dt, which, "request", stride, pad)
+        width = int(self.L.shc_foothold_width(C.byref(spec)))
+        if n_rows != self.n or (width >= 0 and columns < width):
+            raise ValueError(f"footholds: out has shape ({n_rows}, {columns}), {self.n} rows of at least {width} columns are expected")
+        _check(self.L.shc_engine_get_footholds(self.h, C.byref(spec), ptr, on_device), "get_footholds")
+        return None
 
     def joint_commands(self):
         """(position, velocity, effort, position_command) of publishDesiredJointState, each [n][legs * dof]."""

@@ -255,6 +255,52 @@ class MixedFleet:
             raise ValueError(f"set_actions: actions has shape ({rows}, {columns}), {self.n} rows of at least {width} columns are expected")
         _engine._check(self.L.shc_fleet_set_actions_device(self.h, C.byref(spec), ptr), "shc_fleet_set_actions_device")
 
+    def set_footholds(self, rows, fields, which=0, mode="request", ignored=None):
+        """The tip-target requests of every leg of every robot from one 2-D array, row i = the caller's instance i
+        (shc_fleet_set_footholds_device): ``BatchEngine.set_footholds`` for a fleet, with the row geometry ``max_legs`` -
+        ``engine.foothold_columns(fields, max_legs)`` names the columns, those of legs a morphology lacks are ignored.  rows: a 2-D float32 /
+        float64 device array (``__cuda_array_interface__``; a view of some columns of a wider one will do): one kernel per part on the part's
+        stream, no staging, no host wait, the stream rules of ``set_inputs``; the dropped rows of every part are ADDED to ``ignored``, a
+        one-element int64 device array the caller zeroes (or None); returns None.  Or a numpy array: every part takes its rows through its
+        engine's host form, and the number of dropped rows is returned."""
+        ptr, dt, n_rows, columns, stride, on_device, _keep = _engine._foothold_rows(rows, "set_footholds")
+        spec = _engine.foothold_spec(fields, self.max_legs, dt, which, mode, stride)
+        width = int(self.L.shc_foothold_width(C.byref(spec)))
+        if n_rows != self.n or (width >= 0 and columns < width):
+            raise ValueError(f"set_footholds: rows has shape ({n_rows}, {columns}), {self.n} rows of at least {width} columns are expected")
+        if on_device:
+            _engine._check(self.L.shc_fleet_set_footholds_device(self.h, C.byref(spec), ptr, _engine._foothold_ignored(ignored, "set_footholds")),
+                           "shc_fleet_set_footholds_device")
+            return None
+        if ignored is not None:
+            raise ValueError("set_footholds: host rows return the count; ignored goes with device rows")
+        count, spec.row_stride = C.c_int64(0), 0
+        for e, _m, _d, ids in self.parts():
+            part = np.ascontiguousarray(rows[ids, :max(width, 0)])
+            _engine._check(self.L.shc_engine_set_footholds(e, C.byref(spec), part.ctypes.data_as(C.c_void_p), 0, C.cast(C.byref(count), C.c_void_p)),
+                           "shc_engine_set_footholds")
+        return count.value
+
+    def footholds(self, out, fields=_engine.FH_FIELD_NAMES, which=0, pad: float = 0.0):
+        """The requests as the steppers / posers hold them now into the 2-D float32 / float64 array ``out``, row i = the caller's instance i
+        (shc_fleet_get_footholds_device): ``BatchEngine.footholds`` for a fleet with the row geometry ``max_legs``; ``pad`` where a
+        morphology has no such leg; only the first F columns of out are written.  A device array: one kernel per part, no staging, no host
+        wait - complete after ``synchronize()``, or for work queued on a stream after ``order_before(stream)``.  A numpy array: filled part by
+        part through the engines' host form."""
+        ptr, dt, n_rows, columns, stride, on_device, _keep = _engine._foothold_rows(out, "footholds")
+        spec = _engine.foothold_spec(fields, self.max_legs, dt, which, "request", stride, pad)
+        width = int(self.L.shc_foothold_width(C.byref(spec)))
+        if n_rows != self.n or (width >= 0 and columns < width):
+            raise ValueError(f"footholds: out has shape ({n_rows}, {columns}), {self.n} rows of at least {width} columns are expected")
+        if on_device:
+            _engine._check(self.L.shc_fleet_get_footholds_device(self.h, C.byref(spec), ptr), "shc_fleet_get_footholds_device")
+            return
+        spec.row_stride = 0
+        for e, _m, _d, ids in self.parts():
+            part = np.zeros((len(ids), max(width, 0)), dtype=dt)
+            _engine._check(self.L.shc_engine_get_footholds(e, C.byref(spec), part.ctypes.data_as(C.c_void_p), 0), "shc_engine_get_footholds")
+            out[ids, :part.shape[1]] = part
+
     def step_k(self, n_cycles: int, **arrays):
         """K = ``n_cycles`` cycles in one launch per part (shc_fleet_step_k), cycle k with row k of K-deep DEVICE arrays: the names of
         ``set_inputs`` with a leading dimension K - linear_xy (K, n, 2), angular (K, n), imu_orientation_wxyz (K, n, 4), imu_angular_velocity
