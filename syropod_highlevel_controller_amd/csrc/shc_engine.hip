@@ -342,6 +342,19 @@ static int dispatch_morphology(const shc_engine *e, Fn &&fn) {
 #undef SHC_MORPHOLOGY_CASE
   return no_specialisation();
 }
+// ... and of the leg count alone: fn(std::integral_constant<int, legs>)
+template <class Fn>
+static int dispatch_legs(const shc_engine *e, Fn &&fn) {
+  switch (e->L) {
+  case 3: return fn(std::integral_constant<int, 3>{});
+  case 4: return fn(std::integral_constant<int, 4>{});
+  case 5: return fn(std::integral_constant<int, 5>{});
+  case 6: return fn(std::integral_constant<int, 6>{});
+  case 7: return fn(std::integral_constant<int, 7>{});
+  case 8: return fn(std::integral_constant<int, 8>{});
+  default: return no_specialisation();
+  }
+}
 // Everything a launch of the cycle kernel takes from the engine as it is; the caller names what is its own (grid, block, stream, cycles, loop form)
 static CycleLaunch cycle_launch(const shc_engine *e) {
   CycleLaunch a{};
@@ -1586,11 +1599,12 @@ static int derive_tips(shc_engine *e) {
   return SHC_OK;
 }
 
+#include "shc_rows.hpp"     // the row pattern of the passes below: block geometry, LDS tile and mover, resolved specs, launch sizes, host forms
 #include "shc_leg_msgs.hpp" // the derived LegState fields (one host + device implementation) and shc_engine_get_leg_state_msgs
 #include "shc_frames.hpp"   // publishFrameTransforms: every joint / tip frame and the body frames, shc_engine_get_frame_transforms
 #include "shc_health.hpp"   // the reference's IK / clamping warnings per robot, a restore map and the selected robots: shc_engine_scan_health
 #include "shc_observe.hpp"  // chosen fields of every robot as one dense [rows][D] array: shc_engine_get_observations
-#include "shc_actions.hpp"  // ... turned round: chosen input groups of every robot from one dense [n][A] array: shc_engine_set_actions
+#include "shc_actions.hpp"  // chosen input groups of every robot from one dense [n][A] array: shc_engine_set_actions
 
 template <int NJ>
 static Pose host_fk_tip_pose(const shc_params &p, int leg, const double *q) {

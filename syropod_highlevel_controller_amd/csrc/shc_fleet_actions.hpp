@@ -10,21 +10,12 @@
 #pragma once
 
 extern "C" int shc_fleet_set_actions_device(shc_fleet *f, const shc_act_spec *spec, const void *actions) {
-  if (!f || !spec || !actions) return fail(SHC_ERR_INVALID_ARG, "fleet, spec or actions NULL");
-  ActLayout lay;
-  if (const char *why = act_layout(spec, lay)) return fail(SHC_ERR_INVALID_ARG, why);
-  if (spec->legs < f->max_legs || spec->dof < f->max_dof) return fail(SHC_ERR_INVALID_ARG, "shc_act_spec.legs / dof are below the fleet's shape (shc_fleet_shape)");
-  if (reinterpret_cast<uintptr_t>(actions) & (act_element_bytes(spec) - 1)) return fail(SHC_ERR_INVALID_ARG, "actions must be aligned to its element size");
-  int rc = fleet_io_ready(f);
+  RowLayout lay;
+  int rc = fleet_rows_begin<ActRows>(f, spec, actions, "actions", lay, [&](const shc_engine *e) { return actions_check(e, spec); });
   if (rc != SHC_OK) return rc;
-  for (const auto &p : f->parts) // every part is asked before the first launch
-    if ((rc = actions_check(p.engine, spec)) != SHC_OK) return rc;
-  if ((rc = fleet_io_prepare(f)) != SHC_OK) return rc;
-  const int64_t stride = spec->row_stride ? spec->row_stride : lay.width;
-  for (auto &p : f->parts) {
+  return fleet_rows_each(f, spec, lay, [&](FleetPart &p, int64_t stride) {
     const bool ride = actions_ride(p.engine, lay, 1);
-    if (!ride && (rc = shc_engine_join(p.engine)) != SHC_OK) return rc; // split steps in flight: the part's stream follows both halves first
-    if ((rc = actions_apply(p.engine, spec, lay, actions, stride, p.d_ids, ride)) != SHC_OK) return rc;
-  }
-  return SHC_OK;
+    const int rc = ride ? SHC_OK : shc_engine_join(p.engine); // split steps in flight: the part's stream follows both halves first
+    return rc != SHC_OK ? rc : actions_apply(p.engine, spec, lay, actions, stride, p.d_ids, ride);
+  });
 }

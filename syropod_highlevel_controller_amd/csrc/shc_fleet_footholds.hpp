@@ -9,46 +9,25 @@
 // engine's host calls do; after that nothing is staged and nothing is allocated.
 #pragma once
 
-// What both calls ask before anything changes: the spec, the fleet's shape, the array, one device, every part
-static int fleet_footholds_check(const shc_fleet *f, const shc_foothold_spec *spec, const void *rows, FhLayout &lay) {
-  if (!f || !spec || !rows) return fail(SHC_ERR_INVALID_ARG, "fleet, spec or rows NULL");
-  if (const char *why = fh_layout(spec, lay)) return fail(SHC_ERR_INVALID_ARG, why);
-  if (spec->legs < f->max_legs) return fail(SHC_ERR_INVALID_ARG, "shc_foothold_spec.legs is below the fleet's shape (shc_fleet_shape)");
-  if (reinterpret_cast<uintptr_t>(rows) & (fh_element_bytes(spec) - 1)) return fail(SHC_ERR_INVALID_ARG, "rows must be aligned to its element size");
-  int rc = fleet_io_ready(f);
-  if (rc != SHC_OK) return rc;
-  for (const auto &p : f->parts) // every part is asked before the first launch
-    if ((rc = footholds_check(p.engine, spec)) != SHC_OK) return rc;
-  return SHC_OK;
-}
-
 extern "C" int shc_fleet_set_footholds_device(shc_fleet *f, const shc_foothold_spec *spec, const void *rows, int64_t *ignored_device) {
-  FhLayout lay;
-  int rc = fleet_footholds_check(f, spec, rows, lay);
+  RowLayout lay;
+  int rc = fleet_rows_begin<FhRows>(f, spec, rows, "rows", lay, [&](const shc_engine *e) { return footholds_check(e, spec); });
   if (rc != SHC_OK) return rc;
   if (const char *why = fh_set_fields(spec, lay)) return fail(SHC_ERR_INVALID_ARG, why);
   if (reinterpret_cast<uintptr_t>(ignored_device) & 7) return fail(SHC_ERR_INVALID_ARG, "ignored must be aligned to 8 bytes");
-  if ((rc = fleet_io_prepare(f)) != SHC_OK) return rc;
-  const int64_t stride = spec->row_stride ? spec->row_stride : lay.width;
-  for (auto &p : f->parts) {
-    HIP_TRY(hipSetDevice(p.device));
-    if ((rc = shc_engine_join(p.engine)) != SHC_OK) return rc; // split steps in flight: the part's stream follows both halves first
-    if ((rc = footholds_apply(p.engine, spec, lay, rows, stride, p.d_ids, ignored_device)) != SHC_OK) return rc;
-  }
-  return SHC_OK;
+  return fleet_rows_each(f, spec, lay, [&](FleetPart &p, int64_t stride) {
+    const int rc = fleet_part_join(p);
+    return rc != SHC_OK ? rc : footholds_apply(p.engine, spec, lay, rows, stride, p.d_ids, ignored_device);
+  });
 }
 
 extern "C" int shc_fleet_get_footholds_device(shc_fleet *f, const shc_foothold_spec *spec, void *rows) {
-  FhLayout lay;
-  int rc = fleet_footholds_check(f, spec, rows, lay);
+  RowLayout lay;
+  int rc = fleet_rows_begin<FhRows>(f, spec, rows, "rows", lay, [&](const shc_engine *e) { return footholds_check(e, spec); });
   if (rc != SHC_OK) return rc;
   if (spec->mode != SHC_FH_REQUEST) return fail(SHC_ERR_INVALID_ARG, "shc_foothold_spec.mode must be 0 for shc_fleet_get_footholds_device");
-  if ((rc = fleet_io_prepare(f)) != SHC_OK) return rc;
-  const int64_t stride = spec->row_stride ? spec->row_stride : lay.width;
-  for (auto &p : f->parts) {
-    HIP_TRY(hipSetDevice(p.device));
-    if ((rc = shc_engine_join(p.engine)) != SHC_OK) return rc;
-    if ((rc = footholds_read(p.engine, spec, lay, rows, stride, p.d_ids)) != SHC_OK) return rc;
-  }
-  return SHC_OK;
+  return fleet_rows_each(f, spec, lay, [&](FleetPart &p, int64_t stride) {
+    const int rc = fleet_part_join(p);
+    return rc != SHC_OK ? rc : footholds_read(p.engine, spec, lay, rows, stride, p.d_ids);
+  });
 }

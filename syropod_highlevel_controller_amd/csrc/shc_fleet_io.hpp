@@ -133,6 +133,36 @@ static int fleet_io_prepare(shc_fleet *f) {
   return SHC_OK;
 }
 
+// The fleet forms of the row passes (shc_rows.hpp; shc_fleet_observe.hpp, shc_fleet_actions.hpp, shc_fleet_footholds.hpp), straight between the
+// caller's device array and the parts' states.  What every one asks before anything changes: the spec (P: its description for row_layout), the
+// fleet's shape, the array `rows` (named `what` in the messages), one device, and every part - check(engine) - before the first launch.
+template <class P, class Check>
+static int fleet_rows_begin(const shc_fleet *f, const typename P::Spec *spec, const void *rows, const char *what, RowLayout &lay, Check &&check) {
+  if (!f || !spec || !rows) return fail(SHC_ERR_INVALID_ARG, std::string("fleet, spec or ") + what + " NULL");
+  if (const int bad = row_resolve<P>(spec, lay)) return bad;
+  bool below = spec->legs < f->max_legs;
+  if constexpr (P::has_dof) below = below || spec->dof < f->max_dof;
+  if (below) return fail(SHC_ERR_INVALID_ARG, std::string(P::name) + (P::has_dof ? ".legs / dof are" : ".legs is") + " below the fleet's shape (shc_fleet_shape)");
+  int rc = row_aligned(rows, spec->dtype, what);
+  if (rc == SHC_OK) rc = fleet_io_ready(f);
+  for (size_t i = 0; rc == SHC_OK && i < f->parts.size(); ++i) rc = check(f->parts[i].engine);
+  return rc;
+}
+// ... and then: device I/O prepared, part(p, row stride) for every part - its caller ids (p.d_ids) are the kernels' row table.  Nothing is staged;
+// the rows of the parts are disjoint, so the parts' streams need no order among themselves.
+template <class Spec, class Part>
+static int fleet_rows_each(shc_fleet *f, const Spec *spec, const RowLayout &lay, Part &&part) {
+  int rc = fleet_io_prepare(f);
+  const int64_t stride = row_stride_of(spec, lay);
+  for (size_t i = 0; rc == SHC_OK && i < f->parts.size(); ++i) rc = part(f->parts[i], stride);
+  return rc;
+}
+// (a part's stream follows both halves of split steps in flight first)
+static int fleet_part_join(FleetPart &p) {
+  HIP_TRY(hipSetDevice(p.device));
+  return shc_engine_join(p.engine);
+}
+
 extern "C" int shc_fleet_set_io_chunk(shc_fleet *f, int64_t robots) {
   if (!f || robots < 0) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL or a negative chunk");
   if (robots == f->io_chunk) return SHC_OK;

@@ -10,21 +10,11 @@
 #pragma once
 
 extern "C" int shc_fleet_get_observations_device(shc_fleet *f, const shc_obs_spec *spec, void *out) {
-  if (!f || !spec || !out) return fail(SHC_ERR_INVALID_ARG, "fleet, spec or out NULL");
-  ObsLayout lay;
-  if (const char *why = obs_layout(spec, lay)) return fail(SHC_ERR_INVALID_ARG, why);
-  if (spec->legs < f->max_legs || spec->dof < f->max_dof) return fail(SHC_ERR_INVALID_ARG, "shc_obs_spec.legs / dof are below the fleet's shape (shc_fleet_shape)");
-  if (reinterpret_cast<uintptr_t>(out) & (obs_element_bytes(spec) - 1)) return fail(SHC_ERR_INVALID_ARG, "out must be aligned to its element size");
-  int rc = fleet_io_ready(f);
+  RowLayout lay;
+  int rc = fleet_rows_begin<ObsRows>(f, spec, out, "out", lay, [&](const shc_engine *e) { return observe_check(e, spec, lay); });
   if (rc != SHC_OK) return rc;
-  for (const auto &p : f->parts) // every part is asked before the first launch
-    if ((rc = observe_check(p.engine, spec, lay)) != SHC_OK) return rc;
-  if ((rc = fleet_io_prepare(f)) != SHC_OK) return rc;
-  const int64_t stride = spec->row_stride ? spec->row_stride : lay.width;
-  for (auto &p : f->parts) {
-    HIP_TRY(hipSetDevice(p.device));
-    if ((rc = shc_engine_join(p.engine)) != SHC_OK) return rc; // split steps in flight: the part's stream follows both halves first
-    if ((rc = observe_launch(p.engine, spec, lay, out, stride, p.d_ids, 0, int64_t(p.ids.size()))) != SHC_OK) return rc;
-  }
-  return SHC_OK;
+  return fleet_rows_each(f, spec, lay, [&](FleetPart &p, int64_t stride) {
+    const int rc = fleet_part_join(p);
+    return rc != SHC_OK ? rc : observe_launch(p.engine, spec, lay, out, stride, p.d_ids, 0, int64_t(p.ids.size()));
+  });
 }

@@ -2,7 +2,7 @@
 // taken from, or read back into, one dense [n][F] array of float64 or float32 in one device pass: shc_foothold_width, shc_foothold_column,
 // shc_engine_set_footholds, shc_engine_get_footholds.  Included by shc_engine.hip behind the three host calls it is defined against
 // (shc_engine_set_external_target / _set_external_transform / _get_external_target), whose record table (ext_record), checks and lazy
-// allocations (external_select) it uses; the row geometry and the LDS tile are those of shc_actions.hpp / shc_observe.hpp.  The fleet form
+// allocations (external_select) it uses; the row geometry and the LDS tile are those of shc_rows.hpp.  The fleet form
 // (shc_fleet_footholds.hpp) launches the same kernels with a part's caller ids as the row table.
 //
 // The definition is the host calls': per leg, set leaves what set_external_kernel leaves for a row built from the columns, get writes what
@@ -23,37 +23,23 @@ static_assert(ExtFields::T_POSE % 2 == 0 && ExtFields::D_POSE % 2 == 0 && ExtFie
 // columns per leg of a field
 __host__ __device__ constexpr int fh_field_width(int field) { return field == SHC_FH_POSITION ? 3 : field == SHC_FH_ROTATION ? 4 : field == SHC_FH_TRANSFORM ? 7 : 1; }
 
-// A spec resolved: the first column of every field (-1: not selected), the selected fields as a mask, the columns of a row.
-struct FhLayout {
-  int32_t col[kFhFields];
-  uint32_t mask;
-  int64_t width;
-};
-// nullptr when the spec is valid on its own (no engine asked yet), else what is wrong with it
-static const char *fh_layout(const shc_foothold_spec *s, FhLayout &lay) {
-  if (!s) return "spec is NULL";
-  if (s->n_fields < 1 || s->n_fields > kFhFields) return "shc_foothold_spec.n_fields outside 1 .. SHC_FH_FIELD_COUNT";
-  if (s->dtype != SHC_OBS_F64 && s->dtype != SHC_OBS_F32) return "shc_foothold_spec.dtype is neither SHC_OBS_F64 nor SHC_OBS_F32";
-  if (s->which != SHC_EXTERNAL_TARGET && s->which != SHC_EXTERNAL_DEFAULT && s->which != SHC_EXTERNAL_PLANNER_TARGET)
-    return "shc_foothold_spec.which must be SHC_EXTERNAL_TARGET, SHC_EXTERNAL_DEFAULT or SHC_EXTERNAL_PLANNER_TARGET";
-  if (s->mode != SHC_FH_REQUEST && s->mode != SHC_FH_REFRESH_TRANSFORM) return "shc_foothold_spec.mode is neither SHC_FH_REQUEST nor SHC_FH_REFRESH_TRANSFORM";
-  if (s->reserved != 0) return "shc_foothold_spec.reserved must be 0";
-  if (s->legs < 1 || s->legs > SHC_MAX_LEGS) return "shc_foothold_spec.legs outside 1 .. SHC_MAX_LEGS";
-  for (int f = 0; f < kFhFields; ++f) lay.col[f] = -1;
-  lay.mask = 0, lay.width = 0;
-  for (int i = 0; i < s->n_fields; ++i) {
-    const int f = s->fields[i];
-    if (f < 0 || f >= kFhFields) return "shc_foothold_spec.fields names an unknown field";
-    if (lay.mask & (1u << f)) return "shc_foothold_spec.fields names a field twice";
-    lay.mask |= 1u << f;
-    lay.col[f] = int32_t(lay.width);
-    lay.width += fh_field_width(f) * s->legs;
+// shc_foothold_spec for row_layout (shc_rows.hpp): every field is per leg
+struct FhRows {
+  using Spec = shc_foothold_spec;
+  static constexpr const char *name = "shc_foothold_spec", *n_fields_why = ".n_fields outside 1 .. SHC_FH_FIELD_COUNT";
+  static constexpr int fields = kFhFields, most_fields = kFhFields;
+  static constexpr bool has_dof = false;
+  static bool per_leg(int) { return true; }
+  static int width(int field, int) { return fh_field_width(field); }
+  static const char *own(const Spec *s) {
+    if (s->which != SHC_EXTERNAL_TARGET && s->which != SHC_EXTERNAL_DEFAULT && s->which != SHC_EXTERNAL_PLANNER_TARGET)
+      return "shc_foothold_spec.which must be SHC_EXTERNAL_TARGET, SHC_EXTERNAL_DEFAULT or SHC_EXTERNAL_PLANNER_TARGET";
+    if (s->mode != SHC_FH_REQUEST && s->mode != SHC_FH_REFRESH_TRANSFORM) return "shc_foothold_spec.mode is neither SHC_FH_REQUEST nor SHC_FH_REFRESH_TRANSFORM";
+    return nullptr;
   }
-  if (s->row_stride != 0 && s->row_stride < lay.width) return "shc_foothold_spec.row_stride is below the width of a row";
-  return nullptr;
-}
+};
 // ... and what the set calls ask of the fields for the spec's mode (the layout calls and the get calls take any selection)
-static const char *fh_set_fields(const shc_foothold_spec *s, const FhLayout &lay) {
+static const char *fh_set_fields(const shc_foothold_spec *s, const RowLayout &lay) {
   if (s->mode == SHC_FH_REQUEST && !(lay.mask & (1u << SHC_FH_POSITION))) return "SHC_FH_REQUEST needs SHC_FH_POSITION";
   if (s->mode == SHC_FH_REFRESH_TRANSFORM) {
     if (!(lay.mask & (1u << SHC_FH_TRANSFORM))) return "SHC_FH_REFRESH_TRANSFORM needs SHC_FH_TRANSFORM";
@@ -62,34 +48,15 @@ static const char *fh_set_fields(const shc_foothold_spec *s, const FhLayout &lay
   return nullptr;
 }
 
-extern "C" int64_t shc_foothold_width(const shc_foothold_spec *spec) {
-  FhLayout lay;
-  const char *why = fh_layout(spec, lay);
-  if (why) return -int64_t(fail(SHC_ERR_INVALID_ARG, why));
-  return lay.width;
-}
-extern "C" int shc_foothold_column(const shc_foothold_spec *spec, int field, int leg, int k) {
-  FhLayout lay;
-  if (fh_layout(spec, lay) || field < 0 || field >= kFhFields || lay.col[field] < 0) return -1;
-  const int w = fh_field_width(field);
-  if (k < 0 || k >= w || leg < 0 || leg >= spec->legs) return -1;
-  return lay.col[field] + leg * w + k;
-}
+extern "C" int64_t shc_foothold_width(const shc_foothold_spec *spec) { return row_width<FhRows>(spec); }
+extern "C" int shc_foothold_column(const shc_foothold_spec *spec, int field, int leg, int k) { return row_column<FhRows>(spec, field, leg, k); }
 
-// The kernels' view of a spec (launch-uniform: scalar loads of the kernel arguments)
-struct FhArgs {
-  uint32_t mask;
-  int32_t col[kFhFields];
-  int32_t width, pitch; // columns of a row; elements between the rows of the LDS tile
+// The kernels' view of a spec (has_pad, pad: get only)
+struct FhArgs : RowArgs<kFhFields> {
   int32_t which, refresh, rough_terrain;
-  int32_t has_pad; // get: the row has legs the morphology lacks
-  int64_t row_stride;
-  double pad;
 };
 
-// actions_kernel's geometry and copy-in (see there): one leg per lane, floor(64 / L) robots per wavefront, one wavefront per workgroup; block b
-// serves the robot group first / rpw + b, clipped to [first, end); rows come from in[row * row_stride], row = ids[robot] or the robot's own
-// index, through an LDS tile of rpw rows of `pitch` (odd) elements with consecutive lanes on consecutive elements of a row.  Lane (robot, leg)
+// The geometry and the tile of shc_rows.hpp, copy-in: the rows in[row * row_stride], row = ids[robot] or the robot's own index.  Lane (robot, leg)
 // then reads its leg's columns back and does what set_external_kernel does for that leg - the same branches in the same order, so the records,
 // the sequence state and the count of dropped rows are that kernel's.  A record's pose and transform are seven plane pairs from an even
 // field (double2 stores at the lane's slot: consecutive lanes on consecutive 16-byte elements); clearance and flags are the eighth pair of a
@@ -101,37 +68,22 @@ __global__ __launch_bounds__(64) void footholds_set_kernel(const T *__restrict__
                                                            const int64_t *__restrict__ ids, unsigned long long *__restrict__ ignored, int64_t first, int64_t end) {
   using X = ExtFields;
   constexpr int rpw = 64 / L;
-  extern __shared__ double2 fh_tile[];
-  T *tile = reinterpret_cast<T *>(fh_tile);
-  const int lane = threadIdx.x;
-  const int64_t w = first / rpw + blockIdx.x;
-  const int gi = lane / L, leg = lane - gi * L;
-  const int64_t rob = w * rpw + gi;
-  const bool live = gi < rpw && rob >= first && rob < end;
-  // groups [g0, g0 + n_rob) hold the rows of robots rob_lo .. of this block
-  const int64_t rob_lo = w * rpw > first ? w * rpw : first, rob_hi = (w + 1) * rpw < end ? (w + 1) * rpw : end;
-  const int g0 = int(rob_lo - w * rpw), n_rob = int(rob_hi - rob_lo);
+  const RowGroup<L> rg(first, end);
+  const int lane = rg.lane, gi = rg.gi, leg = rg.leg;
+  const int64_t rob = rg.rob;
+  T *tile = row_tile<T>();
 
-  // copy-in: element e = lane, lane + 64, .. of the block's n_rob x width elements; (r, c) follow by addition - 64 = dq * width + dr
-  const int total = n_rob * a.width, dq = 64 / a.width, dr = 64 - dq * a.width;
-  int r = lane / a.width, c = lane - r * a.width;
-  for (int e = lane; e < total; e += 64) {
-    const int64_t rr = rob_lo + r;
-    const int64_t irow = ids ? ids[rr] : rr;
-    tile[(g0 + r) * a.pitch + c] = in[irow * a.row_stride + c];
-    r += dq, c += dr;
-    if (c >= a.width) c -= a.width, ++r;
-  }
+  row_tile_in(tile, in, rg, a, ids, 0);
   __syncthreads();
 
   bool dropped = false;
-  if (live) {
+  if (rg.live) {
     const T *row = tile + gi * a.pitch;
     auto sel = [&](int f) { return (a.mask >> f & 1u) != 0; };
     auto column = [&](int f, int k) { return static_cast<double>(row[a.col[f] + leg * fh_field_width(f) + k]); };
     const double d = sel(SHC_FH_DEFINED) ? column(SHC_FH_DEFINED, 0) : 1.0;
     if (d >= 0.0) { // (negative or NaN: the leg is left alone)
-      const int64_t slot = w * 64 + lane, ns = st.n_slots;
+      const int64_t slot = rg.slot, ns = st.n_slots;
       double2 *planes = reinterpret_cast<double2 *>(st.ext);
       int which = a.which;
       ExtAt at = ext_record(which);
@@ -179,33 +131,22 @@ __global__ __launch_bounds__(64) void footholds_set_kernel(const T *__restrict__
   }
 }
 
-// observe_kernel's geometry and copy-out (see there).  The tile is filled with `pad` first when the row has legs the morphology lacks; lane
+// The geometry and the tile of shc_rows.hpp, copy-out.  The tile is filled with `pad` first when the row has legs the morphology lacks; lane
 // (robot, leg) then loads its leg's record - eight plane pairs of a target, seven and the flags of a default - and writes the selected columns
 // as get_external_kernel and the host getter's conversion give them; the rows leave with consecutive lanes on consecutive elements.
 template <int L, class T>
 __global__ __launch_bounds__(64) void footholds_get_kernel(T *__restrict__ out, DevState st, const FhArgs a, const int64_t *__restrict__ ids, int64_t first, int64_t end) {
   using X = ExtFields;
-  constexpr int rpw = 64 / L;
-  extern __shared__ double2 fh_tile[];
-  T *tile = reinterpret_cast<T *>(fh_tile);
-  const int lane = threadIdx.x;
-  const int64_t w = first / rpw + blockIdx.x;
-  const int gi = lane / L, leg = lane - gi * L;
-  const int64_t rob = w * rpw + gi;
-  const bool live = gi < rpw && rob >= first && rob < end;
-  const int64_t rob_lo = w * rpw > first ? w * rpw : first, rob_hi = (w + 1) * rpw < end ? (w + 1) * rpw : end;
-  const int g0 = int(rob_lo - w * rpw), n_rob = int(rob_hi - rob_lo);
+  const RowGroup<L> rg(first, end);
+  const int gi = rg.gi, leg = rg.leg;
+  T *tile = row_tile<T>();
 
-  if (a.has_pad) {
-    const T pad = static_cast<T>(a.pad);
-    for (int c = lane; c < rpw * a.pitch; c += 64) tile[c] = pad;
-    __syncthreads();
-  }
-  if (live) {
+  row_tile_pad(tile, rg, a);
+  if (rg.live) {
     T *row = tile + gi * a.pitch;
     auto sel = [&](int f) { return (a.mask >> f & 1u) != 0; };
     auto put = [&](int f, int k, double x) { row[a.col[f] + leg * fh_field_width(f) + k] = static_cast<T>(x); };
-    const int64_t slot = w * 64 + lane, ns = st.n_slots;
+    const int64_t slot = rg.slot, ns = st.n_slots;
     const double2 *planes = reinterpret_cast<const double2 *>(st.ext);
     const ExtAt at = ext_record(a.which);
     double v[16];
@@ -238,16 +179,7 @@ __global__ __launch_bounds__(64) void footholds_get_kernel(T *__restrict__ out, 
     if (sel(SHC_FH_DEFINED)) put(SHC_FH_DEFINED, 0, double(flags & 1));
   }
   __syncthreads();
-  // copy-out: element e = lane, lane + 64, .. of the block's n_rob x width elements; (r, c) follow by addition - 64 = dq * width + dr
-  const int total = n_rob * a.width, dq = 64 / a.width, dr = 64 - dq * a.width;
-  int r = lane / a.width, c = lane - r * a.width;
-  for (int e = lane; e < total; e += 64) {
-    const int64_t rr = rob_lo + r;
-    const int64_t orow = ids ? ids[rr] : rr;
-    out[orow * a.row_stride + c] = tile[(g0 + r) * a.pitch + c];
-    r += dq, c += dr;
-    if (c >= a.width) c -= a.width, ++r;
-  }
+  row_tile_out(out, tile, rg, a, ids, 0);
 }
 
 // What an engine refuses of a spec that is valid on its own (the host calls' own answers: external_select)
@@ -257,45 +189,25 @@ static int footholds_check(const shc_engine *e, const shc_foothold_spec *spec) {
     return fail(SHC_ERR_UNSUPPORTED, "external default poses are read in rough_terrain_mode only (walk_controller.cpp:988)");
   return SHC_OK;
 }
-static size_t fh_element_bytes(const shc_foothold_spec *spec) { return spec->dtype == SHC_OBS_F32 ? 4 : 8; }
 
-static FhArgs fh_args(const shc_engine *e, const shc_foothold_spec *spec, const FhLayout &lay, int64_t row_stride) {
+static FhArgs fh_args(const shc_engine *e, const shc_foothold_spec *spec, const RowLayout &lay, int64_t row_stride) {
   FhArgs a{};
-  a.mask = lay.mask;
-  for (int f = 0; f < kFhFields; ++f) a.col[f] = lay.col[f];
-  a.width = int32_t(lay.width), a.pitch = int32_t(lay.width) | 1;
+  row_args(a, lay, spec->dtype, row_stride, spec->legs > e->L, spec->pad);
   a.which = spec->which, a.refresh = spec->mode == SHC_FH_REFRESH_TRANSFORM, a.rough_terrain = e->params.rough_terrain_mode ? 1 : 0;
-  a.has_pad = spec->legs > e->L;
-  a.row_stride = row_stride;
-  a.pad = spec->dtype == SHC_OBS_F32 ? double(static_cast<float>(spec->pad)) : spec->pad;
   return a;
-}
-// fn(std::integral_constant<int, legs>) for the engine's leg count
-template <class Fn>
-static int dispatch_legs(const shc_engine *e, Fn &&fn) {
-  switch (e->L) {
-  case 3: return fn(std::integral_constant<int, 3>{});
-  case 4: return fn(std::integral_constant<int, 4>{});
-  case 5: return fn(std::integral_constant<int, 5>{});
-  case 6: return fn(std::integral_constant<int, 6>{});
-  case 7: return fn(std::integral_constant<int, 7>{});
-  case 8: return fn(std::integral_constant<int, 8>{});
-  default: return no_specialisation();
-  }
 }
 
 // The set pass over every instance of an engine on its stream, with the host call's host-side effects.  `in` and `ignored` are device
 // pointers ready on the engine's stream; rows ids[instance] (ids != NULL, a device table) or instance.  The caller has checked everything and
 // joined split steps.
-static int footholds_apply(shc_engine *e, const shc_foothold_spec *spec, const FhLayout &lay, const void *in, int64_t row_stride, const int64_t *ids, int64_t *ignored) {
+static int footholds_apply(shc_engine *e, const shc_foothold_spec *spec, const RowLayout &lay, const void *in, int64_t row_stride, const int64_t *ids, int64_t *ignored) {
   int64_t n_rows = 0;
   int rc = external_select(e, spec->which, 0, e->n, -1, &n_rows); // the lazy allocations of the host calls (records, sequence state)
   if (rc != SHC_OK) return rc;
   if (spec->mode == SHC_FH_REQUEST) e->rt_flags |= RT_EXTERNAL; // as shc_engine_set_external_target
   const FhArgs a = fh_args(e, spec, lay, row_stride);
-  const int rpw = 64 / e->L;
-  const unsigned grid = (unsigned)((e->n - 1) / rpw + 1);
-  const size_t lds = size_t(rpw) * a.pitch * fh_element_bytes(spec);
+  const unsigned grid = row_grid(e->L, 0, e->n);
+  const size_t lds = row_tile_bytes(e->L, a.pitch, spec->dtype);
   unsigned long long *ign = reinterpret_cast<unsigned long long *>(ignored);
   rc = dispatch_legs(e, [&](auto l) -> int {
     constexpr int L = decltype(l)::value;
@@ -311,14 +223,13 @@ static int footholds_apply(shc_engine *e, const shc_foothold_spec *spec, const F
 }
 
 // The get pass: every instance's records into rows ids[instance] or instance of the device array `out`, on the engine's stream
-static int footholds_read(shc_engine *e, const shc_foothold_spec *spec, const FhLayout &lay, void *out, int64_t row_stride, const int64_t *ids) {
+static int footholds_read(shc_engine *e, const shc_foothold_spec *spec, const RowLayout &lay, void *out, int64_t row_stride, const int64_t *ids) {
   int64_t n_rows = 0;
   int rc = external_select(e, spec->which, 0, e->n, -1, &n_rows); // (the host getter's lazy allocations)
   if (rc != SHC_OK) return rc;
   const FhArgs a = fh_args(e, spec, lay, row_stride);
-  const int rpw = 64 / e->L;
-  const unsigned grid = (unsigned)((e->n - 1) / rpw + 1);
-  const size_t lds = size_t(rpw) * a.pitch * fh_element_bytes(spec);
+  const unsigned grid = row_grid(e->L, 0, e->n);
+  const size_t lds = row_tile_bytes(e->L, a.pitch, spec->dtype);
   rc = dispatch_legs(e, [&](auto l) -> int {
     constexpr int L = decltype(l)::value;
     if (spec->dtype == SHC_OBS_F32)
@@ -335,30 +246,20 @@ static int footholds_read(shc_engine *e, const shc_foothold_spec *spec, const Fh
 extern "C" int shc_engine_set_footholds(shc_engine *e, const shc_foothold_spec *spec, const void *rows, int on_device, int64_t *ignored) {
   SHC_ENTER(e);
   if (!spec || !rows) return fail(SHC_ERR_INVALID_ARG, "spec or rows is NULL");
-  FhLayout lay;
-  if (const char *why = fh_layout(spec, lay)) return fail(SHC_ERR_INVALID_ARG, why);
-  if (const char *why = fh_set_fields(spec, lay)) return fail(SHC_ERR_INVALID_ARG, why);
+  RowLayout lay;
+  if (const int bad = row_resolve<FhRows>(spec, lay)) return bad;
+  if (const char *fields = fh_set_fields(spec, lay)) return fail(SHC_ERR_INVALID_ARG, fields);
   int rc = footholds_check(e, spec);
   if (rc != SHC_OK) return rc;
-  const size_t es = fh_element_bytes(spec);
-  if (reinterpret_cast<uintptr_t>(rows) & (es - 1)) return fail(SHC_ERR_INVALID_ARG, "rows must be aligned to its element size");
+  if ((rc = row_aligned(rows, spec->dtype, "rows")) != SHC_OK) return rc;
   if (reinterpret_cast<uintptr_t>(ignored) & 7) return fail(SHC_ERR_INVALID_ARG, "ignored must be aligned to 8 bytes");
   if ((rc = join_side(e)) != SHC_OK) return rc;
   HIP_TRY(hipSetDevice(e->device));
-  const int64_t stride = spec->row_stride ? spec->row_stride : lay.width;
+  const int64_t stride = row_stride_of(spec, lay);
   if (on_device) return footholds_apply(e, spec, lay, rows, stride, nullptr, ignored);
-  // host form: the columns [0, width) of every row of the caller's array as dense rows on the device (and the count's word behind them), then the pass
-  char *d = nullptr;
-  const size_t row_bytes = size_t(lay.width) * es, rows_bytes = (size_t(e->n) * row_bytes + 7) & ~size_t(7);
-  HIP_TRY(hipMalloc(&d, rows_bytes + 8));
-  int64_t *d_ignored = reinterpret_cast<int64_t *>(d + rows_bytes), h_ignored = 0;
-  hipError_t err = hipMemcpy2DAsync(d, row_bytes, rows, size_t(stride) * es, row_bytes, size_t(e->n), hipMemcpyHostToDevice, e->stream);
-  if (err == hipSuccess) err = hipMemsetAsync(d_ignored, 0, 8, e->stream);
-  if (err == hipSuccess) rc = footholds_apply(e, spec, lay, d, lay.width, nullptr, d_ignored);
-  if (err == hipSuccess && rc == SHC_OK) err = hipMemcpyAsync(&h_ignored, d_ignored, 8, hipMemcpyDeviceToHost, e->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  (void)hipFree(d);
-  if (err != hipSuccess) return fail(SHC_ERR_HIP, std::string("footholds: ") + hipGetErrorString(err));
+  int64_t h_ignored = 0; // (the count's word stands behind the rows on the device)
+  rc = rows_from_host(e, "footholds", rows, e->n, lay.width, stride, spec->dtype, &h_ignored,
+                      [&](const void *d, int64_t *d_ignored) { return footholds_apply(e, spec, lay, d, lay.width, nullptr, d_ignored); });
   if (rc == SHC_OK && ignored) *ignored += h_ignored;
   return rc;
 }
@@ -366,27 +267,15 @@ extern "C" int shc_engine_set_footholds(shc_engine *e, const shc_foothold_spec *
 extern "C" int shc_engine_get_footholds(shc_engine *e, const shc_foothold_spec *spec, void *rows, int on_device) {
   SHC_ENTER(e);
   if (!spec || !rows) return fail(SHC_ERR_INVALID_ARG, "spec or rows is NULL");
-  FhLayout lay;
-  if (const char *why = fh_layout(spec, lay)) return fail(SHC_ERR_INVALID_ARG, why);
+  RowLayout lay;
+  if (const int bad = row_resolve<FhRows>(spec, lay)) return bad;
   if (spec->mode != SHC_FH_REQUEST) return fail(SHC_ERR_INVALID_ARG, "shc_foothold_spec.mode must be 0 for shc_engine_get_footholds");
   int rc = footholds_check(e, spec);
   if (rc != SHC_OK) return rc;
-  const size_t es = fh_element_bytes(spec);
-  if (reinterpret_cast<uintptr_t>(rows) & (es - 1)) return fail(SHC_ERR_INVALID_ARG, "rows must be aligned to its element size");
+  if ((rc = row_aligned(rows, spec->dtype, "rows")) != SHC_OK) return rc;
   if ((rc = join_side(e)) != SHC_OK) return rc;
   HIP_TRY(hipSetDevice(e->device));
-  const int64_t stride = spec->row_stride ? spec->row_stride : lay.width;
+  const int64_t stride = row_stride_of(spec, lay);
   if (on_device) return footholds_read(e, spec, lay, rows, stride, nullptr);
-  // host form: dense rows on the device, then the columns [0, width) of every row of the caller's array
-  void *d = nullptr;
-  const size_t row_bytes = size_t(lay.width) * es;
-  HIP_TRY(hipMalloc(&d, size_t(e->n) * row_bytes));
-  rc = footholds_read(e, spec, lay, d, lay.width, nullptr);
-  hipError_t err = hipSuccess;
-  if (rc == SHC_OK) err = hipMemcpy2DAsync(rows, size_t(stride) * es, d, row_bytes, row_bytes, size_t(e->n), hipMemcpyDeviceToHost, e->stream);
-  if (rc == SHC_OK && err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  (void)hipFree(d);
-  if (rc != SHC_OK) return rc;
-  if (err != hipSuccess) return fail(SHC_ERR_HIP, std::string("footholds: ") + hipGetErrorString(err));
-  return SHC_OK;
+  return rows_to_host(e, "footholds", rows, e->n, lay.width, stride, spec->dtype, [&](void *d) { return footholds_read(e, spec, lay, d, lay.width, nullptr); });
 }

@@ -113,8 +113,7 @@ __device__ __forceinline__ V3 frames_desired_velocity(const DevState &st, int64_
   using R = RobotFields;
   return V3{st.robd[rob_index(rob, R::VLIN, rpw, R::COUNT)], st.robd[rob_index(rob, R::VLIN + 1, rpw, R::COUNT)], st.robd[rob_index(rob, R::VANG, rpw, R::COUNT)]};
 }
-// One leg per lane, floor(64 / L) robots per wavefront (the cycle's slot mapping: the joint-angle planes are read as contiguous double2 per
-// lane); one wavefront per workgroup.  Block b serves the robot group first / rpw + b, clipped to [first, first + count).
+// The geometry of shc_rows.hpp (RowGroup) for [first, first + count); the joint-angle planes are read as contiguous double2 per lane.
 //
 // Output: a lane's leg record is 336 B = 21 chunks of 16 B.  The lanes write their records into LDS at a stride of 336 B (84 dwords = 20 mod
 // 32 banks, an odd multiple of 4: the eight contiguous lanes a ds_write_b128 serves per LDS cycle start on banks {0, 20, 8, 28, 16, 4, 24, 12}
@@ -131,30 +130,26 @@ __global__ __launch_bounds__(64) void frame_transforms_kernel(double2 *__restric
   constexpr int rpw = 64 / L;
   constexpr int kLegChunks = kLegFrameDoubles / 2, kBodyChunks = kBodyFrameDoubles / 2;
   __shared__ double2 strip[64 * kLegChunks];
-  const int lane = threadIdx.x;
-  const int64_t w = first / rpw + blockIdx.x;
-  const int gi = lane / L, leg = lane - gi * L;
-  const int64_t rob = w * rpw + gi, end = first + count;
-  const bool live = gi < rpw && rob >= first && rob < end;
+  const RowGroup<L> rg(first, first + count);
+  const int lane = rg.lane, gi = rg.gi, leg = rg.leg, g0 = rg.g0, n_rob = rg.n_rob;
+  const int64_t rob = rg.rob;
   // lanes [lane0, lane0 + n_rec) hold the leg records legs_out[rec0 ..] of this block, groups [g0, g0 + n_rob) the body records
-  const int64_t rob_lo = w * rpw > first ? w * rpw : first, rob_hi = (w + 1) * rpw < end ? (w + 1) * rpw : end;
-  const int g0 = int(rob_lo - w * rpw), n_rob = int(rob_hi - rob_lo);
   const int lane0 = g0 * L, n_rec = n_rob * L;
-  const int64_t rec0 = (rob_lo - first) * L, brec0 = rob_lo - first;
+  const int64_t rec0 = (rg.rob_lo - first) * L, brec0 = rg.rob_lo - first;
 
   double rec[kLegFrameDoubles], brec[kBodyFrameDoubles];
 #pragma unroll
   for (int k = 0; k < kLegFrameDoubles; ++k) rec[k] = 0.0;
 #pragma unroll
   for (int k = 0; k < kBodyFrameDoubles; ++k) brec[k] = 0.0;
-  if (live) {
+  if (rg.live) {
     Pose o2b = pose_identity();
     if (body_out != nullptr || world) { // every lane of a robot's group forms the robot's record for itself, as the cycle does
       o2b = body_frames(frames_odometry(st, rob, rpw, have_odom), frames_current_pose(st, rob, rpw), frames_desired_velocity(st, rob, rpw), brec);
     }
     if (legs_out != nullptr) {
       double q[NJ]; // Joint::desired_position_: the chain applyFK() left behind
-      load_leg_fields<FD::Q, NJ>(reinterpret_cast<const double2 *>(st.legd), st.n_slots, w * 64 + lane, q);
+      load_leg_fields<FD::Q, NJ>(reinterpret_cast<const double2 *>(st.legd), st.n_slots, rg.slot, q);
       leg_frames<NJ>(gc->leg[leg], q, rec);
       if (world) leg_frames_to_world(o2b, rec);
     }
@@ -193,8 +188,7 @@ extern "C" int shc_engine_get_frame_transforms(shc_engine *e, int64_t first, int
   if (!on_device) HIP_TRY(hipMalloc(&d, leg_bytes + body_bytes));
   double2 *d_legs = legs ? reinterpret_cast<double2 *>(on_device ? reinterpret_cast<char *>(legs) : d) : nullptr;
   double2 *d_body = body ? reinterpret_cast<double2 *>(on_device ? reinterpret_cast<char *>(body) : d + leg_bytes) : nullptr;
-  const int rpw = 64 / e->L;
-  const unsigned grid = (unsigned)((first + count - 1) / rpw - first / rpw + 1);
+  const unsigned grid = row_grid(e->L, first, first + count);
   const int rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
     constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
     frame_transforms_kernel<L, NJ><<<dim3(grid), dim3(64), 0, e->stream>>>(d_legs, d_body, e->st, (const SharedConsts<L, NJ> *)e->d_consts, world,

@@ -90,8 +90,7 @@ static shc_health_criteria health_criteria(const shc_health_criteria *c) {
 }
 
 // ---- the batched form
-// Pass 1.  The mapping of frame_transforms_kernel: one leg per lane, floor(64 / L) robots per wavefront, one wavefront per workgroup, the joint
-// planes read as double2 per lane; block b serves the robot group first / rpw + b, clipped to [first, first + count).  The per-leg figures meet in
+// Pass 1.  The geometry of shc_rows.hpp (RowGroup) for [first, first + count), the joint planes read as double2 per lane.  The per-leg figures meet in
 // the robot over the L lanes of its group (Group<L>: the cycle's cross-lane reads); every lane of a group forms the same record.  The records of a
 // wavefront are consecutive in `health`: each group's first lane puts its 32 bytes into an LDS strip and the wavefront writes the strip out as
 // contiguous 16-byte stores.  restore_map takes i or -1 for the robots of the range here (the entries outside it are filled by the caller), and
@@ -106,6 +105,7 @@ __global__ __launch_bounds__(64) void health_scan_kernel(ulonglong2 *__restrict_
   using R = RobotFields;
   constexpr int rpw = 64 / L;
   __shared__ ulonglong2 strip[2 * rpw];
+  // (RowGroup's lines written out: taken through the struct this kernel, alone of the seven, allocates two more SGPRs)
   const int lane = threadIdx.x;
   const int64_t w = first / rpw + blockIdx.x;
   const int gi = lane / L, leg = lane - gi * L;
@@ -269,7 +269,7 @@ extern "C" int shc_engine_scan_health(shc_engine *e, int64_t first, int64_t coun
   if (count == 0) {
     if (d_nsel && err == hipSuccess) err = hipMemsetAsync(d_nsel, 0, 8, e->stream);
   } else if (err == hipSuccess && (rc = derive_tips(e)) == SHC_OK) {
-    const int64_t wave0 = first / rpw, grid = (end - 1) / rpw - wave0 + 1;
+    const int64_t wave0 = first / rpw, grid = row_grid(e->L, first, end);
     unsigned long long *masks = compact ? reinterpret_cast<unsigned long long *>(e->d_health) : nullptr;
     uint32_t *counts = compact ? reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(e->d_health) + size_t(e->n_waves) * 8) : nullptr;
     rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {

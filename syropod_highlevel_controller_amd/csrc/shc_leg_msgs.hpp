@@ -174,8 +174,7 @@ __device__ __forceinline__ void load_leg_fields(const double2 *__restrict__ plan
   }
 }
 
-// One leg per lane, floor(64 / L) robots per wavefront (the cycle's slot mapping: every plane read is contiguous across the wavefront);
-// one wavefront per workgroup.  Block b serves the robot group first / rpw + b, clipped to [first, first + count).  The records of a
+// The geometry of shc_rows.hpp (RowGroup) for [first, first + count).  The records of a
 // wavefront are consecutive in `out` (consecutive instances, consecutive legs), so after staging the block is written with all 64 lanes,
 // 16 B per lane, contiguous within each 256-byte half record.  MODEL_TIP / POSER_TIP must have been derived (derive_tips).
 template <int L, int NJ>
@@ -186,22 +185,19 @@ __global__ __launch_bounds__(64) void leg_state_msgs_kernel(double2 *__restrict_
   using At = LegMsgAt;
   constexpr int rpw = 64 / L;
   __shared__ double2 strip[64 * kMsgStrip / 2];
-  const int lane = threadIdx.x;
-  const int64_t w = first / rpw + blockIdx.x;
-  const int gi = lane / L, leg = lane - gi * L;
-  const int64_t rob = w * rpw + gi, end = first + count;
-  const bool live = gi < rpw && rob >= first && rob < end;
+  const RowGroup<L> rg(first, first + count);
+  const int lane = rg.lane, leg = rg.leg;
+  const int64_t rob = rg.rob;
   // lanes [lane0, lane0 + n_rec) hold the records out[rec0 ..] of this block
-  const int64_t rob_lo = w * rpw > first ? w * rpw : first, rob_hi = (w + 1) * rpw < end ? (w + 1) * rpw : end;
-  const int lane0 = int(rob_lo - w * rpw) * L, n_rec = int(rob_hi - rob_lo) * L;
-  const int64_t rec0 = (rob_lo - first) * L;
+  const int lane0 = rg.g0 * L, n_rec = rg.n_rob * L;
+  const int64_t rec0 = (rg.rob_lo - first) * L;
 
   double rec[kMsgDoubles];
 #pragma unroll
   for (int k = 0; k < kMsgDoubles; ++k) rec[k] = 0.0;
-  if (live) {
+  if (rg.live) {
     const double2 *planes = reinterpret_cast<const double2 *>(st.legd);
-    const int64_t slot = w * 64 + lane;
+    const int64_t slot = rg.slot;
     const int word = st.legi[slot];
     {
       double v[2 * NJ + 3]; // Q, QD, TIP are consecutive fields
@@ -293,8 +289,7 @@ extern "C" int shc_engine_get_leg_state_msgs(shc_engine *e, int64_t first, int64
   shc_leg_state_msg *d = msgs;
   if (!on_device) HIP_TRY(hipMalloc(&d, bytes));
   const LegMsgArgs args = leg_msg_args(e->params, e->tables);
-  const int rpw = 64 / e->L;
-  const unsigned grid = (unsigned)((first + count - 1) / rpw - first / rpw + 1);
+  const unsigned grid = row_grid(e->L, first, first + count);
   rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
     constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
     leg_state_msgs_kernel<L, NJ><<<dim3(grid), dim3(64), 0, e->stream>>>(reinterpret_cast<double2 *>(d), e->st, (const SharedConsts<L, NJ> *)e->d_consts, args, first, count);

@@ -13,115 +13,56 @@ constexpr int kObsFields = SHC_OBS_FIELD_COUNT;
 static_assert(kObsFields <= 32, "the selected fields are one 32-bit mask");
 static_assert(sizeof(shc_obs_spec) == 4 * (1 + SHC_OBS_MAX_FIELDS + 4) + 4 + 16, "shc_obs_spec: 37 int32, 4 bytes of alignment, row_stride, pad");
 
-static bool obs_per_leg(int field) { return field < SHC_OBS_BODY_POSE; }
-// columns per leg (per-leg fields) or per robot
-static int obs_field_width(int field, int dof) {
-  switch (field) {
-    case SHC_OBS_Q: case SHC_OBS_QD: case SHC_OBS_JOINT_EFFORT: return dof;
-    case SHC_OBS_WALKER_TIP: case SHC_OBS_TARGET_TIP: case SHC_OBS_POSER_TIP: case SHC_OBS_MODEL_TIP: case SHC_OBS_TIP_FORCE: case SHC_OBS_ADMITTANCE_DELTA: return 3;
-    case SHC_OBS_BODY_POSE: case SHC_OBS_ODOM_TO_BASE_LINK: return 7;
-    case SHC_OBS_DESIRED_VELOCITY: case SHC_OBS_POSE_EULER: return 3;
-    default: return 1;
+// shc_obs_spec for row_layout (shc_rows.hpp)
+struct ObsRows {
+  using Spec = shc_obs_spec;
+  static constexpr const char *name = "shc_obs_spec", *n_fields_why = ".n_fields outside 1 .. SHC_OBS_MAX_FIELDS";
+  static constexpr int fields = kObsFields, most_fields = SHC_OBS_MAX_FIELDS;
+  static constexpr bool has_dof = true;
+  static bool per_leg(int field) { return field < SHC_OBS_BODY_POSE; }
+  static int width(int field, int dof) {
+    switch (field) {
+      case SHC_OBS_Q: case SHC_OBS_QD: case SHC_OBS_JOINT_EFFORT: return dof;
+      case SHC_OBS_WALKER_TIP: case SHC_OBS_TARGET_TIP: case SHC_OBS_POSER_TIP: case SHC_OBS_MODEL_TIP: case SHC_OBS_TIP_FORCE: case SHC_OBS_ADMITTANCE_DELTA: return 3;
+      case SHC_OBS_BODY_POSE: case SHC_OBS_ODOM_TO_BASE_LINK: return 7;
+      case SHC_OBS_DESIRED_VELOCITY: case SHC_OBS_POSE_EULER: return 3;
+      default: return 1;
+    }
   }
-}
-// A spec resolved: the first column of every field (-1: not selected), the selected fields as a mask, the columns of a row.
-struct ObsLayout {
-  int32_t col[kObsFields];
-  uint32_t mask;
-  int64_t width;
+  static const char *own(const Spec *) { return nullptr; }
 };
-// nullptr when the spec is valid on its own (no engine asked yet), else what is wrong with it
-static const char *obs_layout(const shc_obs_spec *s, ObsLayout &lay) {
-  if (!s) return "spec is NULL";
-  if (s->n_fields < 1 || s->n_fields > SHC_OBS_MAX_FIELDS) return "shc_obs_spec.n_fields outside 1 .. SHC_OBS_MAX_FIELDS";
-  if (s->dtype != SHC_OBS_F64 && s->dtype != SHC_OBS_F32) return "shc_obs_spec.dtype is neither SHC_OBS_F64 nor SHC_OBS_F32";
-  if (s->reserved != 0) return "shc_obs_spec.reserved must be 0";
-  if (s->legs < 1 || s->legs > SHC_MAX_LEGS || s->dof < 1 || s->dof > SHC_MAX_JOINTS) return "shc_obs_spec.legs / dof outside 1 .. SHC_MAX_LEGS / SHC_MAX_JOINTS";
-  for (int f = 0; f < kObsFields; ++f) lay.col[f] = -1;
-  lay.mask = 0, lay.width = 0;
-  for (int i = 0; i < s->n_fields; ++i) {
-    const int f = s->fields[i];
-    if (f < 0 || f >= kObsFields) return "shc_obs_spec.fields names an unknown field";
-    if (lay.mask & (1u << f)) return "shc_obs_spec.fields names a field twice";
-    lay.mask |= 1u << f;
-    lay.col[f] = int32_t(lay.width);
-    lay.width += obs_field_width(f, s->dof) * (obs_per_leg(f) ? s->legs : 1);
-  }
-  if (s->row_stride != 0 && s->row_stride < lay.width) return "shc_obs_spec.row_stride is below the width of a row";
-  return nullptr;
-}
 
-extern "C" int64_t shc_obs_width(const shc_obs_spec *spec) {
-  ObsLayout lay;
-  const char *why = obs_layout(spec, lay);
-  if (why) return -int64_t(fail(SHC_ERR_INVALID_ARG, why));
-  return lay.width;
-}
-extern "C" int shc_obs_column(const shc_obs_spec *spec, int field, int leg, int k) {
-  ObsLayout lay;
-  if (obs_layout(spec, lay) || field < 0 || field >= kObsFields || lay.col[field] < 0) return -1;
-  const int w = obs_field_width(field, spec->dof);
-  if (k < 0 || k >= w) return -1;
-  if (!obs_per_leg(field)) return lay.col[field] + k;
-  if (leg < 0 || leg >= spec->legs) return -1;
-  return lay.col[field] + leg * w + k;
-}
+extern "C" int64_t shc_obs_width(const shc_obs_spec *spec) { return row_width<ObsRows>(spec); }
+extern "C" int shc_obs_column(const shc_obs_spec *spec, int field, int leg, int k) { return row_column<ObsRows>(spec, field, leg, k); }
 
-// The kernel's view of a spec (launch-uniform: scalar loads of the kernel arguments)
-struct ObsArgs {
-  uint32_t mask;
-  int32_t col[kObsFields];
-  int32_t dof;                      // columns per leg of the joint fields
-  int32_t width, pitch;             // columns of a row; elements between the rows of the LDS tile
-  int32_t has_pad;                  // the row has columns of legs / joints the morphology lacks
+// The kernel's view of a spec
+struct ObsArgs : RowArgs<kObsFields> {
+  int32_t dof;                       // columns per leg of the joint fields
   int32_t derive_poser, keep_marked; // derive_tips' two facts
   int32_t have_odom;
-  int64_t row_stride;
-  double pad;                       // already rounded to the element type
 };
 
-// One leg per lane, floor(64 / L) robots per wavefront (the mapping of leg_state_msgs_kernel: every plane read is contiguous across the
-// wavefront); one wavefront per workgroup.  Block b serves the robot group first / rpw + b, clipped to [first, first + count).
-//
-// Output.  A robot's row is contiguous in `out`, its columns are spread over the robot's lanes (leg l of a per-leg field at l * width + k).  The
-// wavefront therefore builds its rows in LDS - `tile`, rpw rows of `pitch` elements of T - and copies them out with consecutive lanes on
-// consecutive elements of a row: the lanes run through the tile's rows one after the other, so a 64-lane store covers 64 consecutive elements
-// of one row or the end of one and the start of the next (two contiguous runs).  Rows go to out[row * row_stride]: row = ids[robot] (the
-// caller's instance id of a fleet part's robot) or robot - first.
-// LDS.  The lanes' element stores are ds_write_b32 / ds_write_b64: banks are (address / 4) mod 32, per 32 (b32) or 16 (b64) contiguous lanes.
-// Within a robot the lanes are `w` elements apart (w = 1, 3 or dof), robots `pitch` elements: pitch is made odd, so that for 4-byte elements
-// the robots of a lane group start on distinct banks and the 3-column fields of a hexapod's legs (0, 3, .. 15) interleave with them - at
-// most 2-way, which a store does not pay for; 8-byte elements use the even banks only and can meet 2- to 4-way.  The copy-out reads
-// consecutive elements (conflict-free but for the seam between two rows).  The tile is at most 21 rows x 349 x 8 B = 57 KiB (3 legs, every
-// field, 8 x 6 row geometry); the learner-sized selection of a hexapod is 10 x 77 x 4 B = 3.0 KiB.
-// With has_pad the tile is filled with `pad` first, so the columns no lane owns are defined.
+// The geometry and the tile of shc_rows.hpp, copy-out: the lanes build their robots' rows in the tile (filled with `pad` first where the row has
+// columns no lane owns), and the rows leave with consecutive lanes on consecutive elements, for out[row * row_stride]: row = ids[robot] or
+// robot - first.  The tile is at most 21 rows x 349 x 8 B = 57 KiB (3 legs, every field, 8 x 6 row geometry); the learner-sized selection of a
+// hexapod is 10 x 77 x 4 B = 3.0 KiB.
 template <int L, int NJ, class T>
 __global__ __launch_bounds__(64) void observe_kernel(T *__restrict__ out, DevState st, const SharedConsts<L, NJ> *__restrict__ gc, const LegMsgArgs a,
                                                      const ObsArgs o, const int64_t *__restrict__ ids, int64_t first, int64_t count) {
   using FD = Fields<NJ>;
   using R = RobotFields;
   constexpr int rpw = 64 / L;
-  extern __shared__ double2 obs_tile[];
-  T *tile = reinterpret_cast<T *>(obs_tile);
-  const int lane = threadIdx.x;
-  const int64_t w = first / rpw + blockIdx.x;
-  const int gi = lane / L, leg = lane - gi * L;
-  const int64_t rob = w * rpw + gi, end = first + count;
-  const bool live = gi < rpw && rob >= first && rob < end;
-  // groups [g0, g0 + n_rob) hold the rows of robots rob_lo .. of this block
-  const int64_t rob_lo = w * rpw > first ? w * rpw : first, rob_hi = (w + 1) * rpw < end ? (w + 1) * rpw : end;
-  const int g0 = int(rob_lo - w * rpw), n_rob = int(rob_hi - rob_lo);
+  const RowGroup<L> rg(first, first + count);
+  const int gi = rg.gi, leg = rg.leg;
+  const int64_t rob = rg.rob;
+  T *tile = row_tile<T>();
 
-  if (o.has_pad) {
-    const T pad = static_cast<T>(o.pad);
-    for (int c = lane; c < rpw * o.pitch; c += 64) tile[c] = pad;
-    __syncthreads();
-  }
-  if (live) {
+  row_tile_pad(tile, rg, o);
+  if (rg.live) {
     T *row = tile + gi * o.pitch;
     auto sel = [&](int f) { return (o.mask >> f & 1u) != 0; };
     const double2 *planes = reinterpret_cast<const double2 *>(st.legd);
-    const int64_t slot = w * 64 + lane;
+    const int64_t slot = rg.slot;
     if (sel(SHC_OBS_Q) || sel(SHC_OBS_MODEL_TIP)) {
       double q[NJ]; // Joint::desired_position_
       load_leg_fields<FD::Q, NJ>(planes, st.n_slots, slot, q);
@@ -237,20 +178,11 @@ __global__ __launch_bounds__(64) void observe_kernel(T *__restrict__ out, DevSta
     }
   }
   __syncthreads();
-  // copy-out: element e = lane, lane + 64, .. of the block's n_rob x width elements; (r, c) follow by addition - 64 = dq * width + dr
-  const int total = n_rob * o.width, dq = 64 / o.width, dr = 64 - dq * o.width;
-  int r = lane / o.width, c = lane - r * o.width;
-  for (int e = lane; e < total; e += 64) {
-    const int64_t rr = rob_lo + r;
-    const int64_t orow = ids ? ids[rr] : rr - first;
-    out[orow * o.row_stride + c] = tile[(g0 + r) * o.pitch + c];
-    r += dq, c += dr;
-    if (c >= o.width) c -= o.width, ++r;
-  }
+  row_tile_out(out, tile, rg, o, ids, first);
 }
 
 // What an engine refuses of a spec that is valid on its own
-static int observe_check(const shc_engine *e, const shc_obs_spec *spec, const ObsLayout &lay) {
+static int observe_check(const shc_engine *e, const shc_obs_spec *spec, const RowLayout &lay) {
   if (spec->legs < e->L || spec->dof < e->NJ) return fail(SHC_ERR_INVALID_ARG, "shc_obs_spec.legs / dof are below the engine's legs / longest leg's DOF");
   if ((lay.mask & (1u << SHC_OBS_ODOM_TO_BASE_LINK)) && !e->cp.odometry)
     return fail(SHC_ERR_UNSUPPORTED, "SHC_FEAT_ODOMETRY is off: odom_to_base_link needs the ideal odometry");
@@ -258,25 +190,18 @@ static int observe_check(const shc_engine *e, const shc_obs_spec *spec, const Ob
     return fail(SHC_ERR_UNSUPPORTED, "admittance_control is off: updateStiffness never runs");
   return SHC_OK;
 }
-static size_t obs_element_bytes(const shc_obs_spec *spec) { return spec->dtype == SHC_OBS_F32 ? 4 : 8; }
 
 // The launch on the engine's stream: instances [first, first + count) into rows ids[instance] (ids != NULL, a device table) or instance - first
 // of the device array `out`.  The caller has checked everything and joined split steps.
-static int observe_launch(shc_engine *e, const shc_obs_spec *spec, const ObsLayout &lay, void *out, int64_t row_stride, const int64_t *ids, int64_t first, int64_t count) {
+static int observe_launch(shc_engine *e, const shc_obs_spec *spec, const RowLayout &lay, void *out, int64_t row_stride, const int64_t *ids, int64_t first, int64_t count) {
   ObsArgs o{};
-  o.mask = lay.mask;
-  for (int f = 0; f < kObsFields; ++f) o.col[f] = lay.col[f];
+  row_args(o, lay, spec->dtype, row_stride, spec->legs > e->L || spec->dof > e->NJ, spec->pad);
   o.dof = spec->dof;
-  o.width = int32_t(lay.width), o.pitch = int32_t(lay.width) | 1;
-  o.has_pad = spec->legs > e->L || spec->dof > e->NJ;
   o.derive_poser = derive_poser_tips(e), o.keep_marked = keep_marked_poser_tips(e);
   o.have_odom = e->cp.odometry ? 1 : 0;
-  o.row_stride = row_stride;
-  o.pad = spec->dtype == SHC_OBS_F32 ? double(static_cast<float>(spec->pad)) : spec->pad;
   const LegMsgArgs args = leg_msg_args(e->params, e->tables);
-  const int rpw = 64 / e->L;
-  const unsigned grid = (unsigned)((first + count - 1) / rpw - first / rpw + 1);
-  const size_t lds = size_t(rpw) * o.pitch * obs_element_bytes(spec);
+  const unsigned grid = row_grid(e->L, first, first + count);
+  const size_t lds = row_tile_bytes(e->L, o.pitch, spec->dtype);
   const int rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
     constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
     const SharedConsts<L, NJ> *gc = (const SharedConsts<L, NJ> *)e->d_consts;
@@ -294,27 +219,16 @@ static int observe_launch(shc_engine *e, const shc_obs_spec *spec, const ObsLayo
 extern "C" int shc_engine_get_observations(shc_engine *e, int64_t first, int64_t count, const shc_obs_spec *spec, void *out, int on_device) {
   SHC_ENTER_JOINED(e);
   if (!spec || !out) return fail(SHC_ERR_INVALID_ARG, "spec or out is NULL");
-  ObsLayout lay;
-  if (const char *why = obs_layout(spec, lay)) return fail(SHC_ERR_INVALID_ARG, why);
+  RowLayout lay;
+  if (const int bad = row_resolve<ObsRows>(spec, lay)) return bad;
   int rc = observe_check(e, spec, lay);
   if (rc != SHC_OK) return rc;
   if (first < 0 || count < 0 || first > e->n || count > e->n - first) return fail(SHC_ERR_INVALID_ARG, "instance range out of bounds");
-  const size_t es = obs_element_bytes(spec);
-  if (reinterpret_cast<uintptr_t>(out) & (es - 1)) return fail(SHC_ERR_INVALID_ARG, "out must be aligned to its element size");
+  if ((rc = row_aligned(out, spec->dtype, "out")) != SHC_OK) return rc;
   if (count == 0) return SHC_OK;
   HIP_TRY(hipSetDevice(e->device));
-  const int64_t stride = spec->row_stride ? spec->row_stride : lay.width;
+  const int64_t stride = row_stride_of(spec, lay);
   if (on_device) return observe_launch(e, spec, lay, out, stride, nullptr, first, count);
-  // host form: dense rows on the device, then the columns [0, width) of every row of the caller's array
-  void *d = nullptr;
-  const size_t row_bytes = size_t(lay.width) * es;
-  HIP_TRY(hipMalloc(&d, size_t(count) * row_bytes));
-  rc = observe_launch(e, spec, lay, d, lay.width, nullptr, first, count);
-  hipError_t err = hipSuccess;
-  if (rc == SHC_OK) err = hipMemcpy2DAsync(out, size_t(stride) * es, d, row_bytes, row_bytes, size_t(count), hipMemcpyDeviceToHost, e->stream);
-  if (rc == SHC_OK && err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  (void)hipFree(d);
-  if (rc != SHC_OK) return rc;
-  if (err != hipSuccess) return fail(SHC_ERR_HIP, std::string("observations: ") + hipGetErrorString(err));
-  return SHC_OK;
+  return rows_to_host(e, "observations", out, count, lay.width, stride, spec->dtype,
+                      [&](void *d) { return observe_launch(e, spec, lay, d, lay.width, nullptr, first, count); });
 }

@@ -11,7 +11,7 @@ import os
 import time
 import subprocess
 import sys
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -132,17 +132,20 @@ class FleetOutputs(C.Structure):
                                                                                                                  ("criteria", C.POINTER(HealthCriteria))]
 
 
-# The observation pass (include/shc_batch.h, "Observation pass"): SHC_OBS_* by name, in the order of the enum
+# The row passes (include/shc_batch.h: "Observation pass", "Action pass", "Foothold pass"): SHC_OBS_* / SHC_ACT_* / SHC_FH_* by name, in the order
+# of the enums
 OBS_FIELD_NAMES = ("q", "qd", "joint_effort", "walker_tip", "target_tip", "poser_tip", "model_tip", "tip_force", "admittance_delta", "virtual_stiffness",
                    "stance_progress", "swing_progress", "time_to_swing_end", "step_state",
                    "body_pose", "desired_velocity", "pose_euler", "odom_to_base_link", "walk_state")
 OBS_FIELDS = {name: i for i, name in enumerate(OBS_FIELD_NAMES)}
 OBS_MAX_FIELDS = 32
 OBS_DTYPES = {"float64": 0, "float32": 1}  # SHC_OBS_F64 / SHC_OBS_F32
-_OBS_ROBOT_WIDTH = {"body_pose": 7, "desired_velocity": 3, "pose_euler": 3, "odom_to_base_link": 7, "walk_state": 1}
-_OBS_JOINT_FIELDS = ("q", "qd", "joint_effort")
-_OBS_LEG_WIDTH = {"walker_tip": 3, "target_tip": 3, "poser_tip": 3, "model_tip": 3, "tip_force": 3, "admittance_delta": 3, "virtual_stiffness": 1,
-                  "stance_progress": 1, "swing_progress": 1, "time_to_swing_end": 1, "step_state": 1}
+ACT_FIELD_NAMES = ("linear_xy", "angular", "imu_orientation", "imu_angular_velocity", "pose_translation_velocity", "pose_rotation_velocity", "tip_force",
+                   "joint_effort")
+ACT_FIELDS = {name: i for i, name in enumerate(ACT_FIELD_NAMES)}
+FH_FIELD_NAMES = ("position", "rotation", "transform", "swing_clearance", "frame_is_odom_ideal", "defined")  # every field is per leg
+FH_FIELDS = {name: i for i, name in enumerate(FH_FIELD_NAMES)}
+FH_MODES = {"request": 0, "refresh_transform": 1}  # SHC_FH_REQUEST / SHC_FH_REFRESH_TRANSFORM
 
 
 class ObsSpec(C.Structure):
@@ -151,48 +154,143 @@ class ObsSpec(C.Structure):
                 ("reserved", C.c_int32), ("row_stride", C.c_int64), ("pad", C.c_double)]
 
 
+class ActSpec(C.Structure):
+    """shc_act_spec: which input groups, in which order, as which element type, for which row geometry."""
+    _fields_ = [("n_fields", C.c_int32), ("fields", C.c_int32 * len(ACT_FIELD_NAMES)), ("dtype", C.c_int32), ("legs", C.c_int32), ("dof", C.c_int32),
+                ("reserved", C.c_int32), ("row_stride", C.c_int64)]
+
+
+class FootholdSpec(C.Structure):
+    """shc_foothold_spec: which members of the requests, in which order, as which element type, for which row geometry, record and mode."""
+    _fields_ = [("n_fields", C.c_int32), ("fields", C.c_int32 * len(FH_FIELD_NAMES)), ("dtype", C.c_int32), ("legs", C.c_int32), ("which", C.c_int32),
+                ("mode", C.c_int32), ("reserved", C.c_int32), ("row_stride", C.c_int64), ("pad", C.c_double)]
+
+
+class _RowPass(NamedTuple):
+    """What tells one row pass from another on this side: names in enum order and their enum values, columns of the per-robot fields, columns
+    per leg of the per-leg fields, the per-leg fields of ``dof`` columns, the ctypes struct and the library's width / column functions."""
+    names: tuple
+    index: dict
+    robot: dict
+    leg: dict
+    joint: tuple
+    struct: type
+    width: str
+    column: str
+
+
+_ROW_PASSES = {
+    "observation": _RowPass(OBS_FIELD_NAMES, OBS_FIELDS, {"body_pose": 7, "desired_velocity": 3, "pose_euler": 3, "odom_to_base_link": 7, "walk_state": 1},
+                            {"walker_tip": 3, "target_tip": 3, "poser_tip": 3, "model_tip": 3, "tip_force": 3, "admittance_delta": 3, "virtual_stiffness": 1,
+                             "stance_progress": 1, "swing_progress": 1, "time_to_swing_end": 1, "step_state": 1},
+                            ("q", "qd", "joint_effort"), ObsSpec, "shc_obs_width", "shc_obs_column"),
+    "action": _RowPass(ACT_FIELD_NAMES, ACT_FIELDS, {"linear_xy": 2, "angular": 1, "imu_orientation": 4, "imu_angular_velocity": 3,
+                                                     "pose_translation_velocity": 3, "pose_rotation_velocity": 3},
+                       {"tip_force": 3}, ("joint_effort",), ActSpec, "shc_act_width", "shc_act_column"),
+    "foothold": _RowPass(FH_FIELD_NAMES, FH_FIELDS, {}, {"position": 3, "rotation": 4, "transform": 7, "swing_clearance": 1, "frame_is_odom_ideal": 1,
+                                                         "defined": 1}, (), FootholdSpec, "shc_foothold_width", "shc_foothold_column"),
+}
+
+
+def _row_spec(kind: str, fields, dtype, row_stride):
+    """The spec struct of a list of field names or enum integers, but for the members of its own that the caller sets (this runs once per call of
+    a pass: no more work than the assignments).  Nothing is checked here: the library judges the spec."""
+    p = _ROW_PASSES[kind]
+    index = p.index
+    ids = [index[f] if isinstance(f, str) else int(f) for f in fields]
+    st = p.struct()
+    st.n_fields = len(ids)
+    head = ids[:p.struct.fields.size // 4]
+    st.fields[:len(head)] = head
+    st.dtype = OBS_DTYPES[np.dtype(dtype).name] if not isinstance(dtype, int) else dtype
+    st.row_stride = int(row_stride)
+    return st
+
+
+def _row_columns(kind: str, fields, legs: int, dof: int):
+    """({name: slice}, width) of a row of the pass for the row geometry (legs, dof): a per-leg field's slice reshapes to (legs, width per leg),
+    leg-major.  Computed here and checked against the library's own answer (its width and column functions)."""
+    p, legs = _ROW_PASSES[kind], int(legs)
+    names = [f if isinstance(f, str) else p.names[int(f)] for f in fields]
+    cols, at = {}, 0
+    for name in names:
+        if name in cols:
+            raise ValueError(f"{kind} field {name!r} is named twice")
+        if name not in p.names:
+            raise ValueError(f"unknown {kind} field {name!r} (one of {', '.join(p.names)})")
+        w = p.robot[name] if name in p.robot else legs * (int(dof) if name in p.joint else p.leg[name])
+        cols[name] = slice(at, at + w)
+        at += w
+    L, spec = lib(), _row_spec(kind, names, "float32", 0)
+    spec.legs = legs
+    if p.joint:
+        spec.dof = int(dof)
+    column = getattr(L, p.column)
+    width = int(getattr(L, p.width)(C.byref(spec)))
+    if width < 0:
+        msg = L.shc_last_error()
+        raise ValueError(f"{kind} spec refused: {msg.decode() if msg else ''}")
+    for name, sl in cols.items():
+        last = (0, sl.stop - sl.start - 1) if name in p.robot else (legs - 1, (sl.stop - sl.start) // legs - 1)
+        if width != at or column(C.byref(spec), p.index[name], 0, 0) != sl.start or column(C.byref(spec), p.index[name], *last) != sl.stop - 1:
+            raise ShcError(f"{kind}_columns and the library disagree on {name!r}")
+    return cols, at
+
+
 def obs_spec(fields, legs: int, dof: int, dtype="float32", row_stride: int = 0, pad: float = 0.0) -> ObsSpec:
     """The shc_obs_spec of a list of field names (OBS_FIELDS) or SHC_OBS_* integers.  Nothing is checked here: the library judges the spec."""
-    ids = [OBS_FIELDS[f] if isinstance(f, str) else int(f) for f in fields]
-    st = ObsSpec()
-    st.n_fields = len(ids)
-    for i, f in enumerate(ids[:OBS_MAX_FIELDS]):
-        st.fields[i] = f
-    st.dtype = OBS_DTYPES[np.dtype(dtype).name] if not isinstance(dtype, int) else dtype
-    st.legs, st.dof, st.row_stride, st.pad = int(legs), int(dof), int(row_stride), float(pad)
+    st = _row_spec("observation", fields, dtype, row_stride)
+    st.legs, st.dof, st.pad = int(legs), int(dof), float(pad)
     return st
 
 
 def observation_columns(fields, legs: int, dof: int):
     """({name: slice}, width) of a row of observations(fields) for the row geometry (legs, dof): a per-leg field's slice reshapes to (legs, width
     per leg), leg-major.  Computed here and checked against the library's own answer (shc_obs_width / shc_obs_column)."""
-    names = [f if isinstance(f, str) else OBS_FIELD_NAMES[int(f)] for f in fields]
-    cols, at = {}, 0
-    for name in names:
-        if name in cols:
-            raise ValueError(f"observation field {name!r} is named twice")
-        if name not in OBS_FIELDS:
-            raise ValueError(f"unknown observation field {name!r} (one of {', '.join(OBS_FIELD_NAMES)})")
-        w = _OBS_ROBOT_WIDTH[name] if name in _OBS_ROBOT_WIDTH else int(legs) * (int(dof) if name in _OBS_JOINT_FIELDS else _OBS_LEG_WIDTH[name])
-        cols[name] = slice(at, at + w)
-        at += w
-    L, spec = lib(), obs_spec(names, legs, dof)
-    width = int(L.shc_obs_width(C.byref(spec)))
-    if width < 0:
-        msg = L.shc_last_error()
-        raise ValueError(f"observation spec refused: {msg.decode() if msg else ''}")
-    for name, sl in cols.items():
-        per_leg = name not in _OBS_ROBOT_WIDTH
-        last = (int(legs) - 1, (sl.stop - sl.start) // int(legs) - 1) if per_leg else (0, sl.stop - sl.start - 1)
-        if width != at or L.shc_obs_column(C.byref(spec), OBS_FIELDS[name], 0, 0) != sl.start or L.shc_obs_column(C.byref(spec), OBS_FIELDS[name], *last) != sl.stop - 1:
-            raise ShcError(f"observation_columns and the library disagree on {name!r}")
-    return cols, at
+    return _row_columns("observation", fields, legs, dof)
 
 
-def _observation_target(out, what: str):
-    """(pointer, numpy dtype, rows, columns, row stride in elements) of a 2-D float32 / float64 device array whose rows are contiguous - a view
-    of some columns of a wider array included."""
-    cai = getattr(out, "__cuda_array_interface__", None)
+def act_spec(fields, legs: int, dof: int, dtype="float32", row_stride: int = 0) -> ActSpec:
+    """The shc_act_spec of a list of field names (ACT_FIELDS) or SHC_ACT_* integers.  Nothing is checked here: the library judges the spec."""
+    st = _row_spec("action", fields, dtype, row_stride)
+    st.legs, st.dof = int(legs), int(dof)
+    return st
+
+
+def action_columns(fields, legs: int, dof: int):
+    """({name: slice}, width) of a row of set_actions(fields) for the row geometry (legs, dof): the slice of tip_force reshapes to (legs, 3), that
+    of joint_effort to (legs, dof), leg-major.  Computed here and checked against the library's own answer (shc_act_width / shc_act_column)."""
+    return _row_columns("action", fields, legs, dof)
+
+
+def foothold_spec(fields, legs: int, dtype="float32", which: int = 0, mode="request", row_stride: int = 0, pad: float = 0.0) -> FootholdSpec:
+    """The shc_foothold_spec of a list of field names (FH_FIELDS) or SHC_FH_* integers.  Nothing is checked here: the library judges the spec."""
+    st = _row_spec("foothold", fields, dtype, row_stride)
+    st.legs, st.which, st.mode, st.pad = int(legs), int(which), FH_MODES[mode] if isinstance(mode, str) else int(mode), float(pad)
+    return st
+
+
+def foothold_columns(fields, legs: int):
+    """({name: slice}, width) of a row of set_footholds(fields) / footholds(fields) for a row geometry of ``legs`` legs: a field's slice reshapes
+    to (legs, width per leg), leg-major.  Computed here and checked against the library's own answer (shc_foothold_width / shc_foothold_column)."""
+    return _row_columns("foothold", fields, legs, 0)
+
+
+def _rows_array(a, what: str, host: Optional[str] = None):
+    """(pointer, numpy dtype, rows, columns, row stride in elements, on_device, the array that owns a host pointer) of a 2-D float32 / float64
+    array whose rows are contiguous - a view of some columns of a wider array included: a device array (``__cuda_array_interface__``) or, with
+    host = "view", a numpy array as it is, with host = "copy", a contiguous copy of one that is not."""
+    if host and isinstance(a, np.ndarray):
+        if a.ndim != 2 or a.dtype not in (np.float32, np.float64):
+            raise ValueError(f"{what}: a 2-D float32 or float64 array is expected, got {a.dtype} {a.shape}")
+        if host == "copy":
+            a = np.ascontiguousarray(a)
+        size = a.dtype.itemsize
+        if (a.shape[1] > 1 and a.strides[1] != size) or (a.shape[0] > 1 and (a.strides[0] % size or a.strides[0] < a.shape[1] * size)):
+            raise ValueError(f"{what}: the elements of a row must be contiguous and the rows a whole number of elements apart (strides {a.strides})")
+        stride = a.strides[0] // size if a.shape[0] > 1 else a.shape[1]
+        return a.ctypes.data_as(C.c_void_p), a.dtype, a.shape[0], a.shape[1], stride, 0, a
+    cai = getattr(a, "__cuda_array_interface__", None)
     if cai is None:
         raise ValueError(f"{what}: a device array (an object with __cuda_array_interface__) is expected")
     if cai["typestr"] not in ("<f4", "<f8") or len(cai["shape"]) != 2:
@@ -202,122 +300,13 @@ def _observation_target(out, what: str):
     strides = cai.get("strides") or (columns * dt.itemsize, dt.itemsize)
     if strides[1] != dt.itemsize or strides[0] % dt.itemsize or strides[0] < columns * dt.itemsize:
         raise ValueError(f"{what}: the elements of a row must be contiguous and the rows a whole number of elements apart (strides {tuple(strides)})")
-    return C.c_void_p(cai["data"][0]), dt, rows, columns, strides[0] // dt.itemsize
+    return C.c_void_p(cai["data"][0]), dt, rows, columns, strides[0] // dt.itemsize, 1, None
 
 
-# The action pass (include/shc_batch.h, "Action pass"): SHC_ACT_* by name, in the order of the enum
-ACT_FIELD_NAMES = ("linear_xy", "angular", "imu_orientation", "imu_angular_velocity", "pose_translation_velocity", "pose_rotation_velocity", "tip_force",
-                   "joint_effort")
-ACT_FIELDS = {name: i for i, name in enumerate(ACT_FIELD_NAMES)}
-_ACT_ROBOT_WIDTH = {"linear_xy": 2, "angular": 1, "imu_orientation": 4, "imu_angular_velocity": 3, "pose_translation_velocity": 3, "pose_rotation_velocity": 3}
-
-
-class ActSpec(C.Structure):
-    """shc_act_spec: which input groups, in which order, as which element type, for which row geometry."""
-    _fields_ = [("n_fields", C.c_int32), ("fields", C.c_int32 * len(ACT_FIELD_NAMES)), ("dtype", C.c_int32), ("legs", C.c_int32), ("dof", C.c_int32),
-                ("reserved", C.c_int32), ("row_stride", C.c_int64)]
-
-
-def act_spec(fields, legs: int, dof: int, dtype="float32", row_stride: int = 0) -> ActSpec:
-    """The shc_act_spec of a list of field names (ACT_FIELDS) or SHC_ACT_* integers.  Nothing is checked here: the library judges the spec."""
-    ids = [ACT_FIELDS[f] if isinstance(f, str) else int(f) for f in fields]
-    st = ActSpec()
-    st.n_fields = len(ids)
-    for i, f in enumerate(ids[:len(ACT_FIELD_NAMES)]):
-        st.fields[i] = f
-    st.dtype = OBS_DTYPES[np.dtype(dtype).name] if not isinstance(dtype, int) else dtype
-    st.legs, st.dof, st.row_stride = int(legs), int(dof), int(row_stride)
-    return st
-
-
-def action_columns(fields, legs: int, dof: int):
-    """({name: slice}, width) of a row of set_actions(fields) for the row geometry (legs, dof): the slice of tip_force reshapes to (legs, 3), that
-    of joint_effort to (legs, dof), leg-major.  Computed here and checked against the library's own answer (shc_act_width / shc_act_column)."""
-    names = [f if isinstance(f, str) else ACT_FIELD_NAMES[int(f)] for f in fields]
-    cols, at = {}, 0
-    for name in names:
-        if name in cols:
-            raise ValueError(f"action field {name!r} is named twice")
-        if name not in ACT_FIELDS:
-            raise ValueError(f"unknown action field {name!r} (one of {', '.join(ACT_FIELD_NAMES)})")
-        w = _ACT_ROBOT_WIDTH[name] if name in _ACT_ROBOT_WIDTH else int(legs) * (int(dof) if name == "joint_effort" else 3)
-        cols[name] = slice(at, at + w)
-        at += w
-    L, spec = lib(), act_spec(names, legs, dof)
-    width = int(L.shc_act_width(C.byref(spec)))
-    if width < 0:
-        msg = L.shc_last_error()
-        raise ValueError(f"action spec refused: {msg.decode() if msg else ''}")
-    for name, sl in cols.items():
-        per_leg = name not in _ACT_ROBOT_WIDTH
-        last = (int(legs) - 1, (sl.stop - sl.start) // int(legs) - 1) if per_leg else (0, sl.stop - sl.start - 1)
-        if width != at or L.shc_act_column(C.byref(spec), ACT_FIELDS[name], 0, 0) != sl.start or L.shc_act_column(C.byref(spec), ACT_FIELDS[name], *last) != sl.stop - 1:
-            raise ShcError(f"action_columns and the library disagree on {name!r}")
-    return cols, at
-
-
-# The foothold pass (include/shc_batch.h, "Foothold pass"): SHC_FH_* by name, in the order of the enum; every field is per leg
-FH_FIELD_NAMES = ("position", "rotation", "transform", "swing_clearance", "frame_is_odom_ideal", "defined")
-FH_FIELDS = {name: i for i, name in enumerate(FH_FIELD_NAMES)}
-FH_MODES = {"request": 0, "refresh_transform": 1}  # SHC_FH_REQUEST / SHC_FH_REFRESH_TRANSFORM
-_FH_WIDTH = {"position": 3, "rotation": 4, "transform": 7, "swing_clearance": 1, "frame_is_odom_ideal": 1, "defined": 1}
-
-
-class FootholdSpec(C.Structure):
-    """shc_foothold_spec: which members of the requests, in which order, as which element type, for which row geometry, record and mode."""
-    _fields_ = [("n_fields", C.c_int32), ("fields", C.c_int32 * len(FH_FIELD_NAMES)), ("dtype", C.c_int32), ("legs", C.c_int32), ("which", C.c_int32),
-                ("mode", C.c_int32), ("reserved", C.c_int32), ("row_stride", C.c_int64), ("pad", C.c_double)]
-
-
-def foothold_spec(fields, legs: int, dtype="float32", which: int = 0, mode="request", row_stride: int = 0, pad: float = 0.0) -> FootholdSpec:
-    """The shc_foothold_spec of a list of field names (FH_FIELDS) or SHC_FH_* integers.  Nothing is checked here: the library judges the spec."""
-    ids = [FH_FIELDS[f] if isinstance(f, str) else int(f) for f in fields]
-    st = FootholdSpec()
-    st.n_fields = len(ids)
-    for i, f in enumerate(ids[:len(FH_FIELD_NAMES)]):
-        st.fields[i] = f
-    st.dtype = OBS_DTYPES[np.dtype(dtype).name] if not isinstance(dtype, int) else dtype
-    st.legs, st.which, st.mode = int(legs), int(which), FH_MODES[mode] if isinstance(mode, str) else int(mode)
-    st.row_stride, st.pad = int(row_stride), float(pad)
-    return st
-
-
-def foothold_columns(fields, legs: int):
-    """({name: slice}, width) of a row of set_footholds(fields) / footholds(fields) for a row geometry of ``legs`` legs: a field's slice reshapes
-    to (legs, width per leg), leg-major.  Computed here and checked against the library's own answer (shc_foothold_width / shc_foothold_column)."""
-    names = [f if isinstance(f, str) else FH_FIELD_NAMES[int(f)] for f in fields]
-    cols, at = {}, 0
-    for name in names:
-        if name in cols:
-            raise ValueError(f"foothold field {name!r} is named twice")
-        if name not in FH_FIELDS:
-            raise ValueError(f"unknown foothold field {name!r} (one of {', '.join(FH_FIELD_NAMES)})")
-        cols[name] = slice(at, at + int(legs) * _FH_WIDTH[name])
-        at += int(legs) * _FH_WIDTH[name]
-    L, spec = lib(), foothold_spec(names, legs)
-    width = int(L.shc_foothold_width(C.byref(spec)))
-    if width < 0:
-        msg = L.shc_last_error()
-        raise ValueError(f"foothold spec refused: {msg.decode() if msg else ''}")
-    for name, sl in cols.items():
-        if (width != at or L.shc_foothold_column(C.byref(spec), FH_FIELDS[name], 0, 0) != sl.start
-                or L.shc_foothold_column(C.byref(spec), FH_FIELDS[name], int(legs) - 1, _FH_WIDTH[name] - 1) != sl.stop - 1):
-            raise ShcError(f"foothold_columns and the library disagree on {name!r}")
-    return cols, at
-
-
-def _foothold_rows(rows, what: str):
-    """(pointer, numpy dtype, rows, columns, row stride in elements, on_device, the array that owns a host pointer) of a 2-D float32 / float64
-    array of foothold rows: a numpy array, or a device array (``__cuda_array_interface__``; a view of some columns of a wider one will do)."""
-    if isinstance(rows, np.ndarray):
-        if rows.ndim != 2 or rows.dtype not in (np.float32, np.float64):
-            raise ValueError(f"{what}: a 2-D float32 or float64 array is expected, got {rows.dtype} {rows.shape}")
-        size = rows.dtype.itemsize
-        if (rows.shape[1] > 1 and rows.strides[1] != size) or (rows.shape[0] > 1 and (rows.strides[0] % size or rows.strides[0] < rows.shape[1] * size)):
-            raise ValueError(f"{what}: the elements of a row must be contiguous and the rows a whole number of elements apart (strides {rows.strides})")
-        stride = rows.strides[0] // size if rows.shape[0] > 1 else rows.shape[1]
-        return rows.ctypes.data_as(C.c_void_p), rows.dtype, rows.shape[0], rows.shape[1], stride, 0, rows
-    return _observation_target(rows, what) + (1, None)
+def _check_rows(what: str, name: str, rows: int, columns: int, n: int, width: int):
+    """rows == n and columns >= width (a spec the library refuses, width < 0, is left to the call)"""
+    if rows != n or (width >= 0 and columns < width):
+        raise ValueError(f"{what}: {name} has shape ({rows}, {columns}), {n} rows of at least {width} columns are expected")
 
 
 def _foothold_ignored(ignored, what: str):
@@ -913,18 +902,9 @@ class BatchEngine:
         stream without a host wait and never written - or a numpy array, which is copied to the device and waited for.  legs / dof (default: the
         engine's) may be larger than the robot's: the columns of legs and joints it lacks are ignored."""
         legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
-        if isinstance(actions, np.ndarray):
-            if actions.ndim != 2 or actions.dtype not in (np.float32, np.float64):
-                raise ValueError(f"set_actions: a 2-D float32 or float64 array is expected, got {actions.dtype} {actions.shape}")
-            a = np.ascontiguousarray(actions)
-            ptr, dt, rows, columns, stride, on_device = a.ctypes.data_as(C.c_void_p), a.dtype, a.shape[0], a.shape[1], a.shape[1], 0
-        else:
-            ptr, dt, rows, columns, stride = _observation_target(actions, "set_actions")
-            on_device = 1
+        ptr, dt, rows, columns, stride, on_device, _keep = _rows_array(actions, "set_actions", host="copy")
         spec = act_spec(fields, legs, dof, dt, stride)
-        width = int(self.L.shc_act_width(C.byref(spec)))
-        if rows != self.n or (width >= 0 and columns < width):
-            raise ValueError(f"set_actions: actions has shape ({rows}, {columns}), {self.n} rows of at least {width} columns are expected")
+        _check_rows("set_actions", "actions", rows, columns, self.n, int(self.L.shc_act_width(C.byref(spec))))
         _check(self.L.shc_engine_set_actions(self.h, C.byref(spec), ptr, on_device), "set_actions")
 
     # -- inputs (device pointers, e.g. torch tensors' data_ptr())
@@ -1151,11 +1131,9 @@ class BatchEngine:
         count = self.n - first if count is None else count
         legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
         if out is not None:
-            ptr, dt, rows, columns, stride = _observation_target(out, "observations")
+            ptr, dt, rows, columns, stride, _on_device, _keep = _rows_array(out, "observations")
             spec = obs_spec(fields, legs, dof, dt, stride, pad)
-            width = int(self.L.shc_obs_width(C.byref(spec)))
-            if rows != int(count) or (width >= 0 and columns < width):
-                raise ValueError(f"observations: out has shape ({rows}, {columns}), {int(count)} rows of at least {width} columns are expected")
+            _check_rows("observations", "out", rows, columns, int(count), int(self.L.shc_obs_width(C.byref(spec))))
             _check(self.L.shc_engine_get_observations(self.h, int(first), int(count), C.byref(spec), ptr, 1), "get_observations")
             return None
         spec = obs_spec(fields, legs, dof, dtype, 0, pad)
@@ -1418,11 +1396,9 @@ class BatchEngine:
         is returned.  Or a numpy array, which is copied to the device and waited for: the number of dropped rows is returned.  legs (default:
         the engine's) may be larger than the robot's: the columns of legs it lacks are ignored."""
         legs = self.legs if legs is None else legs
-        ptr, dt, n_rows, columns, stride, on_device, _keep = _foothold_rows(rows, "set_footholds")
+        ptr, dt, n_rows, columns, stride, on_device, _keep = _rows_array(rows, "set_footholds", host="view")
         spec = foothold_spec(fields, legs, dt, which, mode, stride)
-        width = int(self.L.shc_foothold_width(C.byref(spec)))
-        if n_rows != self.n or (width >= 0 and columns < width):
-            raise ValueError(f"set_footholds: rows has shape ({n_rows}, {columns}), {self.n} rows of at least {width} columns are expected")
+        _check_rows("set_footholds", "rows", n_rows, columns, self.n, int(self.L.shc_foothold_width(C.byref(spec))))
         if on_device:
             _check(self.L.shc_engine_set_footholds(self.h, C.byref(spec), ptr, 1, _foothold_ignored(ignored, "set_footholds")), "set_footholds")
             return None
@@ -1446,11 +1422,9 @@ class BatchEngine:
             host = np.zeros((self.n, width), dtype=np.dtype(dtype))
             self.footholds(host, fields, which, pad, legs=legs)
             return host
-        ptr, dt, n_rows, columns, stride, on_device, _keep = _foothold_rows(out, "footholds")
+        ptr, dt, n_rows, columns, stride, on_device, _keep = _rows_array(out, "footholds", host="view")
         spec = foothold_spec(fields, legs, dt, which, "request", stride, pad)
-        width = int(self.L.shc_foothold_width(C.byref(spec)))
-        if n_rows != self.n or (width >= 0 and columns < width):
-            raise ValueError(f"footholds: out has shape ({n_rows}, {columns}), {self.n} rows of at least {width} columns are expected")
+        _check_rows("footholds", "out", n_rows, columns, self.n, int(self.L.shc_foothold_width(C.byref(spec))))
         _check(self.L.shc_engine_get_footholds(self.h, C.byref(spec), ptr, on_device), "get_footholds")
         return None
 

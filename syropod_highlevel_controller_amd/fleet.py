@@ -234,11 +234,9 @@ class MixedFleet:
         ``engine.observation_columns(fields, max_legs, max_dof)`` names the columns; every value is the double the matching member of
         ``outputs()`` / ``joints()`` holds, cast to out's type, and ``pad`` where a morphology has no such leg or joint.  No host wait: complete
         after ``synchronize()``, or for work queued on a stream after ``order_before(stream)``."""
-        ptr, dt, rows, columns, stride = _engine._observation_target(out, "observations")
+        ptr, dt, rows, columns, stride, _on_device, _keep = _engine._rows_array(out, "observations")
         spec = _engine.obs_spec(fields, self.max_legs, self.max_dof, dt, stride, pad)
-        width = int(self.L.shc_obs_width(C.byref(spec)))
-        if rows != self.n or (width >= 0 and columns < width):
-            raise ValueError(f"observations: out has shape ({rows}, {columns}), {self.n} rows of at least {width} columns are expected")
+        _engine._check_rows("observations", "out", rows, columns, self.n, int(self.L.shc_obs_width(C.byref(spec))))
         _engine._check(self.L.shc_fleet_get_observations_device(self.h, C.byref(spec), ptr), "shc_fleet_get_observations_device")
 
     def set_actions(self, actions, fields):
@@ -248,11 +246,9 @@ class MixedFleet:
         will do; it is never written.  ``engine.action_columns(fields, max_legs, max_dof)`` names the columns; the fleet is left as ``set_inputs``
         leaves it when given the columns as float64 arrays, groups not named are held, columns of legs and joints a morphology lacks are ignored.
         No host wait, and the stream rules of ``set_inputs``."""
-        ptr, dt, rows, columns, stride = _engine._observation_target(actions, "set_actions")
+        ptr, dt, rows, columns, stride, _on_device, _keep = _engine._rows_array(actions, "set_actions")
         spec = _engine.act_spec(fields, self.max_legs, self.max_dof, dt, stride)
-        width = int(self.L.shc_act_width(C.byref(spec)))
-        if rows != self.n or (width >= 0 and columns < width):
-            raise ValueError(f"set_actions: actions has shape ({rows}, {columns}), {self.n} rows of at least {width} columns are expected")
+        _engine._check_rows("set_actions", "actions", rows, columns, self.n, int(self.L.shc_act_width(C.byref(spec))))
         _engine._check(self.L.shc_fleet_set_actions_device(self.h, C.byref(spec), ptr), "shc_fleet_set_actions_device")
 
     def set_footholds(self, rows, fields, which=0, mode="request", ignored=None):
@@ -263,11 +259,10 @@ class MixedFleet:
         stream, no staging, no host wait, the stream rules of ``set_inputs``; the dropped rows of every part are ADDED to ``ignored``, a
         one-element int64 device array the caller zeroes (or None); returns None.  Or a numpy array: every part takes its rows through its
         engine's host form, and the number of dropped rows is returned."""
-        ptr, dt, n_rows, columns, stride, on_device, _keep = _engine._foothold_rows(rows, "set_footholds")
+        ptr, dt, n_rows, columns, stride, on_device, _keep = _engine._rows_array(rows, "set_footholds", host="view")
         spec = _engine.foothold_spec(fields, self.max_legs, dt, which, mode, stride)
         width = int(self.L.shc_foothold_width(C.byref(spec)))
-        if n_rows != self.n or (width >= 0 and columns < width):
-            raise ValueError(f"set_footholds: rows has shape ({n_rows}, {columns}), {self.n} rows of at least {width} columns are expected")
+        _engine._check_rows("set_footholds", "rows", n_rows, columns, self.n, width)
         if on_device:
             _engine._check(self.L.shc_fleet_set_footholds_device(self.h, C.byref(spec), ptr, _engine._foothold_ignored(ignored, "set_footholds")),
                            "shc_fleet_set_footholds_device")
@@ -287,11 +282,10 @@ class MixedFleet:
         morphology has no such leg; only the first F columns of out are written.  A device array: one kernel per part, no staging, no host
         wait - complete after ``synchronize()``, or for work queued on a stream after ``order_before(stream)``.  A numpy array: filled part by
         part through the engines' host form."""
-        ptr, dt, n_rows, columns, stride, on_device, _keep = _engine._foothold_rows(out, "footholds")
+        ptr, dt, n_rows, columns, stride, on_device, _keep = _engine._rows_array(out, "footholds", host="view")
         spec = _engine.foothold_spec(fields, self.max_legs, dt, which, "request", stride, pad)
         width = int(self.L.shc_foothold_width(C.byref(spec)))
-        if n_rows != self.n or (width >= 0 and columns < width):
-            raise ValueError(f"footholds: out has shape ({n_rows}, {columns}), {self.n} rows of at least {width} columns are expected")
+        _engine._check_rows("footholds", "out", n_rows, columns, self.n, width)
         if on_device:
             _engine._check(self.L.shc_fleet_get_footholds_device(self.h, C.byref(spec), ptr), "shc_fleet_get_footholds_device")
             return
