@@ -248,7 +248,7 @@ constexpr bool phase_fences() {
 // Development-only phase timestamps (build with -DSHC_RES2_TIMING) of the two-wavefront resident kernel: the leader of workgroup 1 keeps
 // the s_memtime stamps of its latest iteration in LDS; shc_engine_resident_end prints them.
 #if defined(SHC_RES2_TIMING) && !defined(SHC_RES2_BUSY_ONLY) // (-DSHC_RES2_BUSY_ONLY: only the two stamps per iteration of each role, no phase ticks)
-__shared__ long long shc_ticks_lds[96]; // 32 per wavefront of pair 0 (threads 0 and 128: walker and model; the three-role form: model, walker, and the helper at thread 256)
+__shared__ long long shc_ticks_lds[96]; // 32 per wavefront of pair 0 (threads 0 and 128: walker and model; the three-role form: and the helper at thread 256)
 __shared__ long long shc_acc_lds[96];   // per phase: clocks since the previous stamp, summed over the steady REAL iterations
 #define SHC_TICK(i) do { __builtin_amdgcn_sched_barrier(0); if (blockIdx.x == 1 && (threadIdx.x & 127) == 0) shc_ticks_lds[(threadIdx.x >> 7) * 32 + (i)] = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
@@ -404,10 +404,15 @@ __device__ __forceinline__ double swing_progress_of(int word, const CycleParams 
 // 45-degree sector of the direction rotated by +0.5 degrees; that sector follows from the signs of the rotated
 // components and one magnitude comparison.  Both forms can only disagree for a direction within one rounding error
 // of a sector edge (as the device atan2 and glibc's already could).
+template <bool WRITTEN_OUT = false>
 __device__ __forceinline__ int bearing_bracket(double y, double x) {
   if (x == 0.0 && y == 0.0) return 0; // atan2(0, 0) = 0
   constexpr double kC = 0.99996192306417128874, kS = 0.0087265354983739347; // cos / sin of 0.5 degrees
-  double xr = kC * x - kS * y, yr = kS * x + kC * y;
+  // WRITTEN_OUT: the contractions as explicit fmas, in the form the compiler picks for this line inside cycle_front - for a caller in other surroundings
+  // (walk_velocity_front on a wavefront of its own), where it may round the other product and the two must agree to the last bit
+  double xr, yr;
+  if constexpr (WRITTEN_OUT) xr = fma(kC, x, -(kS * y)), yr = fma(kS, x, kC * y);
+  else xr = kC * x - kS * y, yr = kS * x + kC * y;
   double ax = fabs(xr), ay = fabs(yr);
   bool upper = yr > 0.0 || (yr == 0.0 && xr > 0.0);
   if (upper) return xr > 0.0 ? (ay < ax ? 0 : 1) : (ay > ax ? 2 : 3);
@@ -996,15 +1001,40 @@ __device__ __forceinline__ void cycle_admittance(LegRegs<NJ> &s, LegOut &out, co
   out.adm_delta = projection(V3{d[0], d[1], d[2]}, s.tipx);
 }
 
+// The front of WalkController::updateWalk (:440-527) that is the same for every leg of a robot: getLimit x 4 and the desired body velocities of this cycle, for
+// a wavefront that runs it for another (cycle_front<..., FRONT_HERE = false> on the walker's side).  The statements are those cycle_front runs itself - one text,
+// shc_walk_front_body.hpp.  In: the velocity command, this leg's tip (x, y) as the previous cycle left it, the walk state BEFORE this cycle's state machine; the
+// desired velocities of the previous cycle are read from the robot tile (VLIN / VANG) and this cycle's written back.  The caller owns the bracket memo in `fb` and
+// the tile's VLIN / VANG for as long as its loop runs.  Contractions written out: it must agree with cycle_front to the last bit.  Returns |linear input|.
+template <int L, int NJ, unsigned F>
+__device__ __forceinline__ double walk_velocity_front(const SharedConsts<L, NJ> &C, const CycleParams &P, const RobTile<64 / L> &rb, const Group<L> g, FrontToBack &fb,
+                                                      const double vin_x, const double vin_y, const double win, const double tip_x, const double tip_y,
+                                                      const int walk_state, const bool frozen, double &vx, double &vy, double &vw) {
+  using R = RobotFields;
+#define SHC_FRONT_TIP_X tip_x
+#define SHC_FRONT_TIP_Y tip_y
+#define SHC_FRONT_WRITTEN_OUT true
+#include "shc_walk_front_body.hpp"
+#undef SHC_FRONT_TIP_X
+#undef SHC_FRONT_TIP_Y
+#undef SHC_FRONT_WRITTEN_OUT
+  return lin_norm;
+}
+
 // The walker / poser half of a cycle: updateCurrentPose, updateStiffness, (ADM_HERE: updateAdmittance,) updateWalk with the
 // LegSteppers, updateStance.  Leaves out.poser_tip (and fb) for the model half.
-template <int L, int NJ, unsigned F, bool ADM_HERE, typename IN, bool ODOM_HERE = true, bool POSE_HERE = true, typename POSEWAIT = NoHook>
+template <int L, int NJ, unsigned F, bool ADM_HERE, typename IN, bool ODOM_HERE = true, bool POSE_HERE = true, bool FRONT_HERE = true, typename POSEWAIT = NoHook,
+          typename FRONTWAIT = NoHook>
 __device__ __forceinline__ void cycle_front(LegRegs<NJ> &s, LegOut &out, const SharedConsts<L, NJ> &C, const RobTile<64 / L> &rb, const Park &pk,
                                             const Group<L> g, int leg, const double *__restrict__ legd, int64_t ns, uint32_t slot, unsigned &dirty,
                                             const bool manual_live, const bool touchdown_detection, double *ext, const ManualRobot *mr, const IN &in,
-                                            FrontToBack &fb, const double *span = nullptr, const POSEWAIT &pose_wait = POSEWAIT()) {
+                                            FrontToBack &fb, const double *span = nullptr, const POSEWAIT &pose_wait = POSEWAIT(),
+                                            const FRONTWAIT &front_wait = FRONTWAIT()) {
   using R = RobotFields;
   using FT = Feat<F>;
+  // FRONT_HERE = false: getLimit and the desired body velocities of this cycle (walk_velocity_front) run on another wavefront; front_wait() returns once they are
+  // in the robot tile (VLIN / VANG).  Only where nothing but the stepper reads them: no manual legs (a frozen robot), no rough terrain, no step-frequency remap.
+  static_assert(FRONT_HERE || (!POSE_HERE && (F & (F_DYN | F_MLEGS | F_ROUGH | F_TERRAIN)) == 0), "the velocity front can run elsewhere only on the plain feature-exact walker");
   // POSE_HERE = false: PoseController::updateCurrentPose of this cycle runs on another wavefront (cycle_pose); pose_wait() returns once
   // Model::current_pose_ (CPOSE) and the walk-plane pose (WPP) of this cycle are in the robot tile.  Only for specialisations whose
   // pose does not feed back into updateWalk (no auto posing: its pose state gates the STOPPING -> STOPPED transition).
@@ -1121,80 +1151,22 @@ __device__ __forceinline__ void cycle_front(LegRegs<NJ> &s, LegOut &out, const S
 
   SHC_PHASE_FENCE();
   // =============================================================== WalkController::updateWalk (:440-648)
-  // ---- getLimit x 4 (:414-436): bracket index per leg, min over the robot's legs
-  double lim[4] = {0.05, 0.3, 0.02, 0.1};
-  if (!(SHC_DBG(P) & 2)) {
-    double sx = vin_x + win * (-s.tip.y), sy = vin_y + win * s.tip.x;
-    int idx = bearing_bracket(sy, sx);
-    if (__all(idx == fb.limit_bracket)) { // every leg of every robot of the wave in the bracket it was in: the same minima
-#pragma unroll
-      for (int k = 0; k < 4; ++k) lim[k] = fb.limit_value[k];
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) lim[k] = kUnassigned;
-#pragma unroll
-      for (int j = 0; j < L; ++j) {
-        int ij = g.get(idx, j);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) lim[k] = fmin(lim[k], C.limit[ij][k]);
-      }
-      fb.limit_bracket = idx;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) fb.limit_value[k] = lim[k];
-    }
+  double vx, vy, vw; // WalkController::desired_linear_velocity_ / desired_angular_velocity_ of this cycle
+  bool has_cmd;
+  if constexpr (FRONT_HERE) {
+#define SHC_FRONT_TIP_X s.tip.x
+#define SHC_FRONT_TIP_Y s.tip.y
+#define SHC_FRONT_WRITTEN_OUT false
+#include "shc_walk_front_body.hpp"
+#undef SHC_FRONT_TIP_X
+#undef SHC_FRONT_TIP_Y
+#undef SHC_FRONT_WRITTEN_OUT
+    has_cmd = (lin_norm != 0.0) || (win != 0.0);
+  } else {
+    // The front runs on another wavefront, which reads the words this cycle starts from (robot word, desired velocities, the tip the last cycle left) while
+    // this one goes on with what does not need the new velocities: they are picked up behind front_wait(), in the stepper.
+    has_cmd = (vin_x * vin_x + vin_y * vin_y != 0.0) || (win != 0.0); // (the truth value of |linear input| != 0: the square root of a non-zero double is non-zero)
   }
-  SHC_PHASE_FENCE();
-  SHC_TICK(5);
-  double vx = rb.get(R::VLIN), vy = rb.get(R::VLIN + 1), vw = rb.get(R::VANG);
-  // |linear input|.  Throttle mode only ever asks "> 1" and "!= 0" of it: while no robot of the wave has n2 > 1 (sqrt(n2) <= 1 then, the
-  // correctly rounded square root being monotone with sqrt(1) = 1) a stand-in with the same two answers saves the FP64 square root.
-  const double lin_n2 = vin_x * vin_x + vin_y * vin_y;
-  double lin_norm;
-  const int velocity_input_mode = fb.uf.velocity_input_mode;
-  if (velocity_input_mode == 0 && __all(lin_n2 <= 1.0)) lin_norm = lin_n2 != 0.0 ? 0.5 : 0.0;
-  else lin_norm = sqrt(lin_n2);
-  if (!(SHC_DBG(P) & 32)) {
-    double nvx, nvy, nw;
-    if (velocity_input_mode == 0) { // throttle (:451-466)
-      double k = 1.0; // clamped to the unit disc
-      if (__any(lin_norm > 1.0)) k = lin_norm > 1.0 ? 1.0 / lin_norm : 1.0;
-      const double cx = lin_norm > 1.0 ? vin_x * k : vin_x, cy = lin_norm > 1.0 ? vin_y * k : vin_y;
-      nw = clampd(win, -1.0, 1.0) * lim[1];
-      const double sc = 1.0 - fabs(win);
-      nvx = (cx * lim[0]) * sc;
-      nvy = (cy * lim[0]) * sc;
-    } else { // real (:467-481)
-      const bool over = lin_norm > lim[0];
-      const double k = lim[0] / lin_norm;
-      const double cx = over ? vin_x * k : vin_x, cy = over ? vin_y * k : vin_y;
-      nw = clampd(win, -lim[1], lim[1]);
-      const double sc = lim[1] != 0.0 ? (1.0 - fabs(nw / lim[1])) : 0.0;
-      nvx = cx * sc;
-      nvy = cy * sc;
-    }
-    if (walk_state == WS_STOPPING) nvx = nvy = nw = 0.0; // :483-487
-    if (frozen) nvx = vx, nvy = vy, nw = vw; // (a robot with a manual leg keeps its desired velocities: zero acceleration below)
-    // acceleration-limited approach (:508-527)
-    const double ax = nvx - vx, ay = nvy - vy;
-    const double an2 = ax * ax + ay * ay;
-    const double an = __all(an2 == 0.0) ? 0.0 : sqrt(an2); // (every robot already at its target velocity: sqrt(0) = 0)
-    const double cap = lim[2] * P.dt;
-    if (__all(an < cap)) { // every robot of the wave reaches its target this cycle (the steady state)
-      vx += ax;
-      vy += ay;
-    } else {
-      const double inv = an2 > 0.0 ? an : 1.0; // normalized() leaves the zero vector unchanged
-      const double sx_ = (ax / inv) * lim[2] * P.dt, sy_ = (ay / inv) * lim[2] * P.dt;
-      vx += an < cap ? ax : sx_;
-      vy += an < cap ? ay : sy_;
-    }
-    const double aa = nw - vw;
-    vw += fabs(aa) < lim[3] * P.dt ? aa : signd(aa) * lim[3] * P.dt;
-    rb.put(R::VLIN, vx);
-    rb.put(R::VLIN + 1, vy);
-    rb.put(R::VANG, vw);
-  }
-  const bool has_cmd = (lin_norm != 0.0) || (win != 0.0);
 
   SHC_PHASE_FENCE();
   SHC_TICK(6);
@@ -1325,7 +1297,7 @@ __device__ __forceinline__ void cycle_front(LegRegs<NJ> &s, LegOut &out, const S
   if (POSE_HERE || !steady) { // (steady: nothing of the robot word changed; with the pose on this wavefront auto posing may have changed its state bits)
     rword = (rword & ~(3 | (15 << RW_LACP_SHIFT) | (15 << RW_LCFS_SHIFT) | RW_RTDA)) | walk_state | (lacp << RW_LACP_SHIFT) |
             (lcfs << RW_LCFS_SHIFT) | (rtda ? RW_RTDA : 0);
-    rb.puti(R::I_WORD, rword);
+    if (FRONT_HERE) rb.puti(R::I_WORD, rword); // (front elsewhere: it reads the word this cycle started from - stored below, behind its flag)
   }
   SHC_TICK(7);
   int my_pm = (s.word >> LW_PM_SHIFT) & 3;
@@ -1382,57 +1354,130 @@ __device__ __forceinline__ void cycle_front(LegRegs<NJ> &s, LegOut &out, const S
 #else
     const bool straight = (F & F_ROUGH) == 0 && !(SHC_DBG(P) & 4) && force_normal_touchdown == 0;
 #endif
+    if constexpr (!FRONT_HERE) {
+      if (!straight) { // the branching form: this cycle's desired velocities before updateStride
+        front_wait();
+        SHC_TICK(18);
+        vx = rb.get(R::VLIN), vy = rb.get(R::VLIN + 1), vw = rb.get(R::VANG);
+      }
+    }
     if (straight) {
-      const V3 sorg_p = pk.get3(PK_SORG), svel_p = pk.get3(PK_SVEL), torg_p = pk.get3(PK_TORG);
-      const bool swing = my_state == SS_SWING;
-      const bool step_sw = stepping && swing, step_st = stepping && !swing;
-      // updateStride (:921-945)
-      const V3 sv{vx - vw * s.tip.y, vy + vw * s.tip.x, 0.0};
-      const V3 strd_new = scaled(sv, P.stride_scale);
-      s.strd = sel3(stepping, strd_new, s.strd);
-      V3 pn = rb.get3(R::PNORM);
-      const bool flat_n = pn.x == 0.0 && pn.y == 0.0 && pn.z == 1.0;
-      if (!__all(flat_n)) pn = normalized(pn);
-      const V3 clearance = scaled(pn, P.swing_height);
-      // swing (:1110-1157)
-      const int it_sw = my_phase - P.swing_start + 1;
-      const bool first_half = it_sw <= P.swing_iterations / 2;
-      const bool first_sw = step_sw && it_sw == 1;
-      const V3 sorg = sel3(first_sw, s.tip, sorg_p), svel = sel3(first_sw, s.tvel, svel_p);
-      pk.put3(PK_SORG, sorg); // (unchanged unless this is the first iteration of a swing: an unconditional LDS store costs less than the branch)
-      pk.put3(PK_SVEL, svel);
-      dirty |= first_sw ? unsigned(DIRTY_SWING_ORG) : 0u;
-      V3 mid{(sorg.x + s.targ.x) / 2.0, (sorg.y + s.targ.y) / 2.0, fmax(sorg.z, s.targ.z)};
-      mid = mid + clearance;
-      mid.y += (lc.stance_y > 0.0) ? P.swing_width : -P.swing_width;
-      const V3 sep1 = scaled(svel * 0.25, P.dt_over_swing_dt);
-      const V3 n1_0 = sorg, n1_1 = sorg + sep1, n1_2 = sorg + scaled(sep1, 2.0);
-      const V3 n1_3{(mid.x + n1_2.x) / 2.0, (mid.y + n1_2.y) / 2.0, mid.z};
-      const V3 n1_4 = mid;
-      const V3 fv = scaled(-s.strd, stance_dt * P.inv_dt);
-      const V3 sep2 = scaled(fv * 0.25, P.dt_over_swing_dt);
-      const V3 n2_0 = n1_4, n2_1 = n1_4 - (n1_3 - n1_4), n2_2 = s.targ - scaled(sep2, 2.0), n2_3 = s.targ - sep2, n2_4 = s.targ;
-      const double t_sw = first_half ? P.swing_delta_t * it_sw : P.swing_delta_t * (it_sw - P.swing_iterations / 2);
-      const V3 b0 = sel3(first_half, n1_0, n2_0), b1 = sel3(first_half, n1_1, n2_1), b2 = sel3(first_half, n1_2, n2_2), b3 = sel3(first_half, n1_3, n2_3),
-               b4 = sel3(first_half, n1_4, n2_4);
-      const V3 dpos_sw = scaled(quartic_bezier_dot(b0, b1, b2, b3, b4, t_sw), P.swing_delta_t);
-      // stance (:1159-1177)
-      int it_st = my_phase + (P.period - mss); // both terms lie in [0, period]: one conditional subtract is the modulo
-      if (it_st >= P.period) it_st -= P.period;
-      if (it_st < 0 || it_st >= P.period) it_st = mod_i(it_st, P.period); // (... except while a step-frequency change waits: the phase offsets are the NEW cycle's then, see below)
-      it_st += 1;
-      const bool first_st = step_st && it_st == 1;
-      const V3 torg = sel3(first_st, s.tip, torg_p);
-      pk.put3(PK_TORG, torg);
-      dirty |= first_st ? unsigned(DIRTY_STANCE_ORG) : 0u;
-      const double stride_scaler = standard ? 1.0 : lc.first_stride_scaler; // modified / standard stance period (:1167)
-      const V3 sep = scaled((-s.strd) * stride_scaler, 0.25);
-      const double t_st = it_st * stance_dt;
-      const V3 dpos_st = scaled(quartic_bezier_dot(torg, torg + sep, torg + scaled(sep, 2.0), torg + scaled(sep, 3.0), torg + scaled(sep, 4.0), t_st), stance_dt);
-      const V3 dpos = sel3(swing, dpos_sw, dpos_st);
-      const V3 tip_new = s.tip + dpos, tvel_new = dpos * P.inv_dt; // delta_pos / time_delta (:1135, :1176)
-      s.tip = sel3(stepping, tip_new, s.tip);
-      s.tvel = sel3(stepping, tvel_new, s.tvel);
+      // TWO COPIES of the straight form follow, one per value of FRONT_HERE: the original order here, and the same statements re-ordered around the front's flag
+      // below.  An edit to one must be mirrored in the other, operation for operation (tests/test_gpu_resident_front.py holds them together byte for byte).  One
+      // body in the second order would do for both - but it changes the code of every kernel that keeps the front, and those are held to their instructions.
+      if constexpr (FRONT_HERE) {
+        const V3 sorg_p = pk.get3(PK_SORG), svel_p = pk.get3(PK_SVEL), torg_p = pk.get3(PK_TORG);
+        const bool swing = my_state == SS_SWING;
+        const bool step_sw = stepping && swing, step_st = stepping && !swing;
+        // updateStride (:921-945)
+        const V3 sv{vx - vw * s.tip.y, vy + vw * s.tip.x, 0.0};
+        const V3 strd_new = scaled(sv, P.stride_scale);
+        s.strd = sel3(stepping, strd_new, s.strd);
+        V3 pn = rb.get3(R::PNORM);
+        const bool flat_n = pn.x == 0.0 && pn.y == 0.0 && pn.z == 1.0;
+        if (!__all(flat_n)) pn = normalized(pn);
+        const V3 clearance = scaled(pn, P.swing_height);
+        // swing (:1110-1157)
+        const int it_sw = my_phase - P.swing_start + 1;
+        const bool first_half = it_sw <= P.swing_iterations / 2;
+        const bool first_sw = step_sw && it_sw == 1;
+        const V3 sorg = sel3(first_sw, s.tip, sorg_p), svel = sel3(first_sw, s.tvel, svel_p);
+        pk.put3(PK_SORG, sorg); // (unchanged unless this is the first iteration of a swing: an unconditional LDS store costs less than the branch)
+        pk.put3(PK_SVEL, svel);
+        dirty |= first_sw ? unsigned(DIRTY_SWING_ORG) : 0u;
+        V3 mid{(sorg.x + s.targ.x) / 2.0, (sorg.y + s.targ.y) / 2.0, fmax(sorg.z, s.targ.z)};
+        mid = mid + clearance;
+        mid.y += (lc.stance_y > 0.0) ? P.swing_width : -P.swing_width;
+        const V3 sep1 = scaled(svel * 0.25, P.dt_over_swing_dt);
+        const V3 n1_0 = sorg, n1_1 = sorg + sep1, n1_2 = sorg + scaled(sep1, 2.0);
+        const V3 n1_3{(mid.x + n1_2.x) / 2.0, (mid.y + n1_2.y) / 2.0, mid.z};
+        const V3 n1_4 = mid;
+        const V3 fv = scaled(-s.strd, stance_dt * P.inv_dt);
+        const V3 sep2 = scaled(fv * 0.25, P.dt_over_swing_dt);
+        const V3 n2_0 = n1_4, n2_1 = n1_4 - (n1_3 - n1_4), n2_2 = s.targ - scaled(sep2, 2.0), n2_3 = s.targ - sep2, n2_4 = s.targ;
+        const double t_sw = first_half ? P.swing_delta_t * it_sw : P.swing_delta_t * (it_sw - P.swing_iterations / 2);
+        const V3 b0 = sel3(first_half, n1_0, n2_0), b1 = sel3(first_half, n1_1, n2_1), b2 = sel3(first_half, n1_2, n2_2), b3 = sel3(first_half, n1_3, n2_3),
+                 b4 = sel3(first_half, n1_4, n2_4);
+        const V3 dpos_sw = scaled(quartic_bezier_dot(b0, b1, b2, b3, b4, t_sw), P.swing_delta_t);
+        // stance (:1159-1177)
+        int it_st = my_phase + (P.period - mss); // both terms lie in [0, period]: one conditional subtract is the modulo
+        if (it_st >= P.period) it_st -= P.period;
+        if (it_st < 0 || it_st >= P.period) it_st = mod_i(it_st, P.period); // (... except while a step-frequency change waits: the phase offsets are the NEW cycle's then, see below)
+        it_st += 1;
+        const bool first_st = step_st && it_st == 1;
+        const V3 torg = sel3(first_st, s.tip, torg_p);
+        pk.put3(PK_TORG, torg);
+        dirty |= first_st ? unsigned(DIRTY_STANCE_ORG) : 0u;
+        const double stride_scaler = standard ? 1.0 : lc.first_stride_scaler; // modified / standard stance period (:1167)
+        const V3 sep = scaled((-s.strd) * stride_scaler, 0.25);
+        const double t_st = it_st * stance_dt;
+        const V3 dpos_st = scaled(quartic_bezier_dot(torg, torg + sep, torg + scaled(sep, 2.0), torg + scaled(sep, 3.0), torg + scaled(sep, 4.0), t_st), stance_dt);
+        const V3 dpos = sel3(swing, dpos_sw, dpos_st);
+        const V3 tip_new = s.tip + dpos, tvel_new = dpos * P.inv_dt; // delta_pos / time_delta (:1135, :1176)
+        s.tip = sel3(stepping, tip_new, s.tip);
+        s.tvel = sel3(stepping, tvel_new, s.tvel);
+      } else {
+        // (The second copy - mirror every edit of the first.)
+        // The same statements, those that do not need this cycle's desired velocities first - the parked origins, last cycle's target, plane normal and clearance,
+        // iteration counters, the origin selects and their stores, the primary swing nodes, the Bezier weights of both curves - then the front's flag, then
+        // updateStride and what follows from it.  Per leg the operations and their operands are those of the form above: bit-identical.
+        const V3 sorg_p = pk.get3(PK_SORG), svel_p = pk.get3(PK_SVEL), torg_p = pk.get3(PK_TORG);
+        const bool swing = my_state == SS_SWING;
+        const bool step_sw = stepping && swing, step_st = stepping && !swing;
+        V3 pn = rb.get3(R::PNORM);
+        const bool flat_n = pn.x == 0.0 && pn.y == 0.0 && pn.z == 1.0;
+        if (!__all(flat_n)) pn = normalized(pn);
+        const V3 clearance = scaled(pn, P.swing_height);
+        // swing (:1110-1157)
+        const int it_sw = my_phase - P.swing_start + 1;
+        const bool first_half = it_sw <= P.swing_iterations / 2;
+        const bool first_sw = step_sw && it_sw == 1;
+        const V3 sorg = sel3(first_sw, s.tip, sorg_p), svel = sel3(first_sw, s.tvel, svel_p);
+        pk.put3(PK_SORG, sorg);
+        pk.put3(PK_SVEL, svel);
+        dirty |= first_sw ? unsigned(DIRTY_SWING_ORG) : 0u;
+        V3 mid{(sorg.x + s.targ.x) / 2.0, (sorg.y + s.targ.y) / 2.0, fmax(sorg.z, s.targ.z)};
+        mid = mid + clearance;
+        mid.y += (lc.stance_y > 0.0) ? P.swing_width : -P.swing_width;
+        const V3 sep1 = scaled(svel * 0.25, P.dt_over_swing_dt);
+        const V3 n1_0 = sorg, n1_1 = sorg + sep1, n1_2 = sorg + scaled(sep1, 2.0);
+        const V3 n1_3{(mid.x + n1_2.x) / 2.0, (mid.y + n1_2.y) / 2.0, mid.z};
+        const V3 n1_4 = mid;
+        const V3 n2_0 = n1_4, n2_1 = n1_4 - (n1_3 - n1_4), n2_4 = s.targ;
+        const double t_sw = first_half ? P.swing_delta_t * it_sw : P.swing_delta_t * (it_sw - P.swing_iterations / 2);
+        const BezierDotWeights w_sw = quartic_bezier_dot_weights(t_sw);
+        // stance (:1159-1177)
+        int it_st = my_phase + (P.period - mss);
+        if (it_st >= P.period) it_st -= P.period;
+        if (it_st < 0 || it_st >= P.period) it_st = mod_i(it_st, P.period);
+        it_st += 1;
+        const bool first_st = step_st && it_st == 1;
+        const V3 torg = sel3(first_st, s.tip, torg_p);
+        pk.put3(PK_TORG, torg);
+        dirty |= first_st ? unsigned(DIRTY_STANCE_ORG) : 0u;
+        const double stride_scaler = standard ? 1.0 : lc.first_stride_scaler;
+        const double t_st = it_st * stance_dt;
+        const BezierDotWeights w_st = quartic_bezier_dot_weights(t_st);
+        front_wait();
+        SHC_TICK(18);
+        vx = rb.get(R::VLIN), vy = rb.get(R::VLIN + 1), vw = rb.get(R::VANG);
+        // updateStride (:921-945)
+        const V3 sv{vx - vw * s.tip.y, vy + vw * s.tip.x, 0.0};
+        const V3 strd_new = scaled(sv, P.stride_scale);
+        s.strd = sel3(stepping, strd_new, s.strd);
+        const V3 fv = scaled(-s.strd, stance_dt * P.inv_dt);
+        const V3 sep2 = scaled(fv * 0.25, P.dt_over_swing_dt);
+        const V3 n2_2 = s.targ - scaled(sep2, 2.0), n2_3 = s.targ - sep2;
+        const V3 b0 = sel3(first_half, n1_0, n2_0), b1 = sel3(first_half, n1_1, n2_1), b2 = sel3(first_half, n1_2, n2_2), b3 = sel3(first_half, n1_3, n2_3),
+                 b4 = sel3(first_half, n1_4, n2_4);
+        const V3 dpos_sw = scaled(quartic_bezier_dot(b0, b1, b2, b3, b4, w_sw), P.swing_delta_t);
+        const V3 sep = scaled((-s.strd) * stride_scaler, 0.25);
+        const V3 dpos_st = scaled(quartic_bezier_dot(torg, torg + sep, torg + scaled(sep, 2.0), torg + scaled(sep, 3.0), torg + scaled(sep, 4.0), w_st), stance_dt);
+        const V3 dpos = sel3(swing, dpos_sw, dpos_st);
+        const V3 tip_new = s.tip + dpos, tvel_new = dpos * P.inv_dt; // delta_pos / time_delta (:1135, :1176)
+        s.tip = sel3(stepping, tip_new, s.tip);
+        s.tvel = sel3(stepping, tvel_new, s.tvel);
+      }
     } else if (stepping && !(SHC_DBG(P) & 4)) {
       // updateStride (:921-945)
       V3 sv{vx - vw * s.tip.y, vy + vw * s.tip.x, 0.0}; // v + w z^ x (tip rejected from z^)
@@ -1662,6 +1707,15 @@ __device__ __forceinline__ void cycle_front(LegRegs<NJ> &s, LegOut &out, const S
       if (ODOM_HERE) odometry_step(rb, P, vx, vy, vw);
       fb.odom_vel = V3{vx, vy, vw};
       fb.odom_run = true;
+    }
+  }
+  if constexpr (!FRONT_HERE) {
+    // The rule that keeps the hand-off free of races: the front's wavefront reads only words that were complete at the last barrier - the robot word, the desired
+    // velocities of the last cycle, the tip slot of this cycle's parity, the held velocity command - and this wavefront stores to none of them before it has
+    // passed the front's flag (the flag is raised behind the front's last read).  Hence the robot word the state machine changed is stored here, not above.
+    if (!steady) { // (wave-uniform; every lane, also those of a robot that starts to walk and skipped the stepper)
+      front_wait();
+      rb.puti(R::I_WORD, rword);
     }
   }
   // =============================================================== WalkController::updateManual x 2 (walk_controller.cpp:652-744)

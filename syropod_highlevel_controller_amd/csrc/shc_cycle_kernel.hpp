@@ -1086,15 +1086,21 @@ template <int L, int NJ>
 struct Resident3Lds : Resident2Lds<L, NJ> { // ... of the three-role form (below)
   int leg_word[2][2][64];     // [pair][cycle parity][lane] walker -> helper: the packed leg words updateWalk left (the helper reduces them to pose_c's value itself)
   unsigned back_seen[2];      // model -> walker at exit: input groups the model wavefront received
+  double tip_xy[2][2][2][64]; // [pair][cycle parity][x, y][lane] walker -> helper: the stepper tips the cycle left (getLimit of the next cycle reads their bearings)
+  unsigned front_done[2];     // helper -> walker: velocity fronts completed (the desired velocities of that cycle are in the tile)
 };
 
 // THREE roles per robot group (HELPER; has_helper_wave: default.yaml's posing set on 6 x 3, the specialisations whose model wavefront carries the pose AND the
 // odometry): the model wavefront's share that belongs to neither Model::updateModel nor the walker's recurrence - PoseController::updateCurrentPose of the walker's
 // next cycle, the odometry accumulator, the leader's duty - runs on a third wavefront, and so does the walker's reduction of its leg words for that pose.
-// 384-thread workgroups = 2 robot groups x (model, walker, helper), six wavefronts on the four SIMDs of a compute unit; the first four waves of a workgroup get
-// the four SIMDs and waves i and i + 4 share one (scripts/ubench/wave_placement.hip: every workgroup measured), so the order [M0, M1, W0, W1, H0, H1] leaves each
-// walker - the recurrence that bounds the cycle - alone on its SIMD and puts each helper behind a model wavefront (equal priorities: lowering the helper's with
-// s_setprio measured 0.5 % slower).  Hand-offs as before: the per-iteration barrier and the bounded PoseWait.
+// 384-thread workgroups = 2 robot groups x (walker, model, helper), six wavefronts on the four SIMDs of a compute unit; the first four waves of a workgroup get
+// the four SIMDs and waves i and i + 4 share one (scripts/ubench/wave_placement.hip: every workgroup measured).  Hand-offs as before: the per-iteration
+// barrier and the bounded PoseWait.
+// The helper also runs the front of the walker's updateWalk - getLimit and the desired body velocities (walk_velocity_front), first thing in its iteration - while
+// the walker runs its state machine and the half of the stepper that does not need them (cycle_front<..., FRONT_HERE = false>); a second bounded wait hands over.
+// The order is [W0, W1, M0, M1, H0, H1]: each helper shares the SIMD of ITS WALKER.  The walker is a latency-bound chain that leaves most issue slots of its SIMD
+// free; the model wavefront's IK / FK is dense FP64 and leaves few - behind it the helper's work only queues (with the front there as well the cycle measured
+// 25 % longer than without, behind the walker 8 % shorter: DESIGN.md 4.1a).  The helper raises its priority for the front alone, which the walker waits for.
 template <int L, int NJ, unsigned F, bool HELPER = false>
 __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(DevState st, const SharedConsts<L, NJ> *gc, ResidentArgs A, unsigned rt_flags) {
   using R = RobotFields;
@@ -1116,8 +1122,8 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
   const int lane = threadIdx.x & 63;
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int pair = wib & 1;
-  // the model wavefront of pair 0 decides what the next iteration is: it has the time to spare (HELPER: the helper of pair 0, in the order [M0, M1, W0, W1, H0, H1])
-  const bool walker = HELPER ? (wib >> 1) == 1 : wib < 2, helper = HELPER && wib >= 4, leader = wib == (HELPER ? 4 : 2);
+  // the model wavefront of pair 0 decides what the next iteration is: it has the time to spare (HELPER: the helper of pair 0, in the order [W0, W1, M0, M1, H0, H1])
+  const bool walker = wib < 2, helper = HELPER && wib >= 4, leader = wib == (HELPER ? 4 : 2);
   const int64_t wave = (int64_t(blockIdx.x) - 1) * 2 + pair;
   const bool active = wave < A.n_waves;
   const int64_t rob0 = wave * RPW;
@@ -1168,6 +1174,7 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
   // wavefront's idle half fills up.
   constexpr bool POSE_SPLIT = (F & (F_DYN | F_AUTO)) == 0;
   if (POSE_SPLIT && walker && lane == 0) X.pose_done[pair] = 0;
+  if constexpr (HELPER) if (walker && lane == 0) X.front_done[pair] = 0;
   __syncthreads();
   const CycleParams &P = C.P;
   Group<L> g{grp * L};
@@ -1203,7 +1210,10 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
         mb[7 * 64] = pp.x, mb[8 * 64] = pp.y, mb[9 * 64] = pp.z, mb[10 * 64] = pn.x, mb[11 * 64] = pn.y, mb[12 * 64] = pn.z;
       }
     }
-    if constexpr (HELPER) X.leg_word[pair][cycle & 1][lane] = s.word; // (the helper evaluates the candidates and picks the group's leg)
+    if constexpr (HELPER) { // (the helper evaluates the candidates and picks the group's leg; the tips are for its velocity front)
+      X.leg_word[pair][cycle & 1][lane] = s.word;
+      X.tip_xy[pair][cycle & 1][0][lane] = s.tip.x, X.tip_xy[pair][cycle & 1][1][lane] = s.tip.y;
+    }
     else X.pose_c[pair][cycle & 1][lane] = walk_plane_control_candidate<L, NJ>(s.word, C, P, swing_c_count_u); // (the model wavefront picks the group's leg)
   };
   if (POSE_SPLIT && walker && active) publish_for_pose(0, true); // (iteration 0 is a bubble: its closing barrier comes before any pose)
@@ -1341,6 +1351,44 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
     if (lane == 0) *const_cast<volatile unsigned *>(&X.pose_done[pair]) = c_front + 1;
     }
   };
+  // The front of the walker's updateWalk of the cycle it is starting (HELPER): getLimit and the desired body velocities, into the tile's VLIN / VANG.  This
+  // wavefront owns them, the bracket memo (its own fb) and the shaping's wave-uniform shortcuts for the length of the loop.  It reads what was complete at the
+  // last barrier: the robot word, its own velocities of the last cycle, the tips the walker left, the held command.  A FRESH command it takes itself, from the
+  // same source and by the same loads as resident_take_inputs<ROBOT_VEL> - the walker is writing that group into the tile right now.
+  // (A direct post loads nothing for robots past n_robots: those lanes hold 0 here where the walker's tile keeps its old value.  No lane reads them - `grp` is
+  //  clamped to the last live robot of the wave above, so every shuffle source below and every value the wave-uniform shortcuts see belongs to a live robot,
+  //  the same on both wavefronts.  Without that clamp this would need the tile's old value instead.)
+  const auto front_of_cycle = [&](const u64 h0, const u64 h1) __attribute__((always_inline)) {
+    if constexpr (HELPER) {
+      __builtin_amdgcn_s_setprio(3); // (the walker - same SIMD - is about to wait for this: measured, profiles/r08_probe_front_on_helper.txt)
+      double vin_x, vin_y, win;
+      if (h0 == u64(c_front) + 1 && (unsigned(h1) & (1u << RG_VEL)) != 0) {
+        const int field = lane / RPW;
+        const int64_t rob = wave * RPW + (lane - field * RPW);
+        double v = 0.0; // lane = field x robots-per-wave + robot, as the tile holds the group
+        if (unsigned(h1) & kResidentDirect) {
+          const int set = int((h1 >> 16) & 3);
+          const double *lin = bound_array(A, set, BND_LIN), *ang = bound_array(A, set, BND_ANG);
+          if (lane < 3 * RPW && rob < st.n_robots) v = field < 2 ? ld_agent_f64(lin + rob * 2 + field) : ld_agent_f64(ang + rob);
+        } else {
+          const int pos = int((h1 >> (16 + 8 * RG_VEL)) & 0xff);
+          const double *rec = A.rin + ((int64_t(pos) * A.n_waves + wave) * RIN_COUNT + RIN_VEL) * RPW;
+          if (lane < 3 * RPW) v = ld_agent_f64(rec + lane);
+        }
+        vin_x = __shfl(v, grp), vin_y = __shfl(v, RPW + grp), win = __shfl(v, 2 * RPW + grp);
+      } else {
+        vin_x = rb.get(R::VIN), vin_y = rb.get(R::VIN + 1), win = rb.get(R::WIN);
+      }
+      const int rword = rb.geti(R::I_WORD); // (as the last cycle left it: the walker stores this cycle's behind the flag below)
+      const double tip_x = X.tip_xy[pair][c_front & 1][0][lane], tip_y = X.tip_xy[pair][c_front & 1][1][lane];
+      double vx, vy, vw;
+      (void)walk_velocity_front<L, NJ, F>(C, P, rb, g, fb, vin_x, vin_y, win, tip_x, tip_y, rword & 3, false, vx, vy, vw);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+      if (lane == 0) *const_cast<volatile unsigned *>(&X.front_done[pair]) = c_front + 1;
+      __builtin_amdgcn_s_setprio(0);
+    }
+  };
   // odometry_ideal_ of the cycle whose walker half ran one iteration ago: the desired body velocity travelled with the poser tip (mailbox `mb`)
   const auto odometry_of_cycle = [&](const double *mb) __attribute__((always_inline)) {
     const V3 ov{mb[192], mb[256], mb[320]};
@@ -1351,7 +1399,7 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
       }
     }
   };
-  constexpr int kWalkerThread = HELPER ? 128 : 0, kModelThread = HELPER ? 0 : 128; // (development stamps: the first thread of each role's wavefront of pair 0)
+  constexpr int kWalkerThread = 0, kModelThread = 128; // (development stamps: the first thread of each role's wavefront of pair 0)
   if (walker) {
     // ---------------------------------------------------------------- walker wavefront: cycle_front of cycle c_front
     for (;;) {
@@ -1363,8 +1411,14 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
         resident_take_inputs<RPW, POSE_SPLIT ? ROBOT_VEL : ROBOT_ALL, false>(A, c_front, h0, h1, wave, lane, tile, tile_i, dirty, held, st.n_robots);
         SHC_TICK(21);
         const PoseWait<RPW> pose_wait{&X.pose_done[pair], c_front + 1, A.ticks_per_ms, &held.fault};
-        cycle_front<L, NJ, F, false, LegInRing<NJ>, false, !POSE_SPLIT>(s, out, C, rb, pk, g, leg, st.legd, ns, slot, dirty, manual_live, false, nullptr, nullptr,
-                                                                        LegInRing<NJ>{}, fb, nullptr, pose_wait);
+        if constexpr (HELPER) { // the velocity front of this cycle comes from the helper
+          const PoseWait<RPW> front_wait{&X.front_done[pair], c_front + 1, A.ticks_per_ms, &held.fault};
+          cycle_front<L, NJ, F, false, LegInRing<NJ>, false, !POSE_SPLIT, false>(s, out, C, rb, pk, g, leg, st.legd, ns, slot, dirty, manual_live, false, nullptr, nullptr,
+                                                                                 LegInRing<NJ>{}, fb, nullptr, pose_wait, front_wait);
+        } else {
+          cycle_front<L, NJ, F, false, LegInRing<NJ>, false, !POSE_SPLIT>(s, out, C, rb, pk, g, leg, st.legd, ns, slot, dirty, manual_live, false, nullptr, nullptr,
+                                                                          LegInRing<NJ>{}, fb, nullptr, pose_wait);
+        }
 #ifdef SHC_ABLATE
         if (!(P.debug_skip & 65536))
 #endif
@@ -1386,14 +1440,18 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
       }
       SHC_TICK(23);
       if (kind == IT_EXIT) break;
-      SHC_R2_ITER_END(kWalkerThread, 19, 20, 21, 2, 3, 4, 5, 6, 7, 16, 8, 17, 15, 29, 22, 23);
+      if constexpr (HELPER) { // (no front on this wavefront: stamp 18 is the end of its wait for the helper's)
+        SHC_R2_ITER_END(kWalkerThread, 19, 20, 21, 2, 3, 4, 6, 7, 18, 16, 8, 17, 15, 29, 22, 23);
+      } else {
+        SHC_R2_ITER_END(kWalkerThread, 19, 20, 21, 2, 3, 4, 5, 6, 7, 16, 8, 17, 15, 29, 22, 23);
+      }
       if (kind == IT_REAL) ++c_front;
       prev_real = kind == IT_REAL;
       __syncthreads();
       ++k;
     }
   } else if (helper) {
-    // ---------------------------------------------------------------- helper wavefront (HELPER): the pose of cycle c_front, the odometry of cycle c_back, the leader's duty
+    // ---------------------------------------------------------------- helper wavefront (HELPER): the velocity front and the pose of cycle c_front, the odometry of cycle c_back, the leader's duty
     if constexpr (HELPER) for (;;) {
       SHC_R2_ITER_BEGIN();
       const int kind = __builtin_amdgcn_readfirstlane(int(X.ctrl[k & 3][0]));
@@ -1404,6 +1462,8 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
       if (leader && kind != IT_EXIT) leader_decide(kind, nk, nh0v, nh1v);
       if (active) { // (the helper of an inactive pair only keeps the barriers)
         SHC_TICK(24);
+        if (kind == IT_REAL) front_of_cycle(h0, h1); // (first: the walker waits for it in mid-stepper, for the pose only at updateStance)
+        SHC_TICK(1);
         if (kind == IT_REAL) pose_of_cycle(h0, h1);
         SHC_TICK(25);
         if (prev_real) { // the cycle whose walker half ran one iteration ago
@@ -1415,7 +1475,7 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
       if (leader && kind != IT_EXIT && lane == 0) leader_announce(nk, nh0v, nh1v);
       SHC_TICK(14);
       if (kind == IT_EXIT) break;
-      SHC_R2_ITER_END(256, 19, 29, 24, 30, 25, 26, 14);
+      SHC_R2_ITER_END(256, 19, 29, 24, 1, 30, 25, 26, 14);
       if (kind == IT_REAL) ++c_front;
       prev_real = kind == IT_REAL;
       __syncthreads();

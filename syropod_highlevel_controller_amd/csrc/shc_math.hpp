@@ -348,6 +348,20 @@ SHC_HD V3 quartic_bezier_dot(V3 p0, V3 p1, V3 p2, V3 p3, V3 p4, double t) {
   r = fma3(p3 - p2, 12.0 * s * t * t, r);
   return fma3(p4 - p3, 4.0 * t * t * t, r);
 }
+// ... with the four weights evaluated apart - ahead of the nodes, where a caller has t before it has them.  The expressions are those above.
+struct BezierDotWeights {
+  double w0, w1, w2, w3;
+};
+SHC_HD BezierDotWeights quartic_bezier_dot_weights(double t) {
+  double s = 1.0 - t;
+  return BezierDotWeights{4.0 * s * s * s, 12.0 * s * s * t, 12.0 * s * t * t, 4.0 * t * t * t};
+}
+SHC_HD V3 quartic_bezier_dot(V3 p0, V3 p1, V3 p2, V3 p3, V3 p4, const BezierDotWeights &w) {
+  V3 r = (p1 - p0) * w.w0;
+  r = fma3(p2 - p1, w.w1, r);
+  r = fma3(p3 - p2, w.w2, r);
+  return fma3(p4 - p3, w.w3, r);
+}
 
 // ---------------------------------------------------------------- small SPD solve  A x = b,  A = A^T > 0  (N <= 6)
 // Reciprocal / reciprocal square root for the DLS solve, whose arithmetic form is this engine's own (shc_leg.hpp): the

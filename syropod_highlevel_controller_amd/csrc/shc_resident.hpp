@@ -684,7 +684,11 @@ extern "C" int shc_engine_resident_end(shc_engine *e, int64_t *cycles_run) {
                            "pose read + updateStance", "control input for the next pose published", "mailbox written", "to the barrier"};
     const double its = c.dbg[1] ? double(c.dbg[1]) : 1.0;
     fprintf(stderr, "[res2 timing] walker of pair 0, mean clocks per phase:\n");
-    for (int i = 0; i < int(sizeof(order) / sizeof(int)); ++i) fprintf(stderr, "[res2 timing]   walker t%-2d %-58s %7.0f\n", order[i], wname[i], double(c.dbg[8 + order[i]]) / its);
+    for (int i = 0; i < int(sizeof(order) / sizeof(int)); ++i) {
+      if (r->helper_wave && order[i] == 5) continue; // (the three-role form: getLimit and the shaping are the helper's "front")
+      if (r->helper_wave && order[i] == 16) fprintf(stderr, "[res2 timing]   walker t%-2d %-58s %7.0f\n", 18, "stepper, first half + wait for the front", double(c.dbg[8 + 18]) / its);
+      fprintf(stderr, "[res2 timing]   walker t%-2d %-58s %7.0f\n", order[i], r->helper_wave && order[i] == 6 ? "command predicate" : wname[i], double(c.dbg[8 + order[i]]) / its);
+    }
     const int morder[] = {29, 24, 30, 25, 31, 26, 9, 10, 11, 12, 27, 13, 28, 14};
     const char *mname[] = {"control words (LDS) read", "leader: gate, what the next iteration is, header prefetch issued", "pose inputs of the cycle taken",
                            "updateCurrentPose of the walker's cycle + flag", "leg inputs in force, joint efforts prefetched", "mailbox read, odometry, admittance",
@@ -697,8 +701,8 @@ extern "C" int shc_engine_resident_end(shc_engine *e, int64_t *cycles_run) {
       fprintf(stderr, "[res2 timing]   model  t%-2d %-58s %7.0f\n", morder[i], mname[i], double(c.dbg[40 + morder[i]]) / mits);
     }
     if (r->helper_wave) {
-      const int horder[] = {29, 24, 30, 25, 26, 14};
-      const char *hname[] = {"control words (LDS) read", "leader: gate, what the next iteration is, header prefetch issued", "pose inputs of the cycle taken",
+      const int horder[] = {29, 24, 1, 30, 25, 26, 14};
+      const char *hname[] = {"control words (LDS) read", "leader: gate, what the next iteration is, header prefetch issued", "front: command, getLimit, velocity shaping + flag", "pose inputs of the cycle taken",
                              "leg words reduced, updateCurrentPose of the walker's cycle + flag", "odometry", "control words written (leader: waits for its loads)"};
       const double hits = c.dbg[73] ? double(c.dbg[73]) : 1.0;
       fprintf(stderr, "[res2 timing] helper wavefront of pair 0 (the leader), mean clocks per phase:\n");
