@@ -1206,7 +1206,8 @@ int shc_fleet_get_observations_device(shc_fleet *f, const shc_obs_spec *spec, vo
  * conversion, the touchdown flag and (rough terrain mode) touchdown detection with its step planes, the switch to the tip-force estimate at the
  * first joint effort (with its one stream synchronisation), the manual-pose flag, the entries of a shorter leg's joints on a mixed-DOF robot.
  * One half of a pair may be named alone.  Columns of legs or joints the morphology lacks and columns [width, row_stride) are ignored.  The
- * pose reset mode stays on its own setter; resident mode and the K-cycle launches take their inputs as before.
+ * pose reset mode stays on its own setter; resident mode takes its inputs as before, the K-cycle launches theirs through
+ * shc_engine_step_k_actions below.
  * The fleet form is defined the same way against shc_fleet_set_inputs_device: robot r of a part reads row ids[r] - its CALLER's instance id -
  * of `actions` ([n][row_stride]) through the ids device I/O keeps on the device; one kernel per part on the part's own stream, no allocation
  * after the fleet's first device I/O call, the staging footprint unchanged.
@@ -1240,6 +1241,48 @@ int64_t shc_act_width(const shc_act_spec *spec);                       /* column
 int shc_act_column(const shc_act_spec *spec, int field, int leg, int k); /* column of component k of `field` (leg ignored for robot fields); -1 if absent */
 int shc_engine_set_actions(shc_engine *e, const shc_act_spec *spec, const void *actions, int on_device);
 int shc_fleet_set_actions_device(shc_fleet *f, const shc_act_spec *spec, const void *actions /* [n][row_stride], caller's order */);
+/*
+ * Rollout tensors: the two passes above for the K-cycle launches.  shc_engine_step_k_actions runs K cycles in one launch, cycle k with the rows
+ * of cycle k of one dense DEVICE array [K][n][A] of float64 or float32 - what a policy emits for a rollout; shc_engine_get_step_k_observations
+ * hands q / qd of a range of those cycles back as one dense DEVICE array [cycles][n][D].  The specs, rows and column rules are those of the
+ * action and observation passes; there is no host form, as shc_engine_step_k has none.
+ * cycle_stride: elements between the rows of consecutive cycles - row i of cycle k lies at array + k * cycle_stride + i * row stride; 0 = n x
+ * the row stride, otherwise at least that.  A view big[:, :, 5:5 + A] of a wider 3-D array is row_stride = its columns, cycle_stride = n x that
+ * or more.
+ * DEFINITION, actions.  After the call the engine is byte for byte what shc_engine_step_k(e, K, in) leaves - every robot's state record and
+ * auxiliary blob, every slot of the K-deep output ring, the held inputs and every host-side fact - when each member of `in` is a dense float64
+ * device array holding static_cast<double> of the matching columns, and NULL for every group the spec does not name.  Columns of legs or joints
+ * the morphology lacks and columns [width, row_stride) are ignored.  One kernel converts the named columns of all K cycles into K-deep float64
+ * arrays the engine owns, and shc_engine_step_k itself runs on those: the batch kernel or the serial form, a pending adjusted parameter's first
+ * cycle, touchdown detection, the first-effort switch, the split halves and the normalisation of the IMU quaternion are that call's, unchanged.
+ * DEFINITION, observations.  SHC_OBS_Q and SHC_OBS_QD only (the ring holds joints).  Column c of row (k, i) holds the double
+ * shc_engine_get_step_k_joint_state(e, first_cycle + k, ..) writes for that robot, leg and joint - unchanged for SHC_OBS_F64, static_cast<float>
+ * for SHC_OBS_F32; `pad` where the robot has no such leg or joint (the joints a shorter leg of a mixed-DOF robot lacks hold what that getter holds
+ * there); columns [width, row_stride) and rows of other cycles are not touched.  The call writes nothing into an engine.
+ * LIFETIMES.  `actions` is read by the staging kernel alone, on the engine's stream: it must be ready there, as for shc_engine_set_actions, and
+ * may be rewritten as soon as that stream has passed the call - an event recorded on the engine's stream right after the call is enough.  That
+ * is LESS than shc_engine_step_k asks of its own arrays (valid until the engine is joined): that rule applies to the staged arrays, which the
+ * engine owns.  They are allocated by the first call that needs them, grown (never shrunk) by a call that needs more - that call joins the engine
+ * and drains its stream first - and freed with the engine; an engine with split launches in flight is joined (events, no host wait) before a
+ * call overwrites them.  The observation call joins split launches, as shc_engine_get_step_k_joint_state, and runs on the engine's stream.
+ * FLEET.  Defined the same way against shc_fleet_step_k and shc_fleet_get_step_k_joints_device, in the row geometry of shc_fleet_shape or
+ * larger: robot r of a part uses row ids[r] - its CALLER's instance id - of each cycle of the [K][n][row_stride] array.  Per part one staging
+ * launch and one read launch, on the part's stream; the staging is the part's K-deep staging of shc_fleet_step_k, counted by
+ * shc_fleet_io_bytes: no allocation after the first call of a given K and set of groups.  The STREAMS rules of shc_fleet_step_k apply.
+ * REFUSALS (decided before anything changes; a fleet asks every part first).  SHC_ERR_INVALID_ARG: a NULL handle, spec or array; whatever the
+ * action / observation pass refuses of a spec; legs / dof below the engine's or the fleet's shape; an array not aligned to its element size;
+ * n_cycles outside 1 .. 4096, or a cycle range outside the latest launch (or no launch yet); cycle_stride non-zero and below n x the row stride;
+ * an output ring or K-deep staging of 2 GiB or more; SHC_ACT_LINEAR_XY without SHC_ACT_ANGULAR or one IMU field without the other (the K-cycle
+ * launches take those in pairs).  SHC_ERR_UNSUPPORTED: the two pose-input fields (set them beforehand: held for the K cycles); an observation
+ * field other than q / qd; an engine still starting up; a fleet that spans devices.  SHC_ERR_BUSY: resident mode.
+ */
+int shc_engine_step_k_actions(shc_engine *e, int n_cycles, const shc_act_spec *spec, const void *actions /* device, [K][n][row_stride] */, int64_t cycle_stride);
+int shc_engine_get_step_k_observations(shc_engine *e, int first_cycle, int n_cycles, const shc_obs_spec *spec, void *out /* device, [n_cycles][n][row_stride] */,
+                                       int64_t cycle_stride);
+int shc_fleet_step_k_actions_device(shc_fleet *f, int n_cycles, const shc_act_spec *spec, const void *actions /* [K][n][row_stride], caller's order */,
+                                    int64_t cycle_stride);
+int shc_fleet_get_step_k_observations_device(shc_fleet *f, int first_cycle, int n_cycles, const shc_obs_spec *spec, void *out /* [n_cycles][n][row_stride], caller's order */,
+                                             int64_t cycle_stride);
 /*
  * Foothold pass: the externally requested tip targets / default stance poses of rough terrain mode (shc_external_target above) of every robot
  * taken from - or read back into - one dense [n][F] array of float64 or float32, in one kernel per engine (per part of a fleet).  What a

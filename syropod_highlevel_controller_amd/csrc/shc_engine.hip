@@ -300,6 +300,8 @@ struct shc_engine {
   double *k_out = nullptr;              // shc_engine_step_k: q / qd of each of the K cycles of the latest launch, [K][dof planes][n_slots] double2
   size_t k_out_bytes = 0;
   int k_out_cycles = 0;
+  char *k_in = nullptr;                 // shc_engine_step_k_actions: the K-deep float64 input arrays staged from the caller's tensor (shc_rollout.hpp); grows on demand, kept
+  size_t k_in_bytes = 0;
   bool side_busy = false;               // launches are outstanding on the split streams that the engine's stream has not been ordered after
   bool main_dirty = true;               // work other than steps was enqueued on the engine's stream since the last split step
   struct shc_checkpoint *checkpoints = nullptr; // the registry of this engine's device checkpoints (shc_checkpoint.hpp): released with the engine
@@ -1004,6 +1006,7 @@ extern "C" int shc_engine_destroy(shc_engine *e) {
   (void)hipFree(e->d_stage);
   (void)hipFree(e->d_span);
   (void)hipFree(e->k_out);
+  (void)hipFree(e->k_in);
   (void)hipFree(e->d_health);
   if (e->half_stream[0]) { // (the streams belong to the process-wide pair)
     (void)hipEventDestroy(e->ev_main);
@@ -1605,6 +1608,7 @@ static int derive_tips(shc_engine *e) {
 #include "shc_health.hpp"   // the reference's IK / clamping warnings per robot, a restore map and the selected robots: shc_engine_scan_health
 #include "shc_observe.hpp"  // chosen fields of every robot as one dense [rows][D] array: shc_engine_get_observations
 #include "shc_actions.hpp"  // chosen input groups of every robot from one dense [n][A] array: shc_engine_set_actions
+#include "shc_rollout.hpp"  // K cycles per launch from one dense [K][n][A] array, their joints as one dense [cycles][n][D] array: shc_engine_step_k_actions / _get_step_k_observations
 
 template <int NJ>
 static Pose host_fk_tip_pose(const shc_params &p, int leg, const double *q) {

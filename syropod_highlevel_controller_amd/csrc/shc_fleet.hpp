@@ -464,6 +464,7 @@ extern "C" int shc_fleet_all_gather_joints(shc_fleet *f, double **device_buffers
 #include "shc_fleet_step_k.hpp" // shc_fleet_step_k, shc_fleet_get_step_k_joints_device: K cycles per launch from K-deep device arrays
 #include "shc_fleet_observe.hpp" // shc_fleet_get_observations_device: chosen fields of every robot straight into the caller's rows
 #include "shc_fleet_actions.hpp" // shc_fleet_set_actions_device: chosen input groups of every robot straight from the caller's rows
+#include "shc_fleet_rollout.hpp" // shc_fleet_step_k_actions_device / _get_step_k_observations_device: K cycles per launch from / into the caller's dense tensors
 #include "shc_fleet_footholds.hpp" // shc_fleet_set_footholds_device / _get_footholds_device: every robot's tip-target requests from / into the caller's rows
 
 // ================================================================================================ one process per GPU: the exchange over peer copies

@@ -107,17 +107,8 @@ extern "C" int shc_fleet_step_k(shc_fleet *f, int n_cycles, const shc_fleet_inpu
   }
   if ((rc = fleet_io_prepare(f)) != SHC_OK) return rc;
   for (auto &p : f->parts) { // staging that is too small: drained (the part's launches may still read it), released, allocated again
-    const size_t need = fleet_step_k_stage_bytes(f, p, n_cycles, rows);
-    if (need <= p.k_stage_bytes) continue;
     HIP_TRY(hipSetDevice(p.device));
-    if (p.k_stage) {
-      if ((rc = shc_engine_join(p.engine)) != SHC_OK) return rc;
-      HIP_TRY(hipStreamSynchronize(p.engine->stream));
-      HIP_TRY(hipFree(p.k_stage));
-      p.k_stage = nullptr, p.k_stage_bytes = 0;
-    }
-    HIP_TRY(hipMalloc(&p.k_stage, need));
-    p.k_stage_bytes = need;
+    if ((rc = rollout_stage_room(p.engine, p.k_stage, p.k_stage_bytes, fleet_step_k_stage_bytes(f, p, n_cycles, rows))) != SHC_OK) return rc;
   }
   for (auto &p : f->parts) {
     const int64_t n_rows = int64_t(p.ids.size());

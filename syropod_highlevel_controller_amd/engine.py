@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "shc_fleet_step_k", "shc_fleet_get_step_k_joints_device",
     "shc_obs_width", "shc_obs_column", "shc_engine_get_observations", "shc_fleet_get_observations_device",
     "shc_act_width", "shc_act_column", "shc_engine_set_actions", "shc_fleet_set_actions_device",
+    "shc_engine_step_k_actions", "shc_engine_get_step_k_observations", "shc_fleet_step_k_actions_device", "shc_fleet_get_step_k_observations_device",
     "shc_foothold_width", "shc_foothold_column", "shc_engine_set_footholds", "shc_engine_get_footholds", "shc_fleet_set_footholds_device",
     "shc_fleet_get_footholds_device",
     "shc_peer_alloc", "shc_peer_open", "shc_peer_close", "shc_peer_scatter",
@@ -301,6 +302,35 @@ def _rows_array(a, what: str, host: Optional[str] = None):
     if strides[1] != dt.itemsize or strides[0] % dt.itemsize or strides[0] < columns * dt.itemsize:
         raise ValueError(f"{what}: the elements of a row must be contiguous and the rows a whole number of elements apart (strides {tuple(strides)})")
     return C.c_void_p(cai["data"][0]), dt, rows, columns, strides[0] // dt.itemsize, 1, None
+
+
+def _cycles_array(a, what: str):
+    """(pointer, numpy dtype, cycles, rows, columns, row stride, cycle stride - both in elements) of a 3-D float32 / float64 DEVICE array
+    (``__cuda_array_interface__``) whose rows are contiguous: a view ``big[:, :, 5:5 + A]`` of a wider array included.  The K-cycle launches have
+    no host form: a numpy array is a TypeError."""
+    if isinstance(a, np.ndarray):
+        raise TypeError(f"{what}: device arrays only (an object with __cuda_array_interface__, e.g. a torch tensor); the K-cycle launches have no host form")
+    cai = getattr(a, "__cuda_array_interface__", None)
+    if cai is None:
+        raise TypeError(f"{what}: device arrays only (an object with __cuda_array_interface__) - got {type(a).__name__}")
+    if cai["typestr"] not in ("<f4", "<f8") or len(cai["shape"]) != 3:
+        raise ValueError(f"{what}: a 3-D float32 or float64 device array is expected, got {cai['typestr']} {tuple(cai['shape'])}")
+    dt = np.dtype(cai["typestr"])
+    size = dt.itemsize
+    cycles, rows, columns = (int(x) for x in cai["shape"])
+    strides = cai.get("strides") or (rows * columns * size, columns * size, size)
+    row = strides[1] // size if rows > 1 else max(columns, 1)
+    if (columns > 1 and strides[2] != size) or (rows > 1 and (strides[1] % size or strides[1] < columns * size)) or \
+            (cycles > 1 and (strides[0] % size or strides[0] < rows * row * size)):
+        raise ValueError(f"{what}: the elements of a row must be contiguous, the rows a whole number of elements apart and the cycles at least "
+                         f"rows x that (strides {tuple(strides)})")
+    return C.c_void_p(cai["data"][0]), dt, cycles, rows, columns, row, strides[0] // size if cycles > 1 else 0
+
+
+def _new_device_array(shape, dtype, device):
+    """An uninitialised torch tensor on the engine's device: what step_k_observations returns when it is given no array to fill."""
+    import torch
+    return torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device="cuda" if device is None else f"cuda:{device}")
 
 
 def _check_rows(what: str, name: str, rows: int, columns: int, n: int, width: int):
@@ -631,6 +661,10 @@ def lib():
         L.shc_act_column.argtypes = [C.POINTER(ActSpec), C.c_int, C.c_int, C.c_int]
         L.shc_engine_set_actions.argtypes = [C.c_void_p, C.POINTER(ActSpec), C.c_void_p, C.c_int]
         L.shc_fleet_set_actions_device.argtypes = [C.c_void_p, C.POINTER(ActSpec), C.c_void_p]
+        L.shc_engine_step_k_actions.argtypes = [C.c_void_p, C.c_int, C.POINTER(ActSpec), C.c_void_p, C.c_int64]
+        L.shc_engine_get_step_k_observations.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(ObsSpec), C.c_void_p, C.c_int64]
+        L.shc_fleet_step_k_actions_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(ActSpec), C.c_void_p, C.c_int64]
+        L.shc_fleet_get_step_k_observations_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(ObsSpec), C.c_void_p, C.c_int64]
         L.shc_foothold_width.restype = C.c_int64
         L.shc_foothold_width.argtypes = [C.POINTER(FootholdSpec)]
         L.shc_foothold_column.argtypes = [C.POINTER(FootholdSpec), C.c_int, C.c_int, C.c_int]
@@ -831,7 +865,7 @@ class BatchEngine:
         else:
             _check(self.L.shc_engine_create_with_tables(C.byref(params), C.byref(tables), self.n, device, C.c_void_p(stream),
                                                         C.byref(h)), "shc_engine_create_with_tables")
-        self.h = h
+        self.h, self.device = h, int(device)
 
     def close(self):
         if getattr(self, "h", None):
@@ -937,6 +971,46 @@ class BatchEngine:
         qd = np.empty_like(q)
         _check(self.L.shc_engine_get_step_k_joint_state(self.h, int(k), _p(q), _p(qd), 0), "shc_engine_get_step_k_joint_state")
         return q, qd
+
+    def step_k_actions(self, actions, fields, legs: Optional[int] = None, dof: Optional[int] = None):
+        """K = ``actions.shape[0]`` cycles in one launch, cycle k with the rows ``actions[k]`` (shc_engine_step_k_actions): ``step_k`` driven by one
+        3-D float32 / float64 DEVICE array (K, n, at least A columns) - ``action_columns(fields, legs, dof)`` names the columns; a view
+        ``big[:, :, 5:5 + A]`` of a wider tensor will do.  The engine is left as ``step_k`` leaves it when given the columns as float64 arrays;
+        groups not named are held; velocity and IMU are named in pairs, the pose inputs are refused.  Read on the engine's stream without a host
+        wait: the array may be rewritten once that stream has passed the call.  A numpy array is a TypeError (device arrays only)."""
+        legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
+        ptr, dt, cycles, rows, columns, stride, cycle_stride = _cycles_array(actions, "step_k_actions")
+        spec = act_spec(fields, legs, dof, dt, stride)
+        _check_rows("step_k_actions", "actions[k]", rows, columns, self.n, int(self.L.shc_act_width(C.byref(spec))))
+        _check(self.L.shc_engine_step_k_actions(self.h, cycles, C.byref(spec), ptr, cycle_stride), "shc_engine_step_k_actions")
+
+    def step_k_observations(self, fields=("q", "qd"), dtype="float32", out=None, first: int = 0, count: Optional[int] = None, pad: float = 0.0,
+                            legs: Optional[int] = None, dof: Optional[int] = None):
+        """q / qd (``fields``: "q", "qd" or both, in column order) of cycles [first, first + count) of the latest ``step_k`` /
+        ``step_k_actions`` as one (count, n, D) DEVICE array in one pass (shc_engine_get_step_k_observations):
+        ``observation_columns(fields, legs, dof)`` names the columns, every value is what ``step_k_joints(first + k)`` holds, cast to the
+        element type, ``pad`` where the row geometry (legs, dof) is larger than the robot.  out: a 3-D float32 / float64 device array (a view
+        of some columns of a wider one will do) whose first D columns are filled on the engine's stream without a host wait - count None: as
+        many cycles as it has; returns None.  Without out (give count) a new torch tensor of ``dtype`` on the engine's device is filled and
+        returned."""
+        legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
+        made = None
+        if out is None:
+            if count is None:
+                raise ValueError("step_k_observations: give count, or an array to fill")
+            spec = obs_spec(fields, legs, dof, dtype, 0, pad)
+            width = int(self.L.shc_obs_width(C.byref(spec)))
+            if width < 0:
+                _check(SHC_ERR_INVALID_ARG, "shc_engine_get_step_k_observations")
+            out = made = _new_device_array((max(int(count), 0), self.n, width), dtype, getattr(self, "device", None))
+        ptr, dt, cycles, rows, columns, stride, cycle_stride = _cycles_array(out, "step_k_observations")
+        count = cycles if count is None else int(count)
+        spec = obs_spec(fields, legs, dof, dt, stride, pad)
+        if count > cycles:
+            raise ValueError(f"step_k_observations: out has {cycles} cycles, {count} are asked for")
+        _check_rows("step_k_observations", "out[k]", rows, columns, self.n, int(self.L.shc_obs_width(C.byref(spec))))
+        _check(self.L.shc_engine_get_step_k_observations(self.h, int(first), count, C.byref(spec), ptr, cycle_stride), "shc_engine_get_step_k_observations")
+        return made
 
     def synchronize(self):
         _check(self.L.shc_engine_synchronize(self.h), "synchronize")

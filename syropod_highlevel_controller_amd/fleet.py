@@ -326,6 +326,46 @@ class MixedFleet:
         pqd = None if qd is None else _engine._device_array(qd, "<f8", shape, "qd")
         _engine._check(self.L.shc_fleet_get_step_k_joints_device(self.h, int(first), int(count), pq, pqd), "shc_fleet_get_step_k_joints_device")
 
+    def step_k_actions(self, actions, fields, legs=None, dof=None):
+        """K = ``actions.shape[0]`` cycles in one launch per part, cycle k with the rows ``actions[k]`` in the caller's instance order
+        (shc_fleet_step_k_actions_device): ``step_k`` driven by one 3-D float32 / float64 DEVICE array (K, n, at least A columns), a view
+        ``big[:, :, 5:5 + A]`` of a wider tensor included.  ``engine.action_columns(fields, legs, dof)`` names the columns (legs / dof default:
+        max_legs / max_dof); the fleet is left as ``step_k`` leaves it when given the columns as float64 arrays, groups not named are held,
+        columns of legs and joints a morphology lacks are ignored.  No host wait, and the stream rules of ``set_inputs``.  A numpy array is a
+        TypeError (device arrays only)."""
+        legs, dof = self.max_legs if legs is None else legs, self.max_dof if dof is None else dof
+        ptr, dt, cycles, rows, columns, stride, cycle_stride = _engine._cycles_array(actions, "step_k_actions")
+        spec = _engine.act_spec(fields, legs, dof, dt, stride)
+        _engine._check_rows("step_k_actions", "actions[k]", rows, columns, self.n, int(self.L.shc_act_width(C.byref(spec))))
+        _engine._check(self.L.shc_fleet_step_k_actions_device(self.h, cycles, C.byref(spec), ptr, cycle_stride), "shc_fleet_step_k_actions_device")
+
+    def step_k_observations(self, fields=("q", "qd"), dtype="float32", out=None, first: int = 0, count=None, pad: float = 0.0, legs=None, dof=None):
+        """q / qd of cycles [first, first + count) of the latest ``step_k`` / ``step_k_actions`` as one (count, n, D) DEVICE array in the
+        caller's instance order, one kernel per part (shc_fleet_get_step_k_observations_device): every value is what ``step_k_joints`` holds,
+        cast to the element type, ``pad`` where a morphology has no such leg or joint.  out: a 3-D float32 / float64 device array (a view of
+        some columns of a wider one will do) - count None: as many cycles as it has; returns None.  Without out (give count) a new torch tensor
+        of ``dtype`` on the fleet's device is filled and returned.  No host wait: complete after ``synchronize()``, or for work queued on a
+        stream after ``order_before(stream)``."""
+        legs, dof = self.max_legs if legs is None else legs, self.max_dof if dof is None else dof
+        made = None
+        if out is None:
+            if count is None:
+                raise ValueError("step_k_observations: give count, or an array to fill")
+            spec = _engine.obs_spec(fields, legs, dof, dtype, 0, pad)
+            width = int(self.L.shc_obs_width(C.byref(spec)))
+            if width < 0:
+                _engine._check(_engine.SHC_ERR_INVALID_ARG, "shc_fleet_get_step_k_observations_device")
+            out = made = _engine._new_device_array((max(int(count), 0), self.n, width), dtype, self.parts()[0][2])
+        ptr, dt, cycles, rows, columns, stride, cycle_stride = _engine._cycles_array(out, "step_k_observations")
+        count = cycles if count is None else int(count)
+        if count > cycles:
+            raise ValueError(f"step_k_observations: out has {cycles} cycles, {count} are asked for")
+        spec = _engine.obs_spec(fields, legs, dof, dt, stride, pad)
+        _engine._check_rows("step_k_observations", "out[k]", rows, columns, self.n, int(self.L.shc_obs_width(C.byref(spec))))
+        _engine._check(self.L.shc_fleet_get_step_k_observations_device(self.h, int(first), count, C.byref(spec), ptr, cycle_stride),
+                       "shc_fleet_get_step_k_observations_device")
+        return made
+
     @staticmethod
     def _stream_handle(stream):
         return C.c_void_p(int(getattr(stream, "cuda_stream", stream) or 0))
