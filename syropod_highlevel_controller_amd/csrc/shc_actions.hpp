@@ -1,7 +1,8 @@
 // shc_actions.hpp — the action pass: chosen input groups of every instance taken from one dense [n][A] array of float64 or float32 in one device
 // pass: shc_act_width, shc_act_column, shc_engine_set_actions.  Included by shc_engine.hip beside shc_observe.hpp (uses the row pattern of shc_rows.hpp,
-// rob_index, leg_field_index, the split-input calls, effort_live and touchdown_detection_kernel of the setters, and the entry-point macros).  The
-// fleet form (shc_fleet_actions.hpp) launches the same kernel with a part's caller ids as the row table.
+// the group table of shc_inputs.hpp - a field of a spec IS an input group: its width, its robot field -, rob_index, leg_field_index, the split-input
+// calls, effort_live and tip_force_given of the setters, and the entry-point macros).  The fleet form (shc_fleet_actions.hpp) launches the same
+// kernel with a part's caller ids as the row table.
 //
 // The definition is the device setters': the pass leaves what shc_engine_set_velocity / _set_imu / _set_pose_input / _set_tip_force /
 // _set_joint_effort leave when they are given the columns as float64 arrays.  Nothing is computed here but the conversion to double and the
@@ -9,32 +10,17 @@
 // (effort_live, the flags, touchdown_detection_kernel).  The field list is launch-uniform: a bit per selected field and the field's first column.
 #pragma once
 
-constexpr int kActFields = SHC_ACT_FIELD_COUNT;
-constexpr int kActRobotFields = SHC_ACT_TIP_FORCE; // the per-robot fields come first in the enum
+constexpr int kActFields = kInputGroups, kActRobotFields = kRobotInputGroups; // the fields are the input groups of shc_inputs.hpp
 static_assert(sizeof(shc_act_spec) == 64 && offsetof(shc_act_spec, row_stride) == 56, "shc_act_spec: 13 int32, 4 bytes of alignment, row_stride");
-static_assert(kActRobotFields == 6 && SHC_ACT_JOINT_EFFORT == 7 && kActFields == 8, "six per-robot fields, then tip force and joint effort");
 
-// columns of a per-robot field, and the robot field its first component is stored at
-__host__ __device__ constexpr int act_robot_width(int field) {
-  return field == SHC_ACT_LINEAR_XY ? 2 : field == SHC_ACT_ANGULAR ? 1 : field == SHC_ACT_IMU_ORIENTATION ? 4 : 3;
-}
-__host__ __device__ constexpr int act_robot_field(int field) {
-  using R = RobotFields;
-  return field == SHC_ACT_LINEAR_XY                   ? R::VIN
-         : field == SHC_ACT_ANGULAR                   ? R::WIN
-         : field == SHC_ACT_IMU_ORIENTATION           ? R::IMUQ
-         : field == SHC_ACT_IMU_ANGULAR_VELOCITY      ? R::GYRO
-         : field == SHC_ACT_POSE_TRANSLATION_VELOCITY ? R::TVI
-                                                      : R::RVI;
-}
 // shc_act_spec for row_layout (shc_rows.hpp)
 struct ActRows {
   using Spec = shc_act_spec;
   static constexpr const char *name = "shc_act_spec", *n_fields_why = ".n_fields outside 1 .. SHC_ACT_FIELD_COUNT";
   static constexpr int fields = kActFields, most_fields = kActFields;
   static constexpr bool has_dof = true;
-  static bool per_leg(int field) { return field >= kActRobotFields; }
-  static int width(int field, int dof) { return field == SHC_ACT_JOINT_EFFORT ? dof : field == SHC_ACT_TIP_FORCE ? 3 : act_robot_width(field); }
+  static bool per_leg(int field) { return input_per_leg(field); }
+  static int width(int field, int dof) { return input_k(field, dof); }
   static const char *own(const Spec *) { return nullptr; }
 };
 
@@ -130,7 +116,7 @@ static int actions_launch(shc_engine *e, const ActArgs &a, const void *in, int f
 // caller has checked everything and - unless `ride` (actions_ride) - joined split steps.
 static int actions_apply(shc_engine *e, const shc_act_spec *spec, const RowLayout &lay, const void *in, int64_t row_stride, const int64_t *ids, bool ride) {
   HIP_TRY(hipSetDevice(e->device));
-  if (lay.mask & (1u << SHC_ACT_POSE_TRANSLATION_VELOCITY | 1u << SHC_ACT_POSE_ROTATION_VELOCITY)) e->rt_flags |= RT_MANUAL_LIVE; // as shc_engine_set_pose_input
+  if (lay.mask & kPoseInputs) e->rt_flags |= RT_MANUAL_LIVE; // as shc_engine_set_pose_input
   int rc;
   if ((lay.mask & (1u << SHC_ACT_JOINT_EFFORT)) && (rc = effort_live(e)) != SHC_OK) return rc; // as shc_engine_set_joint_effort
   ActArgs a{};
@@ -148,21 +134,8 @@ static int actions_apply(shc_engine *e, const shc_act_spec *spec, const RowLayou
     if ((rc = actions_launch(e, a, in, f32, ids, 0, e->n, e->stream)) != SHC_OK) return rc;
     HIP_TRY(hipGetLastError());
   }
-  if (lay.mask & (1u << SHC_ACT_TIP_FORCE)) {
-    e->rt_flags |= RT_TOUCHDOWN; // LegStepper::setTouchdownDetection(true) (state_controller.cpp:1642)
-    if (e->params.rough_terrain_mode) { // Leg::touchdownDetection behind the stored forces, as shc_engine_set_tip_force (never riding: actions_ride)
-      const int64_t threads = e->n * e->L;
-      rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
-        constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
-        touchdown_detection_kernel<L, NJ><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(
-            e->st, (const SharedConsts<L, NJ> *)e->d_consts, e->params.touchdown_threshold, e->params.liftoff_threshold);
-        return SHC_OK;
-      });
-      if (rc != SHC_OK) return rc;
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  return SHC_OK;
+  // Leg::touchdownDetection behind the stored forces, as shc_engine_set_tip_force (in rough terrain mode never riding: actions_ride)
+  return (lay.mask & (1u << SHC_ACT_TIP_FORCE)) ? tip_force_given(e) : SHC_OK;
 }
 
 extern "C" int shc_engine_set_actions(shc_engine *e, const shc_act_spec *spec, const void *actions, int on_device) {

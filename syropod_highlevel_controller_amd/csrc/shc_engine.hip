@@ -1098,6 +1098,8 @@ static int64_t split_first_instance_of_second_half(const shc_engine *e) {
   return r < e->n ? r : e->n;
 }
 
+#include "shc_inputs.hpp" // the eight input groups, their rules and their K-deep staging: the one description every route into the cycle reads
+
 // One input array of the caller into the state.  launch(stream, array, r0, r1): the scatter kernel over instances [r0, r1)
 template <class Launch>
 static int scatter_input(shc_engine *e, const double *src, size_t doubles_per_instance, int on_device, Launch &&launch) {
@@ -1120,12 +1122,15 @@ static int scatter_input(shc_engine *e, const double *src, size_t doubles_per_in
   if (!on_device) HIP_TRY(hipStreamSynchronize(e->stream)); // the staging buffer is reused by the next call
   return SHC_OK;
 }
-static int scatter_rob(shc_engine *e, const double *src, int K, int f0, int on_device, int normalize_quat = 0) {
+// (input group g of shc_inputs.hpp, per robot / per leg; Model::setImuData normalises the orientation)
+static int scatter_rob(shc_engine *e, const double *src, int g, int on_device) {
+  const int K = input_group(g).width, f0 = input_group(g).field, normalize_quat = g == SHC_ACT_IMU_ORIENTATION;
   return scatter_input(e, src, size_t(K), on_device, [=](hipStream_t stream, const double *d, int64_t r0, int64_t r1) {
     scatter_rob_kernel<<<dim3((unsigned)((r1 - r0 + 255) / 256)), dim3(256), 0, stream>>>(d, e->st.robd, 64 / e->L, r1, K, f0, normalize_quat, r0);
   });
 }
-static int scatter_leg(shc_engine *e, const double *src, int K, int f0, int on_device) {
+static int scatter_leg(shc_engine *e, const double *src, int g, int on_device) {
+  const int K = input_k(g, e->NJ), f0 = dispatch_nj(e->NJ, [g](auto nj) { return input_leg_field<decltype(nj)::value>(g); });
   return scatter_input(e, src, size_t(e->L) * K, on_device, [=](hipStream_t stream, const double *d, int64_t r0, int64_t r1) {
     scatter_leg_kernel<<<dim3((unsigned)(((r1 - r0) * e->L + 255) / 256)), dim3(256), 0, stream>>>(d, e->st.legd, e->n_slots, r1, e->L, K, f0, r0);
   });
@@ -1162,16 +1167,16 @@ static int derive_tips(shc_engine *e);
 
 extern "C" int shc_engine_set_velocity(shc_engine *e, const double *linear_xy, const double *angular, int on_device) {
   SHC_ENTER_JOINED_UNLESS(e, split_inputs(e, on_device));
-  int rc = scatter_rob(e, linear_xy, 2, RobotFields::VIN, on_device);
+  int rc = scatter_rob(e, linear_xy, SHC_ACT_LINEAR_XY, on_device);
   if (rc != SHC_OK) return rc;
-  return scatter_rob(e, angular, 1, RobotFields::WIN, on_device);
+  return scatter_rob(e, angular, SHC_ACT_ANGULAR, on_device);
 }
 
 extern "C" int shc_engine_set_imu(shc_engine *e, const double *orientation_wxyz, const double *angular_velocity, int on_device) {
   SHC_ENTER_JOINED_UNLESS(e, split_inputs(e, on_device));
-  int rc = scatter_rob(e, orientation_wxyz, 4, RobotFields::IMUQ, on_device, 1);
+  int rc = scatter_rob(e, orientation_wxyz, SHC_ACT_IMU_ORIENTATION, on_device);
   if (rc != SHC_OK) return rc;
-  return scatter_rob(e, angular_velocity, 3, RobotFields::GYRO, on_device);
+  return scatter_rob(e, angular_velocity, SHC_ACT_IMU_ANGULAR_VELOCITY, on_device);
 }
 
 // Leg::touchdownDetection (model.cpp:712-722), run by tipStatesCallback right after it stored the measured force
@@ -1198,23 +1203,27 @@ __global__ void touchdown_detection_kernel(DevState st, const SharedConsts<L, NJ
   }
 }
 
+// What follows fresh tip forces in the state, on the engine's stream (shc_engine_set_tip_force, the action pass)
+static int tip_force_given(shc_engine *e) {
+  e->rt_flags |= RT_TOUCHDOWN; // LegStepper::setTouchdownDetection(true) (state_controller.cpp:1642)
+  if (!e->params.rough_terrain_mode) return SHC_OK; // the step plane is only read in rough terrain mode (walk_controller.cpp:1065, :1110)
+  const int64_t threads = e->n * e->L;
+  const int rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
+    constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
+    touchdown_detection_kernel<L, NJ><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(
+        e->st, (const SharedConsts<L, NJ> *)e->d_consts, e->params.touchdown_threshold, e->params.liftoff_threshold);
+    return SHC_OK;
+  });
+  if (rc != SHC_OK) return rc;
+  HIP_TRY(hipGetLastError());
+  return SHC_OK;
+}
+
 extern "C" int shc_engine_set_tip_force(shc_engine *e, const double *tip_force, int on_device) {
   SHC_ENTER_JOINED_UNLESS(e, split_inputs(e, on_device && !e->params.rough_terrain_mode));
-  int rc = scatter_leg(e, tip_force, 3, LEG_FIELD(e, FORCE_IN), on_device);
+  int rc = scatter_leg(e, tip_force, SHC_ACT_TIP_FORCE, on_device);
   if (rc != SHC_OK || !tip_force) return rc;
-  e->rt_flags |= RT_TOUCHDOWN; // LegStepper::setTouchdownDetection(true) (state_controller.cpp:1642)
-  if (e->params.rough_terrain_mode) { // the step plane is only read in rough terrain mode (walk_controller.cpp:1065, :1110)
-    const int64_t threads = e->n * e->L;
-    rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
-      constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
-      touchdown_detection_kernel<L, NJ><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(
-          e->st, (const SharedConsts<L, NJ> *)e->d_consts, e->params.touchdown_threshold, e->params.liftoff_threshold);
-      return SHC_OK;
-    });
-    if (rc != SHC_OK) return rc;
-    HIP_TRY(hipGetLastError());
-  }
-  return SHC_OK;
+  return tip_force_given(e);
 }
 
 // First joint effort (or non-zero filter state): switch to the kernels that evaluate the tip-force estimate.
@@ -1231,16 +1240,16 @@ extern "C" int shc_engine_set_joint_effort(shc_engine *e, const double *joint_ef
     const int rc = effort_live(e);
     if (rc != SHC_OK) return rc;
   }
-  return scatter_leg(e, joint_effort, e->NJ, LEG_FIELD(e, EFFORT_IN), on_device);
+  return scatter_leg(e, joint_effort, SHC_ACT_JOINT_EFFORT, on_device);
 }
 
 extern "C" int shc_engine_set_pose_input(shc_engine *e, const double *translation_velocity, const double *rotation_velocity,
                                          int on_device) {
   SHC_ENTER_JOINED_UNLESS(e, split_inputs(e, on_device));
   if (translation_velocity || rotation_velocity) e->rt_flags |= RT_MANUAL_LIVE;
-  int rc = scatter_rob(e, translation_velocity, 3, RobotFields::TVI, on_device);
+  int rc = scatter_rob(e, translation_velocity, SHC_ACT_POSE_TRANSLATION_VELOCITY, on_device);
   if (rc != SHC_OK) return rc;
-  return scatter_rob(e, rotation_velocity, 3, RobotFields::RVI, on_device);
+  return scatter_rob(e, rotation_velocity, SHC_ACT_POSE_ROTATION_VELOCITY, on_device);
 }
 
 extern "C" int shc_engine_set_pose_reset_mode(shc_engine *e, const int32_t *mode, int on_device) {

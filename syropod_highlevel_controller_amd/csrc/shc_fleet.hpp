@@ -7,6 +7,8 @@
 // the boundary whatever the interleaving pattern.  The only exchange is the all-gather of the final joint-state buffer:
 // every device ends up with every instance's joints, copied device to device (hipMemcpyPeerAsync: xGMI on an MI355X node).
 // One-process-per-GPU hosts (bench.py under torch.distributed) do the same exchange with RCCL instead.
+// The host setters of the per-robot input groups take each group's width from the group table of shc_inputs.hpp (fleet_pick), as the device
+// forms behind this file do.
 #pragma once
 
 #include <algorithm>
@@ -209,9 +211,10 @@ static int fleet_part_ids(FleetPart &p) {
   return SHC_OK;
 }
 
-// caller-order rows of `width` doubles -> the part's rows
-static const double *fleet_pick(shc_fleet *f, const FleetPart &p, const double *src, int width, std::vector<double> &buf) {
+// caller-order rows of per-robot input group g (shc_inputs.hpp) -> the part's rows
+static const double *fleet_pick(shc_fleet *f, const FleetPart &p, const double *src, int g, std::vector<double> &buf) {
   if (!src) return nullptr;
+  const int width = input_group(g).width;
   buf.resize(p.ids.size() * size_t(width));
   for (size_t k = 0; k < p.ids.size(); ++k) std::copy(src + p.ids[k] * width, src + (p.ids[k] + 1) * width, buf.begin() + k * width);
   return buf.data();
@@ -220,7 +223,7 @@ static const double *fleet_pick(shc_fleet *f, const FleetPart &p, const double *
 extern "C" int shc_fleet_set_velocity(shc_fleet *f, const double *linear_xy, const double *angular) {
   if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
   for (auto &p : f->parts) {
-    const int rc = shc_engine_set_velocity(p.engine, fleet_pick(f, p, linear_xy, 2, f->host_a), fleet_pick(f, p, angular, 1, f->host_b), 0);
+    const int rc = shc_engine_set_velocity(p.engine, fleet_pick(f, p, linear_xy, SHC_ACT_LINEAR_XY, f->host_a), fleet_pick(f, p, angular, SHC_ACT_ANGULAR, f->host_b), 0);
     if (rc != SHC_OK) return rc;
   }
   return SHC_OK;
@@ -228,7 +231,7 @@ extern "C" int shc_fleet_set_velocity(shc_fleet *f, const double *linear_xy, con
 extern "C" int shc_fleet_set_imu(shc_fleet *f, const double *orientation_wxyz, const double *angular_velocity) {
   if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
   for (auto &p : f->parts) {
-    const int rc = shc_engine_set_imu(p.engine, fleet_pick(f, p, orientation_wxyz, 4, f->host_a), fleet_pick(f, p, angular_velocity, 3, f->host_b), 0);
+    const int rc = shc_engine_set_imu(p.engine, fleet_pick(f, p, orientation_wxyz, SHC_ACT_IMU_ORIENTATION, f->host_a), fleet_pick(f, p, angular_velocity, SHC_ACT_IMU_ANGULAR_VELOCITY, f->host_b), 0);
     if (rc != SHC_OK) return rc;
   }
   return SHC_OK;
@@ -236,8 +239,8 @@ extern "C" int shc_fleet_set_imu(shc_fleet *f, const double *orientation_wxyz, c
 extern "C" int shc_fleet_set_pose_input(shc_fleet *f, const double *translation_velocity, const double *rotation_velocity) {
   if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
   for (auto &p : f->parts) {
-    const int rc =
-        shc_engine_set_pose_input(p.engine, fleet_pick(f, p, translation_velocity, 3, f->host_a), fleet_pick(f, p, rotation_velocity, 3, f->host_b), 0);
+    const int rc = shc_engine_set_pose_input(p.engine, fleet_pick(f, p, translation_velocity, SHC_ACT_POSE_TRANSLATION_VELOCITY, f->host_a),
+                                             fleet_pick(f, p, rotation_velocity, SHC_ACT_POSE_ROTATION_VELOCITY, f->host_b), 0);
     if (rc != SHC_OK) return rc;
   }
   return SHC_OK;

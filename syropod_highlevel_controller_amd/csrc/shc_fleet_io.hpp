@@ -12,7 +12,7 @@
 // One staging buffer per part, allocated by the fleet's first device I/O call and kept.  Every use of it is ordered on the part's stream: the
 // engine getters join split steps before they write it, and a setter that scatters on the half streams orders the part's stream behind those
 // reads (split_inputs_end), so the next pack cannot overwrite rows a half has not read yet.  Its size is the largest of
-//   inputs:   rows x (16 + 3 L + L D) doubles   (all eight groups of one call, packed by one launch),
+//   inputs:   rows x (16 + 3 L + L D) doubles   (all eight groups of one call - input_plan of shc_inputs.hpp -, packed by one launch),
 //   joints:   rows x L x D doubles              (shc_engine_get_joint_state has no range: q, then qd, through the same rows),
 //   records:  chunk x L x 512 bytes             (leg messages; leg frames + body frames of the same chunk need less, health 32 bytes a robot),
 // with rows, L, D the part's own and chunk = min(rows, shc_fleet_set_io_chunk).  Record outputs walk the part in chunks through the engine
@@ -21,15 +21,16 @@
 // trade-off; the record outputs have not been timed (DESIGN 4.6 has the figures of the joint route).
 #pragma once
 
-static_assert(sizeof(shc_fleet_inputs) == 64 && sizeof(shc_fleet_outputs) == 72 && offsetof(shc_fleet_outputs, frame) == 48 && offsetof(shc_fleet_outputs, health) == 56,
-              "shc_fleet_inputs is eight pointers; shc_fleet_outputs six pointers, two int32, two pointers");
+static_assert(sizeof(shc_fleet_outputs) == 72 && offsetof(shc_fleet_outputs, frame) == 48 && offsetof(shc_fleet_outputs, health) == 56,
+              "shc_fleet_outputs is six pointers, two int32, two pointers");
 constexpr int64_t kFleetIoDefaultChunk = 8192;
-constexpr int kFleetIoGroups = 8;
 
-// PACK: one launch per part.  Group g is an input array of the caller, [n][src_robot] doubles, of which a part's robot takes legs x k entries:
-// entry (l, j) of part row r is src[ids[r] * src_robot + l * src_leg + j] and lands at stage[dst + r * legs * k + l * k + j].  The group is
-// blockIdx.y, so its description is wave-uniform (scalar loads of the kernel arguments), the stores of a group are one contiguous run, and -
-// ids ascending - the loads walk the caller's array forwards, skipping the rows of other parts and the padding.
+// PACK: one launch per part, for one cycle or K.  Group g is an input array of the caller, [K][n][src_robot] doubles, of which a part's robot takes
+// legs x k entries: entry (l, j) of part row r in cycle c is src[(c * n + ids[r]) * src_robot + l * src_leg + j] and lands at
+// stage[dst + (c * rows + r) * legs * k + l * k + j], so that each staged group is a dense [K][rows][..] array (input_plan of shc_inputs.hpp).  The
+// group is blockIdx.y and the cycle blockIdx.z, so both are wave-uniform (scalar loads of the kernel arguments), the stores of a group are one
+// contiguous run, and - ids ascending - the loads walk the caller's array forwards, skipping the rows of other parts and the padding.  Bytes are
+// copied as they are.
 // Both kernels number their threads word by word in 64 bits, but divide in 32: a workgroup's first word is split into (row, column) once,
 // wave-uniformly, and a thread adds its lane to the column - at most one row length plus 255, far inside 32 bits.
 struct FleetPackGroup {
@@ -40,10 +41,10 @@ struct FleetPackGroup {
   int32_t src_leg;   // doubles per leg there (per-robot inputs: legs = 1)
 };
 struct FleetPackArgs {
-  FleetPackGroup g[kFleetIoGroups];
+  FleetPackGroup g[kInputGroups];
   int32_t n_groups;
 };
-// (the rows of one group: `dst` the group's staged rows, `src` the caller's array - both of ONE cycle; shc_fleet_step_k.hpp packs K of them in one launch)
+// (the rows of one group: `dst` the group's staged rows, `src` the caller's array - both of ONE cycle)
 __device__ __forceinline__ void fleet_pack_rows(double *__restrict__ dst, const double *__restrict__ src, const int64_t *__restrict__ ids, int64_t rows,
                                                 const FleetPackGroup &g) {
   const uint32_t w = uint32_t(g.legs * g.k), gk = uint32_t(g.k);
@@ -55,9 +56,10 @@ __device__ __forceinline__ void fleet_pack_rows(double *__restrict__ dst, const 
     if (r < rows) dst[r * w + c] = src[ids[r] * g.src_robot + int64_t(l) * g.src_leg + j];
   }
 }
-__global__ void fleet_pack_inputs_kernel(double *__restrict__ stage, const int64_t *__restrict__ ids, int64_t rows, FleetPackArgs a) {
+__global__ void fleet_pack_inputs_kernel(double *__restrict__ stage, const int64_t *__restrict__ ids, int64_t rows, int64_t n, FleetPackArgs a) {
   const FleetPackGroup &g = a.g[blockIdx.y];
-  fleet_pack_rows(stage + g.dst, g.src, ids, rows, g);
+  const int64_t cycle = blockIdx.z;
+  fleet_pack_rows(stage + g.dst + cycle * rows * (g.legs * g.k), g.src + cycle * n * g.src_robot, ids, rows, g);
 }
 
 // PLACE: `count` rows of a part ([count][legs][k] words, dense, in staging) into the caller's buffer ([n][dst_legs][dst_k] words) at the rows
@@ -80,13 +82,47 @@ __global__ void fleet_place_kernel(Word *__restrict__ dst, const Word *__restric
     dst[ids[r] * row + c] = v;
   }
 }
-// one word per thread: at most 2 048 workgroups, the rest by the grid stride
-static unsigned fleet_io_grid(int64_t threads) { return unsigned(std::max<int64_t>(1, std::min<int64_t>((threads + 255) / 256, 2048))); }
+// one word per thread: at most 2 048 workgroups along x - shared among the cycles of a launch that has `cycles` of them along another grid
+// dimension -, the rest by the grid stride
+static unsigned fleet_io_grid(int64_t threads, int cycles = 1) { return unsigned(std::max<int64_t>(1, std::min<int64_t>((threads + 255) / 256, 2048 / cycles))); }
+// the bit pattern shc_fleet_get_joint_state fills the padding with
+static uint64_t nan_word() {
+  const double nan_value = std::nan("");
+  uint64_t word;
+  memcpy(&word, &nan_value, 8);
+  return word;
+}
 
 template <class Word>
 static int fleet_place(const FleetPart &p, Word *dst, int64_t first, int64_t count, int legs, int k, int dst_legs, int dst_k, Word pad) {
   fleet_place_kernel<Word><<<dim3(fleet_io_grid(count * dst_legs * dst_k)), dim3(256), 0, p.engine->stream>>>(dst, reinterpret_cast<const Word *>(p.io_stage), p.d_ids + first,
                                                                                                           count, legs, k, dst_legs, dst_k, pad);
+  HIP_TRY(hipGetLastError());
+  return SHC_OK;
+}
+
+// The K-deep staging of the groups of `mask` for a part (K = 1: the inputs of one shc_fleet_set_inputs_device), and the pack launch that fills
+// it at `stage` from the caller's arrays on the part's stream: every selected group of the table, the part's (legs, dof) on the staged side and
+// the fleet's padded (max_legs, max_dof) on the caller's.
+static InputPlan fleet_input_plan(const shc_fleet *f, const FleetPart &p, unsigned mask, int K) {
+  const shc_params &pp = f->params[p.morph];
+  return input_plan(mask, int64_t(p.ids.size()), pp.leg_count, max_dof(pp), K);
+}
+static int fleet_pack(const shc_fleet *f, const FleetPart &p, const shc_fleet_inputs *in, const InputPlan &plan, int K, double *stage) {
+  const shc_params &pp = f->params[p.morph];
+  const int64_t rows = int64_t(p.ids.size());
+  FleetPackArgs a{};
+  int64_t widest = 0;
+  for (int g = 0; g < kInputGroups; ++g) {
+    if (plan.at[g] < 0) continue;
+    FleetPackGroup &pg = a.g[a.n_groups++];
+    pg.src = in->*kFleetInput[g], pg.dst = plan.at[g];
+    pg.legs = input_per_leg(g) ? pp.leg_count : 1, pg.k = input_k(g, max_dof(pp));
+    pg.src_robot = input_width(g, f->max_legs, f->max_dof), pg.src_leg = input_per_leg(g) ? input_k(g, f->max_dof) : 0;
+    widest = std::max<int64_t>(widest, rows * pg.legs * pg.k);
+  }
+  HIP_TRY(hipSetDevice(p.device));
+  fleet_pack_inputs_kernel<<<dim3(fleet_io_grid(widest, K), unsigned(a.n_groups), unsigned(K)), dim3(256), 0, p.engine->stream>>>(stage, p.d_ids, rows, f->n, a);
   HIP_TRY(hipGetLastError());
   return SHC_OK;
 }
@@ -97,7 +133,7 @@ static int64_t fleet_io_chunk_of(const shc_fleet *f, const FleetPart &p) {
 static size_t fleet_io_stage_bytes(const shc_fleet *f, const FleetPart &p) {
   const shc_params &pp = f->params[p.morph];
   const size_t rows = p.ids.size(), L = size_t(pp.leg_count), D = size_t(max_dof(pp));
-  const size_t inputs = rows * (16 + 3 * L + L * D) * 8, joints = rows * L * D * 8;
+  const size_t inputs = size_t(fleet_input_plan(f, p, kAllInputs, 1).doubles) * 8, joints = rows * L * D * 8;
   const size_t records = size_t(fleet_io_chunk_of(f, p)) * L * sizeof(shc_leg_state_msg);
   static_assert(sizeof(shc_leg_frames) + sizeof(shc_body_frames) <= sizeof(shc_leg_state_msg), "a chunk of leg messages is the largest record output");
   return (std::max(inputs, std::max(joints, records)) + 15) & ~size_t(15);
@@ -217,42 +253,20 @@ extern "C" int shc_fleet_set_inputs_device(shc_fleet *f, const shc_fleet_inputs 
   int rc = fleet_io_ready(f);
   if (rc == SHC_OK) rc = fleet_io_prepare(f);
   if (rc != SHC_OK) return rc;
-  // the caller's arrays in the order of the staged groups: [pointer, entries per robot there]; the per-leg groups are the last two
-  const double *src[kFleetIoGroups] = {in->linear_xy, in->angular, in->imu_orientation_wxyz, in->imu_angular_velocity, in->pose_translation_velocity,
-                                       in->pose_rotation_velocity, in->tip_force, in->joint_effort};
-  const int width[kFleetIoGroups - 2] = {2, 1, 4, 3, 3, 3};
+  const unsigned mask = input_mask(in);
+  if (mask == 0) return SHC_OK; // every input is held
   for (auto &p : f->parts) {
-    const shc_params &pp = f->params[p.morph];
-    const int L = pp.leg_count, D = max_dof(pp);
-    const int64_t rows = int64_t(p.ids.size());
-    double *stage = reinterpret_cast<double *>(p.io_stage);
-    const double *staged[kFleetIoGroups] = {};
-    FleetPackArgs a{};
-    int64_t at = 0, widest = 0;
-    for (int g = 0; g < kFleetIoGroups; ++g) {
-      if (!src[g]) continue;
-      FleetPackGroup &pg = a.g[a.n_groups++];
-      pg.src = src[g], pg.dst = at;
-      if (g < kFleetIoGroups - 2) {
-        pg.legs = 1, pg.k = width[g], pg.src_robot = width[g], pg.src_leg = 0;
-      } else {
-        const int max_k = g == kFleetIoGroups - 1 ? f->max_dof : 3;
-        pg.legs = L, pg.k = g == kFleetIoGroups - 1 ? D : 3, pg.src_robot = f->max_legs * max_k, pg.src_leg = max_k;
-      }
-      staged[g] = stage + at;
-      at += rows * pg.legs * pg.k;
-      widest = std::max<int64_t>(widest, rows * pg.legs * pg.k);
-    }
-    if (a.n_groups == 0) return SHC_OK; // every input is held
-    HIP_TRY(hipSetDevice(p.device));
-    fleet_pack_inputs_kernel<<<dim3(fleet_io_grid(widest), unsigned(a.n_groups)), dim3(256), 0, p.engine->stream>>>(stage, p.d_ids, rows, a);
-    HIP_TRY(hipGetLastError());
+    const InputPlan plan = fleet_input_plan(f, p, mask, 1);
+    if ((rc = fleet_pack(f, p, in, plan, 1, reinterpret_cast<double *>(p.io_stage))) != SHC_OK) return rc;
+    const shc_cycle_inputs staged = input_plan_arrays(plan, reinterpret_cast<const double *>(p.io_stage));
     // a setter none of whose members is given is not called: with nothing to set it would still enter the engine, and some of them join split steps
-    if ((staged[0] || staged[1]) && (rc = shc_engine_set_velocity(p.engine, staged[0], staged[1], 1)) != SHC_OK) return rc;
-    if ((staged[2] || staged[3]) && (rc = shc_engine_set_imu(p.engine, staged[2], staged[3], 1)) != SHC_OK) return rc;
-    if ((staged[4] || staged[5]) && (rc = shc_engine_set_pose_input(p.engine, staged[4], staged[5], 1)) != SHC_OK) return rc;
-    if (staged[6] && (rc = shc_engine_set_tip_force(p.engine, staged[6], 1)) != SHC_OK) return rc;
-    if (staged[7] && (rc = shc_engine_set_joint_effort(p.engine, staged[7], 1)) != SHC_OK) return rc;
+    if ((staged.linear_xy || staged.angular) && (rc = shc_engine_set_velocity(p.engine, staged.linear_xy, staged.angular, 1)) != SHC_OK) return rc;
+    if ((staged.imu_orientation_wxyz || staged.imu_angular_velocity) && (rc = shc_engine_set_imu(p.engine, staged.imu_orientation_wxyz, staged.imu_angular_velocity, 1)) != SHC_OK) return rc;
+    if ((staged.pose_translation_velocity || staged.pose_rotation_velocity) &&
+        (rc = shc_engine_set_pose_input(p.engine, staged.pose_translation_velocity, staged.pose_rotation_velocity, 1)) != SHC_OK)
+      return rc;
+    if (staged.tip_force && (rc = shc_engine_set_tip_force(p.engine, staged.tip_force, 1)) != SHC_OK) return rc;
+    if (staged.joint_effort && (rc = shc_engine_set_joint_effort(p.engine, staged.joint_effort, 1)) != SHC_OK) return rc;
   }
   return SHC_OK;
 }
@@ -280,9 +294,6 @@ extern "C" int shc_fleet_get_outputs_device(shc_fleet *f, const shc_fleet_output
       if (!p.engine->cp.odometry) return fail(SHC_ERR_UNSUPPORTED, "SHC_FEAT_ODOMETRY is off on a part: odom_to_base_link needs the ideal odometry");
   if ((rc = fleet_io_prepare(f)) != SHC_OK) return rc;
 
-  uint64_t nan_word; // the bit pattern shc_fleet_get_joint_state fills the padding with
-  const double nan_value = std::nan("");
-  memcpy(&nan_word, &nan_value, 8);
   constexpr int kMsgWords = int(sizeof(shc_leg_state_msg) / 8), kLegWords = int(sizeof(shc_leg_frames) / 8), kBodyWords = int(sizeof(shc_body_frames) / 8),
                 kHealthWords = int(sizeof(shc_robot_health) / 8);
   for (auto &p : f->parts) {
@@ -294,7 +305,7 @@ extern "C" int shc_fleet_get_outputs_device(shc_fleet *f, const shc_fleet_output
       double *dst = which == 0 ? out->q : out->qd, *stage = reinterpret_cast<double *>(p.io_stage);
       if (!dst) continue;
       if ((rc = shc_engine_get_joint_state(p.engine, which == 0 ? stage : nullptr, which == 0 ? nullptr : stage, 1)) != SHC_OK) return rc;
-      if ((rc = fleet_place<uint64_t>(p, reinterpret_cast<uint64_t *>(dst), 0, rows, L, D, f->max_legs, f->max_dof, nan_word)) != SHC_OK) return rc;
+      if ((rc = fleet_place<uint64_t>(p, reinterpret_cast<uint64_t *>(dst), 0, rows, L, D, f->max_legs, f->max_dof, nan_word())) != SHC_OK) return rc;
     }
     if (out->walk_state) {
       if ((rc = shc_engine_get_body_state(p.engine, nullptr, nullptr, reinterpret_cast<int32_t *>(p.io_stage), 1)) != SHC_OK) return rc;

@@ -13,8 +13,9 @@ extern "C" int shc_fleet_step_k_actions_device(shc_fleet *f, int n_cycles, const
   RowLayout lay;
   // every part is asked before the first launch and before anything is allocated (what is wrong with the call itself is found at the first)
   int rc = fleet_rows_begin<ActRows>(f, spec, actions, "actions", lay, [&](const shc_engine *e) {
-    const int bad = rollout_actions_call_check("shc_fleet_step_k_actions_device", spec, lay, n_cycles, f->n, cycle_stride);
-    return bad != SHC_OK ? bad : rollout_actions_engine_check(e, spec, lay, n_cycles);
+    const char *who = "shc_fleet_step_k_actions_device";
+    const int bad = rollout_actions_call_check(who, spec, lay, n_cycles, f->n, cycle_stride);
+    return bad != SHC_OK ? bad : rollout_actions_engine_check(who, e, spec, lay, n_cycles);
   });
   if (rc != SHC_OK) return rc;
   rc = fleet_rows_each(f, spec, lay, [&](FleetPart &p, int64_t stride) {

@@ -1,13 +1,14 @@
 // shc_fleet_step_k.hpp — K cycles per launch for a mixed fleet, from K-deep device arrays in the caller's order: shc_fleet_step_k,
-// shc_fleet_get_step_k_joints_device.  Included by shc_fleet.hpp behind shc_fleet_io.hpp, whose pack groups, grid rule, readiness checks, ids and
-// ordering events it uses.
+// shc_fleet_get_step_k_joints_device.  Included by shc_fleet.hpp behind shc_fleet_io.hpp, whose pack launch, grid rule, readiness checks, ids and
+// ordering events it uses; the groups, their staging plan and what is refused of them are shc_inputs.hpp's.
 //
 // The cycle-by-cycle device route (shc_fleet_set_inputs_device, shc_fleet_step(1), shc_fleet_get_outputs_device) pays per part and CYCLE one pack
 // launch, the engine's setters, the step, two engine gathers and two place launches.  Here a part and CALL pays one pack launch, one
 // shc_engine_step_k and one place launch per requested array:
-//   K-deep PACK   fleet_pack_inputs_kernel with a cycle dimension (blockIdx.z).  Group g of the caller is [K][n][src_robot] doubles; the part's
-//                 rows of cycle k land at k_stage[g.dst + k * rows * legs * k_width ..], so that each staged group is the dense [K][rows][..]
-//                 array shc_engine_step_k reads with its own kstride (rows x width).  Bytes are copied as they are: the engine normalises.
+//   K-deep PACK   fleet_pack of shc_fleet_io.hpp - the one pack kernel, the cycle its blockIdx.z - with K cycles.  Group g of the caller is
+//                 [K][n][src_robot] doubles; the part's rows of cycle k land at k_stage[g.dst + k * rows * legs * k_width ..], so that each staged
+//                 group is the dense [K][rows][..] array shc_engine_step_k reads with its own kstride (rows x width).  Bytes are copied as they
+//                 are: the engine normalises.
 //   ring PLACE    reads the part's step_k output ring where it lies ([K][NJ planes][n_slots] double2, the leg state's own layout: leg_state_index)
 //                 and writes whole rows of the caller's [cycle][n][max_legs][max_dof] buffer at ids[r], NaN where the morphology has no such leg
 //                 or joint.  No dense copy in between: shc_engine_get_step_k_joint_state + fleet_place would move every joint twice and launch
@@ -15,7 +16,8 @@
 // Everything between the two - the batch kernel or the serial form, a pending adjusted parameter's first cycle, touchdown detection on fresh tip
 // forces, the first-effort switch, the last row staying as the held input - is shc_engine_step_k's, unchanged.
 //
-// K-deep staging: one buffer per part next to io_stage, K x rows x (the widths of the groups GIVEN: 2, 1, 4, 3, 3 L, L D) doubles, allocated by the
+// K-deep staging: one buffer per part next to io_stage, K x rows x (the widths of the groups GIVEN) doubles - fleet_input_plan: input_plan of
+// shc_inputs.hpp for the part, the plan the rollout tensors stage by, and input_plan_arrays the shc_cycle_inputs over it -, allocated by the
 // first call that needs it, grown (never shrunk) by a call that needs more, counted by shc_fleet_io_bytes, released with the fleet.  A call with
 // the same or a smaller K and the same groups allocates nothing.  The part's launch reads it - on the two half streams when the part steps split
 // (alone on its device, 4 096 wavefronts or more), which only a join orders behind the part's stream.  So before a pack overwrites it, a part
@@ -23,18 +25,10 @@
 // drained, as step_k_out_ring does for the ring.  The caller's arrays are read by the pack alone, on the part's stream.
 #pragma once
 
-// A part's output ring (the engine's own bound, asked here before any part has launched) and its K-deep staging both stay below 2 GiB.
-constexpr size_t kFleetStepKMaxBytes = size_t(1) << 31;
-
-__global__ void fleet_pack_inputs_k_kernel(double *__restrict__ stage, const int64_t *__restrict__ ids, int64_t rows, int64_t n, FleetPackArgs a) {
-  const FleetPackGroup &g = a.g[blockIdx.y]; // group and cycle are wave-uniform: kernel arguments and block indices only
-  const int64_t cycle = blockIdx.z;
-  fleet_pack_rows(stage + g.dst + cycle * rows * (g.legs * g.k), g.src + cycle * n * g.src_robot, ids, rows, g);
-}
-
 // PLACE out of the ring.  `ring` is the slot of the first requested cycle; cycle c (blockIdx.y, wave-uniform) lies c * cycle_words further and goes
 // to dst + c * n * row.  One thread per word of a DESTINATION row, as fleet_place_kernel: a robot's stores are one contiguous run and every word
 // of the row is written.  f0: the leg field of joint 0 (Q or QD).  Words are copied as 64-bit patterns.
+// (The index walk is fleet_place_kernel's, written out again: shared through a load functor both kernels ran 1 - 2 % slower.)
 __global__ void fleet_place_ring_kernel(uint64_t *__restrict__ dst, const uint64_t *__restrict__ ring, const int64_t *__restrict__ ids, int64_t rows, int64_t n,
                                         int64_t n_slots, int64_t cycle_words, int legs, int k, int f0, int dst_legs, int dst_k, uint64_t pad) {
   const uint32_t row = uint32_t(dst_legs * dst_k), dk = uint32_t(dst_k);
@@ -51,94 +45,34 @@ __global__ void fleet_place_ring_kernel(uint64_t *__restrict__ dst, const uint64
     out[ids[r] * row + c] = v;
   }
 }
-// workgroups along x of a launch that has `cycles` of them along another grid dimension: the 2 048 of fleet_io_grid shared among the cycles
-static unsigned fleet_step_k_grid(int64_t threads, int cycles) {
-  return unsigned(std::max<int64_t>(1, std::min<int64_t>((threads + 255) / 256, 2048 / cycles)));
-}
-
-// the K-deep groups given, in staging order: the caller's array, which member of shc_cycle_inputs it becomes, and its shape on both sides
-enum { FSK_LIN, FSK_ANG, FSK_IMUQ, FSK_IMUW, FSK_FORCE, FSK_EFFORT, FSK_COUNT };
-struct FleetStepKGroup {
-  const double *src;
-  int member, legs, k, src_robot, src_leg;
-};
-static int fleet_step_k_groups(const shc_fleet *f, const FleetPart &p, const shc_fleet_inputs *rows, FleetStepKGroup (&g)[FSK_COUNT]) {
-  const shc_params &pp = f->params[p.morph];
-  const int L = pp.leg_count, D = max_dof(pp);
-  int n = 0;
-  if (!rows) return 0;
-  if (rows->linear_xy) g[n++] = {rows->linear_xy, FSK_LIN, 1, 2, 2, 0};
-  if (rows->angular) g[n++] = {rows->angular, FSK_ANG, 1, 1, 1, 0};
-  if (rows->imu_orientation_wxyz) g[n++] = {rows->imu_orientation_wxyz, FSK_IMUQ, 1, 4, 4, 0};
-  if (rows->imu_angular_velocity) g[n++] = {rows->imu_angular_velocity, FSK_IMUW, 1, 3, 3, 0};
-  if (rows->tip_force) g[n++] = {rows->tip_force, FSK_FORCE, L, 3, f->max_legs * 3, 3};
-  if (rows->joint_effort) g[n++] = {rows->joint_effort, FSK_EFFORT, L, D, f->max_legs * f->max_dof, f->max_dof};
-  return n;
-}
-static size_t fleet_step_k_stage_bytes(const shc_fleet *f, const FleetPart &p, int K, const shc_fleet_inputs *rows) {
-  FleetStepKGroup g[FSK_COUNT];
-  const int n = fleet_step_k_groups(f, p, rows, g);
-  size_t width = 0;
-  for (int i = 0; i < n; ++i) width += size_t(g[i].legs) * g[i].k;
-  return size_t(K) * p.ids.size() * width * 8;
-}
 
 extern "C" int shc_fleet_step_k(shc_fleet *f, int n_cycles, const shc_fleet_inputs *rows) {
   if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
-  if (n_cycles < 1 || n_cycles > 4096) return fail(SHC_ERR_INVALID_ARG, "shc_fleet_step_k: 1 .. 4096 cycles per launch");
-  if (rows) {
-    if ((rows->linear_xy == nullptr) != (rows->angular == nullptr)) return fail(SHC_ERR_INVALID_ARG, "linear_xy and angular are given together");
-    if ((rows->imu_orientation_wxyz == nullptr) != (rows->imu_angular_velocity == nullptr)) return fail(SHC_ERR_INVALID_ARG, "the two IMU arrays are given together");
-    if (rows->pose_translation_velocity || rows->pose_rotation_velocity)
-      return fail(SHC_ERR_UNSUPPORTED, "shc_fleet_step_k carries velocity, IMU, tip force and joint effort; give pose inputs / reset modes with their setters before the call (held for the K cycles)");
-  }
-  int rc = fleet_io_ready(f);
-  if (rc != SHC_OK) return rc;
+  const char *who = "shc_fleet_step_k";
+  const unsigned mask = input_mask(rows);
+  int rc = k_launch_cycles_check(who, n_cycles);
+  if (rc == SHC_OK) rc = input_pairs_check(mask, kAllInputs & ~kPoseInputs, "given");
+  if (rc == SHC_OK) rc = k_launch_pose_check(who, mask);
+  if (rc == SHC_OK) rc = fleet_io_ready(f);
   // every part is asked before the first launch (and before anything is allocated): what its shc_engine_step_k would refuse
-  for (const auto &p : f->parts) {
-    const shc_engine *e = p.engine;
-    if (e->starting_up) return fail(SHC_ERR_UNSUPPORTED, "shc_fleet_step_k: a part of the fleet is still starting up (finish the start-up first)");
-    if (size_t(e->NJ) * e->n_slots * 16 * size_t(n_cycles) >= kFleetStepKMaxBytes)
-      return fail(SHC_ERR_INVALID_ARG, "shc_fleet_step_k: cycles x a part's batch - the part's output ring must stay below 2 GiB (fewer cycles per launch)");
-    if (fleet_step_k_stage_bytes(f, p, n_cycles, rows) >= kFleetStepKMaxBytes)
-      return fail(SHC_ERR_INVALID_ARG, "shc_fleet_step_k: cycles x a part's rows of the inputs given - the part's K-deep staging must stay below 2 GiB (fewer cycles per launch)");
-    ResidentFit fit;
-    if ((rc = resident_fit(e, fit)) != SHC_OK) return rc;
-  }
-  if ((rc = fleet_io_prepare(f)) != SHC_OK) return rc;
+  for (size_t i = 0; rc == SHC_OK && i < f->parts.size(); ++i)
+    rc = k_launch_engine_check(f->parts[i].engine, who, n_cycles, fleet_input_plan(f, f->parts[i], mask, n_cycles).doubles);
+  if (rc != SHC_OK || (rc = fleet_io_prepare(f)) != SHC_OK) return rc;
   for (auto &p : f->parts) { // staging that is too small: drained (the part's launches may still read it), released, allocated again
     HIP_TRY(hipSetDevice(p.device));
-    if ((rc = rollout_stage_room(p.engine, p.k_stage, p.k_stage_bytes, fleet_step_k_stage_bytes(f, p, n_cycles, rows))) != SHC_OK) return rc;
+    if ((rc = rollout_stage_room(p.engine, p.k_stage, p.k_stage_bytes, size_t(fleet_input_plan(f, p, mask, n_cycles).doubles) * 8)) != SHC_OK) return rc;
   }
   for (auto &p : f->parts) {
-    const int64_t n_rows = int64_t(p.ids.size());
-    FleetStepKGroup groups[FSK_COUNT];
-    const int n_groups = fleet_step_k_groups(f, p, rows, groups);
-    if (n_groups == 0) { // every input is held
+    if (mask == 0) { // every input is held
       if ((rc = shc_engine_step_k(p.engine, n_cycles, nullptr)) != SHC_OK) return rc;
       continue;
     }
-    double *stage = reinterpret_cast<double *>(p.k_stage);
-    const double *where[FSK_COUNT] = {};
-    FleetPackArgs a{};
-    int64_t at = 0, widest = 0;
-    for (int i = 0; i < n_groups; ++i) {
-      const FleetStepKGroup &g = groups[i];
-      FleetPackGroup &pg = a.g[a.n_groups++];
-      pg.src = g.src, pg.dst = at, pg.legs = g.legs, pg.k = g.k, pg.src_robot = g.src_robot, pg.src_leg = g.src_leg;
-      where[g.member] = stage + at;
-      at += int64_t(n_cycles) * n_rows * g.legs * g.k;
-      widest = std::max<int64_t>(widest, n_rows * g.legs * g.k);
-    }
+    const InputPlan plan = fleet_input_plan(f, p, mask, n_cycles);
     HIP_TRY(hipSetDevice(p.device));
     // the halves of an earlier split shc_engine_step_k may still be reading the rows this pack is about to overwrite: the part's stream follows them first
     if (p.engine->side_busy && (rc = shc_engine_join(p.engine)) != SHC_OK) return rc;
-    fleet_pack_inputs_k_kernel<<<dim3(fleet_step_k_grid(widest, n_cycles), unsigned(a.n_groups), unsigned(n_cycles)), dim3(256), 0, p.engine->stream>>>(
-        stage, p.d_ids, n_rows, f->n, a);
-    HIP_TRY(hipGetLastError());
-    shc_cycle_inputs staged{};
-    staged.linear_xy = where[FSK_LIN], staged.angular = where[FSK_ANG], staged.imu_orientation_wxyz = where[FSK_IMUQ], staged.imu_angular_velocity = where[FSK_IMUW];
-    staged.tip_force = where[FSK_FORCE], staged.joint_effort = where[FSK_EFFORT], staged.on_device = 1;
+    if ((rc = fleet_pack(f, p, rows, plan, n_cycles, reinterpret_cast<double *>(p.k_stage))) != SHC_OK) return rc;
+    const shc_cycle_inputs staged = input_plan_arrays(plan, reinterpret_cast<const double *>(p.k_stage));
     if ((rc = shc_engine_step_k(p.engine, n_cycles, &staged)) != SHC_OK) return rc;
   }
   f->k_cycles = n_cycles;
@@ -157,9 +91,6 @@ extern "C" int shc_fleet_get_step_k_joints_device(shc_fleet *f, int first_cycle,
     if (!p.engine->k_out || p.engine->k_out_cycles != f->k_cycles) return fail(SHC_ERR_INVALID_ARG, range);
   if ((rc = fleet_io_prepare(f)) != SHC_OK) return rc;
 
-  uint64_t nan_word; // the bit pattern shc_fleet_get_joint_state fills the padding with
-  const double nan_value = std::nan("");
-  memcpy(&nan_word, &nan_value, 8);
   for (auto &p : f->parts) {
     shc_engine *e = p.engine;
     const int64_t n_rows = int64_t(p.ids.size()), cycle_words = int64_t(e->NJ) * e->n_slots * 2;
@@ -169,9 +100,9 @@ extern "C" int shc_fleet_get_step_k_joints_device(shc_fleet *f, int first_cycle,
     for (int which = 0; which < 2; ++which) {
       double *dst = which == 0 ? q : qd;
       if (!dst) continue;
-      fleet_place_ring_kernel<<<dim3(fleet_step_k_grid(n_rows * f->max_legs * f->max_dof, n_cycles), unsigned(n_cycles)), dim3(256), 0, e->stream>>>(
+      fleet_place_ring_kernel<<<dim3(fleet_io_grid(n_rows * f->max_legs * f->max_dof, n_cycles), unsigned(n_cycles)), dim3(256), 0, e->stream>>>(
           reinterpret_cast<uint64_t *>(dst), ring, p.d_ids, n_rows, f->n, e->n_slots, cycle_words, e->L, e->NJ, which == 0 ? LEG_FIELD(e, Q) : LEG_FIELD(e, QD),
-          f->max_legs, f->max_dof, nan_word);
+          f->max_legs, f->max_dof, nan_word());
       HIP_TRY(hipGetLastError());
     }
   }

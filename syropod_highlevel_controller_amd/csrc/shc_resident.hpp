@@ -1,6 +1,7 @@
 // shc_resident.hpp - host side of resident mode (include/shc_batch.h: shc_engine_resident_*): the node's control loop
 // (src/main.cpp:106-131 around StateController::loop, src/state_controller.cpp:162-193) kept on the chip.  Included by
-// shc_engine.hip; the device side (worker loop, relay) is in shc_cycle_kernel.hpp, the protocol in shc_cycle_launch.hpp.
+// shc_engine.hip; the device side (worker loop, relay) is in shc_cycle_kernel.hpp, the protocol in shc_cycle_launch.hpp.  What the
+// input groups of a shc_cycle_inputs are - widths, BND_* / RG_* numbers, pairs, the refusals of a K-cycle launch - is shc_inputs.hpp's.
 //
 // Buffers (all device memory unless noted):
 //   ResidentHost (pinned host memory, device-mapped)  doorbell / stop / done / exited - the only words that cross PCIe, read and
@@ -183,16 +184,11 @@ extern "C" int shc_engine_resident_bind_inputs(shc_engine *e, int set, const shc
   if (!e) return fail(SHC_ERR_INVALID_ARG, "engine is NULL");
   if (e->res && e->res->active) return fail(SHC_ERR_BUSY, "resident mode: input sets are bound while the loop is not running");
   if (set < 0 || set >= kBoundSets) return fail(SHC_ERR_INVALID_ARG, "input set 0 .. 3");
-  if (arrays && (arrays->linear_xy == nullptr) != (arrays->angular == nullptr)) return fail(SHC_ERR_INVALID_ARG, "linear_xy and angular are bound together");
-  if (arrays && (arrays->imu_orientation_wxyz == nullptr) != (arrays->imu_angular_velocity == nullptr)) return fail(SHC_ERR_INVALID_ARG, "the two IMU arrays are bound together");
-  if (arrays && (arrays->pose_translation_velocity || arrays->pose_rotation_velocity || arrays->pose_reset_mode))
-    return fail(SHC_ERR_INVALID_ARG, "input sets carry velocity, IMU, tip force and joint effort");
-  const double *row[BND_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (arrays) {
-    row[BND_LIN] = arrays->linear_xy, row[BND_ANG] = arrays->angular, row[BND_IMUQ] = arrays->imu_orientation_wxyz, row[BND_IMUW] = arrays->imu_angular_velocity;
-    row[BND_FORCE] = arrays->tip_force, row[BND_EFFORT] = arrays->joint_effort;
-  }
-  memcpy(e->bound_inputs[set], row, sizeof row);
+  const unsigned mask = input_mask(arrays);
+  if (const int rc = input_pairs_check(mask, kAllInputs & ~kPoseInputs, "bound")) return rc;
+  if ((mask & kPoseInputs) || (arrays && arrays->pose_reset_mode)) return fail(SHC_ERR_INVALID_ARG, "input sets carry velocity, IMU, tip force and joint effort");
+  for (int g = 0; g < kInputGroups; ++g)
+    if (input_group(g).bound >= 0) e->bound_inputs[set][input_group(g).bound] = arrays ? arrays->*kCycleInput[g] : nullptr;
   return SHC_OK;
 }
 
@@ -393,17 +389,8 @@ extern "C" int shc_engine_resident_post(shc_engine *e, const shc_cycle_inputs *i
   Resident *r = e->res;
   if ((rc = resident_alive(r)) != SHC_OK) return rc;
   if (!in) return fail(SHC_ERR_INVALID_ARG, "inputs is NULL");
-  if ((in->linear_xy == nullptr) != (in->angular == nullptr)) return fail(SHC_ERR_INVALID_ARG, "linear_xy and angular are posted together");
-  if ((in->imu_orientation_wxyz == nullptr) != (in->imu_angular_velocity == nullptr)) return fail(SHC_ERR_INVALID_ARG, "the two IMU arrays are posted together");
-  if ((in->pose_translation_velocity == nullptr) != (in->pose_rotation_velocity == nullptr))
-    return fail(SHC_ERR_INVALID_ARG, "the two pose input arrays are posted together");
-  unsigned mask = 0;
-  if (in->linear_xy) mask |= 1u << RG_VEL;
-  if (in->imu_orientation_wxyz) mask |= 1u << RG_IMU;
-  if (in->pose_translation_velocity) mask |= 1u << RG_POSE;
-  if (in->pose_reset_mode) mask |= 1u << RG_RESET;
-  if (in->tip_force) mask |= 1u << RG_FORCE;
-  if (in->joint_effort) mask |= 1u << RG_EFFORT;
+  if ((rc = input_pairs_check(input_mask(in), kAllInputs, "posted")) != SHC_OK) return rc;
+  const unsigned mask = input_resident_groups(input_mask(in)) | (in->pose_reset_mode ? 1u << RG_RESET : 0u);
   if ((mask & ((1u << RG_POSE) | (1u << RG_RESET))) && !(e->rt_flags & RT_MANUAL_LIVE))
     return fail(SHC_ERR_UNSUPPORTED, "pose inputs: give the engine one (shc_engine_set_pose_input / set_pose_reset_mode) before shc_engine_resident_begin");
   if ((mask & (1u << RG_EFFORT)) && !(e->rt_flags & RT_EFFORT_LIVE))
@@ -758,10 +745,11 @@ static int step_k_serial(shc_engine *e, int K, const shc_cycle_inputs *in) {
   const int64_t n = e->n, slot = int64_t(e->NJ) * e->n_slots; // double2 per ring slot: the planes that hold Q and QD (Fields: Q = 0, QD = NJ)
   for (int k = 0; k < K; ++k) {
     int rc = SHC_OK;
-    if (in && in->linear_xy) rc = shc_engine_set_velocity(e, in->linear_xy + k * n * 2, in->angular + k * n, 1);
-    if (rc == SHC_OK && in && in->imu_orientation_wxyz) rc = shc_engine_set_imu(e, in->imu_orientation_wxyz + k * n * 4, in->imu_angular_velocity + k * n * 3, 1);
-    if (rc == SHC_OK && in && in->tip_force) rc = shc_engine_set_tip_force(e, in->tip_force + k * n * e->L * 3, 1);
-    if (rc == SHC_OK && in && in->joint_effort) rc = shc_engine_set_joint_effort(e, in->joint_effort + k * n * e->L * e->NJ, 1);
+    const auto row = [&](int g) { return in && in->*kCycleInput[g] ? in->*kCycleInput[g] + k * n * input_width(g, e->L, e->NJ) : nullptr; }; // row k of group g (NULL: held)
+    if (row(SHC_ACT_LINEAR_XY)) rc = shc_engine_set_velocity(e, row(SHC_ACT_LINEAR_XY), row(SHC_ACT_ANGULAR), 1);
+    if (rc == SHC_OK && row(SHC_ACT_IMU_ORIENTATION)) rc = shc_engine_set_imu(e, row(SHC_ACT_IMU_ORIENTATION), row(SHC_ACT_IMU_ANGULAR_VELOCITY), 1);
+    if (rc == SHC_OK && row(SHC_ACT_TIP_FORCE)) rc = shc_engine_set_tip_force(e, row(SHC_ACT_TIP_FORCE), 1);
+    if (rc == SHC_OK && row(SHC_ACT_JOINT_EFFORT)) rc = shc_engine_set_joint_effort(e, row(SHC_ACT_JOINT_EFFORT), 1);
     if (rc == SHC_OK) rc = shc_engine_step(e, 1);
     if (rc == SHC_OK) rc = join_side(e); // (a large batch steps as two halves on the split streams: the copy below is ordered after both)
     if (rc != SHC_OK) return rc;
@@ -775,20 +763,13 @@ static int step_k_serial(shc_engine *e, int K, const shc_cycle_inputs *in) {
 
 extern "C" int shc_engine_step_k(shc_engine *e, int n_cycles, const shc_cycle_inputs *in) {
   SHC_ENTER(e);
-  if (n_cycles < 1 || n_cycles > 4096) return fail(SHC_ERR_INVALID_ARG, "shc_engine_step_k: 1 .. 4096 cycles per launch");
-  if (e->starting_up) return fail(SHC_ERR_UNSUPPORTED, "shc_engine_step_k starts from a running engine (finish the start-up first)");
-  unsigned mask = 0;
-  if (in) {
-    if (!in->on_device) return fail(SHC_ERR_INVALID_ARG, "shc_engine_step_k: the K-deep input arrays are device arrays (on_device = 1)");
-    if ((in->linear_xy == nullptr) != (in->angular == nullptr)) return fail(SHC_ERR_INVALID_ARG, "linear_xy and angular are given together");
-    if ((in->imu_orientation_wxyz == nullptr) != (in->imu_angular_velocity == nullptr)) return fail(SHC_ERR_INVALID_ARG, "the two IMU arrays are given together");
-    if (in->pose_translation_velocity || in->pose_rotation_velocity || in->pose_reset_mode)
-      return fail(SHC_ERR_UNSUPPORTED, "shc_engine_step_k carries velocity, IMU, tip force and joint effort; give pose inputs / reset modes with their setters before the call (held for the K cycles)");
-    if (in->linear_xy) mask |= 1u << RG_VEL;
-    if (in->imu_orientation_wxyz) mask |= 1u << RG_IMU;
-    if (in->tip_force) mask |= 1u << RG_FORCE;
-    if (in->joint_effort) mask |= 1u << RG_EFFORT;
-  }
+  const char *who = "shc_engine_step_k";
+  if (const int rc = k_launch_cycles_check(who, n_cycles)) return rc;
+  if (const int rc = k_launch_running_check(e, who)) return rc;
+  if (in && !in->on_device) return fail(SHC_ERR_INVALID_ARG, "shc_engine_step_k: the K-deep input arrays are device arrays (on_device = 1)");
+  if (const int rc = input_pairs_check(input_mask(in), kAllInputs & ~kPoseInputs, "given")) return rc;
+  if (const int rc = k_launch_pose_check(who, input_mask(in), in && in->pose_reset_mode)) return rc;
+  const unsigned mask = input_resident_groups(input_mask(in));
   HIP_TRY(hipSetDevice(e->device));
   const bool split = e->n_waves >= kSplitWaves && !(e->features & SHC_FEAT_SINGLE_STREAM);
   if (!split || ((mask & (1u << RG_EFFORT)) && !(e->rt_flags & RT_EFFORT_LIVE))) { // (one launch on the engine's stream / the parameter block is about to be re-uploaded)
@@ -804,12 +785,8 @@ extern "C" int shc_engine_step_k(shc_engine *e, int n_cycles, const shc_cycle_in
     const int rc = resident_fit(e, fit);
     if (rc != SHC_OK) return rc;
   }
-  if (size_t(e->NJ) * e->n_slots * 16 * size_t(n_cycles) >= (size_t(1) << 31))
-    return fail(SHC_ERR_INVALID_ARG, "shc_engine_step_k: cycles x batch - the output ring must stay below 2 GiB (fewer cycles per launch)");
-  {
-    const int rc = step_k_out_ring(e, n_cycles);
-    if (rc != SHC_OK) return rc;
-  }
+  if (const int rc = k_launch_ring_check(e, who, n_cycles)) return rc;
+  if (const int rc = step_k_out_ring(e, n_cycles)) return rc;
   if (!fit.batch || (e->features & SHC_FEAT_STEP_K_SERIAL)) return step_k_serial(e, n_cycles, in);
   int k0 = 0;
   if (adjust_pending(e)) { // shc_adjust.hpp, row "shc_engine_step_k, cycle 1": through the serial form (input row 0, ring slot 0), the batch kernel takes the other K - 1
@@ -820,13 +797,11 @@ extern "C" int shc_engine_step_k(shc_engine *e, int n_cycles, const shc_cycle_in
   }
   e->plan_poser_tips_current = false;
   ResidentArgs A{};
-  A.kstride[BND_LIN] = e->n * 2, A.kstride[BND_ANG] = e->n, A.kstride[BND_IMUQ] = e->n * 4, A.kstride[BND_IMUW] = e->n * 3;
-  A.kstride[BND_FORCE] = e->n * e->L * 3, A.kstride[BND_EFFORT] = e->n * e->L * e->NJ;
-  if (in) {
-    const auto row = [&](const double *a, int which) { return a ? a + k0 * A.kstride[which] : a; };
-    A.bound[0][BND_LIN] = row(in->linear_xy, BND_LIN), A.bound[0][BND_ANG] = row(in->angular, BND_ANG);
-    A.bound[0][BND_IMUQ] = row(in->imu_orientation_wxyz, BND_IMUQ), A.bound[0][BND_IMUW] = row(in->imu_angular_velocity, BND_IMUW);
-    A.bound[0][BND_FORCE] = row(in->tip_force, BND_FORCE), A.bound[0][BND_EFFORT] = row(in->joint_effort, BND_EFFORT);
+  for (int g = 0; g < kInputGroups; ++g) { // the K-deep arrays as bound set 0, from row k0 on
+    const int b = input_group(g).bound;
+    if (b < 0) continue;
+    A.kstride[b] = e->n * input_width(g, e->L, e->NJ);
+    if (in && in->*kCycleInput[g]) A.bound[0][b] = in->*kCycleInput[g] + k0 * A.kstride[b];
   }
   A.out = e->k_out + size_t(k0) * size_t(e->NJ) * e->n_slots * 2;
   A.depth = n_cycles - k0;

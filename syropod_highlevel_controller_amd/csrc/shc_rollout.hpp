@@ -1,7 +1,7 @@
 // shc_rollout.hpp — rollout tensors: the two dense-tensor ends of shc_engine_step_k.  shc_engine_step_k_actions takes the inputs of K cycles from
 // one dense [K][n][A] array of float64 or float32, shc_engine_get_step_k_observations hands the joints of a range of cycles back as one dense
 // [cycles][n][D] array.  Included by shc_engine.hip behind shc_actions.hpp (uses the row pattern of shc_rows.hpp, the specs and checks of
-// shc_observe.hpp / shc_actions.hpp, load_leg_fields of shc_leg_msgs.hpp, resident_fit and the output ring of shc_resident.hpp and the
+// shc_observe.hpp / shc_actions.hpp, the group table, the K-cycle rules and the K-deep staging plan of shc_inputs.hpp, load_leg_fields of shc_leg_msgs.hpp, resident_fit and the output ring of shc_resident.hpp and the
 // entry-point macros).  The fleet forms (shc_fleet_rollout.hpp) launch the same kernels with a part's caller ids as the row table.
 //
 // Neither end touches the batch kernel.  shc_engine_step_k reads up to six K-deep float64 arrays, each dense on its own:
@@ -20,19 +20,13 @@
 // alone, on the engine's stream.
 #pragma once
 
-// the staged groups in staging order: the member of shc_cycle_inputs each becomes, the action field it comes from
-enum { RO_LIN, RO_ANG, RO_IMUQ, RO_IMUW, RO_FORCE, RO_EFFORT, RO_COUNT };
-constexpr int kRolloutRobotGroups = RO_FORCE; // the per-robot groups come first, and their number is that of their action field
-static_assert(SHC_ACT_LINEAR_XY == RO_LIN && SHC_ACT_ANGULAR == RO_ANG && SHC_ACT_IMU_ORIENTATION == RO_IMUQ && SHC_ACT_IMU_ANGULAR_VELOCITY == RO_IMUW,
-              "the four per-robot groups shc_engine_step_k carries are the first four action fields");
-constexpr uint32_t kRolloutPoseMask = 1u << SHC_ACT_POSE_TRANSLATION_VELOCITY | 1u << SHC_ACT_POSE_ROTATION_VELOCITY;
-constexpr size_t kRolloutMaxBytes = size_t(1) << 31; // the K-deep staging stays below 2 GiB, as the output ring
+constexpr int kRolloutRobotGroups = SHC_ACT_POSE_TRANSLATION_VELOCITY; // the per-robot groups a K-cycle launch carries come first (shc_inputs.hpp)
 
 // The stage kernel's view of a call
 struct RolloutStageArgs : ActArgs {
   int64_t cycle_stride;  // elements between the rows of consecutive cycles
   int64_t n;             // robots of the engine: the staged arrays are [K][n][..]
-  double *dst[RO_COUNT]; // the staged arrays (unselected: NULL, never read)
+  double *dst[BND_COUNT]; // the staged arrays by BND_* (unselected: NULL, never read)
 };
 
 // The geometry and the tile of shc_rows.hpp, copy-in, as actions_kernel: block (g, k) brings the rows of robot group g at cycle k into the tile
@@ -56,13 +50,13 @@ __global__ __launch_bounds__(64) void rollout_stage_kernel(const T *__restrict__
   auto sel = [&](int f) { return (a.mask >> f & 1u) != 0; };
   if (sel(SHC_ACT_TIP_FORCE)) {
     const T *s = row + a.col[SHC_ACT_TIP_FORCE] + leg * 3;
-    double *d = a.dst[RO_FORCE] + (at * L + leg) * 3;
+    double *d = a.dst[BND_FORCE] + (at * L + leg) * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c) d[c] = static_cast<double>(s[c]);
   }
   if (sel(SHC_ACT_JOINT_EFFORT)) { // all NJ entries of every leg: a shorter leg's surplus joints hold what the caller put there
     const T *s = row + a.col[SHC_ACT_JOINT_EFFORT] + leg * a.dof;
-    double *d = a.dst[RO_EFFORT] + (at * L + leg) * NJ;
+    double *d = a.dst[BND_EFFORT] + (at * L + leg) * NJ;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) d[j] = static_cast<double>(s[j]);
   }
@@ -71,7 +65,7 @@ __global__ __launch_bounds__(64) void rollout_stage_kernel(const T *__restrict__
     for (int g = 0; g < kRolloutRobotGroups; ++g) {
       if (g % L != leg || !sel(g)) continue;
       const T *s = row + a.col[g];
-      double *d = a.dst[g] + at * act_robot_width(g);
+      double *d = a.dst[input_group(g).bound] + at * act_robot_width(g);
 #pragma unroll
       for (int c = 0; c < act_robot_width(g); ++c) d[c] = static_cast<double>(s[c]); // (the quaternion as it is: the engine normalises)
     }
@@ -118,67 +112,38 @@ __global__ __launch_bounds__(64) void rollout_joints_kernel(T *__restrict__ out,
 }
 
 // ---- host side
-// Where the groups of a spec lie in K-deep staging for an engine, in doubles (-1: not selected), and the doubles in all
-struct RolloutPlan {
-  int64_t at[RO_COUNT];
-  int64_t doubles;
-};
-static RolloutPlan rollout_plan(const shc_engine *e, const RowLayout &lay, int K) {
-  const int field[RO_COUNT] = {SHC_ACT_LINEAR_XY, SHC_ACT_ANGULAR, SHC_ACT_IMU_ORIENTATION, SHC_ACT_IMU_ANGULAR_VELOCITY, SHC_ACT_TIP_FORCE, SHC_ACT_JOINT_EFFORT};
-  const int64_t width[RO_COUNT] = {2, 1, 4, 3, int64_t(e->L) * 3, int64_t(e->L) * e->NJ};
-  RolloutPlan p{};
-  for (int m = 0; m < RO_COUNT; ++m) {
-    p.at[m] = -1;
-    if (!(lay.mask >> field[m] & 1u)) continue;
-    p.at[m] = p.doubles;
-    p.doubles += int64_t(K) * e->n * width[m];
-  }
-  return p;
-}
+// Where the groups of a spec lie in K-deep staging for an engine (input_plan of shc_inputs.hpp: shc_fleet_step_k's, too); pose groups are never staged
+static InputPlan rollout_plan(const shc_engine *e, const RowLayout &lay, int K) { return input_plan(lay.mask & ~kPoseInputs, e->n, e->L, e->NJ, K); }
 
 // What is wrong with a call whoever makes it: `n` rows per cycle in the caller's array
-static int rollout_cycles_check(const char *who, int K) {
-  if (K < 1 || K > 4096) return fail(SHC_ERR_INVALID_ARG, std::string(who) + ": 1 .. 4096 cycles per launch");
-  return SHC_OK;
-}
 static int rollout_stride_check(const char *who, int64_t n, int64_t row_stride, int64_t cycle_stride) {
   if (cycle_stride != 0 && cycle_stride < n * row_stride) return fail(SHC_ERR_INVALID_ARG, std::string(who) + ": cycle_stride is non-zero and below n x the row stride");
   return SHC_OK;
 }
 static int rollout_actions_call_check(const char *who, const shc_act_spec *spec, const RowLayout &lay, int K, int64_t n, int64_t cycle_stride) {
-  int rc = rollout_cycles_check(who, K);
+  int rc = k_launch_cycles_check(who, K);
   if (rc != SHC_OK) return rc;
   if ((rc = rollout_stride_check(who, n, row_stride_of(spec, lay), cycle_stride)) != SHC_OK) return rc;
-  const auto sel = [&](int f) { return (lay.mask >> f & 1u) != 0; };
-  if (sel(SHC_ACT_LINEAR_XY) != sel(SHC_ACT_ANGULAR)) return fail(SHC_ERR_INVALID_ARG, std::string(who) + ": SHC_ACT_LINEAR_XY and SHC_ACT_ANGULAR are given together");
-  if (sel(SHC_ACT_IMU_ORIENTATION) != sel(SHC_ACT_IMU_ANGULAR_VELOCITY)) return fail(SHC_ERR_INVALID_ARG, std::string(who) + ": the two IMU fields are given together");
-  if (lay.mask & kRolloutPoseMask)
-    return fail(SHC_ERR_UNSUPPORTED, std::string(who) + " carries velocity, IMU, tip force and joint effort; give pose inputs with their setter before the call (held for the K cycles)");
-  return SHC_OK;
+  if ((rc = input_pairs_check(lay.mask, kAllInputs & ~kPoseInputs, "given")) != SHC_OK) return rc;
+  return k_launch_pose_check(who, lay.mask);
 }
 // ... and what an engine refuses of it: everything its shc_engine_step_k would refuse, asked before anything is staged
-static int rollout_actions_engine_check(const shc_engine *e, const shc_act_spec *spec, const RowLayout &lay, int K) {
-  int rc = actions_check(e, spec);
-  if (rc != SHC_OK) return rc;
-  if (e->starting_up) return fail(SHC_ERR_UNSUPPORTED, "the K-cycle launches start from a running engine (finish the start-up first)");
-  if (size_t(e->NJ) * e->n_slots * 16 * size_t(K) >= kRolloutMaxBytes)
-    return fail(SHC_ERR_INVALID_ARG, "cycles x batch - the output ring must stay below 2 GiB (fewer cycles per launch)");
-  if (size_t(rollout_plan(e, lay, K).doubles) * 8 >= kRolloutMaxBytes)
-    return fail(SHC_ERR_INVALID_ARG, "cycles x batch x the groups named - the K-deep staging must stay below 2 GiB (fewer cycles per launch)");
-  ResidentFit fit;
-  return resident_fit(e, fit);
+static int rollout_actions_engine_check(const char *who, const shc_engine *e, const shc_act_spec *spec, const RowLayout &lay, int K) {
+  const int rc = actions_check(e, spec);
+  return rc != SHC_OK ? rc : k_launch_engine_check(e, who, K, rollout_plan(e, lay, K).doubles);
 }
 
 // The stage launch on the engine's stream: the K x n rows of `actions` (row = ids[robot], a device table, or the robot's own index) into the
 // K-deep arrays at `stage`, and `staged`, the shc_cycle_inputs over them.  The caller has checked everything, made room and joined split steps.
 static int rollout_stage_launch(shc_engine *e, const shc_act_spec *spec, const RowLayout &lay, const void *actions, int64_t row_stride, int64_t cycle_stride,
                                 const int64_t *ids, int K, double *stage, shc_cycle_inputs &staged) {
-  const RolloutPlan plan = rollout_plan(e, lay, K);
+  const InputPlan plan = rollout_plan(e, lay, K);
   RolloutStageArgs a{};
   row_args(a, lay, spec->dtype, row_stride, false, 0.0);
   a.dof = spec->dof;
   a.cycle_stride = cycle_stride, a.n = e->n;
-  for (int m = 0; m < RO_COUNT; ++m) a.dst[m] = plan.at[m] < 0 ? nullptr : stage + plan.at[m];
+  for (int g = 0; g < kInputGroups; ++g)
+    if (plan.at[g] >= 0) a.dst[input_group(g).bound] = stage + plan.at[g];
   const dim3 grid(row_grid(e->L, 0, e->n), unsigned(K));
   const size_t lds = row_tile_bytes(e->L, a.pitch, spec->dtype);
   const int rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
@@ -191,9 +156,7 @@ static int rollout_stage_launch(shc_engine *e, const shc_act_spec *spec, const R
   });
   if (rc != SHC_OK) return rc;
   HIP_TRY(hipGetLastError());
-  staged = shc_cycle_inputs{};
-  staged.linear_xy = a.dst[RO_LIN], staged.angular = a.dst[RO_ANG], staged.imu_orientation_wxyz = a.dst[RO_IMUQ], staged.imu_angular_velocity = a.dst[RO_IMUW];
-  staged.tip_force = a.dst[RO_FORCE], staged.joint_effort = a.dst[RO_EFFORT], staged.on_device = 1;
+  staged = input_plan_arrays(plan, stage);
   return SHC_OK;
 }
 
@@ -220,8 +183,9 @@ extern "C" int shc_engine_step_k_actions(shc_engine *e, int n_cycles, const shc_
   if (const int bad = row_resolve<ActRows>(spec, lay)) return bad;
   int rc = row_aligned(actions, spec->dtype, "actions");
   if (rc != SHC_OK) return rc;
-  if ((rc = rollout_actions_call_check("shc_engine_step_k_actions", spec, lay, n_cycles, e->n, cycle_stride)) != SHC_OK) return rc;
-  if ((rc = rollout_actions_engine_check(e, spec, lay, n_cycles)) != SHC_OK) return rc;
+  const char *who = "shc_engine_step_k_actions";
+  if ((rc = rollout_actions_call_check(who, spec, lay, n_cycles, e->n, cycle_stride)) != SHC_OK) return rc;
+  if ((rc = rollout_actions_engine_check(who, e, spec, lay, n_cycles)) != SHC_OK) return rc;
   HIP_TRY(hipSetDevice(e->device));
   if ((rc = rollout_stage_room(e, e->k_in, e->k_in_bytes, size_t(rollout_plan(e, lay, n_cycles).doubles) * 8)) != SHC_OK) return rc;
   // the halves of an earlier split launch may still be reading the arrays this call is about to overwrite: the engine's stream follows them first
