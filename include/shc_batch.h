@@ -1284,6 +1284,40 @@ int shc_fleet_step_k_actions_device(shc_fleet *f, int n_cycles, const shc_act_sp
 int shc_fleet_get_step_k_observations_device(shc_fleet *f, int first_cycle, int n_cycles, const shc_obs_spec *spec, void *out /* [n_cycles][n][row_stride], caller's order */,
                                              int64_t cycle_stride);
 /*
+ * Rollout kinematics: what is a pure function of the joints a K-cycle launch left in its output ring, per cycle - where the feet were, and
+ * whether (and in which cycle) a robot ran into its joint limits.  DEVICE arrays only, as the rollout tensors; no cycle kernel takes part, and
+ * neither call writes into an engine: state records, auxiliary blobs and the ring are byte for byte what they were.
+ * KINEMATICS.  The spec, row and column rules of shc_engine_get_step_k_observations, for any subset of SHC_OBS_Q, SHC_OBS_QD and
+ * SHC_OBS_MODEL_TIP.  The q / qd columns are what that call writes.  Column c of SHC_OBS_MODEL_TIP in row (k, i) holds the double
+ * shc_engine_get_observations writes for SHC_OBS_MODEL_TIP on an engine whose stored joints are those of ring slot first_cycle + k: Leg::applyFK
+ * (model.cpp:975) on the ring's own q, in the robot frame - unchanged for SHC_OBS_F64, static_cast<float> for SHC_OBS_F32, `pad` where the robot
+ * has no such leg.
+ * HEALTH.  Record (k, i) of health [n_cycles][n] is what shc_debug_robot_health returns for robot i when it is given q and qd of ring slot
+ * first_cycle + k (as shc_engine_get_step_k_joint_state returns them), model_tip = poser_tip, zero admittance, zero leg_status and a finite pose:
+ * min_limit_proximity, max_speed_ratio, bytes 1 and 2 of leg_masks, SHC_HEALTH_POSITION_LIMIT / _SPEED_LIMIT / _NEAR_LIMIT are live, and
+ * SHC_HEALTH_NONFINITE over the q / qd of a leg's own joints; max_tip_deviation and byte 0 of leg_masks are 0.  first_hit[i] is the smallest
+ * cycle index c of the latest launch in [first_cycle, first_cycle + n_cycles) whose record has flags & criteria.select != 0, or -1: the `done`
+ * mask of a rollout and the index of the first bad step.  Either output may be NULL (not both); health is 16-byte aligned, first_hit 4-byte
+ * aligned; criteria is HOST memory, NULL = select 0.  One launch, no atomics: the same bytes on every run.
+ * The tips and forces of the walker and the poser, the body pose and the IK deviation of a cycle are not functions of the ring: not delivered.
+ * ORDER.  Both calls join split launches (events, no host wait), run on the engine's stream and allocate nothing.
+ * FLEET.  Rows, records and first_hit in the CALLER's instance order (shc_fleet_get_step_k_observations_device): one launch per part on the
+ * part's stream, no staging.
+ * REFUSALS (decided before anything is launched; a fleet asks every part first).  SHC_ERR_INVALID_ARG: a NULL handle, spec or out, or both
+ * health outputs NULL; whatever the observation pass refuses of a spec; a misaligned buffer; a cycle range outside the latest K-cycle launch, or
+ * no launch yet; cycle_stride non-zero and below n x the row stride; criteria.reserved != 0 or select bits outside the six.
+ * SHC_ERR_UNSUPPORTED: an observation field outside the three; criteria.select with SHC_HEALTH_IK_DEVIATION or SHC_HEALTH_TIP_DEVIATION (the
+ * ring holds joints: a caller must not believe those are watched); a fleet that spans devices.  SHC_ERR_BUSY: resident mode.
+ */
+int shc_engine_get_step_k_kinematics(shc_engine *e, int first_cycle, int n_cycles, const shc_obs_spec *spec, void *out /* device, [n_cycles][n][row_stride] */,
+                                     int64_t cycle_stride);
+int shc_engine_scan_step_k_health(shc_engine *e, int first_cycle, int n_cycles, const shc_health_criteria *criteria /* host, may be NULL */,
+                                  shc_robot_health *health /* device, [n_cycles][n], may be NULL */, int32_t *first_hit /* device, [n], may be NULL; not both NULL */);
+int shc_fleet_get_step_k_kinematics_device(shc_fleet *f, int first_cycle, int n_cycles, const shc_obs_spec *spec, void *out /* [n_cycles][n][row_stride], caller's order */,
+                                           int64_t cycle_stride);
+int shc_fleet_scan_step_k_health_device(shc_fleet *f, int first_cycle, int n_cycles, const shc_health_criteria *criteria, shc_robot_health *health /* [n_cycles][n], caller's order */,
+                                        int32_t *first_hit /* [n], caller's order */);
+/*
  * Foothold pass: the externally requested tip targets / default stance poses of rough terrain mode (shc_external_target above) of every robot
  * taken from - or read back into - one dense [n][F] array of float64 or float32, in one kernel per engine (per part of a fleet).  What a
  * foothold planner on the GPU emits never crosses the host; the three host calls above stay as they are.

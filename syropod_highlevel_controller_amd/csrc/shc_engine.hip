@@ -1618,6 +1618,7 @@ static int derive_tips(shc_engine *e) {
 #include "shc_observe.hpp"  // chosen fields of every robot as one dense [rows][D] array: shc_engine_get_observations
 #include "shc_actions.hpp"  // chosen input groups of every robot from one dense [n][A] array: shc_engine_set_actions
 #include "shc_rollout.hpp"  // K cycles per launch from one dense [K][n][A] array, their joints as one dense [cycles][n][D] array: shc_engine_step_k_actions / _get_step_k_observations
+#include "shc_rollout_kin.hpp" // what is a pure function of that ring, per cycle: foot tips = FK(q) and the joint-limit health records: shc_engine_get_step_k_kinematics / _scan_step_k_health
 
 template <int NJ>
 static Pose host_fk_tip_pose(const shc_params &p, int leg, const double *q) {

@@ -7,6 +7,8 @@
 // rollout_stage_kernel into the part's K-deep staging (the buffer shc_fleet_step_k uses, with its rules: grown on demand, counted by
 // shc_fleet_io_bytes, joined before it is overwritten), one shc_engine_step_k on it, and for the way back one launch of rollout_joints_kernel
 // out of the part's ring, all on the part's stream.  The rows of the parts are disjoint, so the parts' streams need no order among themselves.
+// The rollout kinematics (shc_rollout_kin.hpp: shc_fleet_get_step_k_kinematics_device, shc_fleet_scan_step_k_health_device) are read launches of
+// the same kind: one per part, the part's caller ids as the row / record table, nothing staged.
 #pragma once
 
 extern "C" int shc_fleet_step_k_actions_device(shc_fleet *f, int n_cycles, const shc_act_spec *spec, const void *actions, int64_t cycle_stride) {
@@ -33,18 +35,46 @@ extern "C" int shc_fleet_step_k_actions_device(shc_fleet *f, int n_cycles, const
   return rc;
 }
 
-extern "C" int shc_fleet_get_step_k_observations_device(shc_fleet *f, int first_cycle, int n_cycles, const shc_obs_spec *spec, void *out, int64_t cycle_stride) {
-  RowLayout lay;
-  int rc = fleet_rows_begin<ObsRows>(f, spec, out, "out", lay, [&](const shc_engine *e) { return rollout_joints_check(e, spec, lay); });
-  if (rc != SHC_OK) return rc;
-  const char *who = "shc_fleet_get_step_k_observations_device";
-  int K = f->k_cycles;
+// The K of the fleet's latest K-cycle launch, 0 when the ring of a part does not hold it
+static int fleet_rollout_cycles(const shc_fleet *f) {
   for (const auto &p : f->parts) // (a part stepped on its own since, through shc_fleet_part: its ring holds another launch)
-    if (!p.engine->k_out || p.engine->k_out_cycles != f->k_cycles) K = 0;
-  if ((rc = rollout_range_check(who, K, first_cycle, n_cycles)) != SHC_OK) return rc;
+    if (!p.engine->k_out || p.engine->k_out_cycles != f->k_cycles) return 0;
+  return f->k_cycles;
+}
+
+// The read of the parts' rings as rows, for the two entry points that differ in the fields they let through (rollout_read of shc_rollout.hpp)
+static int fleet_rollout_read(shc_fleet *f, const char *who, uint32_t readable, int first_cycle, int n_cycles, const shc_obs_spec *spec, void *out, int64_t cycle_stride) {
+  RowLayout lay;
+  int rc = fleet_rows_begin<ObsRows>(f, spec, out, "out", lay, [&](const shc_engine *e) { return rollout_joints_check(e, spec, lay, readable); });
+  if (rc != SHC_OK) return rc;
+  if ((rc = rollout_range_check(who, fleet_rollout_cycles(f), first_cycle, n_cycles)) != SHC_OK) return rc;
   if ((rc = rollout_stride_check(who, f->n, row_stride_of(spec, lay), cycle_stride)) != SHC_OK) return rc;
   return fleet_rows_each(f, spec, lay, [&](FleetPart &p, int64_t stride) {
     const int rc = fleet_part_join(p); // split launches: the part's stream follows both halves before it reads their ring
     return rc != SHC_OK ? rc : rollout_joints_launch(p.engine, spec, lay, out, stride, cycle_stride ? cycle_stride : f->n * stride, p.d_ids, first_cycle, n_cycles);
   });
+}
+extern "C" int shc_fleet_get_step_k_observations_device(shc_fleet *f, int first_cycle, int n_cycles, const shc_obs_spec *spec, void *out, int64_t cycle_stride) {
+  return fleet_rollout_read(f, "shc_fleet_get_step_k_observations_device", kRingJoints, first_cycle, n_cycles, spec, out, cycle_stride);
+}
+// ... and the rollout kinematics (shc_rollout_kin.hpp): model_tip = FK(q) beside the joints, from the same kernel
+extern "C" int shc_fleet_get_step_k_kinematics_device(shc_fleet *f, int first_cycle, int n_cycles, const shc_obs_spec *spec, void *out, int64_t cycle_stride) {
+  return fleet_rollout_read(f, "shc_fleet_get_step_k_kinematics_device", kRingKinematics, first_cycle, n_cycles, spec, out, cycle_stride);
+}
+
+// The joint-limit records of every cycle: one launch of rollout_health_kernel per part on the part's stream, record (k, ids[r]) and first_hit[ids[r]]
+// for robot r of the part - the caller's order without staging.
+extern "C" int shc_fleet_scan_step_k_health_device(shc_fleet *f, int first_cycle, int n_cycles, const shc_health_criteria *criteria, shc_robot_health *health,
+                                                   int32_t *first_hit) {
+  if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
+  shc_health_criteria crit;
+  int rc = rollout_health_call_check(criteria, health, first_hit, crit);
+  if (rc == SHC_OK) rc = fleet_io_ready(f);
+  if (rc == SHC_OK) rc = rollout_range_check("shc_fleet_scan_step_k_health_device", fleet_rollout_cycles(f), first_cycle, n_cycles);
+  if (rc == SHC_OK) rc = fleet_io_prepare(f);
+  for (size_t i = 0; rc == SHC_OK && i < f->parts.size(); ++i) {
+    FleetPart &p = f->parts[i];
+    if ((rc = fleet_part_join(p)) == SHC_OK) rc = rollout_health_launch(p.engine, crit, health, first_hit, f->n, p.d_ids, first_cycle, n_cycles);
+  }
+  return rc;
 }

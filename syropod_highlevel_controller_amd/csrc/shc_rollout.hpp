@@ -10,7 +10,7 @@
 //           kernel or the serial form, a pending adjusted parameter's first cycle, touchdown detection, the first-effort switch, the split halves,
 //           the normalisation of the quaternion are all its own.  Nothing is computed here but static_cast<double>.
 //   JOINTS  one launch reads q / qd of the requested slots of the output ring where they lie (the leg state's own planes: leg_state_index) and
-//           writes whole rows of the caller's array.
+//           writes whole rows of the caller's array.  (Its TIPS instance serves the rollout kinematics of shc_rollout_kin.hpp, included behind this file.)
 // The cycle is the second grid dimension (blockIdx.y): wave-uniform, built from block indices and kernel arguments only.
 //
 // The staged arrays belong to the engine: allocated by the first call that needs them, grown (never shrunk) by a call that needs more, freed with
@@ -72,8 +72,9 @@ __global__ __launch_bounds__(64) void rollout_stage_kernel(const T *__restrict__
   }
 }
 
-// The joints kernel's view of a call
-struct RolloutJointArgs : RowArgs<2> {
+// The joints kernel's view of a call: the columns of q, qd and - for shc_engine_get_step_k_kinematics (shc_rollout_kin.hpp) - model_tip
+constexpr int kRolloutObsFields = SHC_OBS_MODEL_TIP + 1;
+struct RolloutJointArgs : RowArgs<kRolloutObsFields> {
   int32_t dof;          // columns per leg of q / qd
   int64_t cycle_stride; // elements between the rows of consecutive cycles
   int64_t n, n_slots;
@@ -83,10 +84,13 @@ static_assert(SHC_OBS_Q == 0 && SHC_OBS_QD == 1, "q and qd are the first two obs
 // The geometry and the tile of shc_rows.hpp, copy-out, as observe_kernel: `ring` is the slot of the first requested cycle, block (g, k) reads
 // the joints of robot group g in slot k - NJ planes of n_slots double2, Q and QD at the leg state's own addresses (leg_state_index: the lane's
 // slot is slot_of(robot, leg)), read as whole 16-byte planes - and builds the rows in the tile, filled with `pad` first where the row geometry
-// is larger than the robot; the rows leave with consecutive lanes on consecutive elements for out + k * cycle_stride.
-template <int L, int NJ, class T>
-__global__ __launch_bounds__(64) void rollout_joints_kernel(T *__restrict__ out, const double2 *__restrict__ ring, const RolloutJointArgs o,
-                                                            const int64_t *__restrict__ ids) {
+// is larger than the robot; the rows leave with consecutive lanes on consecutive elements for out + k * cycle_stride.  SHC_OBS_MODEL_TIP - only
+// shc_engine_get_step_k_kinematics lets it through - is derived_model_tip on the q just read, as in observe_kernel.  FK costs 102 - 154 VGPRs
+// against the 20 - 24 of the copy, so it is an instance of its own (TIPS) that the host picks by the mask: a spec without model_tip runs the
+// kernel it ran before, at 8 waves per SIMD.
+template <int L, int NJ, class T, bool TIPS>
+__global__ __launch_bounds__(64) void rollout_joints_kernel(T *__restrict__ out, const double2 *__restrict__ ring, const SharedConsts<L, NJ> *__restrict__ gc,
+                                                            const RolloutJointArgs o, const int64_t *__restrict__ ids) {
   using FD = Fields<NJ>;
   static_assert(FD::Q == 0 && FD::QD == NJ, "a ring slot holds the planes of Q and QD");
   const RowGroup<L> rg(0, o.n);
@@ -105,6 +109,14 @@ __global__ __launch_bounds__(64) void rollout_joints_kernel(T *__restrict__ out,
     if (o.mask >> SHC_OBS_QD & 1u) {
 #pragma unroll
       for (int j = 0; j < NJ; ++j) row[o.col[SHC_OBS_QD] + rg.leg * o.dof + j] = static_cast<T>(v[NJ + j]);
+    }
+    if constexpr (TIPS) {
+      double q[NJ];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) q[j] = v[j];
+      const V3 tip = derived_model_tip<NJ>(gc->leg[rg.leg], q);
+      T *d = row + o.col[SHC_OBS_MODEL_TIP] + rg.leg * 3;
+      d[0] = static_cast<T>(tip.x), d[1] = static_cast<T>(tip.y), d[2] = static_cast<T>(tip.z);
     }
   }
   __syncthreads();
@@ -197,10 +209,13 @@ extern "C" int shc_engine_step_k_actions(shc_engine *e, int n_cycles, const shc_
   return shc_engine_step_k(e, n_cycles, &staged);
 }
 
-// What an engine refuses of an observation spec that is valid on its own, for the joints of the ring
-static int rollout_joints_check(const shc_engine *e, const shc_obs_spec *spec, const RowLayout &lay) {
-  if (lay.mask & ~(1u << SHC_OBS_Q | 1u << SHC_OBS_QD))
-    return fail(SHC_ERR_UNSUPPORTED, "the output ring of the K-cycle launches holds joints: SHC_OBS_Q and SHC_OBS_QD only");
+// What an engine refuses of an observation spec that is valid on its own, for the joints of the ring: `readable` is kRingJoints for
+// shc_engine_get_step_k_observations, kRingKinematics - what is a pure function of those joints as well - for shc_engine_get_step_k_kinematics
+constexpr uint32_t kRingJoints = 1u << SHC_OBS_Q | 1u << SHC_OBS_QD, kRingKinematics = kRingJoints | 1u << SHC_OBS_MODEL_TIP;
+static int rollout_joints_check(const shc_engine *e, const shc_obs_spec *spec, const RowLayout &lay, uint32_t readable = kRingJoints) {
+  if (lay.mask & ~readable)
+    return fail(SHC_ERR_UNSUPPORTED, readable == kRingJoints ? "the output ring of the K-cycle launches holds joints: SHC_OBS_Q and SHC_OBS_QD only"
+                                                             : "the output ring of the K-cycle launches holds joints: SHC_OBS_Q, SHC_OBS_QD and SHC_OBS_MODEL_TIP = FK(q) only");
   return observe_check(e, spec, lay);
 }
 // cycles [first, first + count) of the K of the latest launch
@@ -222,10 +237,13 @@ static int rollout_joints_launch(shc_engine *e, const shc_obs_spec *spec, const 
   const size_t lds = row_tile_bytes(e->L, o.pitch, spec->dtype);
   const int rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
     constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
-    if (spec->dtype == SHC_OBS_F32)
-      rollout_joints_kernel<L, NJ, float><<<grid, dim3(64), lds, e->stream>>>(static_cast<float *>(out), ring, o, ids);
-    else
-      rollout_joints_kernel<L, NJ, double><<<grid, dim3(64), lds, e->stream>>>(static_cast<double *>(out), ring, o, ids);
+    const SharedConsts<L, NJ> *gc = (const SharedConsts<L, NJ> *)e->d_consts;
+    auto launch = [&](auto *rows, auto tips) {
+      using T = std::remove_pointer_t<decltype(rows)>;
+      rollout_joints_kernel<L, NJ, T, decltype(tips)::value><<<grid, dim3(64), lds, e->stream>>>(rows, ring, gc, o, ids);
+    };
+    auto typed = [&](auto tips) { spec->dtype == SHC_OBS_F32 ? launch(static_cast<float *>(out), tips) : launch(static_cast<double *>(out), tips); };
+    (o.mask >> SHC_OBS_MODEL_TIP & 1u) ? typed(std::true_type{}) : typed(std::false_type{});
     return SHC_OK;
   });
   if (rc != SHC_OK) return rc;
@@ -233,19 +251,22 @@ static int rollout_joints_launch(shc_engine *e, const shc_obs_spec *spec, const 
   return SHC_OK;
 }
 
-extern "C" int shc_engine_get_step_k_observations(shc_engine *e, int first_cycle, int n_cycles, const shc_obs_spec *spec, void *out, int64_t cycle_stride) {
+// The read of the ring as rows, for the two entry points that differ in the fields they let through (`readable`)
+static int rollout_read(shc_engine *e, const char *who, uint32_t readable, int first_cycle, int n_cycles, const shc_obs_spec *spec, void *out, int64_t cycle_stride) {
   SHC_ENTER(e);
   if (!spec || !out) return fail(SHC_ERR_INVALID_ARG, "spec or out is NULL");
   RowLayout lay;
   if (const int bad = row_resolve<ObsRows>(spec, lay)) return bad;
-  int rc = rollout_joints_check(e, spec, lay);
+  int rc = rollout_joints_check(e, spec, lay, readable);
   if (rc != SHC_OK) return rc;
   if ((rc = row_aligned(out, spec->dtype, "out")) != SHC_OK) return rc;
-  const char *who = "shc_engine_get_step_k_observations";
   if ((rc = rollout_range_check(who, e->k_out ? e->k_out_cycles : 0, first_cycle, n_cycles)) != SHC_OK) return rc;
   const int64_t stride = row_stride_of(spec, lay);
   if ((rc = rollout_stride_check(who, e->n, stride, cycle_stride)) != SHC_OK) return rc;
   if ((rc = join_side(e)) != SHC_OK) return rc; // split launches: the engine's stream follows both halves before it reads their ring
   HIP_TRY(hipSetDevice(e->device));
   return rollout_joints_launch(e, spec, lay, out, stride, cycle_stride ? cycle_stride : e->n * stride, nullptr, first_cycle, n_cycles);
+}
+extern "C" int shc_engine_get_step_k_observations(shc_engine *e, int first_cycle, int n_cycles, const shc_obs_spec *spec, void *out, int64_t cycle_stride) {
+  return rollout_read(e, "shc_engine_get_step_k_observations", kRingJoints, first_cycle, n_cycles, spec, out, cycle_stride);
 }

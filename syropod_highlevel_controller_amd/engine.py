@@ -63,6 +63,7 @@ EXPORTED_SYMBOLS = [
     "shc_obs_width", "shc_obs_column", "shc_engine_get_observations", "shc_fleet_get_observations_device",
     "shc_act_width", "shc_act_column", "shc_engine_set_actions", "shc_fleet_set_actions_device",
     "shc_engine_step_k_actions", "shc_engine_get_step_k_observations", "shc_fleet_step_k_actions_device", "shc_fleet_get_step_k_observations_device",
+    "shc_engine_get_step_k_kinematics", "shc_engine_scan_step_k_health", "shc_fleet_get_step_k_kinematics_device", "shc_fleet_scan_step_k_health_device",
     "shc_foothold_width", "shc_foothold_column", "shc_engine_set_footholds", "shc_engine_get_footholds", "shc_fleet_set_footholds_device",
     "shc_fleet_get_footholds_device",
     "shc_peer_alloc", "shc_peer_open", "shc_peer_close", "shc_peer_scatter",
@@ -330,7 +331,66 @@ def _cycles_array(a, what: str):
 def _new_device_array(shape, dtype, device):
     """An uninitialised torch tensor on the engine's device: what step_k_observations returns when it is given no array to fill."""
     import torch
+    device = device() if callable(device) else device   # (a fleet asks its parts only when a tensor is made)
     return torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device="cuda" if device is None else f"cuda:{device}")
+
+
+def _step_k_rows(lib, call: str, handle, n: int, device, what: str, fields, dtype, out, first, count, pad, legs, dof):
+    """The ring of the latest K-cycle launch as rows, for BatchEngine / MixedFleet.step_k_observations and .step_k_kinematics: ``call`` is the
+    library's entry point (an engine's or a fleet's), ``handle`` its handle, n the rows of a cycle.  out: a 3-D device array to fill (count None:
+    as many cycles as it has; returns None); without out a new torch tensor of ``dtype`` on ``device`` is filled and returned."""
+    made = None
+    if out is None:
+        if count is None:
+            raise ValueError(f"{what}: give count, or an array to fill")
+        spec = obs_spec(fields, legs, dof, dtype, 0, pad)
+        width = int(lib.shc_obs_width(C.byref(spec)))
+        if width < 0:
+            _check(SHC_ERR_INVALID_ARG, call)
+        out = made = _new_device_array((max(int(count), 0), n, width), dtype, device)
+    ptr, dt, cycles, rows, columns, stride, cycle_stride = _cycles_array(out, what)
+    count = cycles if count is None else int(count)
+    spec = obs_spec(fields, legs, dof, dt, stride, pad)
+    if count > cycles:
+        raise ValueError(f"{what}: out has {cycles} cycles, {count} are asked for")
+    _check_rows(what, "out[k]", rows, columns, n, int(lib.shc_obs_width(C.byref(spec))))
+    _check(getattr(lib, call)(handle, int(first), count, C.byref(spec), ptr, cycle_stride), call)
+    return made
+
+
+class DeviceRecords:
+    """A (cycles, n) DEVICE array of 32-byte shc_robot_health records: ``__cuda_array_interface__`` names the bytes (ROBOT_HEALTH_DTYPE's
+    fields), ``tensor`` is the float64 torch tensor (cycles, n, 4) that owns them, ``numpy()`` their host copy as ROBOT_HEALTH_DTYPE."""
+
+    def __init__(self, tensor):
+        self.tensor, self.shape, self.dtype = tensor, tuple(tensor.shape[:2]), ROBOT_HEALTH_DTYPE
+        self.__cuda_array_interface__ = {"shape": self.shape, "typestr": "|V32", "descr": ROBOT_HEALTH_DTYPE.descr, "data": (tensor.data_ptr(), False),
+                                         "strides": None, "version": 3}
+
+    def numpy(self):
+        return self.tensor.cpu().numpy().view(ROBOT_HEALTH_DTYPE).reshape(self.shape)
+
+
+def _step_k_health(lib, call: str, handle, n: int, device, select, near_limit_proximity, first, count, health, first_hit):
+    """BatchEngine / MixedFleet.step_k_health: ``call`` is the library's entry point, n the records of a cycle."""
+    for name, a in (("health", health), ("first_hit", first_hit)):
+        if isinstance(a, np.ndarray):
+            raise TypeError(f"step_k_health: {name}: device arrays only (an object with __cuda_array_interface__, e.g. a torch tensor); "
+                            "the K-cycle launches have no host form")
+    if count is None:
+        shape = getattr(health, "__cuda_array_interface__", {}).get("shape", ())
+        if len(shape) < 2:
+            raise ValueError("step_k_health: give count, or a health array of (count, n, ..) to fill")
+        count = int(shape[0])
+    count = int(count)
+    if health is None:
+        health = DeviceRecords(_new_device_array((max(count, 0), n, 4), np.float64, device))
+    if first_hit is None:
+        first_hit = _new_device_array((n,), np.int32, device)
+    crit = HealthCriteria(int(select), 0, float(near_limit_proximity), 0.0)
+    _check(getattr(lib, call)(handle, int(first), count, C.byref(crit), BatchEngine._device_out(None, health, None, max(count, 0) * n, 32, "health"),
+                              BatchEngine._device_out(None, first_hit, "<i4", n, 4, "first_hit")), call)
+    return health, first_hit
 
 
 def _check_rows(what: str, name: str, rows: int, columns: int, n: int, width: int):
@@ -665,6 +725,10 @@ def lib():
         L.shc_engine_get_step_k_observations.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(ObsSpec), C.c_void_p, C.c_int64]
         L.shc_fleet_step_k_actions_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(ActSpec), C.c_void_p, C.c_int64]
         L.shc_fleet_get_step_k_observations_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(ObsSpec), C.c_void_p, C.c_int64]
+        L.shc_engine_get_step_k_kinematics.argtypes = L.shc_engine_get_step_k_observations.argtypes
+        L.shc_fleet_get_step_k_kinematics_device.argtypes = L.shc_fleet_get_step_k_observations_device.argtypes
+        L.shc_engine_scan_step_k_health.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(HealthCriteria), C.c_void_p, C.c_void_p]
+        L.shc_fleet_scan_step_k_health_device.argtypes = L.shc_engine_scan_step_k_health.argtypes
         L.shc_foothold_width.restype = C.c_int64
         L.shc_foothold_width.argtypes = [C.POINTER(FootholdSpec)]
         L.shc_foothold_column.argtypes = [C.POINTER(FootholdSpec), C.c_int, C.c_int, C.c_int]
@@ -994,23 +1058,31 @@ class BatchEngine:
         many cycles as it has; returns None.  Without out (give count) a new torch tensor of ``dtype`` on the engine's device is filled and
         returned."""
         legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
-        made = None
-        if out is None:
-            if count is None:
-                raise ValueError("step_k_observations: give count, or an array to fill")
-            spec = obs_spec(fields, legs, dof, dtype, 0, pad)
-            width = int(self.L.shc_obs_width(C.byref(spec)))
-            if width < 0:
-                _check(SHC_ERR_INVALID_ARG, "shc_engine_get_step_k_observations")
-            out = made = _new_device_array((max(int(count), 0), self.n, width), dtype, getattr(self, "device", None))
-        ptr, dt, cycles, rows, columns, stride, cycle_stride = _cycles_array(out, "step_k_observations")
-        count = cycles if count is None else int(count)
-        spec = obs_spec(fields, legs, dof, dt, stride, pad)
-        if count > cycles:
-            raise ValueError(f"step_k_observations: out has {cycles} cycles, {count} are asked for")
-        _check_rows("step_k_observations", "out[k]", rows, columns, self.n, int(self.L.shc_obs_width(C.byref(spec))))
-        _check(self.L.shc_engine_get_step_k_observations(self.h, int(first), count, C.byref(spec), ptr, cycle_stride), "shc_engine_get_step_k_observations")
-        return made
+        return _step_k_rows(self.L, "shc_engine_get_step_k_observations", self.h, self.n, getattr(self, "device", None), "step_k_observations", fields, dtype, out,
+                            first, count, pad, legs, dof)
+
+    def step_k_kinematics(self, fields=("q", "qd", "model_tip"), dtype="float32", out=None, first: int = 0, count: Optional[int] = None, pad: float = 0.0,
+                          legs: Optional[int] = None, dof: Optional[int] = None):
+        """``step_k_observations`` with the foot tips: ``fields`` is any of "q", "qd" and "model_tip" (in column order), and model_tip of cycle
+        first + k is what ``observations(("model_tip",))`` gives on an engine whose joints are those of that cycle - FK(q) in the robot frame,
+        3 columns per leg, ``pad`` where the robot has no such leg (shc_engine_get_step_k_kinematics).  One pass over the ring of the latest
+        ``step_k`` / ``step_k_actions`` on the engine's stream, no host wait; nothing is written into the engine.  out, count and the return
+        value as ``step_k_observations``; a numpy array is a TypeError (device arrays only)."""
+        legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
+        return _step_k_rows(self.L, "shc_engine_get_step_k_kinematics", self.h, self.n, getattr(self, "device", None), "step_k_kinematics", fields, dtype, out,
+                            first, count, pad, legs, dof)
+
+    def step_k_health(self, select: int = 0, near_limit_proximity: float = 0.0, first: int = 0, count: Optional[int] = None, health=None, first_hit=None):
+        """The joint-limit half of ``scan_health`` for cycles [first, first + count) of the latest ``step_k`` / ``step_k_actions`` in one pass
+        over its ring (shc_engine_scan_step_k_health): returns the DEVICE arrays (health, first_hit).  health: (count, n) records of
+        ROBOT_HEALTH_DTYPE's bytes - min_limit_proximity, max_speed_ratio, bytes 1 and 2 of leg_masks and the flags HEALTH_POSITION_LIMIT,
+        HEALTH_SPEED_LIMIT, HEALTH_NEAR_LIMIT (below ``near_limit_proximity``) and HEALTH_NONFINITE (joints only) are live, max_tip_deviation
+        is 0.  first_hit: int32 (n,), the first cycle of the launch within the range whose flags meet ``select``, or -1.  select with
+        HEALTH_IK_DEVIATION or HEALTH_TIP_DEVIATION is refused: the ring holds joints.  health / first_hit: device buffers to fill (integer
+        pointers or objects with ``__cuda_array_interface__``; count None: health.shape[0]), returned as given; else a new ``DeviceRecords`` /
+        torch tensor.  On the engine's stream, no host wait; a numpy array is a TypeError (device arrays only)."""
+        return _step_k_health(self.L, "shc_engine_scan_step_k_health", self.h, self.n, getattr(self, "device", None), select, near_limit_proximity, first, count,
+                              health, first_hit)
 
     def synchronize(self):
         _check(self.L.shc_engine_synchronize(self.h), "synchronize")

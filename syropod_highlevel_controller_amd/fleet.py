@@ -347,24 +347,28 @@ class MixedFleet:
         of ``dtype`` on the fleet's device is filled and returned.  No host wait: complete after ``synchronize()``, or for work queued on a
         stream after ``order_before(stream)``."""
         legs, dof = self.max_legs if legs is None else legs, self.max_dof if dof is None else dof
-        made = None
-        if out is None:
-            if count is None:
-                raise ValueError("step_k_observations: give count, or an array to fill")
-            spec = _engine.obs_spec(fields, legs, dof, dtype, 0, pad)
-            width = int(self.L.shc_obs_width(C.byref(spec)))
-            if width < 0:
-                _engine._check(_engine.SHC_ERR_INVALID_ARG, "shc_fleet_get_step_k_observations_device")
-            out = made = _engine._new_device_array((max(int(count), 0), self.n, width), dtype, self.parts()[0][2])
-        ptr, dt, cycles, rows, columns, stride, cycle_stride = _engine._cycles_array(out, "step_k_observations")
-        count = cycles if count is None else int(count)
-        if count > cycles:
-            raise ValueError(f"step_k_observations: out has {cycles} cycles, {count} are asked for")
-        spec = _engine.obs_spec(fields, legs, dof, dt, stride, pad)
-        _engine._check_rows("step_k_observations", "out[k]", rows, columns, self.n, int(self.L.shc_obs_width(C.byref(spec))))
-        _engine._check(self.L.shc_fleet_get_step_k_observations_device(self.h, int(first), count, C.byref(spec), ptr, cycle_stride),
-                       "shc_fleet_get_step_k_observations_device")
-        return made
+        return _engine._step_k_rows(self.L, "shc_fleet_get_step_k_observations_device", self.h, self.n, self._first_device, "step_k_observations", fields,
+                                    dtype, out, first, count, pad, legs, dof)
+
+    def step_k_kinematics(self, fields=("q", "qd", "model_tip"), dtype="float32", out=None, first: int = 0, count=None, pad: float = 0.0, legs=None, dof=None):
+        """``step_k_observations`` with the foot tips, in the caller's instance order (shc_fleet_get_step_k_kinematics_device): ``fields`` is any
+        of "q", "qd" and "model_tip"; model_tip of cycle first + k is FK(q) of that cycle's joints in the robot frame, 3 columns per leg, ``pad``
+        where a morphology has no such leg.  One kernel per part, no staging, nothing written into the fleet; out, count, the return value
+        and the ordering rules as ``step_k_observations``.  A numpy array is a TypeError (device arrays only)."""
+        legs, dof = self.max_legs if legs is None else legs, self.max_dof if dof is None else dof
+        return _engine._step_k_rows(self.L, "shc_fleet_get_step_k_kinematics_device", self.h, self.n, self._first_device, "step_k_kinematics", fields,
+                                    dtype, out, first, count, pad, legs, dof)
+
+    def step_k_health(self, select: int = 0, near_limit_proximity: float = 0.0, first: int = 0, count=None, health=None, first_hit=None):
+        """``BatchEngine.step_k_health`` for the fleet (shc_fleet_scan_step_k_health_device): the DEVICE arrays (health, first_hit) - (count, n)
+        records and int32 (n,) - in the caller's instance order, one kernel per part, no staging.  No host wait: complete after
+        ``synchronize()``, or for work queued on a stream after ``order_before(stream)``."""
+        return _engine._step_k_health(self.L, "shc_fleet_scan_step_k_health_device", self.h, self.n, self._first_device, select, near_limit_proximity,
+                                      first, count, health, first_hit)
+
+    def _first_device(self):
+        """The device a tensor the fleet makes itself goes to: that of the first part (asked only when a tensor is made)."""
+        return self.parts()[0][2]
 
     @staticmethod
     def _stream_handle(stream):
