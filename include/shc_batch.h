@@ -1385,6 +1385,68 @@ int shc_engine_set_footholds(shc_engine *e, const shc_foothold_spec *spec, const
 int shc_engine_get_footholds(shc_engine *e, const shc_foothold_spec *spec, void *rows, int on_device);
 int shc_fleet_set_footholds_device(shc_fleet *f, const shc_foothold_spec *spec, const void *rows /* [n][row_stride], caller's order */, int64_t *ignored_device);
 int shc_fleet_get_footholds_device(shc_fleet *f, const shc_foothold_spec *spec, void *rows /* [n][row_stride], caller's order */);
+/*
+ * Reach probe: which tip targets a leg can reach from its present joints, for C candidate targets per robot, in one kernel per engine (per
+ * part of a fleet) that never writes into an engine.  It is the line search of Leg::generateWorkspace (model.cpp:397-470) run with the per-leg
+ * calls above: a planner - or a learner bounding a task-space action - gets for every (robot, candidate, leg) the answer that a checkpoint
+ * restore and S rounds of shc_leg_set_desired_tip_pose + shc_leg_apply_ik give, without the (2 S + 1) C launches and without the joints, the
+ * desired tip and the tip-force estimate of the engine being overwritten.
+ * DEFINITION.  For robot i, candidate c and leg l < its legs, each on its own: q0, qd0 are the leg's stored joints, o the tip position that
+ * applyIK measures from them (FK of q0 in the robot frame: the frame of shc_leg_set_desired_tip_pose, shc_leg_apply_fk and
+ * SHC_OBS_MODEL_TIP) and t = static_cast<double> of the candidate's three columns, in the same frame.  Then for s = 1 .. S:
+ *   w = double(s) / S;  desired = o * (1.0 - w) + t * w   (per component; each product and the sum rounded once, no contraction - the
+ *   float64 expression of numpy gives the same bits);  setDesiredTipPose(desired, rotation undefined, apply_delta = 0);
+ *   r = applyIK(simulation = true);  stop when r == 0.0.
+ * applyIK is what shc_leg_apply_ik with simulation = 1 runs for the leg - the DLS step, updateJointPositions with the engine's
+ * clamp_joint_positions and no velocity clamp, the 5 mm deviation check - but for the closing tip-force estimate, which feeds nothing back
+ * into the joints; nothing is stored.  With steps_done the number of steps that returned non-zero (0 .. S):
+ *   SHC_REACH_FRACTION         double(steps_done) / S
+ *   SHC_REACH_LIMIT_PROXIMITY  r of the last executed step (0 after a failure)
+ *   SHC_REACH_TIP              the FK tip after the last executed step, the failing one included, as the workspace search measures it
+ *   SHC_REACH_Q                the joints after that step
+ * unchanged for SHC_OBS_F64, static_cast<float> for SHC_OBS_F32.  A candidate with a NaN in any of a leg's three columns is not asked for
+ * that leg: the leg's columns hold `pad` (converted once on the host), as do the columns of legs and joints the robot lacks.
+ * ROWS.  Robot i's target row holds C blocks of legs x 3 columns, its output row C blocks of D columns, D from the width call below.  Within
+ * a block the rule of the observation pass: the fields follow each other in the order of `fields`, every field is per leg and takes
+ * legs x width columns, leg-major (widths 1, 1, 3, dof in the order of the enum).  Columns beyond the C blocks of a row are never touched, and
+ * the target array is never written.  Both arrays are device arrays of the spec's element type, ready on the engine's stream.
+ * NOTHING IS WRITTEN into an engine: state records, auxiliary blobs, held inputs and the output ring of a K-cycle launch are byte for byte
+ * what they were.
+ * FLEET.  Robot r of a part reads row ids[r] - its CALLER's instance id - of the [n][C][legs][3] targets and writes row ids[r] of the
+ * [n][C][D] output; every part is asked first, then one kernel per part on the part's stream with no staging: shc_fleet_io_bytes does not
+ * change after the first device I/O call.  The readiness checks and the ordering calls of fleet device I/O apply as written there.
+ * STREAMS.  The engine call joins split steps by events, as the observation pass does, and runs on the engine's stream: no host wait, no
+ * allocation, no free.  count = 0 is a no-op.
+ * REFUSALS (decided before anything is launched).  SHC_ERR_INVALID_ARG: a NULL handle, spec or array; n_fields outside
+ * 1 .. SHC_REACH_FIELD_COUNT; an unknown or repeated field; an unknown dtype; reserved != 0; legs / dof below the engine's or the fleet's
+ * shape, or above SHC_MAX_LEGS / SHC_MAX_JOINTS; candidates outside 1 .. 64; steps outside 1 .. 4096; row_stride non-zero and below C x D;
+ * target_row_stride non-zero and below C x legs x 3; an instance range outside [0, n); an array not aligned to its element size.
+ * SHC_ERR_BUSY: resident mode.  SHC_ERR_UNSUPPORTED: a fleet that spans devices.
+ */
+enum {
+  SHC_REACH_FRACTION,        /* 1: steps that returned non-zero / S                              */
+  SHC_REACH_LIMIT_PROXIMITY, /* 1: what the last executed applyIK returned                       */
+  SHC_REACH_TIP,             /* 3: FK tip after the last executed step, robot frame              */
+  SHC_REACH_Q,               /* dof: the joints after that step                                  */
+  SHC_REACH_FIELD_COUNT
+};
+typedef struct shc_reach_spec {      /* 72 bytes */
+  int32_t n_fields, fields[SHC_REACH_FIELD_COUNT]; /* column order = this order; a field may appear once                */
+  int32_t dtype;                                /* SHC_OBS_F64 / SHC_OBS_F32: element type of BOTH arrays             */
+  int32_t legs, dof;                            /* row geometry, as shc_obs_spec                                      */
+  int32_t candidates;                           /* C: 1 .. 64                                                         */
+  int32_t steps;                                /* S: 1 .. 4096                                                       */
+  int32_t reserved;                             /* 0 */
+  int64_t row_stride;                           /* out: elements between robots; 0 = C x D                            */
+  int64_t target_row_stride;                    /* targets: elements between robots; 0 = C x legs x 3                 */
+  double pad;                                   /* written where a leg is not asked or a robot has no such leg / joint */
+} shc_reach_spec;
+int64_t shc_reach_width(const shc_reach_spec *spec);                      /* D: columns of ONE candidate's block; < 0 for an invalid spec; no device needed */
+int shc_reach_column(const shc_reach_spec *spec, int field, int leg, int k); /* column of component k of `field` of `leg` within a block; -1 if absent */
+int shc_engine_probe_reach(shc_engine *e, int64_t first, int64_t count, const shc_reach_spec *spec, const void *targets /* device, [count][C][legs][3] */,
+                           void *out /* device, [count][C][D] */);
+int shc_fleet_probe_reach_device(shc_fleet *f, const shc_reach_spec *spec, const void *targets /* [n][C][legs][3], caller's order */,
+                                 void *out /* [n][C][D], caller's order */);
 /* The exchange step of a sharded batch: every device ends up with the desired joint positions of ALL instances
  * ([n][max_legs][max_dof], caller's order, NaN padded) in its own HBM, copied device to device (hipMemcpyPeerAsync: xGMI on an
  * MI355X node).  device_buffers[d] (may be NULL) receives device_ids[d]'s buffer; the buffers belong to the fleet. */

@@ -136,24 +136,24 @@ __global__ void leg_update_joints_kernel(DevState st, const SharedConsts<L_, NJ>
   if (prox_out) prox_out[t] = prox;
 }
 
-// Leg::applyIK(simulation) towards the stored desired tip pose, including the rotation-constrained pass, the unconstrained
-// retry and the closing calculateTipForce (model.cpp:861-941).
-template <int NJ>
-__device__ __forceinline__ double apply_ik_dev(const DevState &st, const LegIO<NJ> &io, const LegConst<NJ> &lc, int simulation, double dt, int clamp_vel,
-                                               int clamp_pos, int tip_force, double force_gain) {
-  using FD = Fields<NJ>;
-  double q[NJ], qd[NJ], dq[NJ];
-  io.joints(q, qd);
-  const V3 desired = io.get3(FD::DES_TIP);
-  bool constrained = io.get(FD::DES_TIP + 3) != 0.0;
-  const V3 desired_dir = io.get3(FD::DES_DIR);
-  const bool cv = clamp_vel && !simulation, cp = clamp_pos != 0;
+// Leg::applyIK on registers (model.cpp:861-936): the rotation-constrained pass and the unconstrained retry, without a load or a store of its
+// own.  q, qd: the joints, stepped in place.  constrained: the desired tip pose has a defined rotation.  cv / cp: the velocity and position
+// clamps of the closing updateJointPositions.  ch: the chain of the joints on return, whose tip the deviation check measured.  What the
+// reference does beside the joints is the caller's, at the two places it happens: retry() when the constrained attempt has failed and the
+// rotation is dropped (desired_tip_pose_.rotation_ = UNDEFINED_ROTATION, :932-936), close(ch, retried) where calculateTipForce closes the
+// frame(s).  One implementation for apply_ik_dev below, which keeps the state, and for the reach probe (shc_reach.hpp), which keeps nothing.
+struct IkOutcome {
+  double success; // the limit proximity of the last updateJointPositions, 0 when the tip ended more than kIkTolerance off
+  bool failed;    // ... in any pass (the deviation warning, model.cpp:921)
+};
+template <int NJ, class Retry, class Close>
+__device__ __forceinline__ IkOutcome apply_ik_core(const LegConst<NJ> &lc, double (&q)[NJ], double (&qd)[NJ], V3 desired, bool constrained, V3 desired_dir,
+                                                   bool cv, bool cp, double dt, Chain<NJ> &ch, Retry &&retry_fn, Close &&close) {
+  double dq[NJ];
   const double inv_dt = 1.0 / dt;
-  Chain<NJ> ch;
   V3 lin[NJ];
   double success = 0.0;
   bool failed = false;
-  V3 tf = io.get3(FD::TF);
   for (int pass = 0; pass < 2; ++pass) { // second pass = the unconstrained retry (a nested applyIK, :932-936)
     fk_chain<NJ>(lc, q, ch);
     const V3 current_dir = ch.xe;
@@ -173,27 +173,50 @@ __device__ __forceinline__ double apply_ik_dev(const DevState &st, const LegIO<N
     }
     const bool retry = constrained && success == 0.0;
     if (!retry || pass == 1) {
-      if (tip_force) { // calculateTipForce closes every applyIK frame: once here, and once more for the outer frame after a retry
-        double effort[NJ];
-        for (int j = 0; j < NJ; ++j) effort[j] = io.get(FD::EFFORT_IN + j);
-        jacobian_columns<NJ>(ch, lin);
-        const V3 raw = tip_force_cols<NJ>(lc, ch, lin, effort);
-        tf = raw * (0.15 * force_gain) + tf * (1 - 0.15);
-        if (pass == 1) tf = raw * (0.15 * force_gain) + tf * (1 - 0.15);
-      }
+      close(ch, pass == 1);
       break;
     }
     constrained = false; // desired_tip_pose_.rotation_ = UNDEFINED_ROTATION
-    io.put(FD::DES_TIP + 3, 0.0);
+    retry_fn();
   }
+  return IkOutcome{success, failed};
+}
+
+// Leg::applyIK(simulation) towards the stored desired tip pose, including the rotation-constrained pass, the unconstrained
+// retry and the closing calculateTipForce (model.cpp:861-941): apply_ik_core between the loads and the stores.
+template <int NJ>
+__device__ __forceinline__ double apply_ik_dev(const DevState &st, const LegIO<NJ> &io, const LegConst<NJ> &lc, int simulation, double dt, int clamp_vel,
+                                               int clamp_pos, int tip_force, double force_gain) {
+  using FD = Fields<NJ>;
+  double q[NJ], qd[NJ];
+  io.joints(q, qd);
+  const V3 desired = io.get3(FD::DES_TIP);
+  const bool constrained = io.get(FD::DES_TIP + 3) != 0.0;
+  const V3 desired_dir = io.get3(FD::DES_DIR);
+  const bool cv = clamp_vel && !simulation, cp = clamp_pos != 0;
+  Chain<NJ> ch;
+  V3 tf = io.get3(FD::TF);
+  const IkOutcome ik = apply_ik_core<NJ>(
+      lc, q, qd, desired, constrained, desired_dir, cv, cp, dt, ch, [&]() { io.put(FD::DES_TIP + 3, 0.0); },
+      [&](const Chain<NJ> &c, bool retried) {
+        if (tip_force) { // calculateTipForce closes every applyIK frame: once here, and once more for the outer frame after a retry
+          double effort[NJ];
+          for (int j = 0; j < NJ; ++j) effort[j] = io.get(FD::EFFORT_IN + j);
+          V3 lin[NJ];
+          jacobian_columns<NJ>(c, lin);
+          const V3 raw = tip_force_cols<NJ>(lc, c, lin, effort);
+          tf = raw * (0.15 * force_gain) + tf * (1 - 0.15);
+          if (retried) tf = raw * (0.15 * force_gain) + tf * (1 - 0.15);
+        }
+      });
   io.put_joints(q, qd);
   if (tip_force) io.put3(FD::TF, tf);
   if (!simulation) { // the deviation warning is the engine's IK-failure bit (model.cpp:921, not raised in simulation)
     int w = st.legi[io.slot];
-    w = failed ? (w | LW_IKFAIL) : (w & ~LW_IKFAIL);
+    w = ik.failed ? (w | LW_IKFAIL) : (w & ~LW_IKFAIL);
     st.legi[io.slot] = w;
   }
-  return success;
+  return ik.success;
 }
 template <int L_, int NJ>
 __global__ void leg_apply_ik_kernel(DevState st, const SharedConsts<L_, NJ> *gc, LegSel sel, int simulation, double *result_out, double dt,

@@ -66,6 +66,7 @@ EXPORTED_SYMBOLS = [
     "shc_engine_get_step_k_kinematics", "shc_engine_scan_step_k_health", "shc_fleet_get_step_k_kinematics_device", "shc_fleet_scan_step_k_health_device",
     "shc_foothold_width", "shc_foothold_column", "shc_engine_set_footholds", "shc_engine_get_footholds", "shc_fleet_set_footholds_device",
     "shc_fleet_get_footholds_device",
+    "shc_reach_width", "shc_reach_column", "shc_engine_probe_reach", "shc_fleet_probe_reach_device",
     "shc_peer_alloc", "shc_peer_open", "shc_peer_close", "shc_peer_scatter",
 ]
 
@@ -148,6 +149,8 @@ ACT_FIELDS = {name: i for i, name in enumerate(ACT_FIELD_NAMES)}
 FH_FIELD_NAMES = ("position", "rotation", "transform", "swing_clearance", "frame_is_odom_ideal", "defined")  # every field is per leg
 FH_FIELDS = {name: i for i, name in enumerate(FH_FIELD_NAMES)}
 FH_MODES = {"request": 0, "refresh_transform": 1}  # SHC_FH_REQUEST / SHC_FH_REFRESH_TRANSFORM
+REACH_FIELD_NAMES = ("fraction", "limit_proximity", "tip", "q")  # SHC_REACH_*: every field is per leg
+REACH_FIELDS = {name: i for i, name in enumerate(REACH_FIELD_NAMES)}
 
 
 class ObsSpec(C.Structure):
@@ -168,9 +171,17 @@ class FootholdSpec(C.Structure):
                 ("mode", C.c_int32), ("reserved", C.c_int32), ("row_stride", C.c_int64), ("pad", C.c_double)]
 
 
+class ReachSpec(C.Structure):
+    """shc_reach_spec: which results, in which order, as which element type, for which row geometry, how many candidates and steps."""
+    _fields_ = [("n_fields", C.c_int32), ("fields", C.c_int32 * len(REACH_FIELD_NAMES)), ("dtype", C.c_int32), ("legs", C.c_int32), ("dof", C.c_int32),
+                ("candidates", C.c_int32), ("steps", C.c_int32), ("reserved", C.c_int32), ("row_stride", C.c_int64), ("target_row_stride", C.c_int64),
+                ("pad", C.c_double)]
+
+
 class _RowPass(NamedTuple):
     """What tells one row pass from another on this side: names in enum order and their enum values, columns of the per-robot fields, columns
-    per leg of the per-leg fields, the per-leg fields of ``dof`` columns, the ctypes struct and the library's width / column functions."""
+    per leg of the per-leg fields, the per-leg fields of ``dof`` columns, the ctypes struct and the library's width / column functions; own:
+    members of the struct that no layout depends on but a valid spec needs."""
     names: tuple
     index: dict
     robot: dict
@@ -179,6 +190,7 @@ class _RowPass(NamedTuple):
     struct: type
     width: str
     column: str
+    own: tuple = ()
 
 
 _ROW_PASSES = {
@@ -191,6 +203,8 @@ _ROW_PASSES = {
                        {"tip_force": 3}, ("joint_effort",), ActSpec, "shc_act_width", "shc_act_column"),
     "foothold": _RowPass(FH_FIELD_NAMES, FH_FIELDS, {}, {"position": 3, "rotation": 4, "transform": 7, "swing_clearance": 1, "frame_is_odom_ideal": 1,
                                                          "defined": 1}, (), FootholdSpec, "shc_foothold_width", "shc_foothold_column"),
+    "reach": _RowPass(REACH_FIELD_NAMES, REACH_FIELDS, {}, {"fraction": 1, "limit_proximity": 1, "tip": 3}, ("q",), ReachSpec, "shc_reach_width",
+                      "shc_reach_column", (("candidates", 1), ("steps", 1))),
 }
 
 
@@ -206,6 +220,8 @@ def _row_spec(kind: str, fields, dtype, row_stride):
     st.fields[:len(head)] = head
     st.dtype = OBS_DTYPES[np.dtype(dtype).name] if not isinstance(dtype, int) else dtype
     st.row_stride = int(row_stride)
+    for member, value in p.own:
+        setattr(st, member, value)
     return st
 
 
@@ -276,6 +292,75 @@ def foothold_columns(fields, legs: int):
     """({name: slice}, width) of a row of set_footholds(fields) / footholds(fields) for a row geometry of ``legs`` legs: a field's slice reshapes
     to (legs, width per leg), leg-major.  Computed here and checked against the library's own answer (shc_foothold_width / shc_foothold_column)."""
     return _row_columns("foothold", fields, legs, 0)
+
+
+def reach_spec(fields, legs: int, dof: int, candidates: int, steps: int, dtype="float32", row_stride: int = 0, target_row_stride: int = 0,
+               pad: float = float("nan")) -> ReachSpec:
+    """The shc_reach_spec of a list of field names (REACH_FIELDS) or SHC_REACH_* integers.  Nothing is checked here: the library judges the spec."""
+    st = _row_spec("reach", fields, dtype, row_stride)
+    st.legs, st.dof, st.candidates, st.steps = int(legs), int(dof), int(candidates), int(steps)
+    st.target_row_stride, st.pad = int(target_row_stride), float(pad)
+    return st
+
+
+def reach_columns(fields, legs: int, dof: int):
+    """({name: slice}, width D) of ONE candidate's block of probe_reach(fields) for the row geometry (legs, dof): a field's slice reshapes to
+    (legs, width per leg), leg-major.  Computed here and checked against the library's own answer (shc_reach_width / shc_reach_column)."""
+    return _row_columns("reach", fields, legs, dof)
+
+
+def _reach_array(a, what: str, ndim: int):
+    """(pointer, numpy dtype, shape, elements between robots) of one of the reach probe's DEVICE arrays (``__cuda_array_interface__``): float32 /
+    float64 of ``ndim`` dimensions, dense behind the first.  The probe has no host form: a numpy array is a TypeError, and so is another element
+    type."""
+    if isinstance(a, np.ndarray):
+        raise TypeError(f"{what}: device arrays only (an object with __cuda_array_interface__, e.g. a torch tensor); the reach probe has no host form")
+    cai = getattr(a, "__cuda_array_interface__", None)
+    if cai is None:
+        raise TypeError(f"{what}: device arrays only (an object with __cuda_array_interface__) - got {type(a).__name__}")
+    if cai["typestr"] not in ("<f4", "<f8"):
+        raise TypeError(f"{what}: float32 or float64 is expected, got {cai['typestr']}")
+    dt, shape = np.dtype(cai["typestr"]), tuple(int(x) for x in cai["shape"])
+    if len(shape) != ndim:
+        raise ValueError(f"{what}: {ndim} dimensions are expected, got the shape {shape}")
+    size, inner = dt.itemsize, int(np.prod(shape[1:], dtype=np.int64))
+    strides = cai.get("strides")
+    if strides is None or shape[0] == 0 or inner == 0:
+        return C.c_void_p(cai["data"][0]), dt, shape, inner
+    dense = size
+    for extent, stride in zip(reversed(shape[1:]), reversed(strides[1:])):
+        if extent != 1 and stride != dense:
+            raise ValueError(f"{what}: everything behind the first dimension must be contiguous (strides {tuple(strides)})")
+        dense *= extent
+    if shape[0] > 1 and (strides[0] % size or strides[0] < inner * size):
+        raise ValueError(f"{what}: the robots must be a whole number of elements, and at least a row, apart (strides {tuple(strides)})")
+    return C.c_void_p(cai["data"][0]), dt, shape, strides[0] // size if shape[0] > 1 else inner
+
+
+def _probe_reach(lib, call: str, handle, n: int, device, ranged: bool, targets, steps, fields, out, first, count, pad, legs, dof):
+    """BatchEngine / MixedFleet.probe_reach: ``call`` is the library's entry point (an engine's, which takes a range, or a fleet's), ``handle``
+    its handle, n its robots.  The arrays are judged before the library is asked."""
+    tptr, dt, tshape, tstride = _reach_array(targets, "probe_reach: targets", 4)
+    rows, cands = tshape[0], tshape[1]
+    if tshape[2:] != (int(legs), 3):
+        raise ValueError(f"probe_reach: targets has the shape {tshape}, (count, C, {int(legs)}, 3) is expected")
+    first, count = int(first), (n - int(first) if ranged else n) if count is None else int(count)
+    if rows != count or (not ranged and (first != 0 or count != n)):
+        raise ValueError(f"probe_reach: targets has {rows} rows for the robots [{first}, {first + count}) of {n}" + ("" if ranged else " (a fleet takes every robot)"))
+    spec = reach_spec(fields, legs, dof, cands, steps, dt, 0, tstride, pad)
+    width = int(lib.shc_reach_width(C.byref(spec)))
+    if width < 0:
+        _check(SHC_ERR_INVALID_ARG, call)
+    if out is None:
+        out = _new_device_array((rows, cands, width), dt, device)
+    optr, odt, oshape, spec.row_stride = _reach_array(out, "probe_reach: out", 3)
+    if odt != dt:
+        raise TypeError(f"probe_reach: out takes the element type of targets ({dt.name}), got {odt.name}")
+    if oshape != (rows, cands, width):
+        raise ValueError(f"probe_reach: out has the shape {oshape}, {(rows, cands, width)} is expected")
+    if rows > 0:   # (an empty tensor has no buffer to speak of, and count = 0 is a no-op in the library)
+        _check(getattr(lib, call)(*((handle, first, count) if ranged else (handle,)), C.byref(spec), tptr, optr), call)
+    return out
 
 
 def _rows_array(a, what: str, host: Optional[str] = None):
@@ -736,6 +821,11 @@ def lib():
         L.shc_engine_get_footholds.argtypes = [C.c_void_p, C.POINTER(FootholdSpec), C.c_void_p, C.c_int]
         L.shc_fleet_set_footholds_device.argtypes = [C.c_void_p, C.POINTER(FootholdSpec), C.c_void_p, C.c_void_p]
         L.shc_fleet_get_footholds_device.argtypes = [C.c_void_p, C.POINTER(FootholdSpec), C.c_void_p]
+        L.shc_reach_width.restype = C.c_int64
+        L.shc_reach_width.argtypes = [C.POINTER(ReachSpec)]
+        L.shc_reach_column.argtypes = [C.POINTER(ReachSpec), C.c_int, C.c_int, C.c_int]
+        L.shc_engine_probe_reach.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(ReachSpec), C.c_void_p, C.c_void_p]
+        L.shc_fleet_probe_reach_device.argtypes = [C.c_void_p, C.POINTER(ReachSpec), C.c_void_p, C.c_void_p]
         L.shc_stream_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
         L.shc_stream_destroy.argtypes = [C.c_int, C.c_void_p]
         L.shc_engine_change_gait.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_int64)]
@@ -1573,6 +1663,23 @@ class BatchEngine:
         _check_rows("footholds", "out", n_rows, columns, self.n, int(self.L.shc_foothold_width(C.byref(spec))))
         _check(self.L.shc_engine_get_footholds(self.h, C.byref(spec), ptr, on_device), "get_footholds")
         return None
+
+    def probe_reach(self, targets, steps: int, fields=("fraction", "limit_proximity"), out=None, first: int = 0, count: Optional[int] = None,
+                    pad: float = float("nan"), legs: Optional[int] = None, dof: Optional[int] = None):
+        """Which candidate tip targets every leg can reach from its present joints, in one device pass that writes nothing into the engine
+        (shc_engine_probe_reach).  targets: a float32 / float64 DEVICE array (count, C, legs, 3) - for each of the instances
+        [first, first + count) C candidate tip positions per leg in the robot frame (the frame of ``leg_set_desired_tip_pose`` and the
+        "model_tip" observation); a NaN leaves that leg of that candidate out.  Per (instance, candidate, leg) the tip walks the straight line
+        from where it is to the target in ``steps`` steps of ``leg_set_desired_tip_pose`` + ``leg_apply_ik(simulation=True)`` and stops at the
+        first step that returns 0.  Returns the DEVICE array (count, C, D) of targets' element type - ``out`` when given, else a new torch
+        tensor - with ``reach_columns(fields, legs, dof)`` naming the D columns of a candidate's block: "fraction" (steps that succeeded /
+        steps), "limit_proximity" (what the last executed step returned), "tip" (3: where the tip ended), "q" (dof: the joints there);
+        ``pad`` where a leg was left out or the row geometry (legs, dof) is larger than the robot.  Both arrays may be views whose robots lie
+        further apart (``big[:, :C * D].unflatten(1, (C, D))``).  On the engine's stream, no host wait; a numpy array is a TypeError (device
+        arrays only)."""
+        legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
+        return _probe_reach(self.L, "shc_engine_probe_reach", self.h, self.n, getattr(self, "device", None), True, targets, steps, fields, out, first, count,
+                            pad, legs, dof)
 
     def joint_commands(self):
         """(position, velocity, effort, position_command) of publishDesiredJointState, each [n][legs * dof]."""

@@ -295,6 +295,18 @@ class MixedFleet:
             _engine._check(self.L.shc_engine_get_footholds(e, C.byref(spec), part.ctypes.data_as(C.c_void_p), 0), "shc_engine_get_footholds")
             out[ids, :part.shape[1]] = part
 
+    def probe_reach(self, targets, steps: int, fields=("fraction", "limit_proximity"), out=None, first: int = 0, count=None, pad: float = float("nan"),
+                    legs=None, dof=None):
+        """``BatchEngine.probe_reach`` for the fleet, in the caller's instance order (shc_fleet_probe_reach_device): targets is a float32 /
+        float64 DEVICE array (n, C, legs, 3), the result the DEVICE array (n, C, D) - ``out`` when given, else a new torch tensor - in the row
+        geometry (legs, dof), default ``max_legs`` / ``max_dof``; ``pad`` where a morphology has no such leg or joint.  One kernel per part on
+        the part's stream, no staging, nothing written into the fleet; a fleet takes every robot (first = 0, count None or n).  No host wait:
+        complete after ``synchronize()``, or for work queued on a stream after ``order_before(stream)``.  A numpy array is a TypeError (device
+        arrays only)."""
+        legs, dof = self.max_legs if legs is None else legs, self.max_dof if dof is None else dof
+        return _engine._probe_reach(self.L, "shc_fleet_probe_reach_device", self.h, self.n, self._first_device, False, targets, steps, fields, out, first, count,
+                                    pad, legs, dof)
+
     def step_k(self, n_cycles: int, **arrays):
         """K = ``n_cycles`` cycles in one launch per part (shc_fleet_step_k), cycle k with row k of K-deep DEVICE arrays: the names of
         ``set_inputs`` with a leading dimension K - linear_xy (K, n, 2), angular (K, n), imu_orientation_wxyz (K, n, 4), imu_angular_velocity
