@@ -11,7 +11,10 @@
 //   reference:  dq = J^T (J J^T + l^2 I6)^-1 d  +  (I - J^+ J) g      with a dynamic 6x6 LU inverse
 //   here:       dq = (Jp^T Jp + l^2 I_N)^-1 (Jp^T d_p + l^2 g)         one N x N SPD solve in registers
 //   (push-through identity; in position-only mode the angular rows of J are zero, so J^T J = Jp^T Jp,
-//    and I - J^+ J = l^2 (J^T J + l^2 I)^-1.)  Differences are at rounding level (~1e-13 rad).
+//    and I - J^+ J = l^2 (J^T J + l^2 I)^-1.)  Differences are at rounding level.  Measured against the reference's own 6x6 form
+//    at 50 digits (tests/leg_reference.py, host and MI355X, NJ = 3 ... 5, singular poses included): the position-only solve is
+//    within 1e-15 rad on steps of a few mm and 1.5e-14 rad on a 0.5 m delta; with the angular rows within 1e-13 rad for rotation
+//    deltas up to 0.5 rad, and 8.1e-13 rad on a delta of 0.5 m and 0.5 rad at once - the largest difference seen.
 #pragma once
 
 #include "shc_math.hpp"
