@@ -151,6 +151,6 @@ extern "C" int shc_engine_set_actions(shc_engine *e, const shc_act_spec *spec, c
   const int64_t stride = row_stride_of(spec, lay);
   if (on_device) return actions_apply(e, spec, lay, actions, stride, nullptr, ride);
   HIP_TRY(hipSetDevice(e->device));
-  return rows_from_host(e, "actions", actions, e->n, lay.width, stride, spec->dtype, nullptr,
+  return rows_from_host(e, actions, e->n, lay.width, stride, spec->dtype, nullptr,
                         [&](const void *d, int64_t *) { return actions_apply(e, spec, lay, d, lay.width, nullptr, false); });
 }

@@ -365,19 +365,14 @@ extern "C" int shc_engine_restore_instances(shc_engine *e, const shc_checkpoint 
   if (ck->live & CK_LIVE_EXT) e->rt_flags |= RT_EXTERNAL;
   const bool tips = (ck->live & CK_LIVE_POSER_TIPS) != 0; // as aux_state: only a restore of the whole batch can raise it
   e->plan_poser_tips_current = whole ? tips : (e->plan_poser_tips_current && tips);
-  const int64_t *d_source = source;
-  if (source && !on_device) { // (stage_bytes holds 64 bytes per instance)
-    d_source = reinterpret_cast<const int64_t *>(e->d_stage);
-    HIP_TRY(hipMemcpyAsync(e->d_stage, source, size_t(e->n) * 8, hipMemcpyHostToDevice, e->stream));
-  }
+  HostCall hc(e);
+  const int64_t *d_source = hc.in(source, size_t(e->n), on_device);
+  if ((rc = hc.status()) != SHC_OK) return rc;
   const CheckpointView view{reinterpret_cast<const double2 *>(ck->legd), ck->legi, ck->robd, ck->robi, reinterpret_cast<const double2 *>(ck->ext), ck->manual, ck->seq, ck->live};
   rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
     constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
     restore_instances_kernel<L, NJ><<<dim3((unsigned)e->n_waves), dim3(64), 0, e->stream>>>(e->st, e->d_seq, view, d_source);
     return SHC_OK;
   });
-  if (rc != SHC_OK) return rc;
-  HIP_TRY(hipGetLastError());
-  if (source && !on_device) HIP_TRY(hipStreamSynchronize(e->stream)); // the caller's array and the staging buffer are free again
-  return SHC_OK;
+  return rc != SHC_OK ? rc : hc.finish();
 }

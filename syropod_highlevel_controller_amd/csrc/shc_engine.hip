@@ -265,6 +265,7 @@ __global__ void init_state_kernel(DevState st, const double *leg_template /*[L][
 constexpr int64_t kPlanePadSlots = 192;
 
 #include "shc_adjust.hpp" // struct PendingAdjust (the operations on it: included again below)
+#include "shc_stage.hpp"  // struct StageArena (the per-call scope over it: included again below)
 
 struct shc_engine {
   shc_params params;
@@ -279,6 +280,7 @@ struct shc_engine {
   void *d_consts;
   double *d_stage;     // staging for host <-> device conversions
   size_t stage_bytes;
+  StageArena stage;    // ... handed out per call (shc_stage.hpp: HostCall)
   uint32_t features;
   uint32_t rt_flags; // RT_* facts passed to every launch
   int starting_up, startup_calls; // shc_engine_begin_direct_startup .. shc_engine_direct_startup
@@ -314,6 +316,7 @@ static void release_checkpoints(shc_engine *e); // free the device arrays of the
 // While the resident kernel owns the engine's stream and state, every other entry point that would touch them is refused.
 static int join_side(shc_engine *e);
 static void rebuild_cycle_params(shc_engine *e);
+#include "shc_stage.hpp" // HostCall: the staging scope of one entry point
 // Every entry point begins with one of these, before it does anything with `e`: a NULL engine is refused, and so is an engine in resident mode ...
 #define SHC_ENTER(e)                                                                                                           \
   do {                                                                                                                         \
@@ -605,17 +608,15 @@ extern "C" const char *shc_last_error(void) { return g_last_error.c_str(); }
 extern "C" int shc_debug_plane_copy(int device, int64_t n_doubles, int reps) {
   if (n_doubles < 2 || (n_doubles & 1) || reps < 1) return fail(SHC_ERR_INVALID_ARG, "n_doubles must be even and >= 2, reps >= 1");
   HIP_TRY(hipSetDevice(device));
-  double *a, *b;
-  HIP_TRY(hipMalloc(&a, size_t(n_doubles) * 8));
-  HIP_TRY(hipMalloc(&b, size_t(n_doubles) * 8));
-  HIP_TRY(hipMemset(a, 0, size_t(n_doubles) * 8));
+  StageArena none{nullptr, 0, 0};
+  HostCall hc(none, nullptr);
+  double *a = hc.scratch<double>(size_t(n_doubles)), *b = hc.scratch<double>(size_t(n_doubles));
+  if (const int rc = hc.status()) return rc;
+  HIP_TRY(hipMemsetAsync(a, 0, size_t(n_doubles) * 8, hc.stream));
   const int64_t n_pairs = n_doubles / 2;
   for (int r = 0; r < reps; ++r)
     shc_plane_copy_kernel<<<dim3((unsigned)((n_pairs + 255) / 256)), dim3(256)>>>((const double2 *)a, (double2 *)b, n_pairs);
-  HIP_TRY(hipDeviceSynchronize());
-  (void)hipFree(a);
-  (void)hipFree(b);
-  return SHC_OK;
+  return hc.finish();
 }
 
 extern "C" int shc_stream_create(int device, void **stream) {
@@ -680,31 +681,22 @@ extern "C" int shc_generate_tables_batch(const shc_params *params, int64_t count
     st[i] = validate_params(&params[i], &L, &NJ);
     np[size_t(i)] = st[i] == SHC_OK ? normalised_params(params[i]) : params[i]; // (neutral entries for the padded joints of legs shorter than the robot's longest)
   }
-  shc_params *d_p = nullptr;
-  shc_tables *d_t = nullptr;
-  int32_t *d_s = nullptr;
-  auto release = [&]() {
-    (void)hipFree(d_p);
-    (void)hipFree(d_t);
-    (void)hipFree(d_s);
-  };
-  HIP_TRY_OR(hipMalloc(&d_p, size_t(count) * sizeof(shc_params)), release());
-  HIP_TRY_OR(hipMalloc(&d_t, size_t(count) * sizeof(shc_tables)), release());
-  HIP_TRY_OR(hipMalloc(&d_s, size_t(count) * 4), release());
-  HIP_TRY_OR(hipMemcpy(d_p, np.data(), size_t(count) * sizeof(shc_params), hipMemcpyHostToDevice), release());
-  HIP_TRY_OR(hipMemcpy(d_s, st.data(), size_t(count) * 4, hipMemcpyHostToDevice), release());
-  HIP_TRY_OR(hipMemset(d_t, 0, size_t(count) * sizeof(shc_tables)), release());
+  StageArena none{nullptr, 0, 0};
+  HostCall hc(none, nullptr);
+  const shc_params *d_p = hc.in(np.data(), size_t(count), 0);
+  shc_tables *d_t = hc.out(out, size_t(count), 0);
+  int32_t *d_s = hc.scratch<int32_t>(size_t(count));
+  if (const int rc = hc.status()) return rc;
+  HIP_TRY(hipMemcpyAsync(d_s, st.data(), size_t(count) * 4, hipMemcpyHostToDevice, hc.stream));
+  HIP_TRY(hipMemsetAsync(d_t, 0, size_t(count) * sizeof(shc_tables), hc.stream));
+  hc.back(st.data(), d_s, size_t(count));
   const unsigned gm = (unsigned)((count + 63) / 64), gl = (unsigned)((count * SHC_MAX_LEGS * 8 + 63) / 64);
   init_chain_head_kernel<<<dim3(gm), dim3(64)>>>(d_p, d_t, d_s, count);
   init_chain_legs_kernel<3><<<dim3(gl), dim3(64)>>>(d_p, d_t, d_s, count);
   init_chain_legs_kernel<4><<<dim3(gl), dim3(64)>>>(d_p, d_t, d_s, count);
   init_chain_legs_kernel<5><<<dim3(gl), dim3(64)>>>(d_p, d_t, d_s, count);
   init_chain_tail_kernel<<<dim3(gm), dim3(64)>>>(d_p, d_t, d_s, count);
-  HIP_TRY_OR(hipGetLastError(), release());
-  HIP_TRY_OR(hipDeviceSynchronize(), release());
-  HIP_TRY_OR(hipMemcpy(out, d_t, size_t(count) * sizeof(shc_tables), hipMemcpyDeviceToHost), release());
-  HIP_TRY_OR(hipMemcpy(st.data(), d_s, size_t(count) * 4, hipMemcpyDeviceToHost), release());
-  release();
+  if (const int rc = hc.finish()) return rc;
   for (int64_t i = 0; i < count; ++i) {
     if (st[i] != SHC_OK) memset(static_cast<void *>(&out[i]), 0, sizeof(shc_tables));
     if (status) status[i] = st[i];
@@ -881,31 +873,16 @@ static int init_state(shc_engine *e) {
   std::vector<double> legt, robt;
   std::vector<int32_t> legw, robi;
   dispatch_nj(e->NJ, [&](auto nj) { build_templates<decltype(nj)::value>(e, legt, legw, robt, robi); });
-  double *d_legt = nullptr, *d_robt = nullptr;
-  int32_t *d_legw = nullptr, *d_robi = nullptr;
-  auto release = [&]() {
-    (void)hipFree(d_legt);
-    (void)hipFree(d_robt);
-    (void)hipFree(d_legw);
-    (void)hipFree(d_robi);
-  };
-  HIP_TRY_OR(hipMalloc(&d_legt, legt.size() * 8), release());
-  HIP_TRY_OR(hipMalloc(&d_robt, robt.size() * 8), release());
-  HIP_TRY_OR(hipMalloc(&d_legw, legw.size() * 4), release());
-  HIP_TRY_OR(hipMalloc(&d_robi, robi.size() * 4), release());
-  HIP_TRY_OR(hipMemcpyAsync(d_legt, legt.data(), legt.size() * 8, hipMemcpyHostToDevice, e->stream), release());
-  HIP_TRY_OR(hipMemcpyAsync(d_robt, robt.data(), robt.size() * 8, hipMemcpyHostToDevice, e->stream), release());
-  HIP_TRY_OR(hipMemcpyAsync(d_legw, legw.data(), legw.size() * 4, hipMemcpyHostToDevice, e->stream), release());
-  HIP_TRY_OR(hipMemcpyAsync(d_robi, robi.data(), robi.size() * 4, hipMemcpyHostToDevice, e->stream), release());
-  HIP_TRY_OR(hipMemsetAsync(e->st.legd, 0, size_t(e->n_leg_fields) * e->n_slots * 8, e->stream), release());
-  HIP_TRY_OR(hipMemsetAsync(e->st.legi, 0, size_t(e->n_slots) * 4, e->stream), release());
+  HostCall hc(e);
+  const double *d_legt = hc.in(legt.data(), legt.size(), 0), *d_robt = hc.in(robt.data(), robt.size(), 0);
+  const int32_t *d_legw = hc.in(legw.data(), legw.size(), 0), *d_robi = hc.in(robi.data(), robi.size(), 0);
+  if (const int rc = hc.status()) return rc;
+  HIP_TRY(hipMemsetAsync(e->st.legd, 0, size_t(e->n_leg_fields) * e->n_slots * 8, e->stream));
+  HIP_TRY(hipMemsetAsync(e->st.legi, 0, size_t(e->n_slots) * 4, e->stream));
   int64_t threads = e->n * e->L;
   init_state_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(
       e->st, d_legt, d_legw, d_robt, d_robi, e->L, e->n_leg_fields, RobotFields::COUNT, RobotFields::I_COUNT);
-  HIP_TRY_OR(hipGetLastError(), release());
-  HIP_TRY_OR(hipStreamSynchronize(e->stream), release());
-  release();
-  return SHC_OK;
+  return hc.finish();
 }
 
 static int engine_create(const shc_params *params, const shc_tables *tables, int64_t n_instances, int device, void *stream,
@@ -973,6 +950,7 @@ static int engine_create(const shc_params *params, const shc_tables *tables, int
   HIP_TRY_OR(hipMemsetAsync(e->st.robi, 0, size_t(RobotFields::I_COUNT) * e->n_rob_pad * 4, e->stream), shc_engine_destroy(e));
   e->stage_bytes = size_t(e->n) * L * (NJ > 3 ? NJ : 3) * 8 + size_t(e->n) * 8 * 8 + size_t(SHC_MAX_LEGS) * SHC_MAX_JOINTS * 8 + 4096;
   HIP_TRY_OR(hipMalloc(&e->d_stage, e->stage_bytes), shc_engine_destroy(e));
+  e->stage = StageArena{reinterpret_cast<char *>(e->d_stage), e->stage_bytes, 0};
   rc = upload_consts(e);
   if (rc == SHC_OK) rc = init_state(e);
   // The reference's loop() that enters RUNNING also executes runningState() once with the (zero) inputs present at
@@ -1040,18 +1018,7 @@ extern "C" int shc_engine_get_tables(const shc_engine *e, shc_tables *out) {
 
 extern "C" int64_t shc_engine_instances(const shc_engine *e) { return e ? e->n : 0; }
 
-// ---- input / output plumbing
-static int to_device(shc_engine *e, const double *src, size_t count, int on_device, const double **dptr) {
-  if (on_device) {
-    *dptr = src;
-    return SHC_OK;
-  }
-  if (count * 8 > e->stage_bytes) return fail(SHC_ERR_INVALID_ARG, "staging buffer too small");
-  HIP_TRY(hipMemcpyAsync(e->d_stage, src, count * 8, hipMemcpyHostToDevice, e->stream));
-  *dptr = e->d_stage;
-  return SHC_OK;
-}
-
+// ---- input / output plumbing (host arrays: shc_stage.hpp)
 // While split steps are in flight (large batches, shc_engine_step) a device-resident input array is scattered by EACH HALF'S OWN
 // stream - ordered after that half's earlier steps and before its later ones by stream order alone, so that new inputs cost no
 // join (a join drains both halves and costs the overlap the split exists for).  The caller's array is ready on the engine's
@@ -1114,13 +1081,11 @@ static int scatter_input(shc_engine *e, const double *src, size_t doubles_per_in
     HIP_TRY(hipGetLastError());
     return split_inputs_end(e);
   }
-  const double *d;
-  int rc = to_device(e, src, size_t(e->n) * doubles_per_instance, on_device, &d);
-  if (rc != SHC_OK) return rc;
+  HostCall hc(e);
+  const double *d = hc.in(src, size_t(e->n) * doubles_per_instance, on_device);
+  if (const int rc = hc.status()) return rc;
   launch(e->stream, d, int64_t(0), e->n);
-  HIP_TRY(hipGetLastError());
-  if (!on_device) HIP_TRY(hipStreamSynchronize(e->stream)); // the staging buffer is reused by the next call
-  return SHC_OK;
+  return hc.finish();
 }
 // (input group g of shc_inputs.hpp, per robot / per leg; Model::setImuData normalises the orientation)
 static int scatter_rob(shc_engine *e, const double *src, int g, int on_device) {
@@ -1136,31 +1101,28 @@ static int scatter_leg(shc_engine *e, const double *src, int g, int on_device) {
   });
 }
 
-static int gather_leg(shc_engine *e, double *dst, int K, int f0, int on_device) {
+// One output array of the caller from the state.  launch(array): the gather kernel on the engine's stream; a host array is copied back and waited for
+template <class T, class Launch>
+static int gather_output(shc_engine *e, T *dst, size_t count, int on_device, Launch &&launch) {
   if (!dst) return SHC_OK;
   HIP_TRY(hipSetDevice(e->device));
-  int64_t threads = e->n * e->L;
-  double *d = on_device ? dst : e->d_stage;
-  gather_leg_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(d, e->st.legd, e->n_slots, e->n, e->L, K, f0);
-  HIP_TRY(hipGetLastError());
-  if (!on_device) {
-    HIP_TRY(hipMemcpyAsync(dst, d, size_t(threads) * K * 8, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-  }
-  return SHC_OK;
+  HostCall hc(e);
+  T *d = hc.out(dst, count, on_device);
+  if (const int rc = hc.status()) return rc;
+  launch(d);
+  return hc.finish();
 }
-
+static dim3 grid256(int64_t threads) { return dim3((unsigned)((threads + 255) / 256)); }
+static int gather_leg(shc_engine *e, double *dst, int K, int f0, int on_device) {
+  const int64_t threads = e->n * e->L;
+  return gather_output(e, dst, size_t(threads) * K, on_device, [&](double *d) {
+    gather_leg_kernel<<<grid256(threads), dim3(256), 0, e->stream>>>(d, e->st.legd, e->n_slots, e->n, e->L, K, f0);
+  });
+}
 static int gather_rob(shc_engine *e, double *dst, int K, int f0, int on_device) {
-  if (!dst) return SHC_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  double *d = on_device ? dst : e->d_stage;
-  gather_rob_kernel<<<dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, e->stream>>>(d, e->st.robd, 64 / e->L, e->n, K, f0);
-  HIP_TRY(hipGetLastError());
-  if (!on_device) {
-    HIP_TRY(hipMemcpyAsync(dst, d, size_t(e->n) * K * 8, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-  }
-  return SHC_OK;
+  return gather_output(e, dst, size_t(e->n) * K, on_device, [&](double *d) {
+    gather_rob_kernel<<<grid256(e->n), dim3(256), 0, e->stream>>>(d, e->st.robd, 64 / e->L, e->n, K, f0);
+  });
 }
 
 static int derive_tips(shc_engine *e);
@@ -1257,16 +1219,11 @@ extern "C" int shc_engine_set_pose_reset_mode(shc_engine *e, const int32_t *mode
   if (!mode) return SHC_OK;
   e->rt_flags |= RT_MANUAL_LIVE;
   HIP_TRY(hipSetDevice(e->device));
-  const int32_t *d = mode;
-  if (!on_device) {
-    HIP_TRY(hipMemcpyAsync(e->d_stage, mode, size_t(e->n) * 4, hipMemcpyHostToDevice, e->stream));
-    d = reinterpret_cast<const int32_t *>(e->d_stage);
-  }
-  scatter_robi_kernel<<<dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, e->stream>>>(d, e->st.robi, 64 / e->L, e->n,
-                                                                                       RobotFields::I_RESET_MODE);
-  HIP_TRY(hipGetLastError());
-  if (!on_device) HIP_TRY(hipStreamSynchronize(e->stream));
-  return SHC_OK;
+  HostCall hc(e);
+  const int32_t *d = hc.in(mode, size_t(e->n), on_device);
+  if (const int rc = hc.status()) return rc;
+  scatter_robi_kernel<<<grid256(e->n), dim3(256), 0, e->stream>>>(d, e->st.robi, 64 / e->L, e->n, RobotFields::I_RESET_MODE);
+  return hc.finish();
 }
 
 // The two streams the halves of split steps run on: ONE pair per device for the whole process, created back to back so that they
@@ -1496,18 +1453,10 @@ extern "C" int shc_engine_get_leg_state(shc_engine *e, double *walker_tip, doubl
   if ((rc = gather_leg(e, model_tip, 3, LEG_FIELD(e, MODEL_TIP), on_device)) != SHC_OK) return rc;
   if ((rc = gather_leg(e, tip_force, 3, LEG_FIELD(e, TF), on_device)) != SHC_OK) return rc;
   if ((rc = gather_leg(e, admittance, 3, LEG_FIELD(e, ADM_DELTA), on_device)) != SHC_OK) return rc;
-  if (leg_status) {
-    HIP_TRY(hipSetDevice(e->device));
-    int64_t threads = e->n * e->L;
-    int32_t *d = on_device ? leg_status : reinterpret_cast<int32_t *>(e->d_stage);
-    gather_leg_status_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(d, e->st.legi, e->n, e->L);
-    HIP_TRY(hipGetLastError());
-    if (!on_device) {
-      HIP_TRY(hipMemcpyAsync(leg_status, d, size_t(threads) * 4, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-  }
-  return SHC_OK;
+  const int64_t threads = e->n * e->L;
+  return gather_output(e, leg_status, size_t(threads), on_device, [&](int32_t *d) {
+    gather_leg_status_kernel<<<grid256(threads), dim3(256), 0, e->stream>>>(d, e->st.legi, e->n, e->L);
+  });
 }
 
 extern "C" int shc_engine_change_gait(shc_engine *e, const shc_params *ng, int64_t *still_walking) {
@@ -1516,13 +1465,15 @@ extern "C" int shc_engine_change_gait(shc_engine *e, const shc_params *ng, int64
   HIP_TRY(hipSetDevice(e->device));
   const unsigned grid = (unsigned)((e->n + 255) / 256);
   const int rpw = 64 / e->L;
-  int32_t *d_count = reinterpret_cast<int32_t *>(e->d_stage);
   int32_t walking = 0;
-  HIP_TRY(hipMemsetAsync(d_count, 0, 4, e->stream));
-  count_walking_kernel<<<dim3(grid), dim3(256), 0, e->stream>>>(d_count, e->st.robi, rpw, e->n);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(&walking, d_count, 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
+  {
+    HostCall hc(e);
+    int32_t *d_count = hc.out(&walking, 1, 0);
+    if (const int rc = hc.status()) return rc;
+    HIP_TRY(hipMemsetAsync(d_count, 0, 4, e->stream));
+    count_walking_kernel<<<dim3(grid), dim3(256), 0, e->stream>>>(d_count, e->st.robi, rpw, e->n);
+    if (const int rc = hc.finish()) return rc;
+  }
   if (still_walking) *still_walking = walking;
   if (walking) { // state_controller.cpp:531-537
     fill_rob_kernel<<<dim3(grid), dim3(256), 0, e->stream>>>(e->st.robd, rpw, e->n, RobotFields::VIN, 3, 0.0);
@@ -1573,16 +1524,9 @@ extern "C" int shc_engine_change_gait(shc_engine *e, const shc_params *ng, int64
 extern "C" int shc_engine_get_odometry(shc_engine *e, double *pose, int on_device) {
   SHC_ENTER_JOINED(e);
   if (!e->cp.odometry) return fail(SHC_ERR_UNSUPPORTED, "SHC_FEAT_ODOMETRY is off");
-  if (!pose) return SHC_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  double *d = on_device ? pose : e->d_stage;
-  gather_odometry_kernel<<<dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, e->stream>>>(d, e->st.robd, 64 / e->L, e->n);
-  HIP_TRY(hipGetLastError());
-  if (!on_device) {
-    HIP_TRY(hipMemcpyAsync(pose, d, size_t(e->n) * 7 * 8, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-  }
-  return SHC_OK;
+  return gather_output(e, pose, size_t(e->n) * 7, on_device, [&](double *d) {
+    gather_odometry_kernel<<<grid256(e->n), dim3(256), 0, e->stream>>>(d, e->st.robd, 64 / e->L, e->n);
+  });
 }
 
 extern "C" int shc_engine_get_virtual_stiffness(shc_engine *e, double *stiffness, int on_device) {
@@ -1637,12 +1581,13 @@ extern "C" int shc_engine_read_leg_state_msg(shc_engine *e, int64_t instance, sh
   if (rc != SHC_OK) return rc;
   const int L = e->L, NJ = e->NJ, per_leg = 12 + 4 * NJ + 8;
   std::vector<double> h(size_t(L) * per_leg + 10);
-  dispatch_nj(NJ, [&](auto nj) {
-    read_instance_kernel<decltype(nj)::value><<<dim3(1), dim3(64), 0, e->stream>>>(e->d_stage, e->st, L, instance, e->params.admittance_control);
-  });
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h.data(), e->d_stage, h.size() * 8, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
+  {
+    HostCall hc(e);
+    double *d = hc.out(h.data(), h.size(), 0);
+    if ((rc = hc.status()) != SHC_OK) return rc;
+    dispatch_nj(NJ, [&](auto nj) { read_instance_kernel<decltype(nj)::value><<<dim3(1), dim3(64), 0, e->stream>>>(d, e->st, L, instance, e->params.admittance_control); });
+    if ((rc = hc.finish()) != SHC_OK) return rc;
+  }
   const double *rb = &h[size_t(L) * per_leg];
   const double vx = rb[0], vy = rb[1], vw = rb[2];
   const LegMsgArgs args = leg_msg_args(e->params, e->tables); // (shc_leg_msgs.hpp: the arithmetic the batched kernel runs)
@@ -1736,33 +1681,27 @@ __global__ void step_plane_range_kernel(DevState st, const SharedConsts<L, NJ> *
   }
 }
 
-static int upload_offsets(shc_engine *e, const double **d_off) {
+static std::vector<double> joint_offsets(const shc_engine *e) { // Joint::offset_, [L][NJ]
   std::vector<double> off(size_t(e->L) * e->NJ);
   for (int l = 0; l < e->L; ++l)
     for (int j = 0; j < e->NJ; ++j) off[size_t(l) * e->NJ + j] = e->params.joint[l][j].offset;
-  // the tail of the staging buffer (the scatter / gather helpers use its head)
-  double *dst = e->d_stage + (e->stage_bytes / 8 - off.size());
-  HIP_TRY(hipMemcpyAsync(dst, off.data(), off.size() * 8, hipMemcpyHostToDevice, e->stream));
-  *d_off = dst;
-  return SHC_OK;
+  return off;
 }
 
 extern "C" int shc_engine_set_joint_states_msg(shc_engine *e, const double *position, const double * /*velocity*/, const double *effort, int on_device) {
   SHC_ENTER_JOINED(e);
   HIP_TRY(hipSetDevice(e->device));
-  int rc = SHC_OK;
   if (position) {
-    const double *d_off, *d;
-    if ((rc = upload_offsets(e, &d_off)) != SHC_OK) return rc;
-    if ((rc = to_device(e, position, size_t(e->n) * e->L * e->NJ, on_device, &d)) != SHC_OK) return rc;
+    const std::vector<double> off = joint_offsets(e);
+    HostCall hc(e);
+    const double *d_off = hc.in(off.data(), off.size(), 0), *d = hc.in(position, size_t(e->n) * e->L * e->NJ, on_device);
+    int rc = hc.status();
+    if (rc != SHC_OK) return rc;
     const int64_t threads = e->n * e->L;
-    store_measured_q_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(d, e->st.legd, e->n_slots, e->n, e->L, e->NJ,
-                                                                                              LEG_FIELD(e, MEAS_Q), d_off);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    store_measured_q_kernel<<<grid256(threads), dim3(256), 0, e->stream>>>(d, e->st.legd, e->n_slots, e->n, e->L, e->NJ, LEG_FIELD(e, MEAS_Q), d_off);
+    if ((rc = hc.finish()) != SHC_OK) return rc;
   }
-  if (effort) rc = shc_engine_set_joint_effort(e, effort, on_device);
-  return rc;
+  return effort ? shc_engine_set_joint_effort(e, effort, on_device) : SHC_OK;
 }
 
 extern "C" int shc_engine_set_tip_states_msg(shc_engine *e, const double *wrench_force, const double *step_plane, int on_device) {
@@ -1772,17 +1711,17 @@ extern "C" int shc_engine_set_tip_states_msg(shc_engine *e, const double *wrench
   if (step_plane) {
     HIP_TRY(hipSetDevice(e->device));
     e->rt_flags |= RT_TOUCHDOWN; // setTouchdownDetection(true) (:1655)
-    const double *d;
-    if ((rc = to_device(e, step_plane, size_t(e->n) * e->L * 3, on_device, &d)) != SHC_OK) return rc;
+    HostCall hc(e);
+    const double *d = hc.in(step_plane, size_t(e->n) * e->L * 3, on_device);
+    if ((rc = hc.status()) != SHC_OK) return rc;
     const int64_t threads = e->n * e->L;
     rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
       constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
-      step_plane_range_kernel<L, NJ><<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(e->st, (const SharedConsts<L, NJ> *)e->d_consts, d);
+      step_plane_range_kernel<L, NJ><<<grid256(threads), dim3(256), 0, e->stream>>>(e->st, (const SharedConsts<L, NJ> *)e->d_consts, d);
       return SHC_OK;
     });
     if (rc != SHC_OK) return rc;
-    HIP_TRY(hipGetLastError());
-    if (!on_device) HIP_TRY(hipStreamSynchronize(e->stream));
+    return hc.finish();
   }
   return rc;
 }
@@ -1870,20 +1809,14 @@ static int external_select(shc_engine *e, int which, int64_t first, int64_t coun
 
 static int external_write(shc_engine *e, int which, int64_t first, int64_t count, int leg, const std::vector<ExtRow> &host, int transform_only,
                           int64_t *ignored) {
-  ExtRow *d_rows = nullptr;
-  unsigned long long *d_ignored = nullptr, h_ignored = 0;
-  HIP_TRY(hipMalloc(&d_rows, host.size() * sizeof(ExtRow) + 8));
-  d_ignored = reinterpret_cast<unsigned long long *>(d_rows + host.size());
-  hipError_t err = hipMemcpyAsync(d_rows, host.data(), host.size() * sizeof(ExtRow), hipMemcpyHostToDevice, e->stream);
-  if (err == hipSuccess) err = hipMemsetAsync(d_ignored, 0, 8, e->stream);
-  if (err == hipSuccess) {
-    set_external_kernel<<<dim3((unsigned)((host.size() + 255) / 256)), dim3(256), 0, e->stream>>>(e->st, e->L, first, count, leg, which, d_rows, transform_only, d_ignored, e->d_seq, e->params.rough_terrain_mode);
-    err = hipGetLastError();
-  }
-  if (err == hipSuccess) err = hipMemcpyAsync(&h_ignored, d_ignored, 8, hipMemcpyDeviceToHost, e->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  (void)hipFree(d_rows);
-  if (err != hipSuccess) return fail(SHC_ERR_HIP, hipGetErrorString(err));
+  unsigned long long h_ignored = 0;
+  HostCall hc(e);
+  const ExtRow *d_rows = hc.in(host.data(), host.size(), 0);
+  unsigned long long *d_ignored = hc.out(&h_ignored, 1, 0);
+  if (const int rc = hc.status()) return rc;
+  HIP_TRY(hipMemsetAsync(d_ignored, 0, 8, e->stream));
+  set_external_kernel<<<grid256(int64_t(host.size())), dim3(256), 0, e->stream>>>(e->st, e->L, first, count, leg, which, d_rows, transform_only, d_ignored, e->d_seq, e->params.rough_terrain_mode);
+  if (const int rc = hc.finish()) return rc;
   if (ignored) *ignored = int64_t(h_ignored);
   return SHC_OK;
 }
@@ -1930,15 +1863,11 @@ extern "C" int shc_engine_get_external_target(shc_engine *e, int which, int64_t 
   if (rc != SHC_OK) return rc;
   if (!rows) return fail(SHC_ERR_INVALID_ARG, "rows is NULL");
   if (n_rows == 0) return SHC_OK;
-  ExtRow *d_rows = nullptr;
-  HIP_TRY(hipMalloc(&d_rows, size_t(n_rows) * sizeof(ExtRow)));
-  get_external_kernel<<<dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, e->stream>>>(e->st, e->L, first, count, leg, which, d_rows);
   std::vector<ExtRow> host((size_t)n_rows);
-  hipError_t err = hipGetLastError();
-  if (err == hipSuccess) err = hipMemcpyAsync(host.data(), d_rows, size_t(n_rows) * sizeof(ExtRow), hipMemcpyDeviceToHost, e->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  (void)hipFree(d_rows);
-  if (err != hipSuccess) return fail(SHC_ERR_HIP, hipGetErrorString(err));
+  if ((rc = gather_output(e, host.data(), host.size(), 0, [&](ExtRow *d_rows) {
+         get_external_kernel<<<grid256(n_rows), dim3(256), 0, e->stream>>>(e->st, e->L, first, count, leg, which, d_rows);
+       })) != SHC_OK)
+    return rc;
   for (int64_t i = 0; i < n_rows; ++i) {
     for (int k = 0; k < 7; ++k) rows[i].pose[k] = host[i].pose[k], rows[i].transform[k] = host[i].transform[k];
     rows[i].swing_clearance = host[i].swing_clearance;
@@ -1954,81 +1883,29 @@ extern "C" int shc_engine_get_external_target(shc_engine *e, int which, int64_t 
 extern "C" int shc_engine_get_joint_commands(shc_engine *e, double *position, double *velocity, double *effort, double *position_command, int on_device) {
   SHC_ENTER_JOINED(e);
   HIP_TRY(hipSetDevice(e->device));
-  const double *d_off;
-  int rc = upload_offsets(e, &d_off);
-  if (rc != SHC_OK) return rc;
+  const std::vector<double> off = joint_offsets(e);
   const size_t rows = size_t(e->n) * e->L * e->NJ;
-  double *out[4] = {position, velocity, effort, position_command}, *dev[4] = {nullptr, nullptr, nullptr, nullptr};
-  std::vector<void *> temps;
-  auto release = [&]() {
-    for (void *t : temps) (void)hipFree(t);
-  };
-  for (int k = 0; k < 4; ++k) {
-    if (!out[k]) continue;
-    if (on_device) {
-      dev[k] = out[k];
-      continue;
-    }
-    void *t = nullptr;
-    HIP_TRY_OR(hipMalloc(&t, rows * 8), release());
-    temps.push_back(t);
-    dev[k] = static_cast<double *>(t);
-  }
+  HostCall hc(e);
+  const double *d_off = hc.in(off.data(), off.size(), 0);
+  double *out[4] = {position, velocity, effort, position_command}, *dev[4];
+  for (int k = 0; k < 4; ++k) dev[k] = hc.out(out[k], rows, on_device);
+  if (const int rc = hc.status()) return rc;
   const int64_t threads = e->n * e->L;
-  joint_commands_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(dev[0], dev[1], dev[2], dev[3], e->st.legd, e->n_slots, e->n,
-                                                                                           e->L, e->NJ, LEG_FIELD(e, Q), LEG_FIELD(e, QD),
-                                                                                           LEG_FIELD(e, EFFORT_IN), d_off);
-  HIP_TRY_OR(hipGetLastError(), release());
-  if (!on_device)
-    for (int k = 0; k < 4; ++k)
-      if (out[k]) HIP_TRY_OR(hipMemcpyAsync(out[k], dev[k], rows * 8, hipMemcpyDeviceToHost, e->stream), release());
-  HIP_TRY_OR(hipStreamSynchronize(e->stream), release());
-  release();
-  return SHC_OK;
+  joint_commands_kernel<<<grid256(threads), dim3(256), 0, e->stream>>>(dev[0], dev[1], dev[2], dev[3], e->st.legd, e->n_slots, e->n, e->L, e->NJ, LEG_FIELD(e, Q),
+                                                                    LEG_FIELD(e, QD), LEG_FIELD(e, EFFORT_IN), d_off);
+  return hc.finish();
 }
 
-// ---- per-leg Leg API (include/shc_batch.h "Per-leg methods"): host arrays travel through temporary device buffers
+// ---- per-leg Leg API (include/shc_batch.h "Per-leg methods")
 struct LegCall {
-  shc_engine *e;
   LegSel sel;
   int64_t rows; // count * selected legs
-  std::vector<void *> temps;
-  ~LegCall() {
-    for (void *p : temps) (void)hipFree(p);
-  }
-  int init(shc_engine *eng, int64_t first, int64_t count, int leg) {
-    e = eng;
+  int init(shc_engine *e, int64_t first, int64_t count, int leg) {
     if (first < 0 || count < 0 || first + count > e->n) return fail(SHC_ERR_INVALID_ARG, "instance range out of bounds");
     if (leg < -1 || leg >= e->L) return fail(SHC_ERR_INVALID_ARG, "leg out of range (-1 = every leg)");
     sel = LegSel{first, count, leg, e->L};
     rows = count * (leg < 0 ? e->L : 1);
     HIP_TRY(hipSetDevice(e->device));
-    return SHC_OK;
-  }
-  // device view of an input array of `width` doubles per row
-  int in(const double *src, int width, int on_device, const double **d) {
-    *d = src;
-    if (!src || on_device || rows == 0) return SHC_OK;
-    void *t = nullptr;
-    HIP_TRY(hipMalloc(&t, size_t(rows) * width * 8));
-    temps.push_back(t);
-    HIP_TRY(hipMemcpyAsync(t, src, size_t(rows) * width * 8, hipMemcpyHostToDevice, e->stream));
-    *d = static_cast<const double *>(t);
-    return SHC_OK;
-  }
-  int out(double *dst, int width, int on_device, double **d) {
-    *d = dst;
-    if (!dst || on_device || rows == 0) return SHC_OK;
-    void *t = nullptr;
-    HIP_TRY(hipMalloc(&t, size_t(rows) * width * 8));
-    temps.push_back(t);
-    *d = static_cast<double *>(t);
-    return SHC_OK;
-  }
-  int finish(double *dst, const double *d, int width, int on_device) {
-    HIP_TRY(hipGetLastError());
-    if (dst && !on_device && rows) HIP_TRY(hipMemcpyAsync(dst, d, size_t(rows) * width * 8, hipMemcpyDeviceToHost, e->stream));
-    if (!temps.empty()) HIP_TRY(hipStreamSynchronize(e->stream)); // the temporaries are freed on return
     return SHC_OK;
   }
   dim3 grid() const { return dim3((unsigned)((rows + 63) / 64)); }
@@ -2047,10 +1924,11 @@ extern "C" int shc_leg_set_desired_tip_pose(shc_engine *e, int64_t first, int64_
   int rc = c.init(e, first, count, leg);
   if (rc != SHC_OK) return rc;
   if (!tip_pose && (rc = derive_tips(e)) != SHC_OK) return rc; // Pose::Undefined() = "the poser's tip pose" (model.cpp:657)
-  const double *d;
-  if ((rc = c.in(tip_pose, 7, on_device, &d)) != SHC_OK) return rc;
+  HostCall hc(e);
+  const double *d = hc.in(tip_pose, size_t(c.rows) * 7, on_device);
+  if ((rc = hc.status()) != SHC_OK) return rc;
   if ((rc = LEG_KERNEL(leg_set_desired_kernel, d, apply_delta, e->params.admittance_control, rotations_tracked(e))) != SHC_OK) return rc;
-  return c.finish(nullptr, nullptr, 0, on_device);
+  return hc.finish();
 }
 
 extern "C" int shc_leg_solve_ik(shc_engine *e, int64_t first, int64_t count, int leg, const double *delta, int solve_rotation,
@@ -2060,11 +1938,12 @@ extern "C" int shc_leg_solve_ik(shc_engine *e, int64_t first, int64_t count, int
   LegCall c;
   int rc = c.init(e, first, count, leg);
   if (rc != SHC_OK) return rc;
-  const double *d;
-  double *o;
-  if ((rc = c.in(delta, 6, on_device, &d)) != SHC_OK || (rc = c.out(joint_delta, e->NJ, on_device, &o)) != SHC_OK) return rc;
+  HostCall hc(e);
+  const double *d = hc.in(delta, size_t(c.rows) * 6, on_device);
+  double *o = hc.out(joint_delta, size_t(c.rows) * e->NJ, on_device);
+  if ((rc = hc.status()) != SHC_OK) return rc;
   if ((rc = LEG_KERNEL(leg_solve_ik_kernel, d, solve_rotation, o)) != SHC_OK) return rc;
-  return c.finish(joint_delta, o, e->NJ, on_device);
+  return hc.finish();
 }
 
 extern "C" int shc_leg_update_joint_positions(shc_engine *e, int64_t first, int64_t count, int leg, const double *joint_delta, int simulation,
@@ -2074,13 +1953,14 @@ extern "C" int shc_leg_update_joint_positions(shc_engine *e, int64_t first, int6
   LegCall c;
   int rc = c.init(e, first, count, leg);
   if (rc != SHC_OK) return rc;
-  const double *d;
-  double *o;
-  if ((rc = c.in(joint_delta, e->NJ, on_device, &d)) != SHC_OK || (rc = c.out(limit_proximity, 1, on_device, &o)) != SHC_OK) return rc;
+  HostCall hc(e);
+  const double *d = hc.in(joint_delta, size_t(c.rows) * e->NJ, on_device);
+  double *o = hc.out(limit_proximity, size_t(c.rows), on_device);
+  if ((rc = hc.status()) != SHC_OK) return rc;
   if ((rc = LEG_KERNEL(leg_update_joints_kernel, d, simulation, o, e->params.time_delta, e->params.clamp_joint_velocities,
                        e->params.clamp_joint_positions)) != SHC_OK)
     return rc;
-  return c.finish(limit_proximity, o, 1, on_device);
+  return hc.finish();
 }
 
 extern "C" int shc_leg_apply_ik(shc_engine *e, int64_t first, int64_t count, int leg, int simulation, double *ik_result, int on_device) {
@@ -2088,12 +1968,13 @@ extern "C" int shc_leg_apply_ik(shc_engine *e, int64_t first, int64_t count, int
   LegCall c;
   int rc = c.init(e, first, count, leg);
   if (rc != SHC_OK) return rc;
-  double *o;
-  if ((rc = c.out(ik_result, 1, on_device, &o)) != SHC_OK) return rc;
+  HostCall hc(e);
+  double *o = hc.out(ik_result, size_t(c.rows), on_device);
+  if ((rc = hc.status()) != SHC_OK) return rc;
   if ((rc = LEG_KERNEL(leg_apply_ik_kernel, simulation, o, e->params.time_delta, e->params.clamp_joint_velocities,
                        e->params.clamp_joint_positions, e->cp.tip_force, e->params.force_gain)) != SHC_OK)
     return rc;
-  return c.finish(ik_result, o, 1, on_device);
+  return hc.finish();
 }
 
 extern "C" int shc_leg_apply_fk(shc_engine *e, int64_t first, int64_t count, int leg, const double *joint_position, double *tip_pose,
@@ -2103,11 +1984,12 @@ extern "C" int shc_leg_apply_fk(shc_engine *e, int64_t first, int64_t count, int
   LegCall c;
   int rc = c.init(e, first, count, leg);
   if (rc != SHC_OK) return rc;
-  const double *d;
-  double *o;
-  if ((rc = c.in(joint_position, e->NJ, on_device, &d)) != SHC_OK || (rc = c.out(tip_pose, 7, on_device, &o)) != SHC_OK) return rc;
+  HostCall hc(e);
+  const double *d = hc.in(joint_position, size_t(c.rows) * e->NJ, on_device);
+  double *o = hc.out(tip_pose, size_t(c.rows) * 7, on_device);
+  if ((rc = hc.status()) != SHC_OK) return rc;
   if ((rc = LEG_KERNEL(leg_apply_fk_kernel, d, o)) != SHC_OK) return rc;
-  return c.finish(tip_pose, o, 7, on_device);
+  return hc.finish();
 }
 
 // ---- sequences
@@ -2119,25 +2001,16 @@ extern "C" int shc_leg_step_to_position(shc_engine *e, int64_t first, int64_t co
   LegCall c;
   int rc = c.init(e, first, count, leg);
   if (rc != SHC_OK) return rc;
-  const double *dt, *dp;
-  double *o, *prog;
-  if ((rc = c.in(target_tip_pose, 7, on_device, &dt)) != SHC_OK) return rc;
-  { // target_pose has one row per INSTANCE
-    const int64_t rows = c.rows;
-    c.rows = count;
-    rc = c.in(target_pose, 7, on_device, &dp);
-    c.rows = rows;
-    if (rc != SHC_OK) return rc;
-  }
-  if ((rc = c.out(tip_pose, 7, on_device, &o)) != SHC_OK) return rc;
-  // int32 progress rows ride in a double-width temporary (4 bytes used per row)
-  if ((rc = c.out(reinterpret_cast<double *>(progress), 1, on_device, &prog)) != SHC_OK) return rc;
+  HostCall hc(e);
+  const double *dt = hc.in(target_tip_pose, size_t(c.rows) * 7, on_device);
+  const double *dp = hc.in(target_pose, size_t(count) * 7, on_device); // one row per INSTANCE
+  double *o = hc.out(tip_pose, size_t(c.rows) * 7, on_device);
+  int32_t *prog = hc.out(progress, size_t(c.rows), on_device);
+  if ((rc = hc.status()) != SHC_OK) return rc;
   if ((rc = LEG_KERNEL(leg_step_to_position_kernel, dt, dp, lift_height, time_to_step, apply_delta, e->params.admittance_control,
-                       e->params.time_delta, o, reinterpret_cast<int32_t *>(prog))) != SHC_OK)
+                       e->params.time_delta, o, prog)) != SHC_OK)
     return rc;
-  HIP_TRY(hipGetLastError());
-  if (progress && !on_device && c.rows) HIP_TRY(hipMemcpyAsync(progress, prog, size_t(c.rows) * 4, hipMemcpyDeviceToHost, e->stream));
-  return c.finish(tip_pose, o, 7, on_device);
+  return hc.finish();
 }
 
 extern "C" int shc_leg_transition_configuration(shc_engine *e, int64_t first, int64_t count, int leg, const double *desired_configuration,
@@ -2147,15 +2020,12 @@ extern "C" int shc_leg_transition_configuration(shc_engine *e, int64_t first, in
   LegCall c;
   int rc = c.init(e, first, count, leg);
   if (rc != SHC_OK) return rc;
-  const double *d;
-  double *prog;
-  if ((rc = c.in(desired_configuration, e->NJ, on_device, &d)) != SHC_OK) return rc;
-  if ((rc = c.out(reinterpret_cast<double *>(progress), 1, on_device, &prog)) != SHC_OK) return rc;
-  if ((rc = LEG_KERNEL(leg_transition_configuration_kernel, d, 1, transition_time, e->params.time_delta, reinterpret_cast<int32_t *>(prog))) != SHC_OK)
-    return rc;
-  HIP_TRY(hipGetLastError());
-  if (progress && !on_device && c.rows) HIP_TRY(hipMemcpyAsync(progress, prog, size_t(c.rows) * 4, hipMemcpyDeviceToHost, e->stream));
-  return c.finish(nullptr, nullptr, 0, on_device);
+  HostCall hc(e);
+  const double *d = hc.in(desired_configuration, size_t(c.rows) * e->NJ, on_device);
+  int32_t *prog = hc.out(progress, size_t(c.rows), on_device);
+  if ((rc = hc.status()) != SHC_OK) return rc;
+  if ((rc = LEG_KERNEL(leg_transition_configuration_kernel, d, 1, transition_time, e->params.time_delta, prog)) != SHC_OK) return rc;
+  return hc.finish();
 }
 
 // Joints of every instance to the configuration Leg::init(true) leaves (model.cpp:286-305: Joint::default_position_ =
@@ -2187,6 +2057,18 @@ __global__ void restore_joints_kernel(DevState st, const double2 *saved_planes, 
   }
 }
 
+// One iteration of LegPoser::transitionConfiguration on every leg of every robot towards one [L][NJ] configuration shared by all instances
+static int transition_every_leg(shc_engine *e, const std::vector<double> &target, double transition_time) {
+  LegCall c;
+  int rc = c.init(e, 0, e->n, -1);
+  if (rc != SHC_OK) return rc;
+  HostCall hc(e);
+  const double *d = hc.in(target.data(), target.size(), 0);
+  if ((rc = hc.status()) != SHC_OK) return rc;
+  if ((rc = LEG_KERNEL(leg_transition_configuration_kernel, d, 0, transition_time, e->params.time_delta, (int32_t *)nullptr)) != SHC_OK) return rc;
+  return hc.finish();
+}
+
 extern "C" int shc_engine_begin_direct_startup(shc_engine *e) {
   SHC_ENTER_JOINED(e);
   int rc = init_state(e);
@@ -2194,12 +2076,11 @@ extern "C" int shc_engine_begin_direct_startup(shc_engine *e) {
   std::vector<double> q0(size_t(e->L) * e->NJ);
   for (int l = 0; l < e->L; ++l)
     for (int j = 0; j < e->NJ; ++j) q0[size_t(l) * e->NJ + j] = clampd(0.0, e->params.joint[l][j].min, e->params.joint[l][j].max);
-  HIP_TRY(hipMemcpyAsync(e->d_stage, q0.data(), q0.size() * 8, hipMemcpyHostToDevice, e->stream));
-  const int64_t threads = e->n * e->L;
-  const dim3 grid((unsigned)((threads + 255) / 256));
-  dispatch_nj(e->NJ, [&](auto nj) { set_initial_joints_kernel<decltype(nj)::value><<<grid, dim3(256), 0, e->stream>>>(e->st, e->d_stage, e->L); });
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(e->stream));
+  HostCall hc(e);
+  const double *d = hc.in(q0.data(), q0.size(), 0);
+  if ((rc = hc.status()) != SHC_OK) return rc;
+  dispatch_nj(e->NJ, [&](auto nj) { set_initial_joints_kernel<decltype(nj)::value><<<grid256(e->n * e->L), dim3(256), 0, e->stream>>>(e->st, d, e->L); });
+  if ((rc = hc.finish()) != SHC_OK) return rc;
   e->startup_calls = 0;
   e->starting_up = 1;
   return SHC_OK;
@@ -2214,14 +2095,8 @@ extern "C" int shc_engine_direct_startup(shc_engine *e, int32_t *progress) {
   std::vector<double> target(size_t(e->L) * e->NJ);
   for (int l = 0; l < e->L; ++l)
     for (int j = 0; j < e->NJ; ++j) target[size_t(l) * e->NJ + j] = e->tables.default_joint_position[l][j];
-  HIP_TRY(hipMemcpyAsync(e->d_stage, target.data(), target.size() * 8, hipMemcpyHostToDevice, e->stream));
-  LegCall c;
-  int rc = c.init(e, 0, e->n, -1);
+  int rc = transition_every_leg(e, target, e->params.time_to_start);
   if (rc != SHC_OK) return rc;
-  const double *d = e->d_stage;
-  if ((rc = LEG_KERNEL(leg_transition_configuration_kernel, d, 0, e->params.time_to_start, e->params.time_delta, (int32_t *)nullptr)) != SHC_OK) return rc;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(e->stream)); // the staging buffer is reused
   // progress is a function of the call count alone (every leg runs the same number of iterations, :1546-1566)
   const int num = hostinit::startup_loops(e->params);
   e->startup_calls++;
@@ -2257,7 +2132,6 @@ extern "C" int shc_engine_begin_sequence_startup(shc_engine *e, const double *jo
   // (arguments first: an INVALID_ARG return leaves the batch as it was)
   if (per_instance && !joint_positions) return fail(SHC_ERR_INVALID_ARG, "per_instance needs joint_positions");
   const size_t rows = per_instance ? size_t(e->n) * e->L : size_t(e->L);
-  if (rows * e->NJ * 8 > e->stage_bytes) return fail(SHC_ERR_INVALID_ARG, "staging buffer too small");
   std::vector<double> q(rows * e->NJ);
   if (joint_positions) {
     memcpy(q.data(), joint_positions, q.size() * 8);
@@ -2269,13 +2143,13 @@ extern "C" int shc_engine_begin_sequence_startup(shc_engine *e, const double *jo
   int rc = init_state(e); // StateController::init(): fresh walker / poser state
   e->fresh_pose_controller = false;
   if (rc != SHC_OK) return rc;
-  HIP_TRY(hipMemcpyAsync(e->d_stage, q.data(), q.size() * 8, hipMemcpyHostToDevice, e->stream));
-  const int64_t threads = e->n * e->L;
-  set_joint_positions_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, e->stream>>>(e->st, e->d_stage, per_instance, e->L, e->NJ, LEG_FIELD(e, Q),
-                                                                                                 LEG_FIELD(e, QD), LEG_FIELD(e, MEAS_Q));
+  HostCall hc(e);
+  const double *d = hc.in(q.data(), q.size(), 0);
+  if ((rc = hc.status()) != SHC_OK) return rc;
+  set_joint_positions_kernel<<<grid256(e->n * e->L), dim3(256), 0, e->stream>>>(e->st, d, per_instance, e->L, e->NJ, LEG_FIELD(e, Q), LEG_FIELD(e, QD), LEG_FIELD(e, MEAS_Q));
   HIP_TRY(hipGetLastError());
   if (e->d_seq) HIP_TRY(hipMemsetAsync(e->d_seq, 0, sizeof(SeqRobotState) * size_t(e->n), e->stream)); // fresh PoseController
-  HIP_TRY(hipStreamSynchronize(e->stream));
+  if ((rc = hc.finish()) != SHC_OK) return rc;
   e->starting_up = 0;
   e->pack_step = e->executing_transition = e->transition_calls = 0;
   return SHC_OK;
@@ -2326,7 +2200,10 @@ static int sequence_launch(shc_engine *e, int which /* 0 / 1: executeSequence(ST
     const Quat r = from_two_vectors(V3{1, 0, 0}, V3{e->cp.target_dir[0], e->cp.target_dir[1], e->cp.target_dir[2]});
     P.target_rotation[0] = r.w, P.target_rotation[1] = r.x, P.target_rotation[2] = r.y, P.target_rotation[3] = r.z;
   }
-  int32_t *d_progress = reinterpret_cast<int32_t *>(e->d_stage); // [n] ints fit the staging buffer (>= n * 8 * 8 bytes)
+  HostCall hc(e);
+  int32_t *d_progress = hc.scratch<int32_t>(size_t(e->n));
+  hc.back(progress, d_progress, size_t(e->n));
+  if ((rc = hc.status()) != SHC_OK) return rc;
   const dim3 grid((unsigned)((e->n + 63) / 64)), block(64);
   // Auto posing on its own clock keeps posing through the sequence (pose_controller.cpp:1134-1187 runs in every loop, state_controller.cpp:165-167): the
   // posing part of this loop runs in the cycle kernel for the robots whose sequence is still running (a pose-only pass, as for leg toggles and plan steps)
@@ -2363,8 +2240,7 @@ static int sequence_launch(shc_engine *e, int which /* 0 / 1: executeSequence(ST
     e->rt_flags = rt_keep;
     HIP_TRY(hipGetLastError());
   }
-  if (progress) HIP_TRY(hipMemcpyAsync(progress, d_progress, size_t(e->n) * 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
+  if ((rc = hc.finish()) != SHC_OK) return rc;
   return which == SHC_SEQUENCE_SHUT_DOWN ? adjust_served_by_loop(e) : SHC_OK; // shc_adjust.hpp, rows "SHUT_DOWN" / "START_UP sequence step, step_to_new_stance"
 }
 
@@ -2382,12 +2258,12 @@ static int ensure_manual_records(shc_engine *e) { // the per-robot ManualRobot r
   if (!e->st.manual) {
     HIP_TRY(hipMalloc(&e->st.manual, sizeof(ManualRobot) * size_t(e->n_rob_pad)));
     HIP_TRY(hipMemsetAsync(e->st.manual, 0, sizeof(ManualRobot) * size_t(e->n_rob_pad), e->stream)); // all WALKING
-    std::vector<int32_t> none(size_t(e->n), -1);
-    HIP_TRY(hipMemcpyAsync(e->d_stage, none.data(), none.size() * 4, hipMemcpyHostToDevice, e->stream));
-    set_manual_inputs_kernel<<<dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, e->stream>>>(e->st.manual, e->n, reinterpret_cast<const int32_t *>(e->d_stage), nullptr,
-                                                                                          nullptr, reinterpret_cast<const int32_t *>(e->d_stage), nullptr, nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    const std::vector<int32_t> none(size_t(e->n), -1);
+    HostCall hc(e);
+    const int32_t *d = hc.in(none.data(), none.size(), 0);
+    if (const int rc = hc.status()) return rc;
+    set_manual_inputs_kernel<<<grid256(e->n), dim3(256), 0, e->stream>>>(e->st.manual, e->n, d, nullptr, nullptr, d, nullptr, nullptr);
+    return hc.finish();
   }
   return SHC_OK;
 }
@@ -2405,8 +2281,12 @@ extern "C" int shc_engine_toggle_leg_state(shc_engine *e, const int32_t *leg_sel
   int rc = ensure_manual(e, false);
   if (rc != SHC_OK) return rc;
   if (!leg_selection) return fail(SHC_ERR_INVALID_ARG, "leg_selection is NULL");
-  int32_t *d_sel = reinterpret_cast<int32_t *>(e->d_stage), *d_res = d_sel + e->n, *d_cycle = d_res + e->n;
-  HIP_TRY(hipMemcpyAsync(d_sel, leg_selection, size_t(e->n) * 4, hipMemcpyHostToDevice, e->stream));
+  int32_t cycle = 0;
+  HostCall hc(e);
+  const int32_t *d_sel = hc.in(leg_selection, size_t(e->n), 0);
+  int32_t *d_res = hc.scratch<int32_t>(size_t(e->n)), *d_cycle = hc.out(&cycle, 1, 0);
+  hc.back(result, d_res, size_t(e->n));
+  if ((rc = hc.status()) != SHC_OK) return rc;
   HIP_TRY(hipMemsetAsync(d_cycle, 0, 4, e->stream));
   const SeqParams P = seq_params(e);
   const double virtual_stiffness = posing_params(e).virtual_stiffness; // (as seq_params)
@@ -2427,11 +2307,7 @@ extern "C" int shc_engine_toggle_leg_state(shc_engine *e, const int32_t *leg_sel
     if ((rc = pose_pass(e)) != SHC_OK) return rc;
   }
   if ((rc = toggle(posed ? LOOP_AFTER_POSE : LOOP_WHOLE)) != SHC_OK) return rc;
-  HIP_TRY(hipGetLastError());
-  int32_t cycle = 0;
-  if (result) HIP_TRY(hipMemcpyAsync(result, d_res, size_t(e->n) * 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(&cycle, d_cycle, 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
+  if ((rc = hc.finish()) != SHC_OK) return rc;
   if (cycle) { // robots without a request, or asked to stop first: their loop is one ordinary control cycle; the others keep out of it
     e->rt_flags |= RT_SKIP_MARKED;
     rc = shc_engine_step(e, 1);
@@ -2447,37 +2323,24 @@ extern "C" int shc_engine_set_manual_inputs(shc_engine *e, const int32_t *primar
   SHC_ENTER_JOINED(e);
   int rc = ensure_manual(e, false);
   if (rc != SHC_OK) return rc;
-  // staging layout: [primary leg | secondary leg] ints, then four [n][3] double blocks
   const size_t n = size_t(e->n);
-  if (n * 8 + 4 * n * 24 > e->stage_bytes) return fail(SHC_ERR_INVALID_ARG, "staging buffer too small");
-  char *base = reinterpret_cast<char *>(e->d_stage);
-  int32_t *d_p = reinterpret_cast<int32_t *>(base), *d_s = d_p + n;
-  double *d_v[4];
-  for (int k = 0; k < 4; ++k) d_v[k] = reinterpret_cast<double *>(base + n * 8) + size_t(k) * n * 3;
-  const double *src[4] = {primary_tip_velocity, primary_tip_position, secondary_tip_velocity, secondary_tip_position};
-  if (primary_leg) HIP_TRY(hipMemcpyAsync(d_p, primary_leg, n * 4, hipMemcpyHostToDevice, e->stream));
-  if (secondary_leg) HIP_TRY(hipMemcpyAsync(d_s, secondary_leg, n * 4, hipMemcpyHostToDevice, e->stream));
-  for (int k = 0; k < 4; ++k)
-    if (src[k]) HIP_TRY(hipMemcpyAsync(d_v[k], src[k], n * 24, hipMemcpyHostToDevice, e->stream));
-  set_manual_inputs_kernel<<<dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, e->stream>>>(e->st.manual, e->n, primary_leg ? d_p : nullptr, src[0] ? d_v[0] : nullptr,
-                                                                                        src[1] ? d_v[1] : nullptr, secondary_leg ? d_s : nullptr,
-                                                                                        src[2] ? d_v[2] : nullptr, src[3] ? d_v[3] : nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return SHC_OK;
+  HostCall hc(e);
+  const int32_t *d_p = hc.in(primary_leg, n, 0), *d_s = hc.in(secondary_leg, n, 0);
+  const double *src[4] = {primary_tip_velocity, primary_tip_position, secondary_tip_velocity, secondary_tip_position}, *d_v[4];
+  for (int k = 0; k < 4; ++k) d_v[k] = hc.in(src[k], n * 3, 0);
+  if ((rc = hc.status()) != SHC_OK) return rc;
+  set_manual_inputs_kernel<<<grid256(e->n), dim3(256), 0, e->stream>>>(e->st.manual, e->n, d_p, d_v[0], d_v[1], d_s, d_v[2], d_v[3]);
+  hc.wait_at_finish(); // (also when every array is NULL)
+  return hc.finish();
 }
 
 extern "C" int shc_engine_get_leg_manipulation_state(shc_engine *e, int32_t *states) {
   SHC_ENTER_JOINED(e);
   if (!states) return fail(SHC_ERR_INVALID_ARG, "states is NULL");
-  HIP_TRY(hipSetDevice(e->device));
-  int32_t *d = reinterpret_cast<int32_t *>(e->d_stage);
   const int64_t rows = e->n * e->L;
-  get_leg_manipulation_state_kernel<<<dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, e->stream>>>(e->st.manual, e->n, e->L, d);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(states, d, size_t(rows) * 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  return SHC_OK;
+  return gather_output(e, states, size_t(rows), 0, [&](int32_t *d) {
+    get_leg_manipulation_state_kernel<<<grid256(rows), dim3(256), 0, e->stream>>>(e->st.manual, e->n, e->L, d);
+  });
 }
 
 // ---- planner mode (shc_sequence.hpp: execute_plan_kernel)
@@ -2492,24 +2355,12 @@ static int plan_inputs(shc_engine *e, int64_t first, int64_t count, int reset_pl
   if (first < 0 || count < 0 || first + count > e->n) return fail(SHC_ERR_INVALID_ARG, "instance range out of bounds");
   if (count == 0) return SHC_OK;
   const size_t cfg_doubles = configuration ? size_t(count) * e->L * e->NJ : 0, pose_doubles = body_pose ? size_t(count) * 7 : 0;
-  double *d = nullptr;
-  if (cfg_doubles + pose_doubles) {
-    HIP_TRY(hipMalloc(&d, (cfg_doubles + pose_doubles) * 8));
-    hipError_t err = hipSuccess;
-    if (configuration) err = hipMemcpyAsync(d, configuration, cfg_doubles * 8, hipMemcpyHostToDevice, e->stream);
-    if (err == hipSuccess && body_pose) err = hipMemcpyAsync(d + cfg_doubles, body_pose, pose_doubles * 8, hipMemcpyHostToDevice, e->stream);
-    if (err != hipSuccess) {
-      (void)hipFree(d);
-      return fail(SHC_ERR_HIP, hipGetErrorString(err));
-    }
-  }
-  plan_inputs_kernel<<<dim3((unsigned)((count + 255) / 256)), dim3(256), 0, e->stream>>>(e->d_seq, first, count, e->L, e->NJ, reset_plan_step,
-                                                                                 configuration ? d : nullptr, body_pose ? d + cfg_doubles : nullptr);
-  hipError_t err = hipGetLastError();
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  (void)hipFree(d);
-  if (err != hipSuccess) return fail(SHC_ERR_HIP, hipGetErrorString(err));
-  return SHC_OK;
+  HostCall hc(e);
+  const double *d_cfg = hc.in(configuration, cfg_doubles, 0), *d_pose = hc.in(body_pose, pose_doubles, 0);
+  if ((rc = hc.status()) != SHC_OK) return rc;
+  plan_inputs_kernel<<<grid256(count), dim3(256), 0, e->stream>>>(e->d_seq, first, count, e->L, e->NJ, reset_plan_step, d_cfg, d_pose);
+  hc.wait_at_finish(); // (also when both arrays are NULL)
+  return hc.finish();
 }
 
 extern "C" int shc_engine_set_planner_mode(shc_engine *e, int on) {
@@ -2533,7 +2384,11 @@ extern "C" int shc_engine_execute_plan(shc_engine *e, int32_t *progress, int32_t
   SHC_ENTER_JOINED(e);
   int rc = ensure_planner(e);
   if (rc != SHC_OK) return rc;
-  int32_t *d_progress = reinterpret_cast<int32_t *>(e->d_stage), *d_step = d_progress + e->n, *d_walking = d_step + e->n;
+  int32_t walking = 0;
+  HostCall hc(e);
+  int32_t *d_progress = hc.scratch<int32_t>(size_t(e->n)), *d_step = hc.scratch<int32_t>(size_t(e->n)), *d_walking = hc.out(&walking, 1, 0);
+  hc.back(progress, d_progress, size_t(e->n)), hc.back(plan_step, d_step, size_t(e->n));
+  if ((rc = hc.status()) != SHC_OK) return rc;
   HIP_TRY(hipMemsetAsync(d_walking, 0, 4, e->stream));
   const SeqParams P = seq_params(e);
   const int reset_poser_tips = e->plan_poser_tips_current ? 0 : 1;
@@ -2555,11 +2410,7 @@ extern "C" int shc_engine_execute_plan(shc_engine *e, int32_t *progress, int32_t
   if ((rc = plan(posed ? LOOP_AFTER_POSE : LOOP_WHOLE)) != SHC_OK) return rc;
   HIP_TRY(hipGetLastError());
   e->plan_poser_tips_current = true;
-  int32_t walking = 0;
-  if (progress) HIP_TRY(hipMemcpyAsync(progress, d_progress, size_t(e->n) * 4, hipMemcpyDeviceToHost, e->stream));
-  if (plan_step) HIP_TRY(hipMemcpyAsync(plan_step, d_step, size_t(e->n) * 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipMemcpyAsync(&walking, d_walking, 4, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
+  if ((rc = hc.finish()) != SHC_OK) return rc;
   if (walking) { // the loop of the robots that are still walking is the normal control cycle (inputs zeroed); the others keep out of it
     e->rt_flags |= RT_SKIP_MARKED;
     rc = shc_engine_step(e, 1);
@@ -2584,14 +2435,8 @@ static int pack_transition(shc_engine *e, const double *packed_positions, int n_
       if (!unpack) target[k] = packed_positions[size_t(e->pack_step) * per_step + k];
       else target[k] = e->pack_step > 0 ? packed_positions[size_t(e->pack_step - 1) * per_step + k] : e->params.joint[l][j].unpacked;
     }
-  HIP_TRY(hipMemcpyAsync(e->d_stage, target.data(), target.size() * 8, hipMemcpyHostToDevice, e->stream));
-  LegCall c;
-  int rc = c.init(e, 0, e->n, -1);
+  const int rc = transition_every_leg(e, target, transition_time);
   if (rc != SHC_OK) return rc;
-  const double *d = e->d_stage;
-  if ((rc = LEG_KERNEL(leg_transition_configuration_kernel, d, 0, transition_time, e->params.time_delta, (int32_t *)nullptr)) != SHC_OK) return rc;
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(e->stream)); // the staging buffer is reused
   // LegPoser::transitionConfiguration's progress is a function of its iteration count alone (:1546-1566)
   int num = round_to_int(transition_time / e->params.time_delta);
   num = num > 1 ? num : 1;
@@ -2697,20 +2542,16 @@ extern "C" int shc_engine_finish_sequence_startup(shc_engine *e) {
   // walker_->init() (:306): fresh LegSteppers / walk state; the joints stay where the sequence left them
   const int n_joint_planes = (2 * e->NJ + 1) / 2 + 1; // planes holding Q and QD (Fields: Q = 0, QD = NJ, TIP = 2 NJ)
   const int64_t count = int64_t(n_joint_planes) * e->n_slots;
-  double2 *keep = nullptr;
-  HIP_TRY(hipMalloc(&keep, size_t(count) * 16));
-  const dim3 grid((unsigned)((count + 255) / 256));
-  copy_joint_planes_kernel<<<grid, dim3(256), 0, e->stream>>>(keep, reinterpret_cast<const double2 *>(e->st.legd), count);
-  hipError_t err = hipGetLastError();
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  if (err == hipSuccess && (rc = init_state(e)) == SHC_OK) {
-    restore_joints_kernel<<<dim3((unsigned)((e->n * e->L + 255) / 256)), dim3(256), 0, e->stream>>>(e->st, keep, e->L, e->NJ);
-    err = hipGetLastError();
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  {
+    HostCall hc(e);
+    double2 *keep = hc.scratch<double2>(size_t(count));
+    if ((rc = hc.status()) != SHC_OK) return rc;
+    copy_joint_planes_kernel<<<grid256(count), dim3(256), 0, e->stream>>>(keep, reinterpret_cast<const double2 *>(e->st.legd), count);
+    if ((rc = hc.finish()) != SHC_OK || (rc = init_state(e)) != SHC_OK) return rc;
+    restore_joints_kernel<<<grid256(e->n * e->L), dim3(256), 0, e->stream>>>(e->st, keep, e->L, e->NJ);
+    hc.wait_at_finish(); // (keep is read again)
+    if ((rc = hc.finish()) != SHC_OK) return rc;
   }
-  (void)hipFree(keep);
-  if (err != hipSuccess) return fail(SHC_ERR_HIP, hipGetErrorString(err));
-  if (rc != SHC_OK) return rc;
   if (own_clock) { // the PoseController's part of the record carries over, one phase back (see above)
     std::vector<shc_instance_state> fresh(size_t(e->n));
     if ((rc = shc_engine_get_state(e, 0, e->n, fresh.data())) != SHC_OK) return rc;
@@ -2743,17 +2584,9 @@ extern "C" int shc_engine_get_body_state(shc_engine *e, double *pose, double *ve
   int rc;
   if ((rc = gather_rob(e, pose, 7, RobotFields::CPOSE, on_device)) != SHC_OK) return rc;
   if ((rc = gather_rob(e, velocity, 3, RobotFields::VLIN, on_device)) != SHC_OK) return rc;
-  if (walk_state) {
-    HIP_TRY(hipSetDevice(e->device));
-    int32_t *d = on_device ? walk_state : reinterpret_cast<int32_t *>(e->d_stage);
-    gather_walk_state_kernel<<<dim3((unsigned)((e->n + 255) / 256)), dim3(256), 0, e->stream>>>(d, e->st.robi, 64 / e->L, e->n);
-    HIP_TRY(hipGetLastError());
-    if (!on_device) {
-      HIP_TRY(hipMemcpyAsync(walk_state, d, size_t(e->n) * 4, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-  }
-  return SHC_OK;
+  return gather_output(e, walk_state, size_t(e->n), on_device, [&](int32_t *d) {
+    gather_walk_state_kernel<<<grid256(e->n), dim3(256), 0, e->stream>>>(d, e->st.robi, 64 / e->L, e->n);
+  });
 }
 
 #include "shc_fleet.hpp" // shc_fleet_*: mixed morphologies + multi-device sharding (uses the entry points above)

@@ -258,7 +258,7 @@ extern "C" int shc_engine_set_footholds(shc_engine *e, const shc_foothold_spec *
   const int64_t stride = row_stride_of(spec, lay);
   if (on_device) return footholds_apply(e, spec, lay, rows, stride, nullptr, ignored);
   int64_t h_ignored = 0; // (the count's word stands behind the rows on the device)
-  rc = rows_from_host(e, "footholds", rows, e->n, lay.width, stride, spec->dtype, &h_ignored,
+  rc = rows_from_host(e, rows, e->n, lay.width, stride, spec->dtype, &h_ignored,
                       [&](const void *d, int64_t *d_ignored) { return footholds_apply(e, spec, lay, d, lay.width, nullptr, d_ignored); });
   if (rc == SHC_OK && ignored) *ignored += h_ignored;
   return rc;
@@ -277,5 +277,5 @@ extern "C" int shc_engine_get_footholds(shc_engine *e, const shc_foothold_spec *
   HIP_TRY(hipSetDevice(e->device));
   const int64_t stride = row_stride_of(spec, lay);
   if (on_device) return footholds_read(e, spec, lay, rows, stride, nullptr);
-  return rows_to_host(e, "footholds", rows, e->n, lay.width, stride, spec->dtype, [&](void *d) { return footholds_read(e, spec, lay, d, lay.width, nullptr); });
+  return rows_to_host(e, rows, e->n, lay.width, stride, spec->dtype, [&](void *d) { return footholds_read(e, spec, lay, d, lay.width, nullptr); });
 }

@@ -183,26 +183,22 @@ extern "C" int shc_engine_get_frame_transforms(shc_engine *e, int64_t first, int
   if (!e->cp.odometry && (body || world)) return fail(SHC_ERR_UNSUPPORTED, "SHC_FEAT_ODOMETRY is off: odom_to_base_link needs the ideal odometry");
   if (count == 0) return SHC_OK;
   HIP_TRY(hipSetDevice(e->device));
-  const size_t leg_bytes = legs ? size_t(count) * e->L * sizeof(shc_leg_frames) : 0, body_bytes = body ? size_t(count) * sizeof(shc_body_frames) : 0;
-  char *d = nullptr; // host form: one device block for both outputs (leg_bytes is a multiple of 16)
-  if (!on_device) HIP_TRY(hipMalloc(&d, leg_bytes + body_bytes));
-  double2 *d_legs = legs ? reinterpret_cast<double2 *>(on_device ? reinterpret_cast<char *>(legs) : d) : nullptr;
-  double2 *d_body = body ? reinterpret_cast<double2 *>(on_device ? reinterpret_cast<char *>(body) : d + leg_bytes) : nullptr;
+  HostCall hc(e);
+  shc_leg_frames *d_legs = legs;
+  shc_body_frames *d_body = body;
+  if (!on_device) { // one device block for both outputs (a leg record is a multiple of 16 bytes): neither fits the arena of a large batch, and one temporary will do
+    const size_t n_legs = legs ? size_t(count) * e->L : 0;
+    char *d = hc.scratch<char>(n_legs * sizeof(shc_leg_frames) + (body ? size_t(count) * sizeof(shc_body_frames) : 0));
+    if (const int rc = hc.status()) return rc;
+    d_legs = legs ? reinterpret_cast<shc_leg_frames *>(d) : nullptr, d_body = body ? reinterpret_cast<shc_body_frames *>(d + n_legs * sizeof(shc_leg_frames)) : nullptr;
+    hc.back(legs, d_legs, n_legs), hc.back(body, d_body, size_t(count));
+  }
   const unsigned grid = row_grid(e->L, first, first + count);
   const int rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
     constexpr int L = decltype(l)::value, NJ = decltype(nj)::value;
-    frame_transforms_kernel<L, NJ><<<dim3(grid), dim3(64), 0, e->stream>>>(d_legs, d_body, e->st, (const SharedConsts<L, NJ> *)e->d_consts, world,
+    frame_transforms_kernel<L, NJ><<<dim3(grid), dim3(64), 0, e->stream>>>(reinterpret_cast<double2 *>(d_legs), reinterpret_cast<double2 *>(d_body), e->st, (const SharedConsts<L, NJ> *)e->d_consts, world,
                                                                           e->cp.odometry ? 1 : 0, first, count);
     return SHC_OK;
   });
-  hipError_t err = rc == SHC_OK ? hipGetLastError() : hipSuccess;
-  if (!on_device) {
-    if (rc == SHC_OK && err == hipSuccess && legs) err = hipMemcpyAsync(legs, d, leg_bytes, hipMemcpyDeviceToHost, e->stream);
-    if (rc == SHC_OK && err == hipSuccess && body) err = hipMemcpyAsync(body, d + leg_bytes, body_bytes, hipMemcpyDeviceToHost, e->stream);
-    if (rc == SHC_OK && err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    (void)hipFree(d);
-  }
-  if (rc != SHC_OK) return rc;
-  if (err != hipSuccess) return fail(SHC_ERR_HIP, std::string("frame transforms: ") + hipGetErrorString(err));
-  return SHC_OK;
+  return rc != SHC_OK ? rc : hc.finish();
 }

@@ -250,15 +250,14 @@ extern "C" int shc_engine_scan_health(shc_engine *e, int64_t first, int64_t coun
     (void)health_levels(e->n_waves, &words);
     HIP_TRY(hipMalloc(&e->d_health, size_t(e->n_waves) * 8 + size_t(words) * 4));
   }
-  // host form: one device block for the four outputs (every part a multiple of 16 bytes)
-  const size_t health_bytes = health ? size_t(count) * sizeof(shc_robot_health) : 0, map_bytes = restore_map ? (size_t(n) * 8 + 15) & ~size_t(15) : 0;
-  const size_t list_bytes = selected ? (size_t(count) * 8 + 15) & ~size_t(15) : 0;
-  char *d = nullptr;
-  if (!on_device) HIP_TRY(hipMalloc(&d, health_bytes + map_bytes + list_bytes + 16));
-  ulonglong2 *d_health = health ? reinterpret_cast<ulonglong2 *>(on_device ? reinterpret_cast<char *>(health) : d) : nullptr;
-  int64_t *d_map = restore_map ? (on_device ? restore_map : reinterpret_cast<int64_t *>(d + health_bytes)) : nullptr;
-  int64_t *d_list = selected ? (on_device ? selected : reinterpret_cast<int64_t *>(d + health_bytes + map_bytes)) : nullptr;
-  int64_t *d_nsel = (n_selected || (selected && !on_device)) ? (on_device ? n_selected : reinterpret_cast<int64_t *>(d + health_bytes + map_bytes + list_bytes)) : nullptr;
+  // host form: the list's length comes back first - it decides how much of `selected` is written
+  int64_t n_sel = 0;
+  HostCall hc(e);
+  ulonglong2 *d_health = reinterpret_cast<ulonglong2 *>(hc.out(health, size_t(count), on_device));
+  int64_t *d_map = hc.out(restore_map, size_t(n), on_device);
+  int64_t *d_list = selected && !on_device && count ? hc.scratch<int64_t>(size_t(count)) : selected;
+  int64_t *d_nsel = on_device ? n_selected : (n_selected || selected) ? hc.out(&n_sel, 1, 0) : nullptr;
+  if (const int rc = hc.status()) return rc;
   const bool compact = d_list != nullptr || d_nsel != nullptr;
 
   int rc = SHC_OK;
@@ -295,22 +294,15 @@ extern "C" int shc_engine_scan_health(shc_engine *e, int64_t first, int64_t coun
       }
     }
   }
-  if (!on_device) {
-    const bool ok = rc == SHC_OK && err == hipSuccess;
-    int64_t n_sel = 0;
-    if (ok && d_nsel) {
-      err = hipMemcpyAsync(&n_sel, d_nsel, 8, hipMemcpyDeviceToHost, e->stream);
-      if (err == hipSuccess) err = hipStreamSynchronize(e->stream); // the list's length decides how much of `selected` is written
-    }
-    if (rc == SHC_OK && err == hipSuccess && health && count) err = hipMemcpyAsync(health, d_health, health_bytes, hipMemcpyDeviceToHost, e->stream);
-    if (rc == SHC_OK && err == hipSuccess && restore_map && n) err = hipMemcpyAsync(restore_map, d_map, size_t(n) * 8, hipMemcpyDeviceToHost, e->stream);
-    if (rc == SHC_OK && err == hipSuccess && selected && n_sel) err = hipMemcpyAsync(selected, d_list, size_t(n_sel) * 8, hipMemcpyDeviceToHost, e->stream);
-    if (rc == SHC_OK && err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    if (rc == SHC_OK && err == hipSuccess && n_selected) *n_selected = n_sel;
-    (void)hipFree(d);
-  }
   if (rc != SHC_OK) return rc;
   if (err != hipSuccess) return fail(SHC_ERR_HIP, std::string("health scan: ") + hipGetErrorString(err));
+  if ((rc = hc.finish()) != SHC_OK || on_device) return rc;
+  if (selected && n_sel) {
+    hc.back(selected, d_list, size_t(n_sel));
+    hc.wait_at_finish();
+    if ((rc = hc.finish()) != SHC_OK) return rc;
+  }
+  if (n_selected) *n_selected = n_sel;
   return SHC_OK;
 }
 

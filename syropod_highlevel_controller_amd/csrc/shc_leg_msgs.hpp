@@ -285,9 +285,9 @@ extern "C" int shc_engine_get_leg_state_msgs(shc_engine *e, int64_t first, int64
   if (count == 0) return SHC_OK;
   int rc = derive_tips(e);
   if (rc != SHC_OK) return rc;
-  const size_t bytes = size_t(count) * e->L * sizeof(shc_leg_state_msg);
-  shc_leg_state_msg *d = msgs;
-  if (!on_device) HIP_TRY(hipMalloc(&d, bytes));
+  HostCall hc(e);
+  shc_leg_state_msg *d = hc.out(msgs, size_t(count) * e->L, on_device);
+  if ((rc = hc.status()) != SHC_OK) return rc;
   const LegMsgArgs args = leg_msg_args(e->params, e->tables);
   const unsigned grid = row_grid(e->L, first, first + count);
   rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
@@ -295,13 +295,5 @@ extern "C" int shc_engine_get_leg_state_msgs(shc_engine *e, int64_t first, int64
     leg_state_msgs_kernel<L, NJ><<<dim3(grid), dim3(64), 0, e->stream>>>(reinterpret_cast<double2 *>(d), e->st, (const SharedConsts<L, NJ> *)e->d_consts, args, first, count);
     return SHC_OK;
   });
-  hipError_t err = rc == SHC_OK ? hipGetLastError() : hipSuccess;
-  if (!on_device) {
-    if (rc == SHC_OK && err == hipSuccess) err = hipMemcpyAsync(msgs, d, bytes, hipMemcpyDeviceToHost, e->stream);
-    if (rc == SHC_OK && err == hipSuccess) err = hipStreamSynchronize(e->stream);
-    (void)hipFree(d);
-  }
-  if (rc != SHC_OK) return rc;
-  if (err != hipSuccess) return fail(SHC_ERR_HIP, std::string("leg state messages: ") + hipGetErrorString(err));
-  return SHC_OK;
+  return rc != SHC_OK ? rc : hc.finish();
 }

@@ -229,6 +229,6 @@ extern "C" int shc_engine_get_observations(shc_engine *e, int64_t first, int64_t
   HIP_TRY(hipSetDevice(e->device));
   const int64_t stride = row_stride_of(spec, lay);
   if (on_device) return observe_launch(e, spec, lay, out, stride, nullptr, first, count);
-  return rows_to_host(e, "observations", out, count, lay.width, stride, spec->dtype,
+  return rows_to_host(e, out, count, lay.width, stride, spec->dtype,
                       [&](void *d) { return observe_launch(e, spec, lay, d, lay.width, nullptr, first, count); });
 }

@@ -851,16 +851,10 @@ extern "C" int shc_engine_get_step_k_joint_state(shc_engine *e, int k, double *q
   const double *slot = e->k_out + size_t(k) * size_t(e->NJ) * e->n_slots * 2;
   const int64_t threads = e->n * e->L;
   for (int which = 0; which < 2; ++which) {
-    double *dst = which ? qd : q;
-    if (!dst) continue;
-    double *d = on_device ? dst : e->d_stage;
-    if (!on_device && size_t(threads) * e->NJ * 8 > e->stage_bytes) return fail(SHC_ERR_INVALID_ARG, "staging buffer too small");
-    gather_leg_kernel<<<dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, e->stream>>>(d, slot, e->n_slots, e->n, e->L, e->NJ, which ? LEG_FIELD(e, QD) : LEG_FIELD(e, Q));
-    HIP_TRY(hipGetLastError());
-    if (!on_device) {
-      HIP_TRY(hipMemcpyAsync(dst, d, size_t(threads) * e->NJ * 8, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipStreamSynchronize(e->stream));
-    }
+    const int rc = gather_output(e, which ? qd : q, size_t(threads) * e->NJ, on_device, [&](double *d) {
+      gather_leg_kernel<<<dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, e->stream>>>(d, slot, e->n_slots, e->n, e->L, e->NJ, which ? LEG_FIELD(e, QD) : LEG_FIELD(e, Q));
+    });
+    if (rc != SHC_OK) return rc;
   }
   return SHC_OK;
 }

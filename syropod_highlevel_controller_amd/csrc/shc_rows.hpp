@@ -183,34 +183,24 @@ static size_t row_tile_bytes(int legs, int pitch, int dtype) { return size_t(64 
 // The host forms.  Dense device rows in: the columns [0, width) of every row of the caller's array as dense rows on the device - with `word`, a
 // zeroed 8-byte word behind them, which is read back after the pass - then pass(rows, word) on the engine's stream, and a wait.
 template <class Pass>
-static int rows_from_host(shc_engine *e, const char *what, const void *rows, int64_t n, int64_t width, int64_t stride, int dtype, int64_t *word, Pass &&pass) {
-  const size_t es = row_element_bytes(dtype), row_bytes = size_t(width) * es;
-  const size_t rows_bytes = word ? (size_t(n) * row_bytes + 7) & ~size_t(7) : size_t(n) * row_bytes;
-  char *d = nullptr;
-  HIP_TRY(hipMalloc(&d, rows_bytes + (word ? 8 : 0)));
-  int64_t *d_word = word ? reinterpret_cast<int64_t *>(d + rows_bytes) : nullptr;
-  int rc = SHC_OK;
-  hipError_t err = hipMemcpy2DAsync(d, row_bytes, rows, size_t(stride) * es, row_bytes, size_t(n), hipMemcpyHostToDevice, e->stream);
-  if (err == hipSuccess && word) err = hipMemsetAsync(d_word, 0, 8, e->stream);
-  if (err == hipSuccess) rc = pass(d, d_word);
-  if (err == hipSuccess && rc == SHC_OK && word) err = hipMemcpyAsync(word, d_word, 8, hipMemcpyDeviceToHost, e->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  (void)hipFree(d);
-  if (err != hipSuccess) return fail(SHC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(err));
-  return rc;
+static int rows_from_host(shc_engine *e, const void *rows, int64_t n, int64_t width, int64_t stride, int dtype, int64_t *word, Pass &&pass) {
+  const size_t es = row_element_bytes(dtype);
+  HostCall hc(e);
+  const char *d = hc.in2d(rows, size_t(width) * es, size_t(stride) * es, size_t(n));
+  int64_t *d_word = hc.out(word, 1, 0);
+  int rc = hc.status();
+  if (rc != SHC_OK) return rc;
+  if (word) HIP_TRY(hipMemsetAsync(d_word, 0, 8, e->stream));
+  if ((rc = pass(d, d_word)) != SHC_OK) return rc;
+  return hc.finish();
 }
 // Dense device rows out: pass(rows) on the engine's stream, then the columns [0, width) of every row of the caller's array, and a wait
 template <class Pass>
-static int rows_to_host(shc_engine *e, const char *what, void *rows, int64_t n, int64_t width, int64_t stride, int dtype, Pass &&pass) {
-  const size_t es = row_element_bytes(dtype), row_bytes = size_t(width) * es;
-  void *d = nullptr;
-  HIP_TRY(hipMalloc(&d, size_t(n) * row_bytes));
-  const int rc = pass(d);
-  hipError_t err = hipSuccess;
-  if (rc == SHC_OK) err = hipMemcpy2DAsync(rows, size_t(stride) * es, d, row_bytes, row_bytes, size_t(n), hipMemcpyDeviceToHost, e->stream);
-  if (rc == SHC_OK && err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  (void)hipFree(d);
-  if (rc != SHC_OK) return rc;
-  if (err != hipSuccess) return fail(SHC_ERR_HIP, std::string(what) + ": " + hipGetErrorString(err));
-  return SHC_OK;
+static int rows_to_host(shc_engine *e, void *rows, int64_t n, int64_t width, int64_t stride, int dtype, Pass &&pass) {
+  const size_t es = row_element_bytes(dtype);
+  HostCall hc(e);
+  char *d = hc.out2d(rows, size_t(width) * es, size_t(stride) * es, size_t(n));
+  int rc = hc.status();
+  if (rc != SHC_OK || (rc = pass(d)) != SHC_OK) return rc;
+  return hc.finish();
 }

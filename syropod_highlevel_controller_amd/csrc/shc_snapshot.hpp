@@ -246,25 +246,17 @@ static int state_transfer(shc_engine *e, int64_t first, int64_t count, shc_insta
   unsigned long_legs = 0;
   for (int l = 0; l < e->L; ++l) long_legs |= e->params.leg_dof[l] > 3 ? 1u << l : 0u;
   HIP_TRY(hipSetDevice(e->device));
-  shc_instance_state *d = nullptr;
-  const size_t bytes = size_t(count) * sizeof(shc_instance_state);
-  HIP_TRY(hipMalloc(&d, bytes));
-  hipError_t err = hipSuccess;
+  HostCall hc(e);
+  const shc_instance_state *d_in = hc.in(in, size_t(count), 0);
+  shc_instance_state *d_out = hc.out(out, size_t(count), 0);
+  if (const int rc = hc.status()) return rc;
   const dim3 grid((unsigned)((count + 63) / 64)), block(64);
-  if (in) err = hipMemcpyAsync(d, in, bytes, hipMemcpyHostToDevice, e->stream);
-  if (err == hipSuccess) {
-    dispatch_nj(e->NJ, [&](auto nj) {
-      constexpr int NJ_ = decltype(nj)::value;
-      if (in) set_state_kernel<NJ_><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, long_legs);
-      else get_state_kernel<NJ_><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, touchdown, long_legs);
-    });
-    err = hipGetLastError();
-  }
-  if (err == hipSuccess && out) err = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, e->stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
-  (void)hipFree(d);
-  if (err != hipSuccess) return fail(SHC_ERR_HIP, std::string("state transfer: ") + hipGetErrorString(err));
-  return SHC_OK;
+  dispatch_nj(e->NJ, [&](auto nj) {
+    constexpr int NJ_ = decltype(nj)::value;
+    if (in) set_state_kernel<NJ_><<<grid, block, 0, e->stream>>>(d_in, e->st, cp, e->L, first, count, long_legs);
+    else get_state_kernel<NJ_><<<grid, block, 0, e->stream>>>(d_out, e->st, cp, e->L, first, count, touchdown, long_legs);
+  });
+  return hc.finish();
 }
 extern "C" int shc_engine_get_state(shc_engine *e, int64_t first, int64_t count, shc_instance_state *states) {
   SHC_ENTER_JOINED(e);
@@ -385,17 +377,14 @@ static int aux_state(shc_engine *e, int64_t first, int64_t count, void *blobs, i
     if (first == 0 && count == e->n) e->plan_poser_tips_current = (want & 8) != 0;
     else e->plan_poser_tips_current = e->plan_poser_tips_current && (want & 8) != 0;
   }
-  unsigned char *d = nullptr;
-  HIP_TRY(hipMalloc(&d, stride * size_t(count)));
-  if (to_engine) HIP_TRY_OR(hipMemcpyAsync(d, blobs, stride * size_t(count), hipMemcpyHostToDevice, e->stream), (void)hipFree(d));
+  HostCall hc(e);
+  unsigned char *const host = static_cast<unsigned char *>(blobs);
+  unsigned char *d = to_engine ? const_cast<unsigned char *>(hc.in(host, stride * size_t(count), 0)) : hc.out(host, stride * size_t(count), 0);
+  if (const int rc = hc.status()) return rc;
   const uint32_t live = aux_live_flags(e);
   aux_state_kernel<<<dim3((unsigned)((count + 127) / 128)), dim3(128), 0, e->stream>>>(d, stride, e->st, e->d_seq, e->L, e->NJ, LEG_FIELD(e, DES_TIP), e->n_leg_fields,
                                                                                    first, count, to_engine, live, LEG_FIELD(e, POSER_TIP));
-  HIP_TRY_OR(hipGetLastError(), (void)hipFree(d));
-  if (!to_engine) HIP_TRY_OR(hipMemcpyAsync(blobs, d, stride * size_t(count), hipMemcpyDeviceToHost, e->stream), (void)hipFree(d));
-  HIP_TRY_OR(hipStreamSynchronize(e->stream), (void)hipFree(d));
-  (void)hipFree(d);
-  return SHC_OK;
+  return hc.finish();
 }
 extern "C" int shc_engine_get_aux_state(shc_engine *e, int64_t first, int64_t count, void *blobs) {
   SHC_ENTER_JOINED(e);
