@@ -4,7 +4,7 @@ Hexapods with config 3's parameter set (wave gait, admittance, IMU posing) after
   (b) the bytes it must move (state planes read + n x legs x 512 B written) over (a), as a fraction of the plane-copy rate that
       shc_debug_plane_copy reaches in this process;
   (c) the per-instance route over --per-instance instances, scaled linearly to n (an extrapolation: each call is independent and
-      synchronous - its own derive pass over the batch, one-block kernel, copy and stream synchronisation - so n calls cost n times one).
+      synchronous - its own derive pass over the batch, the batched pass with count = 1, copy and stream synchronisation - so n calls cost n times one).
 Usage: python scripts/leg_state_msgs_bench.py [--out profiles/bench/leg_state_msgs.json]"""
 import argparse
 import json

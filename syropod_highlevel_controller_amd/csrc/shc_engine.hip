@@ -142,45 +142,6 @@ __global__ void gather_odometry_kernel(double *dst, const double *robd, int rpw,
   o[5] = 0.0;
   o[6] = robd[rob_index(r, RobotFields::ODOM + 3, rpw, nf)];
 }
-// everything publishLegState needs of one instance, packed per leg: tip(3) targ(3) poser(3) model(3) q(NJ) qd(NJ) tf(3)
-// adm(3) stiff word effort(NJ) measured q(NJ) | then vx vy w, robot word, poser latches, pose phase, IMU orientation (4)
-template <int NJ>
-__global__ void read_instance_kernel(double *dst, DevState st, int L, int64_t rob, int have_adm) {
-  using FD = Fields<NJ>;
-  using R = RobotFields;
-  const int leg = threadIdx.x;
-  constexpr int per_leg = 12 + 4 * NJ + 8;
-  if (leg < L) {
-    const int64_t slot = slot_of(rob, leg, L);
-    auto f = [&](int field) { return st.legd[leg_field_index(field, slot, st.n_slots)]; };
-    double *o = dst + leg * per_leg;
-    for (int k = 0; k < 3; ++k) {
-      o[k] = f(FD::TIP + k);
-      o[3 + k] = f(FD::TARG + k);
-      o[6 + k] = f(FD::POSER_TIP + k);
-      o[9 + k] = f(FD::MODEL_TIP + k);
-      o[12 + 2 * NJ + k] = f(FD::TF + k);
-      o[15 + 2 * NJ + k] = have_adm ? f(FD::ADM_DELTA + k) : 0.0;
-    }
-    for (int j = 0; j < NJ; ++j) {
-      o[12 + j] = f(FD::Q + j);
-      o[12 + NJ + j] = f(FD::QD + j);
-      o[20 + 2 * NJ + j] = f(FD::EFFORT_IN + j);
-      o[20 + 3 * NJ + j] = f(FD::MEAS_Q + j);
-    }
-    o[18 + 2 * NJ] = have_adm ? f(FD::ADM_DELTA + 3) : 0.0;
-    o[19 + 2 * NJ] = double(st.legi[slot]);
-  }
-  if (leg == 0) {
-    const int rpw = 64 / L;
-    double *o = dst + L * per_leg;
-    for (int k = 0; k < 3; ++k) o[k] = st.robd[rob_index(rob, R::VLIN + k, rpw, R::COUNT)];
-    o[3] = double(st.robi[rob_index(rob, R::I_WORD, rpw, R::I_COUNT)]);
-    o[4] = double(st.robi[rob_index(rob, R::I_APOSER, rpw, R::I_COUNT)]);
-    o[5] = double(st.robi[rob_index(rob, R::I_POSE_PHASE, rpw, R::I_COUNT)]);
-    for (int k = 0; k < 4; ++k) o[6 + k] = st.robd[rob_index(rob, R::IMUQ + k, rpw, R::COUNT)];
-  }
-}
 // leg_status of shc_engine_get_leg_state from the leg word: bits 0-1 the step state, bit 2 the IK failure, the phase from bit 8
 __device__ __forceinline__ int leg_status_of(int w) {
   int phase = (w >> LW_PHASE_SHIFT) & LW_PHASE_MASK;
@@ -1556,81 +1517,13 @@ static int derive_tips(shc_engine *e) {
 }
 
 #include "shc_rows.hpp"     // the row pattern of the passes below: block geometry, LDS tile and mover, resolved specs, launch sizes, host forms
-#include "shc_leg_msgs.hpp" // the derived LegState fields (one host + device implementation) and shc_engine_get_leg_state_msgs
+#include "shc_leg_msgs.hpp" // the derived LegState fields (one device implementation), shc_engine_get_leg_state_msgs and, through it, shc_engine_read_leg_state_msg
 #include "shc_frames.hpp"   // publishFrameTransforms: every joint / tip frame and the body frames, shc_engine_get_frame_transforms
 #include "shc_health.hpp"   // the reference's IK / clamping warnings per robot, a restore map and the selected robots: shc_engine_scan_health
 #include "shc_observe.hpp"  // chosen fields of every robot as one dense [rows][D] array: shc_engine_get_observations
 #include "shc_actions.hpp"  // chosen input groups of every robot from one dense [n][A] array: shc_engine_set_actions
 #include "shc_rollout.hpp"  // K cycles per launch from one dense [K][n][A] array, their joints as one dense [cycles][n][D] array: shc_engine_step_k_actions / _get_step_k_observations
 #include "shc_rollout_kin.hpp" // what is a pure function of that ring, per cycle: foot tips = FK(q) and the joint-limit health records: shc_engine_get_step_k_kinematics / _scan_step_k_health
-
-template <int NJ>
-static Pose host_fk_tip_pose(const shc_params &p, int leg, const double *q) {
-  LegConst<NJ> lc;
-  hostinit::fill_leg_const<NJ>(p, leg, lc);
-  double qq[NJ];
-  for (int j = 0; j < NJ; ++j) qq[j] = q[j];
-  return fk_tip_pose<NJ>(lc, qq);
-}
-
-extern "C" int shc_engine_read_leg_state_msg(shc_engine *e, int64_t instance, shc_leg_state_msg *legs) {
-  SHC_ENTER_JOINED(e);
-  if (!legs) return fail(SHC_ERR_INVALID_ARG, "legs is NULL");
-  if (instance < 0 || instance >= e->n) return fail(SHC_ERR_INVALID_ARG, "instance out of range");
-  int rc = derive_tips(e);
-  if (rc != SHC_OK) return rc;
-  const int L = e->L, NJ = e->NJ, per_leg = 12 + 4 * NJ + 8;
-  std::vector<double> h(size_t(L) * per_leg + 10);
-  {
-    HostCall hc(e);
-    double *d = hc.out(h.data(), h.size(), 0);
-    if ((rc = hc.status()) != SHC_OK) return rc;
-    dispatch_nj(NJ, [&](auto nj) { read_instance_kernel<decltype(nj)::value><<<dim3(1), dim3(64), 0, e->stream>>>(d, e->st, L, instance, e->params.admittance_control); });
-    if ((rc = hc.finish()) != SHC_OK) return rc;
-  }
-  const double *rb = &h[size_t(L) * per_leg];
-  const double vx = rb[0], vy = rb[1], vw = rb[2];
-  const LegMsgArgs args = leg_msg_args(e->params, e->tables); // (shc_leg_msgs.hpp: the arithmetic the batched kernel runs)
-  // PoseController::auto_pose_ of the last cycle (auto posing runs only where IMU posing does not, pose_controller.cpp:836-846)
-  const bool auto_live = args.auto_live != 0;
-  const int master_phase = leg_msg_master_phase(args, int(rb[5])); // the counter has advanced
-  const Pose auto_pose = auto_live ? leg_msg_auto_pose(args, master_phase, int(rb[4]), Quat{rb[6], rb[7], rb[8], rb[9]}) : pose_identity();
-  for (int l = 0; l < L; ++l) {
-    const double *o = &h[size_t(l) * per_leg];
-    shc_leg_state_msg &m = legs[l];
-    memset(&m, 0, sizeof m);
-    for (int k = 0; k < 3; ++k) {
-      m.walker_tip_position[k] = o[k];
-      m.target_tip_position[k] = o[3 + k];
-      m.poser_tip_position[k] = o[6 + k];
-      m.model_tip_position[k] = o[9 + k];
-      m.tip_force[k] = o[12 + 2 * NJ + k] * e->params.force_gain;
-      m.admittance_delta[k] = o[15 + 2 * NJ + k];
-    }
-    for (int j = 0; j < NJ; ++j) {
-      m.joint_positions[j] = o[12 + j];
-      m.joint_velocities[j] = o[12 + NJ + j];
-      m.joint_efforts[j] = o[20 + 2 * NJ + j]; // desired_effort_ = current_effort_ (state_controller.cpp:1590)
-    }
-    { // actual_tip_pose: Leg::applyFK(false, true) on the measured joint positions (:839)
-      const double *qm = &o[20 + 3 * NJ];
-      const Pose tp = dispatch_nj(NJ, [&](auto nj) { return host_fk_tip_pose<decltype(nj)::value>(e->params, l, qm); });
-      m.actual_tip_pose[0] = tp.p.x, m.actual_tip_pose[1] = tp.p.y, m.actual_tip_pose[2] = tp.p.z;
-      m.actual_tip_pose[3] = tp.r.w, m.actual_tip_pose[4] = tp.r.x, m.actual_tip_pose[5] = tp.r.y, m.actual_tip_pose[6] = tp.r.z;
-    }
-    m.virtual_stiffness = o[18 + 2 * NJ];
-    // LegStepper::swing_progress_ / stance_progress_ as iteratePhase left them, time_to_swing_end :866-873, calculateOdometry :875
-    const int word = int(o[19 + 2 * NJ]);
-    const LegMsgProgress pr = leg_msg_progress(args, word, vx, vy, vw);
-    m.stance_progress = pr.stance_progress, m.swing_progress = pr.swing_progress, m.time_to_swing_end = pr.time_to_swing_end;
-    for (int k = 0; k < 7; ++k) m.pose_delta[k] = pr.pose_delta[k];
-    // (model_tip_velocity stays 0: see the header.)  LegPoser::auto_pose_ :877-880
-    const Pose la = auto_live ? leg_msg_leg_auto_pose(args, l, master_phase, (word & LW_NEG) != 0, auto_pose) : pose_identity();
-    m.auto_pose[0] = la.p.x, m.auto_pose[1] = la.p.y, m.auto_pose[2] = la.p.z;
-    m.auto_pose[3] = la.r.w, m.auto_pose[4] = la.r.x, m.auto_pose[5] = la.r.y, m.auto_pose[6] = la.r.z;
-  }
-  return SHC_OK;
-}
 
 // ---- the other messages of the path (include/shc_batch.h)
 // raw motor positions - Joint::offset_ -> measured joint positions (jointStatesCallback, state_controller.cpp:1581)

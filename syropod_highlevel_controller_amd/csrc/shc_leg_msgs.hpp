@@ -1,14 +1,15 @@
 // shc_leg_msgs.hpp — StateController::publishLegState (state_controller.cpp:809-893) for a range of instances in one device pass:
-// shc_engine_get_leg_state_msgs.  Included by shc_engine.hip (uses its slot_of / rob_index / derive_tips and entry-point macros).
+// shc_engine_get_leg_state_msgs, and for one robot through the same pass: shc_engine_read_leg_state_msg.  Included by shc_engine.hip (uses its
+// slot_of / rob_index / derive_tips and entry-point macros).
 //
 // The derived fields of the payload (swing / stance progress, time_to_swing_end, pose_delta, LegPoser::auto_pose_) are functions of the
-// stored state and of a few launch-uniform parameters; LegMsgArgs carries those parameters, and the functions below are the ONE
-// implementation of that arithmetic - the per-instance host path (shc_engine_read_leg_state_msg) and leg_state_msgs_kernel both call them.
+// stored state and of a few launch-uniform parameters; LegMsgArgs carries those parameters, and the device functions below are the ONE
+// implementation of that arithmetic - leg_state_msgs_kernel and the observation rows (shc_observe.hpp) call them; nothing is recomputed on the host.
 #pragma once
 
 #include <cstddef>
 
-// Launch-uniform inputs of the derived LegState fields: a kernel argument of leg_state_msgs_kernel, a local of the per-instance call.
+// Launch-uniform inputs of the derived LegState fields: a kernel argument of leg_state_msgs_kernel and observe_kernel.
 struct LegMsgArgs {
   double swing_time, stance_time; // (swing / stance period / period) / frequency (state_controller.cpp:863-864)
   double force_gain;
@@ -52,13 +53,13 @@ static LegMsgArgs leg_msg_args(const shc_params &p, const shc_tables &t) {
 }
 
 // The master phase of the cycle the stored poser latches belong to
-SHC_HD int leg_msg_master_phase(const LegMsgArgs &a, int pose_phase) {
+__device__ __forceinline__ int leg_msg_master_phase(const LegMsgArgs &a, int pose_phase) {
   return (a.auto_live && a.pose_clock_ahead) ? mod_i(pose_phase - 1, a.pose_phase_length) : pose_phase;
 }
 
 // PoseController::auto_pose_ of the cycle whose master phase and (post-update) poser latches are given: the sum the cycle
 // kernel forms (AutoPoser::updatePose, pose_controller.cpp:1338-1439), re-derived for LegState.auto_pose.
-SHC_HD Pose leg_msg_auto_pose(const LegMsgArgs &a, int master_phase, int flags, Quat imu) {
+__device__ __forceinline__ Pose leg_msg_auto_pose(const LegMsgArgs &a, int master_phase, int flags, Quat imu) {
   Pose auto_pose = pose_identity();
   const int len = a.pose_phase_length;
   for (int i = 0; i < a.n_auto_posers; ++i) {
@@ -91,7 +92,7 @@ SHC_HD Pose leg_msg_auto_pose(const LegMsgArgs &a, int master_phase, int flags, 
   return auto_pose;
 }
 // LegPoser::updateAutoPose's negation (pose_controller.cpp:1740-1776) for a leg whose negate flag is set
-SHC_HD Pose leg_msg_leg_auto_pose(const LegMsgArgs &a, int leg, int master_phase, bool negate, const Pose &auto_pose) {
+__device__ __forceinline__ Pose leg_msg_leg_auto_pose(const LegMsgArgs &a, int leg, int master_phase, bool negate, const Pose &auto_pose) {
   if (!negate) return auto_pose;
   const int len = a.pose_phase_length;
   int sp = a.neg_start[leg], ep = a.neg_end[leg], np = master_phase;
@@ -110,24 +111,29 @@ SHC_HD Pose leg_msg_leg_auto_pose(const LegMsgArgs &a, int leg, int master_phase
   return remove_pose(auto_pose, interpolate_pose(pose_identity(), ci, auto_pose));
 }
 
-// LegStepper::swing_progress_ / stance_progress_ as iteratePhase left them (walk_controller.cpp:871-897), time_to_swing_end
-// (state_controller.cpp:866-873) and WalkController::calculateOdometry(time_to_swing_end) (walk_controller.cpp:783-791) from the leg
-// word and the desired velocity.  pose_delta: x, y, z, qw, qx, qy, qz.
+// LegStepper::swing_progress_ / stance_progress_ as iteratePhase left them (walk_controller.cpp:871-897): a function of the leg word's progress
+// mode, the phase and the step cycle the phase counts in.  The ONE place this arithmetic is written: leg_msg_progress and the state records
+// (shc_snapshot.hpp) call it, each with the step cycle it holds (Cycle: LegMsgArgs or CycleParams - the members read here carry the same names).
+template <class Cycle>
+SHC_HD void step_progress(const Cycle &c, int pm, int phase, double &swing, double &stance) {
+  swing = stance = -1.0; // walk_controller.h:498-499
+  if (pm == PM_SWING) {
+    swing = clampd(double(phase - c.swing_start + 1) / double(c.swing_end - c.swing_start), 0.0, 1.0);
+  } else if (pm == PM_STANCE) {
+    stance = clampd(double(mod_i(phase + (c.period - c.stance_start), c.period) + 1) / double(mod_i(c.stance_end - c.stance_start, c.period)), 0.0, 1.0);
+  } else if (pm == PM_STOP) {
+    stance = 0.0;
+  }
+}
+
+// ... and from them time_to_swing_end (state_controller.cpp:866-873) and WalkController::calculateOdometry(time_to_swing_end)
+// (walk_controller.cpp:783-791), from the leg word and the desired velocity.  pose_delta: x, y, z, qw, qx, qy, qz.
 struct LegMsgProgress {
   double stance_progress, swing_progress, time_to_swing_end, pose_delta[7];
 };
-SHC_HD LegMsgProgress leg_msg_progress(const LegMsgArgs &a, int word, double vx, double vy, double vw) {
+__device__ __forceinline__ LegMsgProgress leg_msg_progress(const LegMsgArgs &a, int word, double vx, double vy, double vw) {
   LegMsgProgress r;
-  const int pm = (word >> LW_PM_SHIFT) & 3, phase = (word >> LW_PHASE_SHIFT) & LW_PHASE_MASK;
-  r.swing_progress = r.stance_progress = -1.0; // walk_controller.h:498-499
-  if (pm == PM_SWING) {
-    r.swing_progress = clampd(double(phase - a.swing_start + 1) / double(a.swing_end - a.swing_start), 0.0, 1.0);
-  } else if (pm == PM_STANCE) {
-    r.stance_progress =
-        clampd(double(mod_i(phase + (a.period - a.stance_start), a.period) + 1) / double(mod_i(a.stance_end - a.stance_start, a.period)), 0.0, 1.0);
-  } else if (pm == PM_STOP) {
-    r.stance_progress = 0.0;
-  }
+  step_progress(a, (word >> LW_PM_SHIFT) & 3, (word >> LW_PHASE_SHIFT) & LW_PHASE_MASK, r.swing_progress, r.stance_progress);
   r.time_to_swing_end = r.stance_progress >= 0.0 ? a.stance_time * (1.0 - r.stance_progress) + a.swing_time : a.swing_time * (1.0 - r.swing_progress);
   const double t = r.time_to_swing_end;
   r.pose_delta[0] = vx * t;
@@ -141,7 +147,7 @@ SHC_HD LegMsgProgress leg_msg_progress(const LegMsgArgs &a, int word, double vx,
 }
 
 // LegState.tip_force: tip_force_calculated_ * force_gain (state_controller.cpp:883-885)
-SHC_HD double leg_msg_tip_force(const LegMsgArgs &a, double calculated) { return calculated * a.force_gain; }
+__device__ __forceinline__ double leg_msg_tip_force(const LegMsgArgs &a, double calculated) { return calculated * a.force_gain; }
 
 // ---- the batched form
 // Record layout in doubles (shc_leg_state_msg is 64 doubles, no padding: the kernel builds a record as double rec[64])
@@ -296,4 +302,11 @@ extern "C" int shc_engine_get_leg_state_msgs(shc_engine *e, int64_t first, int64
     return SHC_OK;
   });
   return rc != SHC_OK ? rc : hc.finish();
+}
+// One robot's records: the pass above for [instance, instance + 1), so the bytes of the batched call
+extern "C" int shc_engine_read_leg_state_msg(shc_engine *e, int64_t instance, shc_leg_state_msg *legs) {
+  SHC_ENTER_JOINED(e);
+  if (!legs) return fail(SHC_ERR_INVALID_ARG, "legs is NULL");
+  if (instance < 0 || instance >= e->n) return fail(SHC_ERR_INVALID_ARG, "instance out of range");
+  return shc_engine_get_leg_state_msgs(e, instance, 1, legs, 0);
 }

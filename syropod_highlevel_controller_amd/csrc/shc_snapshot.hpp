@@ -2,9 +2,11 @@
 // (include/shc_batch.h), and the auxiliary state blobs.  Checkpoint / restore and state injection; not on the per-cycle path.
 //
 // The record speaks the reference's member names (LegStepper / LegPoser / WalkController / PoseController members, cited in
-// the header); the engine's packed words and direction vectors are converted here:
+// the header); the engine's packed words and direction vectors are converted here, by ONE walk over the record that both
+// directions are instances of (state_kernel<NJ, TO_ENGINE>) - a member added to the walk is read and injected alike:
 //   * swing_progress_ / stance_progress_  <->  the 2-bit "progress mode" + the phase (walk_controller.cpp:871-897 writes
-//     them from the phase alone, so the pair is a function of (mode, phase));
+//     them from the phase alone, so the pair is a function of (mode, phase): step_progress of shc_leg_msgs.hpp, which the
+//     LegState payload calls too);
 //   * the stepping legs' copies of the walk plane (LegStepper::walk_plane_) are one per robot in the engine.
 #pragma once
 
@@ -12,206 +14,157 @@
 
 namespace shc {
 
-__device__ inline void snap_put3(double *dst, V3 v) {
-  dst[0] = v.x;
-  dst[1] = v.y;
-  dst[2] = v.z;
+// ---- the members that are not straight copies of plane fields: a pack (record -> engine) and an unpack (engine -> record) each
+
+// the robot word
+__device__ __forceinline__ int snap_pack_robot_word(const shc_instance_state &o) {
+  return (o.walk_state & 3) | ((o.legs_at_correct_phase & 15) << RW_LACP_SHIFT) | ((o.legs_completed_first_step & 15) << RW_LCFS_SHIFT) |
+         (o.return_to_default_attempted ? RW_RTDA : 0) | ((o.auto_posing_state & 3) << RW_APS_SHIFT);
+}
+__device__ __forceinline__ void snap_unpack_robot_word(int w, shc_instance_state &o) {
+  o.walk_state = w & 3;
+  o.legs_at_correct_phase = (w >> RW_LACP_SHIFT) & 15;
+  o.legs_completed_first_step = (w >> RW_LCFS_SHIFT) & 15;
+  o.return_to_default_attempted = (w & RW_RTDA) ? 1 : 0;
+  o.auto_posing_state = (w >> RW_APS_SHIFT) & 3;
+}
+// odometry_ideal_ is stored as (x, y, qw, qz), pure yaw: the pack ignores slots 2, 4 and 5 of the 7-double pose, the unpack writes zeros there
+__device__ __forceinline__ void snap_pack_odometry(const double (&pose)[7], double (&s)[4]) { s[0] = pose[0], s[1] = pose[1], s[2] = pose[3], s[3] = pose[6]; }
+__device__ __forceinline__ void snap_unpack_odometry(const double (&s)[4], double (&pose)[7]) {
+  pose[0] = s[0], pose[1] = s[1], pose[2] = 0.0, pose[3] = s[2], pose[4] = 0.0, pose[5] = 0.0, pose[6] = s[3];
+}
+// the leg word; pm: its progress mode (below).  The pack builds the whole word.  rotations: this leg's tip rotations are tracked - only then
+// do the two rotation bits travel, in either direction
+__device__ __forceinline__ int snap_pack_leg_word(const shc_leg_snapshot &g, int pm, bool rotations) {
+  return (g.step_state & 3) | (g.at_correct_phase ? LW_ACP : 0) | (g.completed_first_step ? LW_CFS : 0) | (pm << LW_PM_SHIFT) |
+         (g.negate_auto_pose ? LW_NEG : 0) | (g.ik_failed ? LW_IKFAIL : 0) | ((g.phase & LW_PHASE_MASK) << LW_PHASE_SHIFT) |
+         (rotations && g.tip_rotation_defined ? LW_ROTDEF : 0) | (rotations && g.target_rotation_defined ? LW_TARGROT : 0);
+}
+__device__ __forceinline__ void snap_unpack_leg_word(int w, shc_leg_snapshot &g, bool rotations) {
+  g.step_state = w & 3;
+  g.phase = (w >> LW_PHASE_SHIFT) & LW_PHASE_MASK;
+  g.at_correct_phase = (w & LW_ACP) ? 1 : 0;
+  g.completed_first_step = (w & LW_CFS) ? 1 : 0;
+  g.negate_auto_pose = (w & LW_NEG) ? 1 : 0;
+  g.ik_failed = (w & LW_IKFAIL) ? 1 : 0;
+  if (rotations) {
+    g.tip_rotation_defined = (w & LW_ROTDEF) ? 1 : 0;
+    g.target_rotation_defined = (w & LW_TARGROT) ? 1 : 0;
+  }
+}
+// the progress mode of (swing_progress, stance_progress); its unpack is step_progress (shc_leg_msgs.hpp: LegStepper::iteratePhase)
+__device__ __forceinline__ int snap_pack_progress_mode(double swing, double stance) {
+  return swing >= 0.0 ? PM_SWING : stance > 0.0 ? PM_STANCE : stance == 0.0 ? PM_STOP : PM_NONE;
+}
+// the step plane (x, y, z, defined flag).  The pack writes position-or-zeros and the flag 1.0 / 0.0 whatever rough_terrain says; the unpack
+// calls the plane defined only in rough terrain mode with a non-zero flag, and copies the position only then
+__device__ __forceinline__ void snap_pack_step_plane(const shc_leg_snapshot &g, double (&s)[4]) {
+  for (int k = 0; k < 3; ++k) s[k] = g.step_plane_defined ? g.step_plane_position[k] : 0.0;
+  s[3] = g.step_plane_defined ? 1.0 : 0.0;
+}
+__device__ __forceinline__ void snap_unpack_step_plane(const double (&s)[4], bool rough_terrain, shc_leg_snapshot &g) {
+  g.step_plane_defined = (rough_terrain && s[3] != 0.0) ? 1 : 0;
+  if (g.step_plane_defined)
+    for (int k = 0; k < 3; ++k) g.step_plane_position[k] = s[k];
 }
 
-template <int NJ>
-__global__ void get_state_kernel(shc_instance_state *out, DevState st, CycleParams P, int L, int64_t first, int64_t count, int touchdown, unsigned long_legs) {
-  // long_legs: bit l = leg l has more than 3 joints (its stepper tracks a tip rotation under gravity_aligned_tips / rough terrain mode; a shorter
-  // leg of the same robot, padded up to the kernel's joint count, does not - its record fields stay zero, as for a robot of 3-joint legs)
+// ---- the one walk over a record: every (record member, plane field) pair is named once; TO_ENGINE picks the direction (set_state : get_state).
+// touchdown: RT_TOUCHDOWN, for the records read (the host side of state_transfer raises it from the records injected).
+// long_legs: bit l = leg l has more than 3 joints (its stepper tracks a tip rotation under gravity_aligned_tips / rough terrain mode; a shorter
+// leg of the same robot, padded up to the kernel's joint count, does not: its record fields stay zero, as for a robot of 3-joint legs, and an
+// injected record leaves its direction planes alone, so that get_state -> set_state is the identity on every leg).
+template <int NJ, bool TO_ENGINE>
+__global__ void state_kernel(shc_instance_state *recs, DevState st, CycleParams P, int L, int64_t first, int64_t count, int touchdown, unsigned long_legs) {
   using FD = Fields<NJ>;
   using R = RobotFields;
   const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (t >= count) return;
   const int64_t rob = first + t;
   const int rpw = 64 / L;
-  shc_instance_state &o = out[t];
-  auto rd = [&](int f) { return st.robd[rob_index(rob, f, rpw, R::COUNT)]; };
-  auto ri = [&](int f) { return st.robi[rob_index(rob, f, rpw, R::I_COUNT)]; };
-  o.desired_linear_velocity[0] = rd(R::VLIN);
-  o.desired_linear_velocity[1] = rd(R::VLIN + 1);
-  o.desired_angular_velocity = rd(R::VANG);
-  for (int k = 0; k < 3; ++k) {
-    o.walk_plane[k] = rd(R::PLANE + k);
-    o.walk_plane_normal[k] = rd(R::PNORM + k);
-    o.stepper_walk_plane[k] = rd(R::PLANE_PREV + k);
-    o.stepper_walk_plane_normal[k] = rd(R::PNORM_PREV + k);
-    o.translation_velocity_input[k] = rd(R::TVI + k);
-    o.rotation_velocity_input[k] = rd(R::RVI + k);
-    o.rotation_absement_error[k] = rd(R::ABSE + k);
-    o.rotation_velocity_error[k] = rd(R::VERR + k);
+  shc_instance_state &o = recs[t];
+  auto move = [](auto &plane, auto &member) {
+    if constexpr (TO_ENGINE) plane = member;
+    else member = plane;
+  };
+  auto rd = [&](int f) -> double & { return st.robd[rob_index(rob, f, rpw, R::COUNT)]; };
+  auto ri = [&](int f) -> int32_t & { return st.robi[rob_index(rob, f, rpw, R::I_COUNT)]; };
+  auto robot = [&](int f0, double *member, int n) { // n consecutive robot fields from f0
+    for (int k = 0; k < n; ++k) move(rd(f0 + k), member[k]);
+  };
+  robot(R::VLIN, o.desired_linear_velocity, 2);
+  robot(R::VANG, &o.desired_angular_velocity, 1);
+  robot(R::PLANE, o.walk_plane, 3);
+  robot(R::PNORM, o.walk_plane_normal, 3);
+  robot(R::PLANE_PREV, o.stepper_walk_plane, 3);
+  robot(R::PNORM_PREV, o.stepper_walk_plane_normal, 3);
+  robot(R::TVI, o.translation_velocity_input, 3);
+  robot(R::RVI, o.rotation_velocity_input, 3);
+  robot(R::ABSE, o.rotation_absement_error, 3);
+  robot(R::VERR, o.rotation_velocity_error, 3);
+  robot(R::OWPP, o.origin_walk_plane_pose, 7);
+  robot(R::MPOSE, o.manual_pose, 7);
+  robot(R::CPOSE, o.current_pose, 7);
+  robot(R::TALIGN, o.tip_align_pose, 7);
+  robot(R::OTALIGN, o.origin_tip_align_pose, 7);
+  robot(R::APREV, o.auto_pose_rotation, 4);
+  move(ri(R::I_POSE_PHASE), o.pose_phase);
+  {
+    double s[4];
+    if constexpr (TO_ENGINE) snap_pack_odometry(o.odometry, s);
+    robot(R::ODOM, s, 4);
+    if constexpr (!TO_ENGINE) snap_unpack_odometry(s, o.odometry);
   }
-  for (int k = 0; k < 7; ++k) {
-    o.origin_walk_plane_pose[k] = rd(R::OWPP + k);
-    o.manual_pose[k] = rd(R::MPOSE + k);
-    o.current_pose[k] = rd(R::CPOSE + k);
-    o.odometry[k] = 0.0;
-    o.tip_align_pose[k] = rd(R::TALIGN + k);
-    o.origin_tip_align_pose[k] = rd(R::OTALIGN + k);
+  if constexpr (TO_ENGINE) ri(R::I_WORD) = snap_pack_robot_word(o);
+  else snap_unpack_robot_word(ri(R::I_WORD), o);
+  int latches = TO_ENGINE ? 0 : ri(R::I_APOSER); // the poser-latch word: four bits per poser
+  for (int i = 0; i < SHC_MAX_AUTO_POSERS; ++i) {
+    if constexpr (TO_ENGINE) latches |= (o.auto_poser_flags[i] & 15) << (4 * i);
+    else o.auto_poser_flags[i] = (latches >> (4 * i)) & 15;
   }
-  for (int k = 0; k < 4; ++k) o.auto_pose_rotation[k] = rd(R::APREV + k);
-  o.odometry[0] = rd(R::ODOM); // stored as (x, y, qw, qz): pure yaw
-  o.odometry[1] = rd(R::ODOM + 1);
-  o.odometry[3] = rd(R::ODOM + 2);
-  o.odometry[6] = rd(R::ODOM + 3);
-  const int rword = ri(R::I_WORD);
-  o.walk_state = rword & 3;
-  o.legs_at_correct_phase = (rword >> RW_LACP_SHIFT) & 15;
-  o.legs_completed_first_step = (rword >> RW_LCFS_SHIFT) & 15;
-  o.return_to_default_attempted = (rword & RW_RTDA) ? 1 : 0;
-  o.auto_posing_state = (rword >> RW_APS_SHIFT) & 3;
-  o.pose_phase = ri(R::I_POSE_PHASE);
-  const int ap = ri(R::I_APOSER);
-  for (int i = 0; i < SHC_MAX_AUTO_POSERS; ++i) o.auto_poser_flags[i] = (ap >> (4 * i)) & 15;
-  o.touchdown_detection = touchdown;
-  o.pad_ = 0;
+  if constexpr (TO_ENGINE) ri(R::I_APOSER) = latches;
+  if constexpr (!TO_ENGINE) o.touchdown_detection = touchdown, o.pad_ = 0; // read only: injected, the host side has looked at touchdown_detection
   for (int l = 0; l < SHC_MAX_LEGS; ++l) {
     shc_leg_snapshot &g = o.leg[l];
-    __builtin_memset(&g, 0, sizeof g);
-    if (l >= L) continue;
+    if constexpr (!TO_ENGINE) __builtin_memset(&g, 0, sizeof g); // read: what the walk does not write is zero ...
+    if (l >= L) continue;                                        // ... the legs the robot lacks whole; injected, they are skipped
     const int64_t slot = slot_of(rob, l, L);
-    auto f = [&](int field) { return st.legd[leg_field_index(field, slot, st.n_slots)]; };
-    for (int j = 0; j < NJ; ++j) {
-      g.joint_position[j] = f(FD::Q + j);
-      g.joint_velocity[j] = f(FD::QD + j);
+    auto leg = [&](int f0, double *member, int n) { // n consecutive leg fields from f0
+      for (int k = 0; k < n; ++k) move(st.legd[leg_field_index(f0 + k, slot, st.n_slots)], member[k]);
+    };
+    leg(FD::Q, g.joint_position, NJ);
+    leg(FD::QD, g.joint_velocity, NJ);
+    leg(FD::TIP, g.walker_tip, 3);
+    leg(FD::TVEL, g.walker_tip_velocity, 3);
+    leg(FD::SORG, g.swing_origin_tip, 3);
+    leg(FD::SVEL, g.swing_origin_tip_velocity, 3);
+    leg(FD::TORG, g.stance_origin_tip, 3);
+    leg(FD::DFLT, g.default_tip, 3);
+    leg(FD::TARG, g.target_tip, 3);
+    leg(FD::STRD, g.stride_vector, 3);
+    leg(FD::ADM_DELTA, g.admittance_delta, 3);
+    leg(FD::ADM_DELTA + 3, &g.virtual_stiffness, 1);
+    leg(FD::TF, g.tip_force_calculated, 3);
+    leg(FD::ADM, g.admittance_state, 2);
+    {
+      double s[4];
+      if constexpr (TO_ENGINE) snap_pack_step_plane(g, s);
+      leg(FD::STEP_PLANE, s, 4);
+      if constexpr (!TO_ENGINE) snap_unpack_step_plane(s, P.rough_terrain, g);
     }
-    for (int k = 0; k < 3; ++k) {
-      g.walker_tip[k] = f(FD::TIP + k);
-      g.walker_tip_velocity[k] = f(FD::TVEL + k);
-      g.swing_origin_tip[k] = f(FD::SORG + k);
-      g.swing_origin_tip_velocity[k] = f(FD::SVEL + k);
-      g.stance_origin_tip[k] = f(FD::TORG + k);
-      g.default_tip[k] = f(FD::DFLT + k);
-      g.target_tip[k] = f(FD::TARG + k);
-      g.stride_vector[k] = f(FD::STRD + k);
-      g.admittance_delta[k] = f(FD::ADM_DELTA + k);
-      g.tip_force_calculated[k] = f(FD::TF + k);
+    // tip rotations tracked (joint_control: a MANUAL 3-joint leg holds its FK tip rotation)
+    const bool rotations = (P.gravity_aligned && ((long_legs >> l) & 1u)) || P.joint_control == 2;
+    int32_t &w = st.legi[slot];
+    if constexpr (TO_ENGINE) {
+      w = snap_pack_leg_word(g, snap_pack_progress_mode(g.swing_progress, g.stance_progress), rotations);
+    } else {
+      snap_unpack_leg_word(w, g, rotations);
+      step_progress(P, (w >> LW_PM_SHIFT) & 3, g.phase, g.swing_progress, g.stance_progress); // (P: the step cycle the phase counts in)
     }
-    g.admittance_state[0] = f(FD::ADM);
-    g.admittance_state[1] = f(FD::ADM + 1);
-    g.virtual_stiffness = f(FD::ADM_DELTA + 3);
-    const int w = st.legi[slot];
-    g.step_state = w & 3;
-    g.phase = (w >> LW_PHASE_SHIFT) & LW_PHASE_MASK;
-    g.at_correct_phase = (w & LW_ACP) ? 1 : 0;
-    g.completed_first_step = (w & LW_CFS) ? 1 : 0;
-    g.negate_auto_pose = (w & LW_NEG) ? 1 : 0;
-    g.ik_failed = (w & LW_IKFAIL) ? 1 : 0;
-    g.step_plane_defined = (P.rough_terrain && f(FD::STEP_PLANE + 3) != 0.0) ? 1 : 0;
-    if (g.step_plane_defined)
-      for (int k = 0; k < 3; ++k) g.step_plane_position[k] = f(FD::STEP_PLANE + k);
-    // LegStepper::iteratePhase (walk_controller.cpp:871-897)
-    const int pm = (w >> LW_PM_SHIFT) & 3;
-    g.swing_progress = g.stance_progress = -1.0; // walk_controller.h:498-499
-    if (pm == PM_SWING) {
-      g.swing_progress = clampd(double(g.phase - P.swing_start + 1) / double(P.swing_end - P.swing_start), 0.0, 1.0);
-    } else if (pm == PM_STANCE) {
-      g.stance_progress = clampd(double(mod_i(g.phase + (P.period - P.stance_start), P.period) + 1) /
-                                     double(mod_i(P.stance_end - P.stance_start, P.period)),
-                                 0.0, 1.0);
-    } else if (pm == PM_STOP) {
-      g.stance_progress = 0.0;
+    if (rotations) { // an untracked leg's direction planes are never touched
+      leg(FD::ORG_DIR, g.origin_tip_direction, 3);
+      leg(FD::CUR_DIR, g.walker_tip_direction, 3);
+      if (TO_ENGINE || (w & LW_TARGROT)) leg(FD::TARG_DIR, g.target_tip_direction, 3); // read only while the target rotation is defined, written always
     }
-    if ((P.gravity_aligned && ((long_legs >> l) & 1u)) || P.joint_control == 2) { // tip rotations tracked (joint_control: a MANUAL 3-joint leg holds its FK tip rotation)
-      for (int k = 0; k < 3; ++k) {
-        g.origin_tip_direction[k] = f(FD::ORG_DIR + k);
-        g.walker_tip_direction[k] = f(FD::CUR_DIR + k);
-        g.target_tip_direction[k] = (w & LW_TARGROT) ? f(FD::TARG_DIR + k) : 0.0;
-      }
-      g.tip_rotation_defined = (w & LW_ROTDEF) ? 1 : 0;
-      g.target_rotation_defined = (w & LW_TARGROT) ? 1 : 0;
-    }
-  }
-}
-
-template <int NJ>
-__global__ void set_state_kernel(const shc_instance_state *in, DevState st, CycleParams P, int L, int64_t first, int64_t count, unsigned long_legs) {
-  // long_legs: as in get_state_kernel - a shorter leg of a gravity-aligned robot tracks no tip rotation: its direction planes and word bits stay
-  // what the engine holds (the record carries zeros for them), so that get_state -> set_state is the identity on every leg
-  using FD = Fields<NJ>;
-  using R = RobotFields;
-  const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t >= count) return;
-  const int64_t rob = first + t;
-  const int rpw = 64 / L;
-  const shc_instance_state &o = in[t];
-  auto wr = [&](int f, double v) { st.robd[rob_index(rob, f, rpw, R::COUNT)] = v; };
-  auto wi = [&](int f, int v) { st.robi[rob_index(rob, f, rpw, R::I_COUNT)] = v; };
-  wr(R::VLIN, o.desired_linear_velocity[0]);
-  wr(R::VLIN + 1, o.desired_linear_velocity[1]);
-  wr(R::VANG, o.desired_angular_velocity);
-  for (int k = 0; k < 3; ++k) {
-    wr(R::PLANE + k, o.walk_plane[k]);
-    wr(R::PNORM + k, o.walk_plane_normal[k]);
-    wr(R::PLANE_PREV + k, o.stepper_walk_plane[k]);
-    wr(R::PNORM_PREV + k, o.stepper_walk_plane_normal[k]);
-    wr(R::TVI + k, o.translation_velocity_input[k]);
-    wr(R::RVI + k, o.rotation_velocity_input[k]);
-    wr(R::ABSE + k, o.rotation_absement_error[k]);
-    wr(R::VERR + k, o.rotation_velocity_error[k]);
-  }
-  for (int k = 0; k < 7; ++k) {
-    wr(R::OWPP + k, o.origin_walk_plane_pose[k]);
-    wr(R::MPOSE + k, o.manual_pose[k]);
-    wr(R::CPOSE + k, o.current_pose[k]);
-    wr(R::TALIGN + k, o.tip_align_pose[k]);
-    wr(R::OTALIGN + k, o.origin_tip_align_pose[k]);
-  }
-  for (int k = 0; k < 4; ++k) wr(R::APREV + k, o.auto_pose_rotation[k]);
-  wr(R::ODOM, o.odometry[0]);
-  wr(R::ODOM + 1, o.odometry[1]);
-  wr(R::ODOM + 2, o.odometry[3]);
-  wr(R::ODOM + 3, o.odometry[6]);
-  wi(R::I_WORD, (o.walk_state & 3) | ((o.legs_at_correct_phase & 15) << RW_LACP_SHIFT) | ((o.legs_completed_first_step & 15) << RW_LCFS_SHIFT) |
-                    (o.return_to_default_attempted ? RW_RTDA : 0) | ((o.auto_posing_state & 3) << RW_APS_SHIFT));
-  wi(R::I_POSE_PHASE, o.pose_phase);
-  int ap = 0;
-  for (int i = 0; i < SHC_MAX_AUTO_POSERS; ++i) ap |= (o.auto_poser_flags[i] & 15) << (4 * i);
-  wi(R::I_APOSER, ap);
-  for (int l = 0; l < L; ++l) {
-    const shc_leg_snapshot &g = o.leg[l];
-    const int64_t slot = slot_of(rob, l, L);
-    auto f = [&](int field, double v) { st.legd[leg_field_index(field, slot, st.n_slots)] = v; };
-    for (int j = 0; j < NJ; ++j) {
-      f(FD::Q + j, g.joint_position[j]);
-      f(FD::QD + j, g.joint_velocity[j]);
-    }
-    for (int k = 0; k < 3; ++k) {
-      f(FD::TIP + k, g.walker_tip[k]);
-      f(FD::TVEL + k, g.walker_tip_velocity[k]);
-      f(FD::SORG + k, g.swing_origin_tip[k]);
-      f(FD::SVEL + k, g.swing_origin_tip_velocity[k]);
-      f(FD::TORG + k, g.stance_origin_tip[k]);
-      f(FD::DFLT + k, g.default_tip[k]);
-      f(FD::TARG + k, g.target_tip[k]);
-      f(FD::STRD + k, g.stride_vector[k]);
-      f(FD::ADM_DELTA + k, g.admittance_delta[k]);
-      f(FD::TF + k, g.tip_force_calculated[k]);
-    }
-    f(FD::ADM, g.admittance_state[0]);
-    f(FD::ADM + 1, g.admittance_state[1]);
-    f(FD::ADM_DELTA + 3, g.virtual_stiffness);
-    for (int k = 0; k < 3; ++k) f(FD::STEP_PLANE + k, g.step_plane_defined ? g.step_plane_position[k] : 0.0);
-    f(FD::STEP_PLANE + 3, g.step_plane_defined ? 1.0 : 0.0);
-    int pm = PM_NONE;
-    if (g.swing_progress >= 0.0) pm = PM_SWING;
-    else if (g.stance_progress > 0.0) pm = PM_STANCE;
-    else if (g.stance_progress == 0.0) pm = PM_STOP;
-    int w = (g.step_state & 3) | (g.at_correct_phase ? LW_ACP : 0) | (g.completed_first_step ? LW_CFS : 0) | (pm << LW_PM_SHIFT) |
-            (g.negate_auto_pose ? LW_NEG : 0) | (g.ik_failed ? LW_IKFAIL : 0) | ((g.phase & LW_PHASE_MASK) << LW_PHASE_SHIFT);
-    if ((P.gravity_aligned && ((long_legs >> l) & 1u)) || P.joint_control == 2) { // tip rotations tracked (joint_control: a MANUAL 3-joint leg holds its FK tip rotation)
-      for (int k = 0; k < 3; ++k) {
-        f(FD::ORG_DIR + k, g.origin_tip_direction[k]);
-        f(FD::CUR_DIR + k, g.walker_tip_direction[k]);
-        f(FD::TARG_DIR + k, g.target_tip_direction[k]);
-      }
-      if (g.tip_rotation_defined) w |= LW_ROTDEF;
-      if (g.target_rotation_defined) w |= LW_TARGROT;
-    }
-    st.legi[slot] = w;
   }
 }
 
@@ -224,7 +177,7 @@ extern "C" int64_t shc_sizeof_instance_state(void) { return (int64_t)sizeof(shc_
 // Neither direction consumes an adjustParameter that waits for its loop: a record shows the legs' phases in the period they still count in (as the
 // reference's state between the two loops), an injected record's phases are mapped onto the new period inside the accepting loop.
 static int state_transfer(shc_engine *e, int64_t first, int64_t count, shc_instance_state *out, const shc_instance_state *in) {
-    if (first < 0 || count < 0 || first + count > e->n) return fail(SHC_ERR_INVALID_ARG, "instance range out of bounds");
+  if (first < 0 || count < 0 || first + count > e->n) return fail(SHC_ERR_INVALID_ARG, "instance range out of bounds");
   if (count == 0) return SHC_OK;
   if (in) e->rt_flags |= RT_MANUAL_LIVE; // an injected state may carry any manual pose
   if (in) // touchdown detection is one flag per engine: on as soon as any injected record has it (tip-state messages arrive for a whole robot)
@@ -241,20 +194,19 @@ static int state_transfer(shc_engine *e, int64_t first, int64_t count, shc_insta
     }
   }
   const int touchdown = (e->rt_flags & RT_TOUCHDOWN) ? 1 : 0;
-  CycleParams cp = e->cp; // (get_state_kernel derives swing / stance progress from the phase: in the step cycle the phase counts in)
+  CycleParams cp = e->cp; // (a record read derives swing / stance progress from the phase: in the step cycle the phase counts in)
   set_step_cycle(cp, phase_step_cycle(e));
   unsigned long_legs = 0;
   for (int l = 0; l < e->L; ++l) long_legs |= e->params.leg_dof[l] > 3 ? 1u << l : 0u;
   HIP_TRY(hipSetDevice(e->device));
   HostCall hc(e);
-  const shc_instance_state *d_in = hc.in(in, size_t(count), 0);
-  shc_instance_state *d_out = hc.out(out, size_t(count), 0);
+  shc_instance_state *d = in ? const_cast<shc_instance_state *>(hc.in(in, size_t(count), 0)) : hc.out(out, size_t(count), 0); // (in: the staged copy)
   if (const int rc = hc.status()) return rc;
   const dim3 grid((unsigned)((count + 63) / 64)), block(64);
   dispatch_nj(e->NJ, [&](auto nj) {
     constexpr int NJ_ = decltype(nj)::value;
-    if (in) set_state_kernel<NJ_><<<grid, block, 0, e->stream>>>(d_in, e->st, cp, e->L, first, count, long_legs);
-    else get_state_kernel<NJ_><<<grid, block, 0, e->stream>>>(d_out, e->st, cp, e->L, first, count, touchdown, long_legs);
+    if (in) state_kernel<NJ_, true><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, touchdown, long_legs);
+    else state_kernel<NJ_, false><<<grid, block, 0, e->stream>>>(d, e->st, cp, e->L, first, count, touchdown, long_legs);
   });
   return hc.finish();
 }

@@ -192,15 +192,13 @@ def walking_hexapods(Engine, n, seed, cycles, with_oracle=False):
 def check_against_per_instance_call(eng, got, instances):
     for i in instances:
         one = as_records(eng.leg_state_msg(int(i)), got.dtype)
-        for name in COPIED:
+        for name in FIELDS:  # the per-instance call is the batched pass for [i, i + 1): the device's bits in every field
             assert np.array_equal(got[name][i], one[name]), (name, i)
-        for name in DERIVED:  # host and device sin / cos and contraction may differ in the last bits
-            np.testing.assert_allclose(got[name][i], one[name], rtol=0, atol=1e-12 if name == "auto_pose" else 1e-8, err_msg=f"{name} instance {i}")
 
 
 def test_agreement_with_the_existing_getters(Engine):
     """Test 4: the copied fields are the bytes of shc_engine_get_leg_state / get_joint_state / get_virtual_stiffness; against the per-instance
-    call the copied fields and the two progresses are byte-equal and the derived fields agree within the oracle tolerances."""
+    call every field is byte-equal."""
     n = 53
     p, eng = walking_hexapods(Engine, n, 91, 77)
     got = eng.leg_state_msgs()
