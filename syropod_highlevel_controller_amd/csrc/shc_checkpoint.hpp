@@ -357,7 +357,7 @@ extern "C" int shc_engine_restore_instances(shc_engine *e, const shc_checkpoint 
   }
   HIP_TRY(hipSetDevice(e->device));
   // ---- the engine-wide facts, by the rules state_transfer and aux_state apply to injected records; the values are the checkpoint's, captured on the host
-  if ((ck->live & CK_LIVE_MANUAL) && !e->st.manual && (rc = ensure_manual(e, false)) != SHC_OK) return rc; // (cannot happen on the same engine: records are never freed)
+  if ((ck->live & CK_LIVE_MANUAL) && !e->st.manual && (rc = ensure_manual(e)) != SHC_OK) return rc; // (cannot happen on the same engine: records are never freed)
   if ((ck->live & CK_LIVE_SEQ) && !e->d_seq && (rc = ensure_seq(e)) != SHC_OK) return rc;
   if ((ck->rt_flags & RT_EFFORT_LIVE) && (rc = effort_live(e)) != SHC_OK) return rc; // (already on: the flag is never taken back)
   e->rt_flags |= RT_MANUAL_LIVE | (ck->rt_flags & RT_TOUCHDOWN);

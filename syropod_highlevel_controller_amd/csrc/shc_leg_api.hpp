@@ -52,14 +52,35 @@ struct LegIO {
   }
 };
 
+// One robot's record in the robot planes (RobotFields), as LegIO is one leg's in the leg planes: L legs per robot, 64 / L robots per wavefront group.
+template <int L>
+struct RobIO {
+  using R = RobotFields;
+  const DevState &st;
+  int64_t rob;
+  __device__ __forceinline__ double get(int f) const { return st.robd[rob_index(rob, f, 64 / L, R::COUNT)]; }
+  __device__ __forceinline__ void put(int f, double v) const { st.robd[rob_index(rob, f, 64 / L, R::COUNT)] = v; }
+  __device__ __forceinline__ int geti(int f) const { return st.robi[rob_index(rob, f, 64 / L, R::I_COUNT)]; }
+  __device__ __forceinline__ void puti(int f, int v) const { st.robi[rob_index(rob, f, 64 / L, R::I_COUNT)] = v; }
+  __device__ __forceinline__ Quat quat(int f) const { return Quat{get(f), get(f + 1), get(f + 2), get(f + 3)}; }
+  __device__ __forceinline__ Pose pose(int f) const { return Pose{V3{get(f), get(f + 1), get(f + 2)}, quat(f + 3)}; } // seven doubles: position, w x y z
+  __device__ __forceinline__ void put_pose(int f, const Pose &p) const {
+    put(f, p.p.x), put(f + 1, p.p.y), put(f + 2, p.p.z);
+    put(f + 3, p.r.w), put(f + 4, p.r.x), put(f + 5, p.r.y), put(f + 6, p.r.z);
+  }
+  __device__ __forceinline__ int walk_state() const { return geti(R::I_WORD) & 3; } // enum WalkState (WS_*)
+  // "Stopping Syropod": the node forces its velocity inputs to zero
+  __device__ __forceinline__ void stop_velocity_inputs() const { put(R::VIN, 0.0), put(R::VIN + 1, 0.0), put(R::WIN, 0.0); }
+};
+
 __device__ __forceinline__ int leg_state_of(const DevState &st, int64_t rob, int leg) { // enum LegState; WALKING until a leg has ever been toggled
   return st.manual ? st.manual[rob].leg_state[leg] : LS_WALKING;
 }
 // Leg::setDesiredTipPose(tip_pose, apply_delta): tip_pose == NULL is the reference's default argument Pose::Undefined(),
 // "use the poser's tip pose" (model.cpp:657-660; POSER_TIP must have been derived, see derive_tips_kernel).
-template <int NJ>
-__device__ __forceinline__ void set_desired_dev(const DevState &st, const LegIO<NJ> &io, int L, int64_t rob, const double *pose7, int apply_delta,
-                                                int have_adm, int gravity_aligned) {
+template <int L, int NJ>
+__device__ __forceinline__ void set_desired_dev(const DevState &st, const LegIO<NJ> &io, int64_t rob, const double *pose7, int apply_delta, int have_adm,
+                                                int gravity_aligned) {
   using FD = Fields<NJ>;
   using R = RobotFields;
   V3 pos, dir{0, 0, 0};
@@ -73,9 +94,7 @@ __device__ __forceinline__ void set_desired_dev(const DevState &st, const LegIO<
   } else {
     pos = io.get3(FD::POSER_TIP);
     if (gravity_aligned && (st.legi[io.slot] & LW_ROTDEF)) { // pose.rotation^-1 * walker tip rotation (pose_controller.cpp:129-130)
-      const int rpw = 64 / L;
-      const Quat cr{st.robd[rob_index(rob, R::CPOSE + 3, rpw, R::COUNT)], st.robd[rob_index(rob, R::CPOSE + 4, rpw, R::COUNT)],
-                    st.robd[rob_index(rob, R::CPOSE + 5, rpw, R::COUNT)], st.robd[rob_index(rob, R::CPOSE + 6, rpw, R::COUNT)]};
+      const Quat cr = RobIO<L>{st, rob}.quat(R::CPOSE + 3);
       const int ls = leg_state_of(st, rob, int(io.slot & 63) % L);
       dir = io.get3(FD::CUR_DIR); // (manually manipulated legs: the stepper's tip pose as it is, :135-139)
       if (ls != LS_MANUAL && ls != LS_WALKING_TO_MANUAL) dir = rotate(inverse(cr), dir);
@@ -97,7 +116,7 @@ __global__ void leg_set_desired_kernel(DevState st, const SharedConsts<L_, NJ> *
   const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (!sel.map(t, rob, l)) return;
   const LegIO<NJ> io{st, slot_of(rob, l, sel.L)};
-  set_desired_dev<NJ>(st, io, sel.L, rob, tip_pose ? tip_pose + t * 7 : nullptr, apply_delta, have_adm, gravity_aligned);
+  set_desired_dev<L_, NJ>(st, io, rob, tip_pose ? tip_pose + t * 7 : nullptr, apply_delta, have_adm, gravity_aligned); // (sel.L is this kernel's L_)
 }
 
 template <int L_, int NJ>

@@ -740,7 +740,6 @@ static int step_k_out_ring(shc_engine *e, int K) {
 // cycles like the pose inputs), the runtime-flag families in a build without SHC_GENERIC_LOOP_FORMS - run the K cycles as the caller's loop would:
 // row k of each K-deep array through its setter (which is what a direct post is defined against: test_step_k_is_byte_identical_to_single_launches),
 // one shc_engine_step, q / qd into slot k of the output ring.  Same results, K launches instead of one.
-__global__ void copy_joint_planes_kernel(double2 *dst, const double2 *src, int64_t count);
 static int step_k_serial(shc_engine *e, int K, const shc_cycle_inputs *in) {
   const int64_t n = e->n, slot = int64_t(e->NJ) * e->n_slots; // double2 per ring slot: the planes that hold Q and QD (Fields: Q = 0, QD = NJ)
   for (int k = 0; k < K; ++k) {

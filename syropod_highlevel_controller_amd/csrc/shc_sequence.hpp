@@ -60,11 +60,7 @@ __global__ void sequence_mark_kernel(ManualRobot *manual, const SeqRobotState *s
   const bool completed = which < 2 && seq[rob].initialised && seq[rob].completed_sequence == which + 1; // (left alone: its node would have left transitionRobotState)
   manual[rob].skip_cycle = (set && !completed) ? 1 : 0;
 }
-// One StateController::loop() of the robots that stand while a leg toggle / plan step runs = posing part (:165-181), then legStateToggle /
-// executePlan.  With walk-plane + manual posing only, the loop-level kernel does both (LOOP_WHOLE).  With time-dependent posing (IMU / auto /
-// inclination) the posing part is the cycle kernel's: the loop-level kernel first only marks its robots (LOOP_MARK), the cycle kernel
-// runs PoseController::updateCurrentPose + the admittance update for them (RT_POSE_MARKED), then the loop-level kernel does the rest
-// (LOOP_AFTER_POSE).
+// The phase a loop-level kernel is launched in (the mark / pose pass / body protocol: DESIGN.md section 4.3, its host side: loop_call in shc_loop_calls.hpp)
 enum : int { LOOP_WHOLE = 0, LOOP_MARK = 1, LOOP_AFTER_POSE = 2 };
 
 template <int NJ>
@@ -75,13 +71,6 @@ __device__ __forceinline__ Pose leg_current_tip_pose(const LegIO<NJ> &io, const 
 }
 __device__ __forceinline__ void put_pose7(double *o, V3 p, Quat r) { o[0] = p.x, o[1] = p.y, o[2] = p.z, o[3] = r.w, o[4] = r.x, o[5] = r.y, o[6] = r.z; }
 __device__ __forceinline__ void put_pose7(double *o, const Pose &p) { put_pose7(o, p.p, p.r); }
-template <int L>
-__device__ __forceinline__ Pose robot_current_pose(const DevState &st, int64_t rob) { // Model::current_pose_
-  using R = RobotFields;
-  double v[7];
-  for (int k = 0; k < 7; ++k) v[k] = st.robd[rob_index(rob, R::CPOSE + k, 64 / L, R::COUNT)];
-  return Pose{V3{v[0], v[1], v[2]}, Quat{v[3], v[4], v[5], v[6]}};
-}
 __device__ __forceinline__ void seq_defaults(SeqRobotState &s) { // member initialisers (pose_controller.h:296-304)
   if (s.initialised) return;
   s.set_target = 1;
@@ -100,14 +89,10 @@ __device__ __forceinline__ void seq_defaults(SeqRobotState &s) { // member initi
 template <int L>
 __device__ __forceinline__ void standing_pose_prologue_dev(const DevState &st, int64_t rob, const bool tip_align = false) {
   using R = RobotFields;
-  constexpr int rpw = 64 / L;
-  auto rd = [&](int f) -> double & { return st.robd[rob_index(rob, f, rpw, R::COUNT)]; };
-  const Pose owpp{V3{rd(R::OWPP), rd(R::OWPP + 1), rd(R::OWPP + 2)}, Quat{rd(R::OWPP + 3), rd(R::OWPP + 4), rd(R::OWPP + 5), rd(R::OWPP + 6)}};
-  const Pose manual{V3{rd(R::MPOSE), rd(R::MPOSE + 1), rd(R::MPOSE + 2)}, Quat{rd(R::MPOSE + 3), rd(R::MPOSE + 4), rd(R::MPOSE + 5), rd(R::MPOSE + 6)}};
-  Pose cp = add_pose(owpp, manual);
-  if (tip_align) cp = add_pose(cp, Pose{V3{rd(R::TALIGN), rd(R::TALIGN + 1), rd(R::TALIGN + 2)}, Quat{rd(R::TALIGN + 3), rd(R::TALIGN + 4), rd(R::TALIGN + 5), rd(R::TALIGN + 6)}});
-  rd(R::CPOSE) = cp.p.x, rd(R::CPOSE + 1) = cp.p.y, rd(R::CPOSE + 2) = cp.p.z;
-  rd(R::CPOSE + 3) = cp.r.w, rd(R::CPOSE + 4) = cp.r.x, rd(R::CPOSE + 5) = cp.r.y, rd(R::CPOSE + 6) = cp.r.z;
+  const RobIO<L> rb{st, rob};
+  Pose cp = add_pose(rb.pose(R::OWPP), rb.pose(R::MPOSE));
+  if (tip_align) cp = add_pose(cp, rb.pose(R::TALIGN));
+  rb.put_pose(R::CPOSE, cp);
 }
 
 // AdmittanceController::updateAdmittance for one leg (admittance_controller.cpp:22-63) as the posing part of a StateController
@@ -153,6 +138,31 @@ __device__ __forceinline__ Quat leg_target_rotation(const LegConst<NJ> &lc, cons
   }
 }
 
+// The posing part of one robot's loop where the loop-level kernel runs it itself: the standing pose where the caller's loop
+// computes one (the start-up sequence runs before any control cycle has written the pose), and the admittance update of every leg.
+template <int L, int NJ>
+__device__ __forceinline__ void posing_part_dev(const DevState &st, const SharedConsts<L, NJ> *gc, int64_t rob, bool with_standing_pose) {
+  if (with_standing_pose) standing_pose_prologue_dev<L>(st, rob, gc->P.tip_align != 0);
+  for (int l = 0; l < L; ++l) admittance_prologue_dev<NJ>(LegIO<NJ>{st, slot_of(rob, l, L)}, gc->leg[l], gc->P);
+}
+
+// One leg's step of a posing loop: LegPoser::stepToPosition towards target7 (lift, duration, body pose to ease to, admittance delta or not), its result
+// into current7 (LegPoser::current_tip_pose_), then Leg::setDesiredTipPose(current7, desired_delta) and Leg::applyIK.
+struct PoseStep {
+  int progress;           // of stepToPosition
+  double limit_proximity; // of applyIK
+};
+template <int L, int NJ>
+__device__ __forceinline__ PoseStep pose_step_dev(const DevState &st, const LegIO<NJ> &io, const LegConst<NJ> &lc, int64_t rob, int leg, const SeqParams &P,
+                                                  const double *target7, const Pose &body, double lift_height, double time_to_step, int step_delta,
+                                                  int desired_delta, int gravity_aligned, double *current7) {
+  Pose tip;
+  const int progress = step_to_position_dev<NJ>(st, io, lc, target7, body, lift_height, time_to_step, step_delta, P.have_adm, P.dt, tip, leg_state_of(st, rob, leg));
+  put_pose7(current7, tip);
+  set_desired_dev<L, NJ>(st, io, rob, current7, desired_delta, P.have_adm, gravity_aligned);
+  return PoseStep{progress, apply_ik_dev<NJ>(st, io, lc, 0, P.dt, P.clamp_vel, P.clamp_pos, P.tip_force, P.force_gain)};
+}
+
 template <int L, int NJ>
 __global__ void execute_sequence_kernel(DevState st, const SharedConsts<L, NJ> *gc, SeqRobotState *seq, int sequence /* 0 START_UP, 1 SHUT_DOWN */,
                                         SeqParams P, int32_t *progress_out) {
@@ -168,10 +178,7 @@ __global__ void execute_sequence_kernel(DevState st, const SharedConsts<L, NJ> *
     return;
   }
   s.completed_sequence = 0;
-  if (!P.posed) {
-    standing_pose_prologue_dev<L>(st, rob, gc->P.tip_align != 0);
-    for (int l = 0; l < L; ++l) admittance_prologue_dev<NJ>(LegIO<NJ>{st, slot_of(rob, l, L)}, gc->leg[l], gc->P); // posing part of the loop
-  }
+  if (!P.posed) posing_part_dev<L, NJ>(st, gc, rob, true);
   const bool start_up = sequence == 0;
   // Initialise / reset any saved transition sequence (:149-162)
   if (s.reset_transition_sequence && start_up) {
@@ -206,7 +213,7 @@ __global__ void execute_sequence_kernel(DevState st, const SharedConsts<L, NJ> *
   const bool final_transition = first ? (s.horizontal_transition_complete || s.vertical_transition_complete) : (next_transition_step == transition_step_target);
   bool sequence_complete = false;
   const double safety_factor = first ? kSafetyFactor / (s.transition_step + 1) : 0.0;
-  const Pose current_pose = robot_current_pose<L>(st, rob);
+  const Pose current_pose = RobIO<L>{st, rob}.pose(RobotFields::CPOSE); // Model::current_pose_
   const Quat target_rotation{P.target_rotation[0], P.target_rotation[1], P.target_rotation[2], P.target_rotation[3]};
   const int apply_delta = (start_up && final_transition) ? 1 : 0;
   const Pose identity = pose_identity();
@@ -224,17 +231,20 @@ __global__ void execute_sequence_kernel(DevState st, const SharedConsts<L, NJ> *
     }
   };
 
-  if (execute_horizontal) {
-    if (s.set_target) {
-      s.set_target = 0;
-      for (int l = 0; l < L; ++l) {
-        const LegIO<NJ> io{st, slot_of(rob, l, L)};
-        s.leg[l].completed = 0;
-        V3 target = transition_target(l, io);
-        target.z = leg_current_tip_pose<NJ>(io, gc->leg[l]).p.z; // maintain horizontal position
-        put_pose7(s.leg[l].target, target, leg_target_rotation<NJ>(gc->leg[l], target_rotation));
-      }
+  auto set_targets = [&](bool horizontal) { // a horizontal transition keeps every tip's height, a vertical one its horizontal position (:236, :375)
+    s.set_target = 0;
+    for (int l = 0; l < L; ++l) {
+      const LegIO<NJ> io{st, slot_of(rob, l, L)};
+      V3 target = transition_target(l, io);
+      const V3 tip = leg_current_tip_pose<NJ>(io, gc->leg[l]).p;
+      if (horizontal) target.z = tip.z, s.leg[l].completed = 0;
+      else target.x = tip.x, target.y = tip.y;
+      put_pose7(s.leg[l].target, target, leg_target_rotation<NJ>(gc->leg[l], target_rotation));
     }
+  };
+
+  if (execute_horizontal) {
+    if (s.set_target) set_targets(true);
     double height = 0.0; // Model::legsBearingLoad (model.cpp:78-88)
     for (int l = 0; l < L; ++l) height += leg_current_tip_pose<NJ>(LegIO<NJ>{st, slot_of(rob, l, L)}, gc->leg[l]).p.z;
     const bool direct_step = !(-(height / L) > kHalfBodyDepth);
@@ -246,12 +256,9 @@ __global__ void execute_sequence_kernel(DevState st, const SharedConsts<L, NJ> *
         const double step_height = direct_step ? 0.0 : P.swing_height;
         double time_to_step = kHorizontalTransitionTime / P.step_frequency;
         time_to_step *= first ? 2.0 : 1.0;
-        Pose tip;
-        progress = step_to_position_dev<NJ>(st, io, gc->leg[l], g.target, identity, step_height, time_to_step, apply_delta, P.have_adm, P.dt, tip, leg_state_of(st, rob, l));
-        put_pose7(g.current, tip);
-        set_desired_dev<NJ>(st, io, L, rob, g.current, 1, P.have_adm, P.gravity_aligned);
-        const double limit_proximity = apply_ik_dev<NJ>(st, io, gc->leg[l], 0, P.dt, P.clamp_vel, P.clamp_pos, P.tip_force, P.force_gain);
-        const bool exceeded_workspace = limit_proximity < safety_factor;
+        const PoseStep step = pose_step_dev<L, NJ>(st, io, gc->leg[l], rob, l, P, g.target, identity, step_height, time_to_step, apply_delta, 1, P.gravity_aligned, g.current);
+        progress = step.progress;
+        const bool exceeded_workspace = step.limit_proximity < safety_factor;
         if (first && exceeded_workspace) { // stop the transition early (:264-270)
           for (int k = 0; k < 7; ++k) g.target[k] = g.current[k];
           io.put(FD::SEQ_DIR + 3, 0.0); // resetStepToPosition: first_iteration_ = true
@@ -286,28 +293,16 @@ __global__ void execute_sequence_kernel(DevState st, const SharedConsts<L, NJ> *
   }
 
   if (execute_vertical) {
-    if (s.set_target) {
-      s.set_target = 0;
-      for (int l = 0; l < L; ++l) {
-        const LegIO<NJ> io{st, slot_of(rob, l, L)};
-        V3 target = transition_target(l, io);
-        const V3 tip = leg_current_tip_pose<NJ>(io, gc->leg[l]).p;
-        target.x = tip.x, target.y = tip.y; // maintain horizontal position
-        put_pose7(s.leg[l].target, target, leg_target_rotation<NJ>(gc->leg[l], target_rotation));
-      }
-    }
+    if (s.set_target) set_targets(false);
     bool all_legs_within_workspace = true;
     for (int l = 0; l < L; ++l) {
       SeqLegState &g = s.leg[l];
       const LegIO<NJ> io{st, slot_of(rob, l, L)};
       double time_to_step = kVerticalTransitionTime / P.step_frequency;
       time_to_step *= first ? 2.0 : 1.0;
-      Pose tip;
-      progress = step_to_position_dev<NJ>(st, io, gc->leg[l], g.target, identity, 0.0, time_to_step, apply_delta, P.have_adm, P.dt, tip, leg_state_of(st, rob, l));
-      put_pose7(g.current, tip);
-      set_desired_dev<NJ>(st, io, L, rob, g.current, 0, P.have_adm, P.gravity_aligned);
-      const double limit_proximity = apply_ik_dev<NJ>(st, io, gc->leg[l], 0, P.dt, P.clamp_vel, P.clamp_pos, P.tip_force, P.force_gain);
-      all_legs_within_workspace = all_legs_within_workspace && !(limit_proximity < safety_factor);
+      const PoseStep step = pose_step_dev<L, NJ>(st, io, gc->leg[l], rob, l, P, g.target, identity, 0.0, time_to_step, apply_delta, 0, P.gravity_aligned, g.current);
+      progress = step.progress;
+      all_legs_within_workspace = all_legs_within_workspace && !(step.limit_proximity < safety_factor);
     }
     if ((!all_legs_within_workspace && first) || progress == 100) {
       for (int l = 0; l < L; ++l) {
@@ -353,21 +348,16 @@ __global__ void step_to_new_stance_kernel(DevState st, const SharedConsts<L, NJ>
   if (rob >= st.n_robots) return;
   SeqRobotState &s = seq[rob];
   seq_defaults(s);
-  const Pose current_pose = robot_current_pose<L>(st, rob);
+  const Pose current_pose = RobIO<L>{st, rob}.pose(RobotFields::CPOSE); // Model::current_pose_ (the control cycles before this call keep it)
   const Quat target_rotation{P.target_rotation[0], P.target_rotation[1], P.target_rotation[2], P.target_rotation[3]};
   int progress = 0;
-  if (!P.posed)
-    for (int l = 0; l < L; ++l) admittance_prologue_dev<NJ>(LegIO<NJ>{st, slot_of(rob, l, L)}, gc->leg[l], gc->P); // posing part of the loop
+  if (!P.posed) posing_part_dev<L, NJ>(st, gc, rob, false);
   for (int l = 0; l < L; ++l) {
     if ((l % 2) != s.current_group) continue;
     const LegIO<NJ> io{st, slot_of(rob, l, L)};
     double target[7];
     put_pose7(target, io.get3(FD::DFLT), leg_target_rotation<NJ>(gc->leg[l], target_rotation)); // leg_stepper->getDefaultTipPose()
-    Pose tip;
-    progress = step_to_position_dev<NJ>(st, io, gc->leg[l], target, current_pose, P.swing_height, 1.0 / P.step_frequency, 1, P.have_adm, P.dt, tip, leg_state_of(st, rob, l));
-    put_pose7(s.leg[l].current, tip);
-    set_desired_dev<NJ>(st, io, L, rob, s.leg[l].current, 1, P.have_adm, P.gravity_aligned);
-    apply_ik_dev<NJ>(st, io, gc->leg[l], 0, P.dt, P.clamp_vel, P.clamp_pos, P.tip_force, P.force_gain);
+    progress = pose_step_dev<L, NJ>(st, io, gc->leg[l], rob, l, P, target, current_pose, P.swing_height, 1.0 / P.step_frequency, 1, 1, P.gravity_aligned, s.leg[l].current).progress;
     s.legs_completed_step += (progress == 100);
   }
   progress = progress / 2 + s.current_group * 50;
@@ -397,15 +387,15 @@ __global__ void execute_plan_kernel(DevState st, const SharedConsts<L, NJ> *gc, 
   using X = ExtFields;
   const int64_t rob = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (rob >= st.n_robots) return;
-  constexpr int rpw = 64 / L;
-  const int walk_state = st.robi[rob_index(rob, R::I_WORD, rpw, R::I_COUNT)] & 3;
+  const RobIO<L> rb{st, rob};
+  const int walk_state = rb.walk_state();
   if (phase == LOOP_MARK) { // which robots run their loop here: those that stand (their posing part then runs in the cycle kernel, RT_POSE_MARKED)
     const bool standing = walk_state == WS_STOPPED;
     // LegPoser::current_tip_pose_ is what the last PoseController::updateStance left - with a pose that has moved on since.  A robot
     // whose last loop was a control cycle (this call follows cycles, or the robot was still walking in the previous plan call) gets
     // it re-derived here from Model::current_pose_ of that cycle, BEFORE the pose pass overwrites it; from then on it is state.
     if (standing && !P.poser_tip_kept && (reset_poser_tips || st.manual[rob].skip_cycle == 0)) {
-      const Pose pose_of_last_cycle = robot_current_pose<L>(st, rob);
+      const Pose pose_of_last_cycle = rb.pose(R::CPOSE);
       for (int l = 0; l < L; ++l) {
         const LegIO<NJ> io{st, slot_of(rob, l, L)};
         const int ls = leg_state_of(st, rob, l);
@@ -421,18 +411,15 @@ __global__ void execute_plan_kernel(DevState st, const SharedConsts<L, NJ> *gc, 
   if (reset_poser_tips) s.poser_tip_from_plan = 0; // control cycles ran since the last plan call: updateStance rewrote the poser tips
   int progress;
   if (walk_state != WS_STOPPED) {
-    st.robd[rob_index(rob, R::VIN, rpw, R::COUNT)] = 0.0;
-    st.robd[rob_index(rob, R::VIN + 1, rpw, R::COUNT)] = 0.0;
-    st.robd[rob_index(rob, R::WIN, rpw, R::COUNT)] = 0.0;
+    rb.stop_velocity_inputs();
     st.manual[rob].skip_cycle = 0;
     *walking_out = 1;
     progress = -1;
   } else {
     st.manual[rob].skip_cycle = 1;
-    if (phase != LOOP_AFTER_POSE) // (... unless the cycle kernel has just run it)
-      for (int l = 0; l < L; ++l) admittance_prologue_dev<NJ>(LegIO<NJ>{st, slot_of(rob, l, L)}, gc->leg[l], gc->P); // posing part of the loop
+    if (phase != LOOP_AFTER_POSE) posing_part_dev<L, NJ>(st, gc, rob, false); // (... unless the cycle kernel has just run it)
     if (!s.configuration_acquired && !s.tip_pose_acquired && !s.body_pose_acquired) {
-      const Pose current_pose = robot_current_pose<L>(st, rob);
+      const Pose current_pose = rb.pose(R::CPOSE);
       for (int l = 0; l < L; ++l) { // Model::updateModel: setDesiredTipPose() = the poser's tip pose + admittance delta, applyIK
         const LegIO<NJ> io{st, slot_of(rob, l, L)};
         double tip[7];
@@ -454,7 +441,7 @@ __global__ void execute_plan_kernel(DevState st, const SharedConsts<L, NJ> *gc, 
           else             // updateStance (pose_controller.cpp:122-131)
             put_pose7(tip, inverse_transform_vector(current_pose, io.get3(FD::TIP)), rotation);
         }
-        set_desired_dev<NJ>(st, io, L, rob, tip, 1, P.have_adm, 0);
+        set_desired_dev<L, NJ>(st, io, rob, tip, 1, P.have_adm, 0);
         apply_ik_dev<NJ>(st, io, gc->leg[l], 0, P.dt, P.clamp_vel, P.clamp_pos, P.tip_force, P.force_gain);
       }
       progress = -2;
@@ -491,10 +478,7 @@ __global__ void execute_plan_kernel(DevState st, const SharedConsts<L, NJ> *gc, 
           // "Update target rotation if gravity alignment is set" (:786-790): FromTwoVectors(UnitX, Model::estimateGravity())
           bool gravity_rotation = false;
           if (P.gravity_aligned_tips && target[3] == 0.0 && target[4] == 0.0 && target[5] == 0.0 && target[6] == 0.0) {
-            constexpr int rpw = 64 / L;
-            const Quat imu{st.robd[rob_index(rob, R::IMUQ, rpw, R::COUNT)], st.robd[rob_index(rob, R::IMUQ + 1, rpw, R::COUNT)],
-                           st.robd[rob_index(rob, R::IMUQ + 2, rpw, R::COUNT)], st.robd[rob_index(rob, R::IMUQ + 3, rpw, R::COUNT)]};
-            const V3 e = quat_to_euler(imu, false); // Model::estimateGravity (model.cpp:156-165)
+            const V3 e = quat_to_euler(rb.quat(R::IMUQ), false); // Model::estimateGravity (model.cpp:156-165)
             V3 gv{0, 0, kGravity};
             gv = rotate(angle_axis_y(-e.y), gv);
             gv = rotate(angle_axis_x(-e.x), gv);
@@ -502,11 +486,7 @@ __global__ void execute_plan_kernel(DevState st, const SharedConsts<L, NJ> *gc, 
             target[3] = r.w, target[4] = r.x, target[5] = r.y, target[6] = r.z;
             gravity_rotation = true;
           }
-          Pose tip;
-          const int p = step_to_position_dev<NJ>(st, io, gc->leg[l], (defined || gravity_rotation) ? target : nullptr, body, clearance, kPlanTransitionTime, 1, P.have_adm, P.dt, tip, leg_state_of(st, rob, l));
-          put_pose7(s.leg[l].current, tip);
-          set_desired_dev<NJ>(st, io, L, rob, s.leg[l].current, 1, P.have_adm, 0);
-          apply_ik_dev<NJ>(st, io, gc->leg[l], 0, P.dt, P.clamp_vel, P.clamp_pos, P.tip_force, P.force_gain);
+          const int p = pose_step_dev<L, NJ>(st, io, gc->leg[l], rob, l, P, (defined || gravity_rotation) ? target : nullptr, body, clearance, kPlanTransitionTime, 1, 1, 0, s.leg[l].current).progress;
           progress = p < progress ? p : progress;
           if (defined && p == 100) xf(X::P_FLAGS) = double(int(xf(X::P_FLAGS)) & ~1); // target achieved (:801-805)
         }
@@ -570,20 +550,17 @@ __global__ void leg_state_toggle_kernel(DevState st, const SharedConsts<L, NJ> *
   if (phase == LOOP_MARK && !(sel >= 0 && sel < L)) return;
   if (sel >= 0 && sel < L) {
     ManualRobot &m = st.manual[rob];
-    constexpr int rpw = 64 / L;
-    const int walk_state = st.robi[rob_index(rob, R::I_WORD, rpw, R::I_COUNT)] & 3;
+    const RobIO<L> rb{st, rob};
+    const int walk_state = rb.walk_state();
     if (walk_state == WS_STOPPED) { // the posing part of this loop (a robot that is still walking runs its whole loop in the cycle kernel)
       m.skip_cycle = 1;
       if (phase == LOOP_MARK) return;
-      if (phase != LOOP_AFTER_POSE) // (... unless the cycle kernel has just run it: RT_POSE_MARKED)
-        for (int l = 0; l < L; ++l) admittance_prologue_dev<NJ>(LegIO<NJ>{st, slot_of(rob, l, L)}, gc->leg[l], gc->P);
+      if (phase != LOOP_AFTER_POSE) posing_part_dev<L, NJ>(st, gc, rob, false); // (... unless the cycle kernel has just run it: RT_POSE_MARKED)
     }
     if (phase == LOOP_MARK) return;
     if (walk_state != WS_STOPPED) {
       result = -1; // "Stopping Syropod to transition leg state": the velocity inputs are forced to zero (:641-645)
-      st.robd[rob_index(rob, R::VIN, rpw, R::COUNT)] = 0.0;
-      st.robd[rob_index(rob, R::VIN + 1, rpw, R::COUNT)] = 0.0;
-      st.robd[rob_index(rob, R::WIN, rpw, R::COUNT)] = 0.0;
+      rb.stop_velocity_inputs();
     } else if (m.leg_state[sel] == LS_WALKING) {
       if (m.manual_leg_count < kMaxManualLegs) {
         m.leg_state[sel] = LS_WALKING_TO_MANUAL;
@@ -601,9 +578,8 @@ __global__ void leg_state_toggle_kernel(DevState st, const SharedConsts<L, NJ> *
       // poser_->setPoseResetMode(IMMEDIATE_ALL_RESET): the next pose update puts manual_pose_ on default_pose_ (identity: calculateDefaultPose
       // is never called), and with walk-plane + manual posing only Model::current_pose_ becomes the walk-plane pose of a standing robot
       // (the reset takes effect in the pose update of the NEXT loop: this call still sees the poses of the last update)
-      auto rd = [&](int f) -> double & { return st.robd[rob_index(rob, f, rpw, R::COUNT)]; };
-      Pose current_pose = robot_current_pose<L>(st, rob);
-      const V3 manual_position{rd(R::MPOSE), rd(R::MPOSE + 1), rd(R::MPOSE + 2)};
+      const Pose current_pose = rb.pose(R::CPOSE);
+      const V3 manual_position = rb.pose(R::MPOSE).p;
       // ---- poseForLegManipulation
       int min_progress = 2147483647;
       for (int l = 0; l < L; ++l) {
@@ -615,8 +591,8 @@ __global__ void leg_state_toggle_kernel(DevState st, const SharedConsts<L, NJ> *
         if (ls == LS_WALKING_TO_MANUAL) {
           target_pose = pose_identity();
           if (P.inclination_posing) { // + inclination_pose_.position_ as this loop's updateInclinationPose left it (the cycle kernel's pose pass)
-            target_pose.p.x += rd(R::INCL);
-            target_pose.p.y += rd(R::INCL + 1);
+            target_pose.p.x += rb.get(R::INCL);
+            target_pose.p.y += rb.get(R::INCL + 1);
           }
           target_pose.p.z -= step_height;
         } else {
@@ -636,13 +612,14 @@ __global__ void leg_state_toggle_kernel(DevState st, const SharedConsts<L, NJ> *
           //  next updateTipRotation recomputes it, so only a snapshot taken in between could tell.)
           st.legi[io.slot] &= ~LW_ROTDEF;
         }
+        // (not pose_step_dev: a leg whose step is complete keeps its desired tip pose and takes no IK step - setDesiredTipPose / applyIK are skipped at 100)
         Pose tip;
         const int progress = step_to_position_dev<NJ>(st, io, gc->leg[l], target, pose_identity(), step_height, step_time, 1, P.have_adm, P.dt, tip, ls);
         min_progress = progress < min_progress ? progress : min_progress;
         if (progress != 100) {
           double cur[7];
           put_pose7(cur, tip);
-          set_desired_dev<NJ>(st, io, L, rob, cur, 1, P.have_adm, P.gravity_aligned);
+          set_desired_dev<L, NJ>(st, io, rob, cur, 1, P.have_adm, P.gravity_aligned);
           apply_ik_dev<NJ>(st, io, gc->leg[l], 0, P.dt, P.clamp_vel, P.clamp_pos, P.tip_force, P.force_gain);
         }
       }
@@ -657,15 +634,15 @@ __global__ void leg_state_toggle_kernel(DevState st, const SharedConsts<L, NJ> *
         if (m.leg_state[a2] != LS_MANUAL) stiff(a2) = load;
       }
       if (phase != LOOP_AFTER_POSE) { // (with time-dependent posing the next loop's pose pass applies the reset itself)
-        for (int k = 0; k < 7; ++k) rd(R::MPOSE + k) = (k == 3) ? 1.0 : 0.0; // the next pose update: manual_pose_ = default_pose_ ...
-        for (int k = 0; k < 7; ++k) rd(R::CPOSE + k) = rd(R::OWPP + k);      // ... and current_pose_ = the standing walk-plane pose
+        rb.put_pose(R::MPOSE, pose_identity());      // the next pose update: manual_pose_ = default_pose_ ...
+        rb.put_pose(R::CPOSE, rb.pose(R::OWPP)); // ... and current_pose_ = the standing walk-plane pose
       }
-      st.robi[rob_index(rob, R::I_RESET_MODE, rpw, R::I_COUNT)] = 5; // IMMEDIATE_ALL_RESET while the transition runs
+      rb.puti(R::I_RESET_MODE, 5); // IMMEDIATE_ALL_RESET while the transition runs
       result = 0;
       if (min_progress == 100) {
         m.leg_state[sel] = to_manual ? LS_MANUAL : LS_WALKING;
         m.manual_leg_count += to_manual ? 1 : -1;
-        st.robi[rob_index(rob, R::I_RESET_MODE, rpw, R::I_COUNT)] = 0; // NO_RESET
+        rb.puti(R::I_RESET_MODE, 0); // NO_RESET
         result = 1;
       }
     }
@@ -694,6 +671,54 @@ __global__ void get_leg_manipulation_state_kernel(const ManualRobot *manual, int
   const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   if (t >= n * L) return;
   out[t] = manual ? manual[t / L].leg_state[t % L] : LS_WALKING;
+}
+
+// ---------------------------------------------------------------------------------------------------- joints set / kept by the start-ups
+// Joints of every instance to the configuration Leg::init(true) leaves (model.cpp:286-305: Joint::default_position_ =
+// clamped(0, min, max), :1038), everything else to the engine's post-start-up template.
+template <int NJ>
+__global__ void set_initial_joints_kernel(DevState st, const double *q0 /*[L][NJ]*/, int L) {
+  using FD = Fields<NJ>;
+  const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (t >= st.n_robots * L) return;
+  const int64_t rob = t / L;
+  const int leg = int(t - rob * L);
+  const int64_t slot = slot_of(rob, leg, L);
+  for (int j = 0; j < NJ; ++j) {
+    st.legd[leg_field_index(FD::Q + j, slot, st.n_slots)] = q0[leg * NJ + j];
+    st.legd[leg_field_index(FD::QD + j, slot, st.n_slots)] = 0.0;
+  }
+}
+// Leg::init(false) (model.cpp:286-305): desired = current = the reported positions (one row per leg, or per (instance, leg)), velocities 0
+__global__ void set_joint_positions_kernel(DevState st, const double *q, int per_instance, int L, int NJ, int f_q, int f_qd, int f_meas) {
+  const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (t >= st.n_robots * L) return;
+  const int64_t rob = t / L;
+  const int leg = int(t - rob * L);
+  const int64_t slot = slot_of(rob, leg, L);
+  const double *row = q + (per_instance ? t : leg) * NJ;
+  for (int j = 0; j < NJ; ++j) {
+    st.legd[leg_field_index(f_q + j, slot, st.n_slots)] = row[j];
+    st.legd[leg_field_index(f_qd + j, slot, st.n_slots)] = 0.0;
+    st.legd[leg_field_index(f_meas + j, slot, st.n_slots)] = row[j];
+  }
+}
+// finish_sequence_startup re-initialises the state around the joints the sequence ended on: a copy of the planes that hold Q / QD ...
+__global__ void copy_joint_planes_kernel(double2 *dst, const double2 *src, int64_t count) {
+  const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (t < count) dst[t] = src[t];
+}
+// ... and Q / QD of every leg slot back from it (the TIP fields sharing the last plane keep their new values)
+__global__ void restore_joints_kernel(DevState st, const double2 *saved_planes, int L, int NJ) {
+  const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (t >= st.n_robots * L) return;
+  const int64_t rob = t / L;
+  const int64_t slot = slot_of(rob, int(t - rob * L), L);
+  const double *saved = reinterpret_cast<const double *>(saved_planes);
+  for (int f = 0; f < 2 * NJ; ++f) {
+    const int64_t i = leg_field_index(f, slot, st.n_slots);
+    st.legd[i] = saved[i];
+  }
 }
 
 } // namespace shc

@@ -308,7 +308,7 @@ static int aux_state(shc_engine *e, int64_t first, int64_t count, void *blobs, i
       want |= h->flags;
     }
     int rc = SHC_OK;
-    if ((want & 1) && !e->st.manual) rc = ensure_manual(e, false);
+    if ((want & 1) && !e->st.manual) rc = ensure_manual(e);
     if (rc == SHC_OK && (want & 4) && !e->d_seq) rc = ensure_seq(e);
     double *ext_new = nullptr;
     if (rc == SHC_OK && (want & 2) && !e->st.ext) { // (allocated and cleared completely before the engine sees it: a failure leaves nothing half-grown)
