@@ -366,6 +366,40 @@ int shc_engine_resident_get_joint_state(shc_engine *e, int64_t cycle, double *q,
 int shc_engine_resident_get_joint_state_async(shc_engine *e, int64_t cycle, double *q, double *qd, int timeout_ms);
 int shc_engine_resident_status(shc_engine *e, int64_t *published, int64_t *completed, int32_t *running);
 int shc_engine_resident_end(shc_engine *e, int64_t *cycles_run);
+/*
+ * Resident tensors: the resident loop driven from the dense DEVICE arrays of the action and observation passes (shc_act_spec / shc_obs_spec,
+ * declared with those passes below) - what a policy on the GPU emits and takes per tick, without a conversion on the way.
+ * shc_engine_resident_post_actions: shc_engine_resident_post for the next unposted cycle (*cycle receives its index) from one array
+ * [n][row_stride] of float64 or float32.  The spec, row and column rules are those of shc_engine_set_actions, legs / dof at least the engine's.
+ * DEFINITION.  The loop runs the posted cycle, every later cycle and the state shc_engine_resident_end leaves byte for byte as after a
+ * shc_engine_resident_post with on_device = 1 and the same `publish`, given dense float64 arrays that hold static_cast<double> of the named
+ * columns and NULL for every group the spec does not name (those are held, like a callback that did not fire).  The IMU quaternion is
+ * normalised in double after the conversion.  Columns of legs or joints the morphology lacks and columns [width, row_stride) are ignored; a
+ * shorter leg's joints on a mixed-DOF robot get what the ordinary post stores there.  One kernel launch per call: it reads the array and stores
+ * into the loop's input rings, writes the cycle's header and - with publish - rings the doorbell; nothing is staged.  Ring positions, the
+ * back-pressure (ring_depth input sets of a group, 1 024 headers) and the rules of direct posts are the ordinary post's own.
+ * STREAMS.  `actions` must be ready on the ENGINE's stream when the call is made (the rule of shc_engine_set_actions): the input stream follows
+ * that stream before the post kernel, and the engine's stream follows the post kernel behind it, so work queued on the engine's stream after
+ * the call may overwrite the array.  No host wait but the back-pressure.  A stream-ordered read (shc_engine_resident_get_joint_state_async, the
+ * observation call below) parks the engine's stream until its cycle has run; while the highest cycle such a read was queued for is still
+ * unpublished the call is refused - publish (or post the ordinary way with publish) first.
+ * shc_engine_resident_get_observations_async: shc_engine_resident_get_joint_state_async as one array [n][row_stride]: the rules of
+ * shc_engine_get_step_k_kinematics for any subset of SHC_OBS_Q, SHC_OBS_QD, SHC_OBS_MODEL_TIP.  The q / qd columns hold what
+ * shc_engine_resident_get_joint_state returns for `cycle` - unchanged for SHC_OBS_F64, static_cast<float> for SHC_OBS_F32 -, model_tip is
+ * Leg::applyFK on the ring's own q, `pad` where the robot has no such leg or joint, columns beyond the width untouched.  On the engine's stream
+ * it queues the bounded device-side wait for `cycle` (which may still be unpublished; timeout_ms, 0 = 5 s) and ONE read kernel; nothing is
+ * written into the engine.  A wait that gave up is reported by shc_engine_resident_end.
+ * REFUSALS (decided before anything changes).  SHC_ERR_INVALID_ARG: NULL handle, spec or array; an engine not in resident mode; whatever
+ * shc_engine_set_actions / shc_engine_get_step_k_kinematics refuse of a spec; SHC_ACT_LINEAR_XY without SHC_ACT_ANGULAR, one IMU or pose field
+ * without its partner; a misaligned array; a cycle already published without inputs; a post or a `cycle` past max_cycles; a read whose slot may
+ * have been overwritten; the stream rule above.  SHC_ERR_UNSUPPORTED: pose fields or joint efforts on an engine that was not given one before
+ * shc_engine_resident_begin; an observation field outside the three.  SHC_ERR_TIMEOUT: the ordinary post's cases.
+ * No fleet form (fleets have no resident mode), no host-array form.
+ */
+struct shc_act_spec;
+struct shc_obs_spec;
+int shc_engine_resident_post_actions(shc_engine *e, const struct shc_act_spec *spec, const void *actions /* device, [n][row_stride] */, int publish, int64_t *cycle);
+int shc_engine_resident_get_observations_async(shc_engine *e, int64_t cycle, const struct shc_obs_spec *spec, void *out /* device, [n][row_stride] */, int timeout_ms);
 
 /*
  * K loop iterations in ONE launch, each with its own inputs - for batches of any size (resident mode needs the whole batch on the chip at
@@ -1206,7 +1240,7 @@ int shc_fleet_get_observations_device(shc_fleet *f, const shc_obs_spec *spec, vo
  * conversion, the touchdown flag and (rough terrain mode) touchdown detection with its step planes, the switch to the tip-force estimate at the
  * first joint effort (with its one stream synchronisation), the manual-pose flag, the entries of a shorter leg's joints on a mixed-DOF robot.
  * One half of a pair may be named alone.  Columns of legs or joints the morphology lacks and columns [width, row_stride) are ignored.  The
- * pose reset mode stays on its own setter; resident mode takes its inputs as before, the K-cycle launches theirs through
+ * pose reset mode stays on its own setter; resident mode takes such an array through shc_engine_resident_post_actions, the K-cycle launches through
  * shc_engine_step_k_actions below.
  * The fleet form is defined the same way against shc_fleet_set_inputs_device: robot r of a part reads row ids[r] - its CALLER's instance id -
  * of `actions` ([n][row_stride]) through the ids device I/O keeps on the device; one kernel per part on the part's own stream, no allocation

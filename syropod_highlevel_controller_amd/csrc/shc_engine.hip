@@ -1525,6 +1525,7 @@ static int derive_tips(shc_engine *e) {
 #include "shc_actions.hpp"  // chosen input groups of every robot from one dense [n][A] array: shc_engine_set_actions
 #include "shc_rollout.hpp"  // K cycles per launch from one dense [K][n][A] array, their joints as one dense [cycles][n][D] array: shc_engine_step_k_actions / _get_step_k_observations
 #include "shc_rollout_kin.hpp" // what is a pure function of that ring, per cycle: foot tips = FK(q) and the joint-limit health records: shc_engine_get_step_k_kinematics / _scan_step_k_health
+#include "shc_resident_rows.hpp" // the resident loop driven from one dense [n][A] array, its joints and tips as one dense [n][D] array: shc_engine_resident_post_actions / _get_observations_async
 
 // ---- the other messages of the path (include/shc_batch.h)
 // raw motor positions - Joint::offset_ -> measured joint positions (jointStatesCallback, state_controller.cpp:1581)

@@ -47,15 +47,18 @@ struct Resident {
   bool two_wave = false;                    // the two-wavefront (walker / model) pipeline is running
   bool helper_wave = false;                 // ... in its three-role form (walker / model / helper)
   long long direct_last = -1;               // cycle of the latest direct post (the doorbell only moves once the relay has released it)
+  // shc_engine_resident_post_actions (shc_resident_rows.hpp) reads a tensor that is ready on the ENGINE's stream: the input stream follows the
+  // engine's stream before the post kernel (rows_ev[0]) and the engine's stream the input stream behind it (rows_ev[1])
+  hipEvent_t rows_ev[2] = {};
+  long long read_queued = -1;               // highest cycle a stream-ordered read has been queued for on the engine's stream (it parks that stream until the cycle has run)
 };
 
 __global__ void resident_doorbell_kernel(ResidentHost *host, unsigned long long value) {
   __hip_atomic_store(&host->doorbell, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-struct ResidentPost {
-  const double *lin, *ang, *imu_q, *imu_w, *tvi, *rvi, *force, *effort;
-  const int32_t *reset;
+// Where a posted input set goes - what every post kernel is told, whatever it reads the set from
+struct ResidentPostSlot {
   int pos[RG_COUNT];
   unsigned mask;
   unsigned long long cycle;
@@ -63,15 +66,45 @@ struct ResidentPost {
   ResidentHost *host;
   unsigned *blocks_done;       // device counter of that election
 };
+struct ResidentPost : ResidentPostSlot {
+  const double *lin, *ang, *imu_q, *imu_w, *tvi, *rvi, *force, *effort;
+  const int32_t *reset;
+};
+// The write-through store of the input rings: the resident kernel reads them with agent-scope loads while it runs
+__device__ __forceinline__ void resident_put(double *p, double v) {
+  __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// The header of the posted cycle: the groups that are fresh and their ring positions (one thread of the launch)
+__device__ __forceinline__ void resident_post_header(const ResidentPostSlot &pp, ResidentHeader *headers) {
+  unsigned long long h1 = pp.mask & 0xffffu;
+  for (int gi = 0; gi < RG_COUNT; ++gi) h1 |= (unsigned long long)(pp.pos[gi] & 0xff) << (16 + 8 * gi);
+  unsigned long long *hp = reinterpret_cast<unsigned long long *>(headers + (pp.cycle & (kResidentHeaders - 1)));
+  __hip_atomic_store(hp + 1, h1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(hp, pp.cycle + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// Post + publish in one launch: release the cycle once every block's stores are out - the last block to arrive rings the doorbell (every thread
+// of the launch calls this behind its stores).
+// (No LDS here: a resident loop that fills the chip leaves none, and a kernel that asks for any would never be scheduled.)
+__device__ __forceinline__ void resident_post_doorbell(const ResidentPostSlot &pp) {
+  if (pp.doorbell == 0) return;
+  __threadfence(); // this thread's write-through stores are visible device-wide before its block is counted
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned arrived = __hip_atomic_fetch_add(pp.blocks_done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (arrived == gridDim.x - 1) {
+      __hip_atomic_store(pp.blocks_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (the next post on this stream starts from zero)
+      __threadfence_system();
+      __hip_atomic_store(&pp.host->doorbell, pp.doorbell, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
 // One posted input set -> the data rings (write-through stores: the resident kernel reads them with agent-scope loads while it
 // runs) + the header of its cycle.  The doorbell moves only after this kernel has completed (stream order).
 __global__ void resident_post_kernel(ResidentPost pp, ResidentArgs A, ResidentHeader *headers, double *rin, int32_t *rini, double *force, double *effort,
                                      int64_t n, int L, int NJ, int64_t n_slots) {
   const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   const int rpw = 64 / L;
-  auto put = [](double *p, double v) {
-    __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
+  auto put = [](double *p, double v) { resident_put(p, v); };
   if (t < n) {
     const int64_t w = t / rpw;
     const int r = int(t - w * rpw);
@@ -111,26 +144,8 @@ __global__ void resident_post_kernel(ResidentPost pp, ResidentArgs A, ResidentHe
       for (int k = 0; k < NJ; ++k) put(base + leg_field_index(k, slot, n_slots), pp.effort[t * NJ + k]);
     }
   }
-  if (t == 0) {
-    unsigned long long h1 = pp.mask & 0xffffu;
-    for (int gi = 0; gi < RG_COUNT; ++gi) h1 |= (unsigned long long)(pp.pos[gi] & 0xff) << (16 + 8 * gi);
-    unsigned long long *hp = reinterpret_cast<unsigned long long *>(headers + (pp.cycle & (kResidentHeaders - 1)));
-    __hip_atomic_store(hp + 1, h1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(hp, pp.cycle + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (pp.doorbell != 0) { // release the cycle once every block's stores are out: the last block to arrive rings the doorbell.
-    // (No LDS here: a resident loop that fills the chip leaves none, and a kernel that asks for any would never be scheduled.)
-    __threadfence(); // this thread's write-through stores are visible device-wide before its block is counted
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const unsigned arrived = __hip_atomic_fetch_add(pp.blocks_done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-      if (arrived == gridDim.x - 1) {
-        __hip_atomic_store(pp.blocks_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (the next post on this stream starts from zero)
-        __threadfence_system();
-        __hip_atomic_store(&pp.host->doorbell, pp.doorbell, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
-  }
+  if (t == 0) resident_post_header(pp, headers);
+  resident_post_doorbell(pp);
 }
 
 static void resident_free(Resident *r) {
@@ -148,6 +163,8 @@ static void resident_free(Resident *r) {
   (void)hipFree(r->post_blocks_done);
   if (r->pin) (void)hipHostFree(r->pin);
   for (hipEvent_t ev : r->pin_ev)
+    if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : r->rows_ev)
     if (ev) (void)hipEventDestroy(ev);
   if (r->in_stream) (void)hipStreamDestroy(r->in_stream);
   if (r->loop_stream) (void)hipStreamDestroy(r->loop_stream);
@@ -295,6 +312,8 @@ extern "C" int shc_engine_resident_begin(shc_engine *e, int ring_depth, int64_t 
     if ((err = hipHostGetDevicePointer(reinterpret_cast<void **>(&r->pin_dev), r->pin, 0)) != hipSuccess) return bail(err, "hipHostGetDevicePointer");
     for (hipEvent_t &ev : r->pin_ev)
       if ((err = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return bail(err, "hipEventCreate");
+    for (hipEvent_t &ev : r->rows_ev)
+      if ((err = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return bail(err, "hipEventCreate");
     for (int gi = 0; gi < RG_COUNT; ++gi) r->post_cycle[gi].assign(D, 0);
   }
   Resident *r = e->res;
@@ -311,6 +330,7 @@ extern "C" int shc_engine_resident_begin(shc_engine *e, int ring_depth, int64_t 
   __sync_synchronize();
   r->published = r->posted = 0;
   r->direct_last = -1;
+  r->read_queued = -1;
   r->groups_posted = 0;
   r->stream_doorbell_pending = false;
   for (int gi = 0; gi < RG_COUNT; ++gi) {
@@ -383,6 +403,67 @@ static int resident_alive(Resident *r) {
   return SHC_OK;
 }
 
+// The host route of a post, whatever its kernel reads the input set from (shc_engine_resident_post below: arrays in the setters' layouts;
+// shc_engine_resident_post_actions of shc_resident_rows.hpp: one dense tensor) - three steps before the launch, one behind it.
+// The header slot of cycle c last served cycle c - 1024; a ring position of group g last served post k - depth, which stays in
+// force until the cycle post k - depth + 1 was made for has been reached by every wave.
+constexpr double kResidentPostPatience = 5.0;
+// 1. May the resident groups `mask` be posted, and for which cycle c?  Waits until the header slot of c is free (1 024 headers).
+static int resident_post_admit(shc_engine *e, unsigned mask, unsigned long long &c) {
+  Resident *r = e->res;
+  if ((mask & ((1u << RG_POSE) | (1u << RG_RESET))) && !(e->rt_flags & RT_MANUAL_LIVE))
+    return fail(SHC_ERR_UNSUPPORTED, "pose inputs: give the engine one (shc_engine_set_pose_input / set_pose_reset_mode) before shc_engine_resident_begin");
+  if ((mask & (1u << RG_EFFORT)) && !(e->rt_flags & RT_EFFORT_LIVE))
+    return fail(SHC_ERR_UNSUPPORTED, "joint efforts: give the engine one (shc_engine_set_joint_effort) before shc_engine_resident_begin");
+  c = r->posted;
+  if (c < r->published) return fail(SHC_ERR_INVALID_ARG, "resident mode: this cycle has already been published without inputs");
+  if (c >= r->max_cycles) return fail(SHC_ERR_INVALID_ARG, "resident mode: past max_cycles");
+  HIP_TRY(hipSetDevice(e->device));
+  if (c >= kResidentHeaders && !spin_until([&] { return host_load(&r->host->done) > c - kResidentHeaders; }, kResidentPostPatience))
+    return fail(SHC_ERR_TIMEOUT, "resident mode: 1024 posted cycles are waiting to run");
+  return SHC_OK;
+}
+// 2. Where the set goes: the ring position of each group of `mask` - waiting while ring_depth sets of a group are still to be consumed
+static int resident_post_place(Resident *r, unsigned mask, unsigned long long c, ResidentPostSlot &pp) {
+  pp.mask = mask;
+  pp.cycle = c;
+  for (int gi = 0; gi < RG_COUNT; ++gi) {
+    if (!(mask & (1u << gi))) continue;
+    const unsigned long long k = r->posts[gi];
+    pp.pos[gi] = int(k % r->depth);
+    if (k >= (unsigned long long)r->depth) {
+      const unsigned long long successor_cycle = r->post_cycle[gi][(k + 1) % r->depth]; // cycle of post k - depth + 1
+      if (!spin_until([&] { return host_load(&r->host->done) >= successor_cycle || host_load(&r->host->exited) != 0; }, kResidentPostPatience))
+        return fail(SHC_ERR_TIMEOUT, "resident mode: ring_depth posted input sets are waiting to be consumed (publish them)");
+    }
+  }
+  return SHC_OK;
+}
+// 3. publish: release this cycle (and any cycles before it that were left unpublished) as soon as its inputs are in place - the post
+//    kernel rings the doorbell itself, one launch instead of two per loop iteration.  The last step before the launch: the direct-post
+//    installation rule, as in shc_engine_resident_publish.
+static int resident_post_release(Resident *r, ResidentPostSlot &pp) {
+  if (const int rc = resident_wait_direct_installed(r)) return rc; // (the post kernel rings the doorbell itself: the same rule as in publish)
+  pp.doorbell = pp.cycle + 1;
+  pp.host = r->host_dev;
+  pp.blocks_done = r->post_blocks_done;
+  return SHC_OK;
+}
+// 4. The post kernel has been launched on the input stream: the books
+static void resident_post_commit(Resident *r, const ResidentPostSlot &pp, int64_t *cycle) {
+  const unsigned long long c = pp.cycle;
+  for (int gi = 0; gi < RG_COUNT; ++gi)
+    if (pp.mask & (1u << gi)) {
+      r->post_cycle[gi][r->posts[gi] % r->depth] = c;
+      r->posts[gi]++;
+    }
+  r->groups_posted |= pp.mask;
+  r->posted = c + 1;
+  if (pp.doorbell != 0) r->published = c + 1;
+  r->stream_doorbell_pending = true; // (a post is in flight on in_stream: the doorbell that releases it must follow it there)
+  if (cycle) *cycle = int64_t(c);
+}
+
 extern "C" int shc_engine_resident_post(shc_engine *e, const shc_cycle_inputs *in, int64_t *cycle) {
   int rc = resident_require(e, true);
   if (rc != SHC_OK) return rc;
@@ -391,19 +472,8 @@ extern "C" int shc_engine_resident_post(shc_engine *e, const shc_cycle_inputs *i
   if (!in) return fail(SHC_ERR_INVALID_ARG, "inputs is NULL");
   if ((rc = input_pairs_check(input_mask(in), kAllInputs, "posted")) != SHC_OK) return rc;
   const unsigned mask = input_resident_groups(input_mask(in)) | (in->pose_reset_mode ? 1u << RG_RESET : 0u);
-  if ((mask & ((1u << RG_POSE) | (1u << RG_RESET))) && !(e->rt_flags & RT_MANUAL_LIVE))
-    return fail(SHC_ERR_UNSUPPORTED, "pose inputs: give the engine one (shc_engine_set_pose_input / set_pose_reset_mode) before shc_engine_resident_begin");
-  if ((mask & (1u << RG_EFFORT)) && !(e->rt_flags & RT_EFFORT_LIVE))
-    return fail(SHC_ERR_UNSUPPORTED, "joint efforts: give the engine one (shc_engine_set_joint_effort) before shc_engine_resident_begin");
-  const unsigned long long c = r->posted;
-  if (c < r->published) return fail(SHC_ERR_INVALID_ARG, "resident mode: this cycle has already been published without inputs");
-  if (c >= r->max_cycles) return fail(SHC_ERR_INVALID_ARG, "resident mode: past max_cycles");
-  HIP_TRY(hipSetDevice(e->device));
-  // the header slot of cycle c last served cycle c - 1024; a ring position of group g last served post k - depth, which stays in
-  // force until the cycle post k - depth + 1 was made for has been reached by every wave
-  const double patience = 5.0;
-  if (c >= kResidentHeaders && !spin_until([&] { return host_load(&r->host->done) > c - kResidentHeaders; }, patience))
-    return fail(SHC_ERR_TIMEOUT, "resident mode: 1024 posted cycles are waiting to run");
+  unsigned long long c = 0;
+  if ((rc = resident_post_admit(e, mask, c)) != SHC_OK) return rc;
   if (in->direct) {
     // Launch-free post: one 16-byte record in the host-mapped ring; the relay turns it into the cycle's header and releases the cycle.
     const int set = in->direct - 1;
@@ -429,18 +499,7 @@ extern "C" int shc_engine_resident_post(shc_engine *e, const shc_cycle_inputs *i
     return SHC_OK;
   }
   ResidentPost pp{};
-  pp.mask = mask;
-  pp.cycle = c;
-  for (int gi = 0; gi < RG_COUNT; ++gi) {
-    if (!(mask & (1u << gi))) continue;
-    const unsigned long long k = r->posts[gi];
-    pp.pos[gi] = int(k % r->depth);
-    if (k >= (unsigned long long)r->depth) {
-      const unsigned long long successor_cycle = r->post_cycle[gi][(k + 1) % r->depth]; // cycle of post k - depth + 1
-      if (!spin_until([&] { return host_load(&r->host->done) >= successor_cycle || host_load(&r->host->exited) != 0; }, patience))
-        return fail(SHC_ERR_TIMEOUT, "resident mode: ring_depth posted input sets are waiting to be consumed (publish them)");
-    }
-  }
+  if ((rc = resident_post_place(r, mask, c, pp)) != SHC_OK) return rc;
   // host arrays: into the next pinned staging slot (free once the post kernel that read it kPinSlots posts ago has completed)
   size_t off = 0;
   const int pin_slot = int(r->pin_uses % Resident::kPinSlots);
@@ -475,15 +534,7 @@ extern "C" int shc_engine_resident_post(shc_engine *e, const shc_cycle_inputs *i
   STAGE(effort, joint_effort, nl * e->NJ * 8)
 #undef STAGE
   const int64_t threads = (mask & ((1u << RG_FORCE) | (1u << RG_EFFORT))) ? int64_t(nl) : int64_t(n);
-  // publish: release this cycle (and any cycles before it that were left unpublished) as soon as its inputs are in place - the post
-  // kernel rings the doorbell itself, one launch instead of two per loop iteration
-  const bool publish = in->publish != 0;
-  if (publish) {
-    if ((rc = resident_wait_direct_installed(r)) != SHC_OK) return rc; // (the post kernel rings the doorbell itself: the same rule as in publish)
-    pp.doorbell = c + 1;
-    pp.host = r->host_dev;
-    pp.blocks_done = r->post_blocks_done;
-  }
+  if (in->publish != 0 && (rc = resident_post_release(r, pp)) != SHC_OK) return rc;
   resident_post_kernel<<<dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, r->in_stream>>>(pp, r->args, r->headers, r->rin, r->rini, r->force, r->effort,
                                                                                               e->n, e->L, e->NJ, e->n_slots);
   HIP_TRY(hipGetLastError());
@@ -491,16 +542,7 @@ extern "C" int shc_engine_resident_post(shc_engine *e, const shc_cycle_inputs *i
     HIP_TRY(hipEventRecord(r->pin_ev[pin_slot], r->in_stream));
     r->pin_uses++;
   }
-  for (int gi = 0; gi < RG_COUNT; ++gi)
-    if (mask & (1u << gi)) {
-      r->post_cycle[gi][r->posts[gi] % r->depth] = c;
-      r->posts[gi]++;
-    }
-  r->groups_posted |= mask;
-  r->posted = c + 1;
-  if (publish) r->published = c + 1;
-  r->stream_doorbell_pending = true; // (a post is in flight on in_stream: the doorbell that releases it must follow it there)
-  if (cycle) *cycle = int64_t(c);
+  resident_post_commit(r, pp, cycle);
   return SHC_OK;
 }
 
@@ -588,6 +630,21 @@ __global__ void resident_wait_done_kernel(const ResidentCtl *ctl, ResidentHost *
   __hip_atomic_fetch_add(&host->late_reads, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// The head of a stream-ordered read (the call below; shc_engine_resident_get_observations_async of shc_resident_rows.hpp): is `cycle` readable,
+// then the bounded device-side wait for it on the engine's stream
+static int resident_read_wait(shc_engine *e, int64_t cycle, int timeout_ms) {
+  Resident *r = e->res;
+  if (cycle < 0 || (unsigned long long)cycle >= r->max_cycles) return fail(SHC_ERR_INVALID_ARG, "resident mode: no such cycle (max_cycles)");
+  if (r->published > (unsigned long long)cycle + r->depth)
+    return fail(SHC_ERR_INVALID_ARG, "resident mode: that cycle's outputs may have been overwritten (ring_depth newer cycles were published)");
+  HIP_TRY(hipSetDevice(e->device));
+  const unsigned long long ticks = (unsigned long long)(timeout_ms > 0 ? timeout_ms : 5000) * r->wall_khz; // wall_clock64 ticks per millisecond
+  if (cycle > r->read_queued) r->read_queued = cycle; // (the engine's stream is parked until that cycle has run: shc_engine_resident_post_actions asks)
+  resident_wait_done_kernel<<<dim3(1), dim3(1), 0, e->stream>>>(r->ctl, r->host_dev, (unsigned long long)cycle + 1, ticks);
+  HIP_TRY(hipGetLastError());
+  return SHC_OK;
+}
+
 // Stream-ordered variant of shc_engine_resident_get_joint_state: nothing here waits on the host.  The engine's stream gets a
 // device-side wait for `cycle` followed by the gather into the caller's device buffers, so whatever the caller queues on that
 // stream afterwards (the all-gather of the fleet's joint buffer) runs as soon as the cycle's outputs exist - its launch latency
@@ -597,13 +654,7 @@ extern "C" int shc_engine_resident_get_joint_state_async(shc_engine *e, int64_t 
   if (rc != SHC_OK) return rc;
   Resident *r = e->res;
   if ((rc = resident_alive(r)) != SHC_OK) return rc;
-  if (cycle < 0 || (unsigned long long)cycle >= r->max_cycles) return fail(SHC_ERR_INVALID_ARG, "resident mode: no such cycle (max_cycles)");
-  if (r->published > (unsigned long long)cycle + r->depth)
-    return fail(SHC_ERR_INVALID_ARG, "resident mode: that cycle's outputs may have been overwritten (ring_depth newer cycles were published)");
-  HIP_TRY(hipSetDevice(e->device));
-  const unsigned long long ticks = (unsigned long long)(timeout_ms > 0 ? timeout_ms : 5000) * r->wall_khz; // wall_clock64 ticks per millisecond
-  resident_wait_done_kernel<<<dim3(1), dim3(1), 0, e->stream>>>(r->ctl, r->host_dev, (unsigned long long)cycle + 1, ticks);
-  HIP_TRY(hipGetLastError());
+  if ((rc = resident_read_wait(e, cycle, timeout_ms)) != SHC_OK) return rc;
   const double *slot = r->out + size_t(cycle % r->depth) * size_t(e->NJ) * e->n_slots * 2;
   const int64_t threads = e->n * e->L;
   for (int which = 0; which < 2; ++which) {

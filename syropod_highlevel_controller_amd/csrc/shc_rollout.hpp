@@ -214,8 +214,8 @@ extern "C" int shc_engine_step_k_actions(shc_engine *e, int n_cycles, const shc_
 constexpr uint32_t kRingJoints = 1u << SHC_OBS_Q | 1u << SHC_OBS_QD, kRingKinematics = kRingJoints | 1u << SHC_OBS_MODEL_TIP;
 static int rollout_joints_check(const shc_engine *e, const shc_obs_spec *spec, const RowLayout &lay, uint32_t readable = kRingJoints) {
   if (lay.mask & ~readable)
-    return fail(SHC_ERR_UNSUPPORTED, readable == kRingJoints ? "the output ring of the K-cycle launches holds joints: SHC_OBS_Q and SHC_OBS_QD only"
-                                                             : "the output ring of the K-cycle launches holds joints: SHC_OBS_Q, SHC_OBS_QD and SHC_OBS_MODEL_TIP = FK(q) only");
+    return fail(SHC_ERR_UNSUPPORTED, readable == kRingJoints ? "an output ring (K-cycle launches, resident loop) holds joints: SHC_OBS_Q and SHC_OBS_QD only"
+                                                             : "an output ring (K-cycle launches, resident loop) holds joints: SHC_OBS_Q, SHC_OBS_QD and SHC_OBS_MODEL_TIP = FK(q) only");
   return observe_check(e, spec, lay);
 }
 // cycles [first, first + count) of the K of the latest launch
@@ -224,15 +224,15 @@ static int rollout_range_check(const char *who, int K, int first_cycle, int n_cy
     return fail(SHC_ERR_INVALID_ARG, std::string(who) + ": cycles [first_cycle, first_cycle + n_cycles) of the K of the latest K-cycle launch");
   return SHC_OK;
 }
-// The joints launch on the engine's stream: every robot's q / qd of ring slots [first_cycle, first_cycle + n_cycles) into rows ids[robot] (a
-// device table) or robot of out + cycle * cycle_stride.  The caller has checked everything and joined split steps.
-static int rollout_joints_launch(shc_engine *e, const shc_obs_spec *spec, const RowLayout &lay, void *out, int64_t row_stride, int64_t cycle_stride,
-                                 const int64_t *ids, int first_cycle, int n_cycles) {
+// The joints launch on the engine's stream: every robot's q / qd of the n_cycles slots from `ring` on - NJ planes of n_slots double2 each, the
+// layout of the K-cycle launches' output ring and of a slot of the resident loop's - into rows ids[robot] (a device table) or robot of
+// out + cycle * cycle_stride.  The caller has checked everything.
+static int rollout_joints_launch_at(shc_engine *e, const shc_obs_spec *spec, const RowLayout &lay, void *out, int64_t row_stride, int64_t cycle_stride,
+                                    const int64_t *ids, const double2 *ring, int n_cycles) {
   RolloutJointArgs o{};
   row_args(o, lay, spec->dtype, row_stride, spec->legs > e->L || spec->dof > e->NJ, spec->pad);
   o.dof = spec->dof;
   o.cycle_stride = cycle_stride, o.n = e->n, o.n_slots = e->n_slots;
-  const double2 *ring = reinterpret_cast<const double2 *>(e->k_out) + int64_t(first_cycle) * e->NJ * e->n_slots;
   const dim3 grid(row_grid(e->L, 0, e->n), unsigned(n_cycles));
   const size_t lds = row_tile_bytes(e->L, o.pitch, spec->dtype);
   const int rc = dispatch_morphology(e, [&](auto l, auto nj) -> int {
@@ -249,6 +249,13 @@ static int rollout_joints_launch(shc_engine *e, const shc_obs_spec *spec, const 
   if (rc != SHC_OK) return rc;
   HIP_TRY(hipGetLastError());
   return SHC_OK;
+}
+
+// ... of ring slots [first_cycle, first_cycle + n_cycles) of the latest K-cycle launch.  The caller has joined split steps, too.
+static int rollout_joints_launch(shc_engine *e, const shc_obs_spec *spec, const RowLayout &lay, void *out, int64_t row_stride, int64_t cycle_stride,
+                                 const int64_t *ids, int first_cycle, int n_cycles) {
+  const double2 *ring = reinterpret_cast<const double2 *>(e->k_out) + int64_t(first_cycle) * e->NJ * e->n_slots;
+  return rollout_joints_launch_at(e, spec, lay, out, row_stride, cycle_stride, ids, ring, n_cycles);
 }
 
 // The read of the ring as rows, for the two entry points that differ in the fields they let through (`readable`)

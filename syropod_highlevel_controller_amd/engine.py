@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "shc_fleet_all_gather_joints",
     "shc_engine_resident_begin", "shc_engine_resident_bind_inputs", "shc_engine_resident_post", "shc_engine_resident_publish", "shc_engine_resident_wait",
     "shc_engine_resident_get_joint_state", "shc_engine_resident_get_joint_state_async", "shc_engine_resident_status", "shc_engine_resident_end", "shc_engine_join",
+    "shc_engine_resident_post_actions", "shc_engine_resident_get_observations_async",
     "shc_engine_aux_state_bytes", "shc_engine_get_aux_state", "shc_engine_set_aux_state",
     "shc_engine_step_k", "shc_engine_get_step_k_joint_state", "shc_engine_adjust_parameter",
     "shc_engine_get_leg_state_msgs", "shc_fleet_get_leg_state_msgs",
@@ -388,6 +389,13 @@ def _rows_array(a, what: str, host: Optional[str] = None):
     if strides[1] != dt.itemsize or strides[0] % dt.itemsize or strides[0] < columns * dt.itemsize:
         raise ValueError(f"{what}: the elements of a row must be contiguous and the rows a whole number of elements apart (strides {tuple(strides)})")
     return C.c_void_p(cai["data"][0]), dt, rows, columns, strides[0] // dt.itemsize, 1, None
+
+
+def _device_only(a, what: str):
+    """``a``, unless it is no device array: the resident tensors have no host form, as the K-cycle launches (a TypeError)."""
+    if isinstance(a, np.ndarray) or getattr(a, "__cuda_array_interface__", None) is None:
+        raise TypeError(f"{what}: device arrays only (an object with __cuda_array_interface__, e.g. a torch tensor) - got {type(a).__name__}")
+    return a
 
 
 def _cycles_array(a, what: str):
@@ -781,6 +789,8 @@ def lib():
         L.shc_engine_resident_wait.argtypes = [C.c_void_p, C.c_int64, C.c_int]
         L.shc_engine_resident_get_joint_state.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
         L.shc_engine_resident_get_joint_state_async.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
+        L.shc_engine_resident_post_actions.argtypes = [C.c_void_p, C.POINTER(ActSpec), C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+        L.shc_engine_resident_get_observations_async.argtypes = [C.c_void_p, C.c_int64, C.POINTER(ObsSpec), C.c_void_p, C.c_int]
         L.shc_engine_resident_status.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L.shc_engine_resident_end.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         L.shc_engine_synchronize.argtypes = [C.c_void_p]
@@ -1274,6 +1284,45 @@ class BatchEngine:
         wait for `cycle`; returns at once."""
         _check(self.L.shc_engine_resident_get_joint_state_async(self.h, int(cycle), C.c_void_p(q_ptr or None), C.c_void_p(qd_ptr or None), int(timeout_ms)),
                "resident_get_joint_state_async")
+
+    def resident_post_actions(self, actions, fields, publish: bool = False, legs: Optional[int] = None, dof: Optional[int] = None) -> int:
+        """``resident_post`` for the next unposted cycle from one 2-D float32 / float64 DEVICE array of n rows
+        (shc_engine_resident_post_actions): ``action_columns(fields, legs, dof)`` names the columns, a view of some columns of a wider tensor
+        will do.  The loop runs as after ``resident_post(on_device=True)`` with the columns as float64 arrays; groups not named are held;
+        velocity, IMU and pose fields are named in pairs.  One kernel launch, nothing staged.  The array must be ready on the ENGINE's stream
+        and may be overwritten by work queued there behind the call; no host wait.  publish: release the cycle in the same launch.  Refused
+        while a stream-ordered read (``resident_observations``, ``resident_joints_async``) of an unpublished cycle is pending.  Returns the
+        cycle index.  A numpy array is a TypeError (device arrays only)."""
+        legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
+        ptr, dt, rows, columns, stride, _on_device, _keep = _rows_array(_device_only(actions, "resident_post_actions"), "resident_post_actions")
+        spec = act_spec(fields, legs, dof, dt, stride)
+        _check_rows("resident_post_actions", "actions", rows, columns, self.n, int(self.L.shc_act_width(C.byref(spec))))
+        cyc = C.c_int64(-1)
+        _check(self.L.shc_engine_resident_post_actions(self.h, C.byref(spec), ptr, 1 if publish else 0, C.byref(cyc)), "resident_post_actions")
+        return int(cyc.value)
+
+    def resident_observations(self, cycle: int, fields=("q", "qd"), dtype="float32", out=None, pad: float = 0.0, legs: Optional[int] = None,
+                              dof: Optional[int] = None, timeout_ms: int = 0):
+        """q / qd / model_tip (``fields``, in column order) of iteration ``cycle`` of the resident loop as one (n, D) DEVICE array, stream-ordered
+        (shc_engine_resident_get_observations_async): ``observation_columns(fields, legs, dof)`` names the columns; q / qd are what
+        ``resident_joints(cycle)`` holds, cast to the element type, model_tip is FK(q) in the robot frame, ``pad`` where the row geometry
+        (legs, dof) is larger than the robot.  Queued on the engine's stream behind a device-side wait for the cycle (which may still be
+        unpublished; bounded by timeout_ms, 0 = 5 s); returns at once and writes nothing into the engine.  out: a 2-D float32 / float64 device
+        array (a view of some columns of a wider one will do) whose first D columns are filled; returns None.  Without out a new torch tensor
+        of ``dtype`` on the engine's device is filled and returned.  A numpy array is a TypeError (device arrays only)."""
+        legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
+        made = None
+        if out is None:
+            spec = obs_spec(fields, legs, dof, dtype, 0, pad)
+            width = int(self.L.shc_obs_width(C.byref(spec)))
+            if width < 0:
+                _check(SHC_ERR_INVALID_ARG, "resident_observations")
+            out = made = _new_device_array((self.n, width), dtype, getattr(self, "device", None))
+        ptr, dt, rows, columns, stride, _on_device, _keep = _rows_array(_device_only(out, "resident_observations"), "resident_observations")
+        spec = obs_spec(fields, legs, dof, dt, stride, pad)
+        _check_rows("resident_observations", "out", rows, columns, self.n, int(self.L.shc_obs_width(C.byref(spec))))
+        _check(self.L.shc_engine_resident_get_observations_async(self.h, int(cycle), C.byref(spec), ptr, int(timeout_ms)), "resident_observations")
+        return made
 
     def resident_status(self):
         pub, done, run = C.c_int64(), C.c_int64(), C.c_int32()
