@@ -42,9 +42,11 @@ def main(argv):
         total, unused = collections.Counter(), []
         for d in dem:
             m = re.match(r"void shc::(shc_\w+)<(\d+), (\d+), (\d+)u(?:, (\d|true|false))?>", d)
-            if not m or m.group(5) == "2":
+            if not m or (m.group(5) == "2" and m.group(1) != "shc_resident2_kernel"):
                 continue
-            kind = "resident3" if m.group(5) == "true" else KIND[m.group(1)]   # (the three-role form of shc_resident2_kernel is logged under its own name)
+            kind = KIND[m.group(1)]
+            if m.group(1) == "shc_resident2_kernel" and m.group(5) in ("1", "2"):   # (the helper forms of shc_resident2_kernel are logged under names of their own)
+                kind = "resident3" if m.group(5) == "2" else "resident3_one_helper"
             key = (kind, int(m.group(2)), int(m.group(3)), int(m.group(4)))
             total[key[0]] += 1
             if key not in used:

@@ -12,8 +12,8 @@ for b in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
             continue
         m = re.search(r"ILi(\d)ELi(\d)E", name)
         g = lambda k: re.search(k + r": (\d+)", b).group(1)
-        f = re.search(r"ILi\dELi\dELj(\d+)E(?:Lb([01])E)?", name)   # the loop forms: feature word, and the three-role flag of shc_resident2_kernel
-        form = ("features %-10s %s" % (f.group(1), "helper" if f.group(2) == "1" else "      "),) if f else ()
+        f = re.search(r"ILi\dELi\dELj(\d+)E(?:Li([012])E)?", name)   # the loop forms: feature word, and the helper wavefronts per robot group of shc_resident2_kernel
+        form = ("features %-10s %s" % (f.group(1), {"1": "1 helper ", "2": "2 helpers"}.get(f.group(2), "         ")),) if f else ()
         one = re.search(r"ILi(\d)E([fd])E", name)   # kernels on the leg count and an element type only (footholds_set_kernel / footholds_get_kernel)
         head = "legs %s dof %s" % m.groups() if m else "legs %s %s" % (one.group(1), {"f": "float32", "d": "float64"}[one.group(2)]) if one else "legs ? dof ?"
         print(head, name.split("I")[0][4:], *form, "VGPR", g("VGPRs"), "AGPR", g("AGPRs"), "SGPR", g("TotalSGPRs"),

@@ -1,7 +1,7 @@
 // Where do the wavefronts of a small grid land?  For every wave: XCC, SE, CU, SIMD (s_getreg HW_ID / XCC_ID), for 64- and
 // 128-thread workgroups - the question behind the two-wave (front / back) resident kernel: do the two waves of a 128-thread
-// workgroup get two different SIMDs of their CU? - and for 256- and 384-thread workgroups (the resident pipelines: 2 robot groups x 2 or 3
-// roles): which SIMD does wave i of a workgroup get?  The three-role kernel orders its roles for "the first four waves on four SIMDs, waves i and i + 4 on the same one".
+// workgroup get two different SIMDs of their CU? - and for 256-, 384- and 512-thread workgroups (the resident pipelines: 2 robot groups x 2, 3 or 4
+// roles): which SIMD does wave i of a workgroup get?  The helper forms order their roles for "the first four waves on four SIMDs, waves i and i + 4 on the same one".
 // build: hipcc --offload-arch=gfx950 -O2 -o wave_placement wave_placement.hip ; run: ./wave_placement [workgroups]
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -26,7 +26,7 @@ __global__ void probe(unsigned *out, int spin) {
 
 int main(int argc, char **argv) {
   const int wgs = argc > 1 ? atoi(argv[1]) : 410;
-  for (int block : {64, 128, 256, 384}) {
+  for (int block : {64, 128, 256, 384, 512}) {
     const int waves = wgs * block / 64;
     unsigned *d;
     hipMalloc(&d, waves * 8);

@@ -248,8 +248,9 @@ constexpr bool phase_fences() {
 // Development-only phase timestamps (build with -DSHC_RES2_TIMING) of the two-wavefront resident kernel: the leader of workgroup 1 keeps
 // the s_memtime stamps of its latest iteration in LDS; shc_engine_resident_end prints them.
 #if defined(SHC_RES2_TIMING) && !defined(SHC_RES2_BUSY_ONLY) // (-DSHC_RES2_BUSY_ONLY: only the two stamps per iteration of each role, no phase ticks)
-__shared__ long long shc_ticks_lds[96]; // 32 per wavefront of pair 0 (threads 0 and 128: walker and model; the three-role form: and the helper at thread 256)
-__shared__ long long shc_acc_lds[96];   // per phase: clocks since the previous stamp, summed over the steady REAL iterations
+__shared__ long long shc_ticks_lds[128]; // 32 per wavefront of pair 0 (threads 0 and 128: walker and model; the three-role form: and the helper at thread 256; the four-role
+                                         // form: the pose helper at thread 256, the front helper at thread 384)
+__shared__ long long shc_acc_lds[128];   // per phase: clocks since the previous stamp, summed over the steady REAL iterations
 #define SHC_TICK(i) do { __builtin_amdgcn_sched_barrier(0); if (blockIdx.x == 1 && (threadIdx.x & 127) == 0) shc_ticks_lds[(threadIdx.x >> 7) * 32 + (i)] = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
 #define SHC_TICK(i) do {} while (0)

@@ -60,11 +60,17 @@ static void launch_cycle(const CycleLaunch &a) {
       note_kernel("batch", L, NJ, F);
       shc_batch_kernel<L, NJ, F><<<dim3(a.grid), dim3(a.block), wave_bytes * (a.block / 64), a.stream>>>(a.st, (const SharedConsts<L, NJ> *)a.consts, *a.resident, a.rt_flags);
     }
-  } else if (a.block == 384) {
+  } else if (a.block == 512) { // the helper form: four roles (logged as "resident3", the name the helper form has had since it had one helper)
     if constexpr (has_helper_wave(L, NJ, F)) {
-      static_assert(has_two_wave(F), "the three-role form is a form of the two-wavefront pipeline");
+      static_assert(has_two_wave(F), "the helper forms are forms of the two-wavefront pipeline");
       note_kernel("resident3", L, NJ, F);
-      shc_resident2_kernel<L, NJ, F, true><<<dim3(a.grid), dim3(384), 2 * wave_bytes + sizeof(Resident3Lds<L, NJ>), a.stream>>>(
+      shc_resident2_kernel<L, NJ, F, 2><<<dim3(a.grid), dim3(512), 2 * wave_bytes + sizeof(Resident3Lds<L, NJ>), a.stream>>>(
+          a.st, (const SharedConsts<L, NJ> *)a.consts, *a.resident, a.rt_flags);
+    }
+  } else if (a.block == 384) { // its three-role predecessor, one helper wavefront per robot group: grids that leave the four-role form no room, and SHC_RESIDENT_THREE_ROLE=1
+    if constexpr (has_helper_wave(L, NJ, F)) {
+      note_kernel("resident3_one_helper", L, NJ, F);
+      shc_resident2_kernel<L, NJ, F, 1><<<dim3(a.grid), dim3(384), 2 * wave_bytes + sizeof(Resident3Lds<L, NJ>), a.stream>>>(
           a.st, (const SharedConsts<L, NJ> *)a.consts, *a.resident, a.rt_flags);
     }
   } else if (a.block == 256) {

@@ -1088,6 +1088,7 @@ struct Resident3Lds : Resident2Lds<L, NJ> { // ... of the three-role form (below
   unsigned back_seen[2];      // model -> walker at exit: input groups the model wavefront received
   double tip_xy[2][2][2][64]; // [pair][cycle parity][x, y][lane] walker -> helper: the stepper tips the cycle left (getLimit of the next cycle reads their bearings)
   unsigned front_done[2];     // helper -> walker: velocity fronts completed (the desired velocities of that cycle are in the tile)
+  unsigned front_dirty[2], front_seen[2], front_fault[2]; // the four-role form, front helper -> walker at exit (the pose helper reports through model_*)
 };
 
 // THREE roles per robot group (HELPER; has_helper_wave: default.yaml's posing set on 6 x 3, the specialisations whose model wavefront carries the pose AND the
@@ -1101,13 +1102,29 @@ struct Resident3Lds : Resident2Lds<L, NJ> { // ... of the three-role form (below
 // The order is [W0, W1, M0, M1, H0, H1]: each helper shares the SIMD of ITS WALKER.  The walker is a latency-bound chain that leaves most issue slots of its SIMD
 // free; the model wavefront's IK / FK is dense FP64 and leaves few - behind it the helper's work only queues (with the front there as well the cycle measured
 // 25 % longer than without, behind the walker 8 % shorter: DESIGN.md 4.1a).  The helper raises its priority for the front alone, which the walker waits for.
-template <int L, int NJ, unsigned F, bool HELPER = false>
-__global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(DevState st, const SharedConsts<L, NJ> *gc, ResidentArgs A, unsigned rt_flags) {
+// (HELPERS = 1.  Since the four-role form this one runs only where that one has no room - a grid that fills the last compute unit of every XCD, shc_resident.hpp -
+//  and for A/B runs: SHC_RESIDENT_THREE_ROLE=1.)
+//
+// FOUR roles per robot group (HELPERS = 2; the same two specialisations, what they run by default): the helper's work on two wavefronts.
+// 512-thread workgroups = 2 robot groups x (walker W, model M, pose helper P, front helper F), eight wavefronts, two on every SIMD of the compute unit, waves i
+// and i + 4 on the same one (wave_placement.hip: all 205 workgroups of a 512-thread grid).  The order is [W0, W1, M0, M1, P0, P1, F0, F1]:
+//   F - front_of_cycle alone, straight after the control words, at s_setprio 3 - shares the SIMD of the MODEL wavefront.  The front is the one block on the
+//       walker's recurrence.  At raised priority behind the walker it took the walker's own issue slots (the walker and the old helper were co-critical:
+//       5 205 / 5 340 busy clocks); the model wavefront has a third of the iteration to spare and gives way for the front's ~1 600 clocks without being missed.
+//   P - everything else the helper ran: the pose (first: the walker asks for it four fifths into its iteration), then the leader's decision on pair 0 (its loads
+//       still have the odometry's length to arrive in), the odometry, the announcement, the emergency bound - at priority 0 behind ITS WALKER, filling the
+//       issue slots that latency-bound chain leaves.
+// The same inline blocks in other loops - results are byte-identical; no new kind of wait: the front / pose flags behind a workgroup release fence, the bounded
+// PoseWait, one barrier per iteration, and every loop leaves on the same IT_EXIT.  2.186 -> 2.04 us per cycle at 4 096 hexapods; the order the first probe
+// started from ([.., F0, F1, P0, P1]: F behind its walker, P behind the model) measured 2.20 (profiles/r09_probe_four_roles.txt).
+template <int L, int NJ, unsigned F, int HELPERS = 0>
+__global__ void __launch_bounds__(256 + 128 * HELPERS, 1) shc_resident2_kernel(DevState st, const SharedConsts<L, NJ> *gc, ResidentArgs A, unsigned rt_flags) {
   using R = RobotFields;
   using FD = Fields<NJ>;
   using FT = Feat<F>;
   constexpr int RPW = 64 / L;
-  constexpr int kThreads = HELPER ? 384 : 256;
+  constexpr bool HELPER = HELPERS > 0, FOUR = HELPERS == 2;
+  constexpr int kThreads = 256 + 128 * HELPERS;
   if (blockIdx.x == 0) { // the relay workgroup: one wave per direction
     if (threadIdx.x < 64) resident_relay<PART_GATE>(A);
     else if (threadIdx.x < 128) resident_relay<PART_DONE>(A);
@@ -1122,8 +1139,10 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
   const int lane = threadIdx.x & 63;
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int pair = wib & 1;
-  // the model wavefront of pair 0 decides what the next iteration is: it has the time to spare (HELPER: the helper of pair 0, in the order [W0, W1, M0, M1, H0, H1])
+  // the model wavefront of pair 0 decides what the next iteration is: it has the time to spare (HELPER: the helper of pair 0, in the order [W0, W1, M0, M1, H0, H1];
+  // FOUR: the pose helper of pair 0, in the order [W0, W1, M0, M1, P0, P1, F0, F1])
   const bool walker = wib < 2, helper = HELPER && wib >= 4, leader = wib == (HELPER ? 4 : 2);
+  const bool fronter = FOUR ? wib >= 6 : helper; // the helper that runs the velocity front (FOUR: and nothing else, behind the model wavefront of its pair)
   const int64_t wave = (int64_t(blockIdx.x) - 1) * 2 + pair;
   const bool active = wave < A.n_waves;
   const int64_t rob0 = wave * RPW;
@@ -1230,7 +1249,7 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
   fb.uf = load_uni_flags(C.P); // (once: the parameter block does not change while the loop runs)
   OdomCache odom_cache;        // walker wavefront: (sin, cos) of the half yaw step while the desired angular velocities stay as they are
   Pose owpp_cache = pose_identity();
-  const bool poser = HELPER ? helper : !walker; // the wavefront that runs the pose (and, where it is not the walker's, the odometry)
+  const bool poser = HELPER ? helper && !(FOUR && fronter) : !walker; // the wavefront that runs the pose (and, where it is not the walker's, the odometry)
   if (POSE_SPLIT && active && poser) owpp_cache = rb.getpose(R::OWPP); // ... and the origin walk-plane pose (the walker wavefront filled the tile before the barrier)
   // ... and WalkController::odometry_ideal_ itself: nothing inside the loop reads it, so the wavefront that advances it (ODOM_WALKER below) accumulates it in registers and
   // puts it back into the tile when the loop ends (4 LDS reads + 4 writes per cycle less on the longer of the two wavefronts).  Short chains
@@ -1251,7 +1270,7 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
 #ifdef SHC_RES2_TIMING
   long long tm_busy = 0, tm_total0 = __builtin_readcyclecounter(), tm_real = 0;
 #ifndef SHC_RES2_BUSY_ONLY
-  if (threadIdx.x < 96) shc_acc_lds[threadIdx.x] = 0;
+  if (threadIdx.x < 128) shc_acc_lds[threadIdx.x] = 0;
 #endif
 #endif
   // The two roles run SEPARATE loops - one barrier per iteration each, and the same number of iterations: what an iteration is comes from the
@@ -1360,7 +1379,7 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
   //  the same on both wavefronts.  Without that clamp this would need the tile's old value instead.)
   const auto front_of_cycle = [&](const u64 h0, const u64 h1) __attribute__((always_inline)) {
     if constexpr (HELPER) {
-      __builtin_amdgcn_s_setprio(3); // (the walker - same SIMD - is about to wait for this: measured, profiles/r08_probe_front_on_helper.txt)
+      __builtin_amdgcn_s_setprio(3); // (the walker is about to wait for this: measured, profiles/r08_probe_front_on_helper.txt; FOUR: ahead of the model wavefront, r09)
       double vin_x, vin_y, win;
       if (h0 == u64(c_front) + 1 && (unsigned(h1) & (1u << RG_VEL)) != 0) {
         const int field = lane / RPW;
@@ -1452,34 +1471,54 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
     }
   } else if (helper) {
     // ---------------------------------------------------------------- helper wavefront (HELPER): the velocity front and the pose of cycle c_front, the odometry of cycle c_back, the leader's duty
-    if constexpr (HELPER) for (;;) {
-      SHC_R2_ITER_BEGIN();
-      const int kind = __builtin_amdgcn_readfirstlane(int(X.ctrl[k & 3][0]));
-      const u64 h0 = uni64(X.ctrl[k & 3][1]), h1 = uni64(X.ctrl[k & 3][2]);
-      SHC_TICK(29);
-      int nk = IT_EXIT;
-      u64 nh0v = 0, nh1v = 0;
-      if (leader && kind != IT_EXIT) leader_decide(kind, nk, nh0v, nh1v);
-      if (active) { // (the helper of an inactive pair only keeps the barriers)
+    // (FOUR: two helper wavefronts, two loops of the same text - FRONT: the velocity front alone, straight after the control words; REST: everything else, the
+    //  leader's decision BEHIND the pose - 440 clocks earlier for what the walker waits for, 2.09 -> 2.04 us per cycle - where the three-role form has it first)
+    const auto helper_loop = [&](auto with_front, auto with_rest) __attribute__((always_inline)) {
+      constexpr bool FRONT = decltype(with_front)::value, REST = decltype(with_rest)::value;
+      constexpr int kThread = FOUR && FRONT ? 384 : 256; // (development stamps: the first thread of this role's wavefront of pair 0)
+      for (;;) {
+        SHC_R2_ITER_BEGIN();
+        const int kind = __builtin_amdgcn_readfirstlane(int(X.ctrl[k & 3][0]));
+        const u64 h0 = uni64(X.ctrl[k & 3][1]), h1 = uni64(X.ctrl[k & 3][2]);
+        SHC_TICK(29);
+        [[maybe_unused]] int nk = IT_EXIT;
+        [[maybe_unused]] u64 nh0v = 0, nh1v = 0;
+        if constexpr (REST && !FOUR) if (leader && kind != IT_EXIT) leader_decide(kind, nk, nh0v, nh1v);
         SHC_TICK(24);
-        if (kind == IT_REAL) front_of_cycle(h0, h1); // (first: the walker waits for it in mid-stepper, for the pose only at updateStance)
-        SHC_TICK(1);
-        if (kind == IT_REAL) pose_of_cycle(h0, h1);
-        SHC_TICK(25);
-        if (prev_real) { // the cycle whose walker half ran one iteration ago
-          if (FT::odom(P)) odometry_of_cycle(&X.mailbox[pair][c_back & 1][0][lane]);
-          ++c_back;
+        if (active) { // (the helper of an inactive pair only keeps the barriers)
+          if constexpr (FRONT) if (kind == IT_REAL) front_of_cycle(h0, h1); // (first: the walker waits for it in mid-stepper, for the pose only at updateStance)
+          SHC_TICK(1);
+          if constexpr (REST) {
+            if (kind == IT_REAL) pose_of_cycle(h0, h1);
+            SHC_TICK(25);
+            if constexpr (FOUR) if (leader && kind != IT_EXIT) leader_decide(kind, nk, nh0v, nh1v); // (pair 0, the leader's, is active in every workgroup of the grid)
+            SHC_TICK(2);
+            if (prev_real) { // the cycle whose walker half ran one iteration ago
+              if (FT::odom(P)) odometry_of_cycle(&X.mailbox[pair][c_back & 1][0][lane]);
+              ++c_back;
+            }
+            SHC_TICK(26);
+          }
         }
-        SHC_TICK(26);
+        if constexpr (REST) if (leader && kind != IT_EXIT && lane == 0) leader_announce(nk, nh0v, nh1v);
+        SHC_TICK(14);
+        if (kind == IT_EXIT) break;
+        if constexpr (REST) {
+          SHC_R2_ITER_END(kThread, 19, 29, 24, 1, 30, 25, 2, 26, 14);
+        } else {
+          SHC_R2_ITER_END(kThread, 19, 29, 24, 1, 14);
+        }
+        if (kind == IT_REAL) ++c_front;
+        prev_real = kind == IT_REAL;
+        __syncthreads();
+        ++k;
       }
-      if (leader && kind != IT_EXIT && lane == 0) leader_announce(nk, nh0v, nh1v);
-      SHC_TICK(14);
-      if (kind == IT_EXIT) break;
-      SHC_R2_ITER_END(256, 19, 29, 24, 1, 30, 25, 26, 14);
-      if (kind == IT_REAL) ++c_front;
-      prev_real = kind == IT_REAL;
-      __syncthreads();
-      ++k;
+    };
+    if constexpr (FOUR) {
+      if (fronter) helper_loop(std::true_type{}, std::false_type{});
+      else helper_loop(std::false_type{}, std::true_type{});
+    } else if constexpr (HELPER) {
+      helper_loop(std::true_type{}, std::true_type{});
     }
   } else {
     // ---------------------------------------------------------------- model wavefront: (the pose of cycle c_front,) cycle_back of cycle c_back
@@ -1560,11 +1599,13 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
 #undef SHC_R2_PHASES
 #ifdef SHC_RES2_TIMING
   if (blockIdx.x == 1 && lane == 0 && pair == 0) { // development: clocks from iteration start to the barrier, REAL iterations in steady state
-    // ResidentCtl::dbg: busy clocks of the walker [0, 4), the model [4, 8), the helper wavefront [72, 76); phase clocks [8, 40), [40, 72), [80, 112)
-    unsigned long long *rec = reinterpret_cast<unsigned long long *>(A.ctl) + 8, *dbg = rec + (walker ? 0 : helper ? 72 : 4);
+    // ResidentCtl::dbg: busy clocks of the walker [0, 4), the model [4, 8), the (pose) helper wavefront [72, 76), the front helper [112, 116); phase clocks [8, 40),
+    // [40, 72), [80, 112), [120, 152)
+    const bool second_helper = FOUR && fronter;
+    unsigned long long *rec = reinterpret_cast<unsigned long long *>(A.ctl) + 8, *dbg = rec + (walker ? 0 : second_helper ? 112 : helper ? 72 : 4);
     dbg[0] = tm_busy, dbg[1] = tm_real, dbg[2] = __builtin_readcyclecounter() - tm_total0, dbg[3] = k;
 #ifndef SHC_RES2_BUSY_ONLY
-    const int from = int(threadIdx.x >> 7) * 32, to = walker ? 8 : helper ? 80 : 40; // (the stamps are kept per wavefront of pair 0: SHC_TICK)
+    const int from = int(threadIdx.x >> 7) * 32, to = walker ? 8 : second_helper ? 120 : helper ? 80 : 40; // (the stamps are kept per wavefront of pair 0: SHC_TICK)
     for (int i = 0; i < 32; ++i) rec[to + i] = (unsigned long long)shc_acc_lds[from + i];
 #endif
   }
@@ -1590,6 +1631,13 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
         }
         if (lane == 0) X.model_fault[pair] = held.fault ? 1u : 0u; // (the leader's emergency bound)
       }
+      if constexpr (FOUR) if (fronter) { // (a role of its own reports for itself, whatever it comes to own)
+        unsigned d = 0;
+#pragma unroll
+        for (unsigned b = 1; b <= DIRTY_LAST; b <<= 1)
+          if (__any((dirty & b) != 0)) d |= b;
+        if (lane == 0) X.front_dirty[pair] = d, X.front_seen[pair] = held.seen, X.front_fault[pair] = held.fault ? 1u : 0u;
+      }
     }
   }
   __syncthreads();
@@ -1598,6 +1646,10 @@ __global__ void __launch_bounds__(HELPER ? 384 : 256, 1) shc_resident2_kernel(De
     if (POSE_SPLIT) dirty |= X.model_dirty[pair], held.seen |= X.model_seen[pair];
     if constexpr (HELPER) held.seen |= X.back_seen[pair];
     if (X.model_fault[pair]) held.fault = true;
+    if constexpr (FOUR) {
+      dirty |= X.front_dirty[pair], held.seen |= X.front_seen[pair];
+      if (X.front_fault[pair]) held.fault = true;
+    }
     if (c_front > 0) s.word = (s.word & ~LW_IKFAIL) | X.ikfail[pair][lane];
     {
       unsigned d = 0;

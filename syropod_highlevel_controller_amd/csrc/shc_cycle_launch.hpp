@@ -31,8 +31,9 @@ struct ResidentCtl { // device memory, polled with agent-scope loads; written by
   unsigned long long exited;    // worker waves that have left the loop
   unsigned long long fault;     // != 0: a worker gave up waiting (emergency bound) - state may be inconsistent
   unsigned long long pad[5];    // [0] exit reason, [1] cycles completed by every wave (device copy of ResidentHost::done), [2] the relay has left
-  unsigned long long dbg[112];  // development builds (-DSHC_RES2_TIMING): [0, 8) busy clocks, [8, 40) phase clocks of the walker, [40, 72) of the model wavefront of workgroup 1;
-                                // the three-role form: [72, 76) busy clocks and [80, 112) phase clocks of its helper wavefront
+  unsigned long long dbg[152];  // development builds (-DSHC_RES2_TIMING): [0, 8) busy clocks, [8, 40) phase clocks of the walker, [40, 72) of the model wavefront of workgroup 1;
+                                // the three-role form: [72, 76) busy clocks and [80, 112) phase clocks of its helper wavefront; the four-role form: those are its pose
+                                // helper's, [112, 116) and [120, 152) its front helper's
 };
 struct ResidentHost { // pinned host memory mapped into the device (fine-grained): the host side of the handshake
   unsigned long long doorbell;  // host / producer -> device: cycles published since resident_begin
@@ -92,8 +93,8 @@ struct CycleLaunch {
   int block;
   int n_cycles;
   const ResidentArgs *resident; // != nullptr: launch the resident kernel (block = 64: grid = n_waves + 1 relay block of 64 threads, one
-                                // wavefront per robot group; block = 256: the two-wavefront pipeline, grid = ceil(n_waves / 2) + 1; block = 384: its
-                                // three-role form, same grid)
+                                // wavefront per robot group; block = 256: the two-wavefront pipeline, grid = ceil(n_waves / 2) + 1; block = 384 / 512: its
+                                // three-role / four-role form, same grid)
   struct ResidentFit *fit;      // != nullptr: launch nothing, report whether / how densely the resident kernel of this specialisation fits
   int64_t wave0;                // first wave of this launch (a step of a large batch is two launches on two streams)
   int half_steps;               // gravity-aligned tips, legs of more than 3 joints: 0 = a cycle is two launches (walker half, model half) when
@@ -103,7 +104,7 @@ struct ResidentFit {
   int supported;          // this specialisation has a resident kernel
   int blocks_per_cu;      // hipOccupancyMaxActiveBlocksPerMultiprocessor of it (64-thread blocks with its per-wave LDS)
   int two_wave;           // the two-wavefront pipeline exists for it (256-thread blocks, at most one per compute unit)
-  int helper_wave;        // ... and its three-role form (384-thread blocks: a helper wavefront per robot group)
+  int helper_wave;        // ... and its helper forms (four roles, 512-thread blocks: a front and a pose helper wavefront per robot group; three roles, 384: one helper)
   int batch;              // the batch form (shc_engine_step_k's kernel) exists for it; without one step_k runs the K cycles as single launches
 };
 

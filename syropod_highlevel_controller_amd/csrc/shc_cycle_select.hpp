@@ -97,8 +97,8 @@ constexpr bool has_batch(unsigned F) { return (F & F_MLEGS) == 0 && (SHC_GENERIC
 // Rough terrain and tip rotations run as ONE wavefront per robot group (Leg::applyIK feeds back into the stepper there - touchdown detection,
 // the FK tip rotation - so the walker / model halves cannot be pipelined); every other resident kernel also has the two-wavefront form.
 constexpr bool has_two_wave(unsigned F) { return has_resident(F) && (F & (F_TERRAIN | F_ROT)) == 0; }
-// ... and default.yaml's posing set on the BASELINE hexapods also the three-role form of it (a helper wavefront takes the pose, the odometry and the
-// leader's duty off the model wavefront: 384-thread workgroups, shc_cycle_kernel.hpp)
+// ... and default.yaml's posing set on the BASELINE hexapods also the helper forms of it (helper wavefronts take the velocity front off the walker and the pose,
+// the odometry and the leader's duty off the model wavefront: four roles in 512-thread workgroups, three in 384-thread ones, shc_cycle_kernel.hpp)
 constexpr bool has_helper_wave(int L, int NJ, unsigned F) { return L == 6 && NJ == 3 && (F == F_C2 || F == (F_C2 | F_TIPF)); }
 // Rotation-constrained cycles of the feature-exact kernels: a cycle can run as the walker / poser launch + the model launch
 constexpr bool has_half_kernels(unsigned F) { return (F & F_ROT) != 0 && (F & (F_DYN | F_TERRAIN | F_MLEGS | F_AUTO)) == 0; }

@@ -45,7 +45,7 @@ struct Resident {
   bool stream_doorbell_pending = false;     // a doorbell value travels on in_stream behind the posts it releases
   unsigned groups_posted = 0;
   bool two_wave = false;                    // the two-wavefront (walker / model) pipeline is running
-  bool helper_wave = false;                 // ... in its three-role form (walker / model / helper)
+  int helper_waves = 0;                     // ... with this many helper wavefronts per robot group (2: walker / model / front helper / pose helper; 1: the three-role form)
   long long direct_last = -1;               // cycle of the latest direct post (the doorbell only moves once the relay has released it)
   // shc_engine_resident_post_actions (shc_resident_rows.hpp) reads a tensor that is ready on the ENGINE's stream: the input stream follows the
   // engine's stream before the post kernel (rows_ev[0]) and the engine's stream the input stream behind it (rows_ev[1])
@@ -364,14 +364,19 @@ extern "C" int shc_engine_resident_begin(shc_engine *e, int ring_depth, int64_t 
   // - two robot groups - and the relay get a compute unit of their own; one wavefront per group above that.
   const bool two_wave = fit.two_wave && !(e->features & SHC_FEAT_RESIDENT_ONE_WAVE) && (e->n_waves + 1) / 2 + 1 <= prop.multiProcessorCount;
   r->two_wave = two_wave;
-  // ... in its three-role form where the specialisation has one (same workgroup count).  Development: SHC_RESIDENT_TWO_ROLE=1 keeps the two-role form (A/B in one build)
-  const char *two_role = getenv("SHC_RESIDENT_TWO_ROLE");
-  r->helper_wave = two_wave && fit.helper_wave && !(two_role && atoi(two_role) > 0);
+  // ... in its four-role form where the specialisation has one (same workgroup count).  Eight wavefronts of ~250 VGPRs are the whole register file of a
+  // compute unit: the four-role form runs while one compute unit per XCD stays free for the kernels that post inputs and read the output ring (as above;
+  // at 5 100 hexapods - 256 workgroups on 256 compute units - a post kernel is never scheduled beside it); the last workgroups up to the chip's size
+  // run the three-role form, whose six wavefronts leave two SIMDs of every compute unit half empty.
+  // Development: SHC_RESIDENT_TWO_ROLE=1 keeps the two-role form, SHC_RESIDENT_THREE_ROLE=1 the three-role form (A/B in one build)
+  const char *two_role = getenv("SHC_RESIDENT_TWO_ROLE"), *three_role = getenv("SHC_RESIDENT_THREE_ROLE");
+  const bool room_for_four = (e->n_waves + 1) / 2 + 1 <= prop.multiProcessorCount - kXcds;
+  r->helper_waves = !(two_wave && fit.helper_wave) || (two_role && atoi(two_role) > 0) ? 0 : (three_role && atoi(three_role) > 0) || !room_for_four ? 1 : 2;
   HIP_TRY(hipEventRecord(r->loop_ev, e->stream)); // everything the engine's stream holds (state, the buffers set up above) comes first
   HIP_TRY(hipStreamWaitEvent(r->loop_stream, r->loop_ev, 0));
   CycleLaunch a = cycle_launch(e);
   a.stream = r->loop_stream, a.resident = &A;
-  a.grid = two_wave ? unsigned((e->n_waves + 1) / 2 + 1) : unsigned(e->n_waves + 1), a.block = r->helper_wave ? 384 : two_wave ? 256 : 64;
+  a.grid = two_wave ? unsigned((e->n_waves + 1) / 2 + 1) : unsigned(e->n_waves + 1), a.block = r->helper_waves ? 256 + 128 * r->helper_waves : two_wave ? 256 : 64;
   {
     const int rc = launch_cycle_for(e, a);
     if (rc != SHC_OK) return rc;
@@ -710,10 +715,11 @@ extern "C" int shc_engine_resident_end(shc_engine *e, int64_t *cycles_run) {
   if (err == hipSuccess) {
     ResidentCtl c;
     (void)hipMemcpy(&c, r->ctl, sizeof c, hipMemcpyDeviceToHost);
-    for (int w = 0; w < (r->helper_wave ? 3 : 2); ++w) {
-      const unsigned long long *b = c.dbg + (w == 2 ? 72 : 4 * w); // (the helper's record lies behind the phase clocks of the other two)
-      fprintf(stderr, "[res2 timing] %s: %.0f clocks busy per steady REAL iteration (%llu of them), loop %llu clocks, %llu iterations\n", w == 0 ? "walker" : w == 1 ? "model " : "helper",
-              b[1] ? double(b[0]) / double(b[1]) : 0.0, b[1], b[2], b[3]);
+    const bool helper_wave = r->helper_waves > 0;
+    for (int w = 0; w < 2 + r->helper_waves; ++w) {
+      const unsigned long long *b = c.dbg + (w == 3 ? 112 : w == 2 ? 72 : 4 * w); // (the helpers' records lie behind the phase clocks of the other two)
+      fprintf(stderr, "[res2 timing] %s: %.0f clocks busy per steady REAL iteration (%llu of them), loop %llu clocks, %llu iterations\n",
+              w == 0 ? "walker" : w == 1 ? "model " : w == 3 ? "front helper" : r->helper_waves == 2 ? "pose helper" : "helper", b[1] ? double(b[0]) / double(b[1]) : 0.0, b[1], b[2], b[3]);
     }
 #ifndef SHC_RES2_BUSY_ONLY
     const int order[] = {20, 21, 2, 3, 4, 5, 6, 7, 16, 8, 17, 15, 29, 22, 23};
@@ -723,9 +729,9 @@ extern "C" int shc_engine_resident_end(shc_engine *e, int64_t *cycles_run) {
     const double its = c.dbg[1] ? double(c.dbg[1]) : 1.0;
     fprintf(stderr, "[res2 timing] walker of pair 0, mean clocks per phase:\n");
     for (int i = 0; i < int(sizeof(order) / sizeof(int)); ++i) {
-      if (r->helper_wave && order[i] == 5) continue; // (the three-role form: getLimit and the shaping are the helper's "front")
-      if (r->helper_wave && order[i] == 16) fprintf(stderr, "[res2 timing]   walker t%-2d %-58s %7.0f\n", 18, "stepper, first half + wait for the front", double(c.dbg[8 + 18]) / its);
-      fprintf(stderr, "[res2 timing]   walker t%-2d %-58s %7.0f\n", order[i], r->helper_wave && order[i] == 6 ? "command predicate" : wname[i], double(c.dbg[8 + order[i]]) / its);
+      if (helper_wave && order[i] == 5) continue; // (the helper forms: getLimit and the shaping are the helper's "front")
+      if (helper_wave && order[i] == 16) fprintf(stderr, "[res2 timing]   walker t%-2d %-58s %7.0f\n", 18, "stepper, first half + wait for the front", double(c.dbg[8 + 18]) / its);
+      fprintf(stderr, "[res2 timing]   walker t%-2d %-58s %7.0f\n", order[i], helper_wave && order[i] == 6 ? "command predicate" : wname[i], double(c.dbg[8 + order[i]]) / its);
     }
     const int morder[] = {29, 24, 30, 25, 31, 26, 9, 10, 11, 12, 27, 13, 28, 14};
     const char *mname[] = {"control words (LDS) read", "leader: gate, what the next iteration is, header prefetch issued", "pose inputs of the cycle taken",
@@ -735,16 +741,23 @@ extern "C" int shc_engine_resident_end(shc_engine *e, int64_t *cycles_run) {
     const double mits = c.dbg[5] ? double(c.dbg[5]) : 1.0;
     fprintf(stderr, "[res2 timing] model wavefront of pair 0 (the leader), mean clocks per phase:\n");
     for (int i = 0; i < int(sizeof(morder) / sizeof(int)); ++i) {
-      if (r->helper_wave && (morder[i] == 30 || morder[i] == 25)) continue; // (the three-role form: the pose's stamps are the helper's)
+      if (helper_wave && (morder[i] == 30 || morder[i] == 25)) continue; // (the helper forms: the pose's stamps are the helper's)
       fprintf(stderr, "[res2 timing]   model  t%-2d %-58s %7.0f\n", morder[i], mname[i], double(c.dbg[40 + morder[i]]) / mits);
     }
-    if (r->helper_wave) {
-      const int horder[] = {29, 24, 1, 30, 25, 26, 14};
+    for (int h = 0; h < r->helper_waves; ++h) { // (the four-role form: the front helper keeps stamps 29, 24, 1 and 14 only; the pose helper's t24 and t1 are empty, the
+      //                                             three-role helper's t2)
+      const int horder[] = {29, 24, 1, 30, 25, 2, 26, 14};
       const char *hname[] = {"control words (LDS) read", "leader: gate, what the next iteration is, header prefetch issued", "front: command, getLimit, velocity shaping + flag", "pose inputs of the cycle taken",
-                             "leg words reduced, updateCurrentPose of the walker's cycle + flag", "odometry", "control words written (leader: waits for its loads)"};
-      const double hits = c.dbg[73] ? double(c.dbg[73]) : 1.0;
-      fprintf(stderr, "[res2 timing] helper wavefront of pair 0 (the leader), mean clocks per phase:\n");
-      for (int i = 0; i < int(sizeof(horder) / sizeof(int)); ++i) fprintf(stderr, "[res2 timing]   helper t%-2d %-58s %7.0f\n", horder[i], hname[i], double(c.dbg[80 + horder[i]]) / hits);
+                             "leg words reduced, updateCurrentPose of the walker's cycle + flag", "leader (four roles): gate, next iteration, header prefetch issued", "odometry",
+                             "control words written (leader: waits for its loads)"};
+      const int busy = h ? 112 : 72, phases = h ? 120 : 80;
+      const double hits = c.dbg[busy + 1] ? double(c.dbg[busy + 1]) : 1.0;
+      const char *who = r->helper_waves == 1 ? "helper" : h ? "front helper" : "pose helper";
+      fprintf(stderr, "[res2 timing] %s wavefront of pair 0%s, mean clocks per phase:\n", who, h == 0 ? " (the leader)" : "");
+      for (int i = 0; i < int(sizeof(horder) / sizeof(int)); ++i) {
+        if (h == 1 && (horder[i] == 30 || horder[i] == 25 || horder[i] == 2 || horder[i] == 26)) continue;
+        fprintf(stderr, "[res2 timing]   %s t%-2d %-58s %7.0f\n", who, horder[i], hname[i], double(c.dbg[phases + horder[i]]) / hits);
+      }
     }
 #endif
   }
