@@ -15,61 +15,19 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 
-from .params import FEAT_DEFAULT, FRAME_IDS, BodyFrames, InstanceState, LegFrames, LegStateMsg, Params, Tables
+from . import cheader
+from .params import (FEAT_DEFAULT, FRAME_IDS, HEADER, BodyFrames, ExternalTarget, InstanceState, JointParams, LegFrames, LegSnapshot, LegStateMsg,
+                     LinkParams, Params, StepCycle, Tables, _shc)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("SHC_LIB") or os.path.join(_HERE, "libshc_batch.so")
 _SRC = os.path.join(_HERE, "csrc")
 _INC = os.path.join(os.path.dirname(_HERE), "include")
 
-SHC_OK, SHC_ERR_INVALID_ARG, SHC_ERR_NO_DEVICE, SHC_ERR_HIP, SHC_ERR_UNSUPPORTED, SHC_ERR_UNSTABLE, SHC_ERR_BUSY, SHC_ERR_TIMEOUT = range(8)
+(SHC_OK, SHC_ERR_INVALID_ARG, SHC_ERR_NO_DEVICE, SHC_ERR_HIP, SHC_ERR_UNSUPPORTED, SHC_ERR_UNSTABLE, SHC_ERR_BUSY,
+ SHC_ERR_TIMEOUT) = _shc("OK", "ERR_INVALID_ARG", "ERR_NO_DEVICE", "ERR_HIP", "ERR_UNSUPPORTED", "ERR_UNSTABLE", "ERR_BUSY", "ERR_TIMEOUT")
 
-EXPORTED_SYMBOLS = [
-    "shc_abi_version", "shc_sizeof_params", "shc_sizeof_tables", "shc_device_count", "shc_last_error", "shc_debug_plane_copy", "shc_generate_tables", "shc_engine_create",
-    "shc_engine_destroy", "shc_engine_set_stream", "shc_engine_set_features", "shc_engine_get_tables",
-    "shc_engine_instances", "shc_engine_set_velocity", "shc_engine_set_imu", "shc_engine_set_tip_force",
-    "shc_engine_set_joint_effort", "shc_engine_set_pose_input", "shc_engine_set_pose_reset_mode", "shc_engine_step", "shc_engine_synchronize",
-    "shc_engine_get_joint_state", "shc_engine_joint_buffer", "shc_engine_joint_index", "shc_engine_get_leg_state",
-    "shc_engine_get_body_state", "shc_engine_get_odometry", "shc_engine_get_virtual_stiffness",
-    "shc_engine_change_gait", "shc_stream_create", "shc_stream_destroy", "shc_engine_read_leg_state_msg",
-    "shc_generate_tables_batch", "shc_engine_create_with_tables",
-    "shc_sizeof_instance_state", "shc_engine_get_state", "shc_engine_set_state",
-    "shc_engine_set_joint_states_msg", "shc_engine_set_tip_states_msg", "shc_engine_get_joint_commands",
-    "shc_engine_set_external_target", "shc_engine_set_external_transform", "shc_engine_get_external_target",
-    "shc_leg_set_desired_tip_pose", "shc_leg_solve_ik", "shc_leg_update_joint_positions", "shc_leg_apply_ik", "shc_leg_apply_fk",
-    "shc_leg_step_to_position", "shc_leg_transition_configuration", "shc_engine_begin_direct_startup", "shc_engine_direct_startup",
-    "shc_engine_begin_sequence_startup", "shc_engine_execute_sequence", "shc_engine_finish_sequence_startup", "shc_engine_step_to_new_stance",
-    "shc_engine_pack_legs", "shc_engine_unpack_legs",
-    "shc_engine_toggle_leg_state", "shc_engine_set_manual_inputs", "shc_engine_get_leg_manipulation_state",
-    "shc_engine_set_planner_mode", "shc_engine_set_target_configuration", "shc_engine_set_target_body_pose", "shc_engine_execute_plan",
-    "shc_fleet_create", "shc_fleet_destroy", "shc_fleet_instances", "shc_fleet_shape", "shc_fleet_part_count", "shc_fleet_part",
-    "shc_fleet_part_instances", "shc_fleet_set_velocity", "shc_fleet_set_imu", "shc_fleet_set_pose_input", "shc_fleet_set_tip_force",
-    "shc_fleet_set_joint_effort", "shc_fleet_step", "shc_fleet_synchronize", "shc_fleet_get_joint_state", "shc_fleet_get_walk_state",
-    "shc_fleet_all_gather_joints",
-    "shc_engine_resident_begin", "shc_engine_resident_bind_inputs", "shc_engine_resident_post", "shc_engine_resident_publish", "shc_engine_resident_wait",
-    "shc_engine_resident_get_joint_state", "shc_engine_resident_get_joint_state_async", "shc_engine_resident_status", "shc_engine_resident_end", "shc_engine_join",
-    "shc_engine_resident_post_actions", "shc_engine_resident_get_observations_async",
-    "shc_engine_aux_state_bytes", "shc_engine_get_aux_state", "shc_engine_set_aux_state",
-    "shc_engine_step_k", "shc_engine_get_step_k_joint_state", "shc_engine_adjust_parameter",
-    "shc_engine_get_leg_state_msgs", "shc_fleet_get_leg_state_msgs",
-    "shc_engine_get_frame_transforms", "shc_fleet_get_frame_transforms",
-    "shc_engine_checkpoint_create", "shc_engine_checkpoint_update", "shc_checkpoint_destroy", "shc_engine_restore_instances", "shc_checkpoint_bytes",
-    "shc_debug_checkpoint_field_class",
-    "shc_engine_scan_health", "shc_fleet_scan_health", "shc_debug_robot_health",
-    "shc_fleet_checkpoint_create", "shc_fleet_checkpoint_update", "shc_fleet_checkpoint_destroy", "shc_fleet_checkpoint_bytes",
-    "shc_fleet_restore_instances", "shc_fleet_scan_and_restore",
-    "shc_fleet_set_inputs_device", "shc_fleet_get_outputs_device", "shc_fleet_order_after_stream", "shc_fleet_order_stream_after",
-    "shc_fleet_set_io_chunk", "shc_fleet_io_bytes",
-    "shc_fleet_step_k", "shc_fleet_get_step_k_joints_device",
-    "shc_obs_width", "shc_obs_column", "shc_engine_get_observations", "shc_fleet_get_observations_device",
-    "shc_act_width", "shc_act_column", "shc_engine_set_actions", "shc_fleet_set_actions_device",
-    "shc_engine_step_k_actions", "shc_engine_get_step_k_observations", "shc_fleet_step_k_actions_device", "shc_fleet_get_step_k_observations_device",
-    "shc_engine_get_step_k_kinematics", "shc_engine_scan_step_k_health", "shc_fleet_get_step_k_kinematics_device", "shc_fleet_scan_step_k_health_device",
-    "shc_foothold_width", "shc_foothold_column", "shc_engine_set_footholds", "shc_engine_get_footholds", "shc_fleet_set_footholds_device",
-    "shc_fleet_get_footholds_device",
-    "shc_reach_width", "shc_reach_column", "shc_engine_probe_reach", "shc_fleet_probe_reach_device",
-    "shc_peer_alloc", "shc_peer_open", "shc_peer_close", "shc_peer_scatter",
-]
+EXPORTED_SYMBOLS = list(HEADER.functions)  # every prototype of include/shc_batch.h
 
 
 def _struct_dtype(struct) -> np.dtype:
@@ -93,8 +51,9 @@ LEG_FRAMES_DTYPE, BODY_FRAMES_DTYPE = _struct_dtype(LegFrames), _struct_dtype(Bo
 
 
 # shc_engine_scan_health (include/shc_batch.h): the SHC_HEALTH_* bits of shc_robot_health.flags / shc_health_criteria.select
-HEALTH_IK_DEVIATION, HEALTH_POSITION_LIMIT, HEALTH_SPEED_LIMIT, HEALTH_NEAR_LIMIT, HEALTH_TIP_DEVIATION, HEALTH_NONFINITE = 1, 2, 4, 8, 16, 32
-HEALTH_ALL = 63
+HEALTH_IK_DEVIATION, HEALTH_POSITION_LIMIT, HEALTH_SPEED_LIMIT, HEALTH_NEAR_LIMIT, HEALTH_TIP_DEVIATION, HEALTH_NONFINITE = _shc(
+    "HEALTH_IK_DEVIATION", "HEALTH_POSITION_LIMIT", "HEALTH_SPEED_LIMIT", "HEALTH_NEAR_LIMIT", "HEALTH_TIP_DEVIATION", "HEALTH_NONFINITE")
+HEALTH_ALL = HEALTH_IK_DEVIATION | HEALTH_POSITION_LIMIT | HEALTH_SPEED_LIMIT | HEALTH_NEAR_LIMIT | HEALTH_TIP_DEVIATION | HEALTH_NONFINITE
 
 
 class HealthCriteria(C.Structure):
@@ -142,14 +101,14 @@ OBS_FIELD_NAMES = ("q", "qd", "joint_effort", "walker_tip", "target_tip", "poser
                    "stance_progress", "swing_progress", "time_to_swing_end", "step_state",
                    "body_pose", "desired_velocity", "pose_euler", "odom_to_base_link", "walk_state")
 OBS_FIELDS = {name: i for i, name in enumerate(OBS_FIELD_NAMES)}
-OBS_MAX_FIELDS = 32
-OBS_DTYPES = {"float64": 0, "float32": 1}  # SHC_OBS_F64 / SHC_OBS_F32
+OBS_MAX_FIELDS, = _shc("OBS_MAX_FIELDS")
+OBS_DTYPES = dict(zip(("float64", "float32"), _shc("OBS_F64", "OBS_F32")))
 ACT_FIELD_NAMES = ("linear_xy", "angular", "imu_orientation", "imu_angular_velocity", "pose_translation_velocity", "pose_rotation_velocity", "tip_force",
                    "joint_effort")
 ACT_FIELDS = {name: i for i, name in enumerate(ACT_FIELD_NAMES)}
 FH_FIELD_NAMES = ("position", "rotation", "transform", "swing_clearance", "frame_is_odom_ideal", "defined")  # every field is per leg
 FH_FIELDS = {name: i for i, name in enumerate(FH_FIELD_NAMES)}
-FH_MODES = {"request": 0, "refresh_transform": 1}  # SHC_FH_REQUEST / SHC_FH_REFRESH_TRANSFORM
+FH_MODES = dict(zip(("request", "refresh_transform"), _shc("FH_REQUEST", "FH_REFRESH_TRANSFORM")))
 REACH_FIELD_NAMES = ("fraction", "limit_proximity", "tip", "q")  # SHC_REACH_*: every field is per leg
 REACH_FIELDS = {name: i for i, name in enumerate(REACH_FIELD_NAMES)}
 
@@ -177,6 +136,16 @@ class ReachSpec(C.Structure):
     _fields_ = [("n_fields", C.c_int32), ("fields", C.c_int32 * len(REACH_FIELD_NAMES)), ("dtype", C.c_int32), ("legs", C.c_int32), ("dof", C.c_int32),
                 ("candidates", C.c_int32), ("steps", C.c_int32), ("reserved", C.c_int32), ("row_stride", C.c_int64), ("target_row_stride", C.c_int64),
                 ("pad", C.c_double)]
+
+
+# every struct of include/shc_batch.h that has a body, and its ctypes mirror (tests/test_abi_header.py holds each to the header, member by member)
+STRUCT_MIRRORS = {
+    "shc_joint_params": JointParams, "shc_link_params": LinkParams, "shc_params": Params, "shc_step_cycle": StepCycle, "shc_tables": Tables,
+    "shc_cycle_inputs": CycleInputs, "shc_leg_state_msg": LegStateMsg, "shc_leg_frames": LegFrames, "shc_body_frames": BodyFrames,
+    "shc_leg_snapshot": LegSnapshot, "shc_instance_state": InstanceState, "shc_external_target": ExternalTarget,
+    "shc_health_criteria": HealthCriteria, "shc_robot_health": RobotHealth, "shc_fleet_inputs": FleetInputs, "shc_fleet_outputs": FleetOutputs,
+    "shc_obs_spec": ObsSpec, "shc_act_spec": ActSpec, "shc_foothold_spec": FootholdSpec, "shc_reach_spec": ReachSpec,
+}
 
 
 class _RowPass(NamedTuple):
@@ -726,167 +695,7 @@ def lib():
     if _lib is None:
         _share_torch_hip_runtime()
         L = C.CDLL(_SO if os.environ.get("SHC_LIB") else build_library())
-        L.shc_last_error.restype = C.c_char_p
-        L.shc_sizeof_params.restype = C.c_int64
-        L.shc_debug_plane_copy.argtypes = [C.c_int, C.c_int64, C.c_int]
-        L.shc_sizeof_tables.restype = C.c_int64
-        L.shc_generate_tables.argtypes = [C.POINTER(Params), C.POINTER(Tables)]
-        L.shc_generate_tables_batch.argtypes = [C.POINTER(Params), C.c_int64, C.POINTER(Tables), C.POINTER(C.c_int32), C.c_int]
-        L.shc_engine_create_with_tables.argtypes = [C.POINTER(Params), C.POINTER(Tables), C.c_int64, C.c_int, C.c_void_p,
-                                                    C.POINTER(C.c_void_p)]
-        L.shc_engine_create.argtypes = [C.POINTER(Params), C.c_int64, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
-        L.shc_engine_destroy.argtypes = [C.c_void_p]
-        L.shc_engine_set_stream.argtypes = [C.c_void_p, C.c_void_p]
-        L.shc_engine_set_features.argtypes = [C.c_void_p, C.c_uint32]
-        L.shc_engine_get_tables.argtypes = [C.c_void_p, C.POINTER(Tables)]
-        L.shc_engine_instances.restype = C.c_int64
-        L.shc_engine_instances.argtypes = [C.c_void_p]
-        for name, n in (("shc_engine_set_velocity", 2), ("shc_engine_set_imu", 2), ("shc_engine_set_tip_force", 1),
-                        ("shc_engine_set_joint_effort", 1), ("shc_engine_set_pose_input", 2), ("shc_engine_set_pose_reset_mode", 1)):
-            getattr(L, name).argtypes = [C.c_void_p] + [C.c_void_p] * n + [C.c_int]
-        L.shc_engine_step.argtypes = [C.c_void_p, C.c_int]
-        L.shc_engine_step_k.argtypes = [C.c_void_p, C.c_int, C.POINTER(CycleInputs)]
-        L.shc_peer_alloc.argtypes = [C.c_int, C.c_int64, C.POINTER(C.c_void_p), C.c_char_p]
-        L.shc_peer_open.argtypes = [C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]
-        L.shc_peer_close.argtypes = [C.c_int, C.c_void_p, C.c_int]
-        L.shc_peer_scatter.argtypes = [C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.c_int, C.c_void_p]
-        L.shc_engine_get_step_k_joint_state.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-        L.shc_engine_join.argtypes = [C.c_void_p]
-        L.shc_engine_aux_state_bytes.argtypes = [C.c_void_p]
-        L.shc_engine_aux_state_bytes.restype = C.c_int64
-        L.shc_engine_get_aux_state.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
-        L.shc_engine_set_aux_state.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
-        L.shc_engine_checkpoint_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-        L.shc_engine_checkpoint_update.argtypes = [C.c_void_p, C.c_void_p]
-        L.shc_checkpoint_destroy.argtypes = [C.c_void_p]
-        L.shc_engine_restore_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.shc_checkpoint_bytes.argtypes = [C.c_void_p]
-        L.shc_checkpoint_bytes.restype = C.c_int64
-        L.shc_debug_checkpoint_field_class.argtypes = [C.c_int, C.c_int, C.c_int]
-        L.shc_engine_scan_health.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(HealthCriteria)] + [C.c_void_p] * 4 + [C.c_int]
-        L.shc_fleet_scan_health.argtypes = [C.c_void_p, C.POINTER(HealthCriteria), C.c_void_p]
-        L.shc_debug_robot_health.argtypes = [C.POINTER(Params), C.POINTER(HealthCriteria)] + [C.c_void_p] * 7 + [C.POINTER(RobotHealth)]
-        L.shc_fleet_checkpoint_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-        L.shc_fleet_checkpoint_update.argtypes = [C.c_void_p, C.c_void_p]
-        L.shc_fleet_checkpoint_destroy.argtypes = [C.c_void_p]
-        L.shc_fleet_checkpoint_bytes.argtypes = [C.c_void_p]
-        L.shc_fleet_checkpoint_bytes.restype = C.c_int64
-        L.shc_fleet_restore_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.shc_fleet_scan_and_restore.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(HealthCriteria), C.c_void_p, C.POINTER(C.c_int64)]
-        L.shc_fleet_set_inputs_device.argtypes = [C.c_void_p, C.POINTER(FleetInputs)]
-        L.shc_fleet_get_outputs_device.argtypes = [C.c_void_p, C.POINTER(FleetOutputs)]
-        L.shc_fleet_order_after_stream.argtypes = [C.c_void_p, C.c_void_p]
-        L.shc_fleet_order_stream_after.argtypes = [C.c_void_p, C.c_void_p]
-        L.shc_fleet_set_io_chunk.argtypes = [C.c_void_p, C.c_int64]
-        L.shc_fleet_io_bytes.argtypes = [C.c_void_p]
-        L.shc_fleet_io_bytes.restype = C.c_int64
-        L.shc_fleet_step_k.argtypes = [C.c_void_p, C.c_int, C.POINTER(FleetInputs)]
-        L.shc_fleet_get_step_k_joints_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        L.shc_engine_resident_begin.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int]
-        L.shc_engine_resident_post.argtypes = [C.c_void_p, C.POINTER(CycleInputs), C.POINTER(C.c_int64)]
-        L.shc_engine_resident_bind_inputs.argtypes = [C.c_void_p, C.c_int, C.POINTER(CycleInputs)]
-        L.shc_engine_resident_publish.argtypes = [C.c_void_p, C.c_int64]
-        L.shc_engine_resident_wait.argtypes = [C.c_void_p, C.c_int64, C.c_int]
-        L.shc_engine_resident_get_joint_state.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
-        L.shc_engine_resident_get_joint_state_async.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
-        L.shc_engine_resident_post_actions.argtypes = [C.c_void_p, C.POINTER(ActSpec), C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
-        L.shc_engine_resident_get_observations_async.argtypes = [C.c_void_p, C.c_int64, C.POINTER(ObsSpec), C.c_void_p, C.c_int]
-        L.shc_engine_resident_status.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-        L.shc_engine_resident_end.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-        L.shc_engine_synchronize.argtypes = [C.c_void_p]
-        L.shc_engine_get_joint_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.shc_engine_joint_buffer.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
-        L.shc_engine_joint_index.restype = C.c_int64
-        L.shc_engine_joint_index.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int]
-        L.shc_engine_get_leg_state.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_int]
-        L.shc_engine_get_body_state.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int]
-        L.shc_engine_get_odometry.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.shc_engine_read_leg_state_msg.argtypes = [C.c_void_p, C.c_int64, C.POINTER(LegStateMsg)]
-        L.shc_engine_get_leg_state_msgs.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int]
-        L.shc_fleet_get_leg_state_msgs.argtypes = [C.c_void_p, C.c_void_p]
-        L.shc_engine_get_frame_transforms.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-        L.shc_fleet_get_frame_transforms.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.shc_obs_width.restype = C.c_int64
-        L.shc_obs_width.argtypes = [C.POINTER(ObsSpec)]
-        L.shc_obs_column.argtypes = [C.POINTER(ObsSpec), C.c_int, C.c_int, C.c_int]
-        L.shc_engine_get_observations.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(ObsSpec), C.c_void_p, C.c_int]
-        L.shc_fleet_get_observations_device.argtypes = [C.c_void_p, C.POINTER(ObsSpec), C.c_void_p]
-        L.shc_act_width.restype = C.c_int64
-        L.shc_act_width.argtypes = [C.POINTER(ActSpec)]
-        L.shc_act_column.argtypes = [C.POINTER(ActSpec), C.c_int, C.c_int, C.c_int]
-        L.shc_engine_set_actions.argtypes = [C.c_void_p, C.POINTER(ActSpec), C.c_void_p, C.c_int]
-        L.shc_fleet_set_actions_device.argtypes = [C.c_void_p, C.POINTER(ActSpec), C.c_void_p]
-        L.shc_engine_step_k_actions.argtypes = [C.c_void_p, C.c_int, C.POINTER(ActSpec), C.c_void_p, C.c_int64]
-        L.shc_engine_get_step_k_observations.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(ObsSpec), C.c_void_p, C.c_int64]
-        L.shc_fleet_step_k_actions_device.argtypes = [C.c_void_p, C.c_int, C.POINTER(ActSpec), C.c_void_p, C.c_int64]
-        L.shc_fleet_get_step_k_observations_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(ObsSpec), C.c_void_p, C.c_int64]
-        L.shc_engine_get_step_k_kinematics.argtypes = L.shc_engine_get_step_k_observations.argtypes
-        L.shc_fleet_get_step_k_kinematics_device.argtypes = L.shc_fleet_get_step_k_observations_device.argtypes
-        L.shc_engine_scan_step_k_health.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(HealthCriteria), C.c_void_p, C.c_void_p]
-        L.shc_fleet_scan_step_k_health_device.argtypes = L.shc_engine_scan_step_k_health.argtypes
-        L.shc_foothold_width.restype = C.c_int64
-        L.shc_foothold_width.argtypes = [C.POINTER(FootholdSpec)]
-        L.shc_foothold_column.argtypes = [C.POINTER(FootholdSpec), C.c_int, C.c_int, C.c_int]
-        L.shc_engine_set_footholds.argtypes = [C.c_void_p, C.POINTER(FootholdSpec), C.c_void_p, C.c_int, C.c_void_p]
-        L.shc_engine_get_footholds.argtypes = [C.c_void_p, C.POINTER(FootholdSpec), C.c_void_p, C.c_int]
-        L.shc_fleet_set_footholds_device.argtypes = [C.c_void_p, C.POINTER(FootholdSpec), C.c_void_p, C.c_void_p]
-        L.shc_fleet_get_footholds_device.argtypes = [C.c_void_p, C.POINTER(FootholdSpec), C.c_void_p]
-        L.shc_reach_width.restype = C.c_int64
-        L.shc_reach_width.argtypes = [C.POINTER(ReachSpec)]
-        L.shc_reach_column.argtypes = [C.POINTER(ReachSpec), C.c_int, C.c_int, C.c_int]
-        L.shc_engine_probe_reach.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(ReachSpec), C.c_void_p, C.c_void_p]
-        L.shc_fleet_probe_reach_device.argtypes = [C.c_void_p, C.POINTER(ReachSpec), C.c_void_p, C.c_void_p]
-        L.shc_stream_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.shc_stream_destroy.argtypes = [C.c_int, C.c_void_p]
-        L.shc_engine_change_gait.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(C.c_int64)]
-        L.shc_engine_adjust_parameter.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_int64)]
-        L.shc_engine_get_virtual_stiffness.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.shc_sizeof_instance_state.restype = C.c_int64
-        L.shc_engine_set_joint_states_msg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.shc_engine_set_tip_states_msg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-        L.shc_engine_begin_sequence_startup.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.shc_engine_execute_sequence.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.shc_engine_finish_sequence_startup.argtypes = [C.c_void_p]
-        L.shc_engine_step_to_new_stance.argtypes = [C.c_void_p, C.c_void_p]
-        L.shc_engine_toggle_leg_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.shc_engine_set_planner_mode.argtypes = [C.c_void_p, C.c_int]
-        L.shc_engine_set_target_configuration.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
-        L.shc_engine_set_target_body_pose.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
-        L.shc_engine_execute_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.shc_engine_set_manual_inputs.argtypes = [C.c_void_p] + [C.c_void_p] * 6
-        L.shc_engine_get_leg_manipulation_state.argtypes = [C.c_void_p, C.c_void_p]
-        L.shc_engine_pack_legs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_int32)]
-        L.shc_engine_unpack_legs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_int32)]
-        L.shc_engine_set_external_target.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.POINTER(C.c_int64)]
-        L.shc_engine_set_external_transform.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p]
-        L.shc_engine_get_external_target.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_void_p]
-        L.shc_engine_get_joint_commands.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int]
-        sel = [C.c_void_p, C.c_int64, C.c_int64, C.c_int]
-        L.shc_leg_set_desired_tip_pose.argtypes = sel + [C.c_void_p, C.c_int, C.c_int]
-        L.shc_leg_solve_ik.argtypes = sel + [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-        L.shc_leg_update_joint_positions.argtypes = sel + [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-        L.shc_leg_apply_ik.argtypes = sel + [C.c_int, C.c_void_p, C.c_int]
-        L.shc_leg_apply_fk.argtypes = sel + [C.c_void_p, C.c_void_p, C.c_int]
-        L.shc_leg_step_to_position.argtypes = sel + [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-        L.shc_leg_transition_configuration.argtypes = sel + [C.c_void_p, C.c_double, C.c_void_p, C.c_int]
-        L.shc_engine_begin_direct_startup.argtypes = [C.c_void_p]
-        L.shc_fleet_create.argtypes = [C.POINTER(Params), C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]
-        L.shc_fleet_destroy.argtypes = [C.c_void_p]
-        L.shc_fleet_instances.argtypes = [C.c_void_p]
-        L.shc_fleet_instances.restype = C.c_int64
-        L.shc_fleet_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        L.shc_fleet_part_count.argtypes = [C.c_void_p]
-        L.shc_fleet_part.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64)]
-        L.shc_fleet_part_instances.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        for name, k in (("shc_fleet_set_velocity", 2), ("shc_fleet_set_imu", 2), ("shc_fleet_set_pose_input", 2), ("shc_fleet_set_tip_force", 1),
-                        ("shc_fleet_set_joint_effort", 1), ("shc_fleet_get_joint_state", 2), ("shc_fleet_get_walk_state", 1)):
-            getattr(L, name).argtypes = [C.c_void_p] + [C.c_void_p] * k
-        L.shc_fleet_step.argtypes = [C.c_void_p, C.c_int]
-        L.shc_fleet_synchronize.argtypes = [C.c_void_p]
-        L.shc_fleet_all_gather_joints.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-        L.shc_engine_direct_startup.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-        L.shc_engine_get_state.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(InstanceState)]
-        L.shc_engine_set_state.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(InstanceState)]
+        cheader.bind(L, HEADER.functions)
         # a binding whose struct layouts disagree with the library must not run
         for name, typ in (("shc_sizeof_params", Params), ("shc_sizeof_tables", Tables), ("shc_sizeof_instance_state", InstanceState)):
             if getattr(L, name)() != C.sizeof(typ):
@@ -1665,7 +1474,6 @@ class BatchEngine:
         _check(self.L.shc_engine_set_external_transform(self.h, which, first, count, leg, _p(a)), "set_external_transform")
 
     def get_external_target(self, which=0, first=0, count=None, leg=-1):
-        from .params import ExternalTarget
         count, n_rows = self._rows(first, count, leg)
         rows = (ExternalTarget * n_rows)()
         _check(self.L.shc_engine_get_external_target(self.h, which, first, count, leg, rows), "get_external_target")

@@ -12,23 +12,27 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 
-SHC_MAX_LEGS = 8
-SHC_MAX_JOINTS = 6
-SHC_MAX_LINKS = 7
-SHC_MAX_AUTO_POSERS = 8
-SHC_N_BEARINGS = 9
+from . import cheader
 
+HEADER = cheader.read(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "shc_batch.h"))
+
+
+def _shc(*names):
+    return (HEADER.constants["SHC_" + n] for n in names)   # the header's own values
+
+
+SHC_MAX_LEGS, SHC_MAX_JOINTS, SHC_MAX_LINKS, SHC_MAX_AUTO_POSERS, SHC_N_BEARINGS = _shc("MAX_LEGS", "MAX_JOINTS", "MAX_LINKS", "MAX_AUTO_POSERS", "N_BEARINGS")
 # enums of include/shc_batch.h
-WALK_STARTING, WALK_MOVING, WALK_STOPPING, WALK_STOPPED = 0, 1, 2, 3
-STEP_SWING, STEP_STANCE, STEP_FORCE_STANCE, STEP_FORCE_STOP = 0, 1, 2, 3
-VEL_THROTTLE, VEL_REAL = 0, 1
-FEAT_TIP_FORCE = 1
-FEAT_ODOMETRY = 2
-FEAT_GENERIC_KERNEL = 1 << 30  # diagnostic: runtime-flag kernel instead of the compile-time specialisation
-FEAT_SINGLE_STREAM = 1 << 28  # diagnostic: no two-stream split of large batches
-FEAT_RESIDENT_ONE_WAVE = 1 << 29  # diagnostic: resident mode without the two-wavefront (walker / model) pipeline
-FEAT_STEP_K_SERIAL = 1 << 27  # diagnostic: shc_engine_step_k as K single launches (the form configurations without a batch kernel take)
+WALK_STARTING, WALK_MOVING, WALK_STOPPING, WALK_STOPPED = _shc("WALK_STARTING", "WALK_MOVING", "WALK_STOPPING", "WALK_STOPPED")
+STEP_SWING, STEP_STANCE, STEP_FORCE_STANCE, STEP_FORCE_STOP = _shc("STEP_SWING", "STEP_STANCE", "STEP_FORCE_STANCE", "STEP_FORCE_STOP")
+VEL_THROTTLE, VEL_REAL = _shc("VEL_THROTTLE", "VEL_REAL")
+FEAT_TIP_FORCE, FEAT_ODOMETRY = _shc("FEAT_TIP_FORCE", "FEAT_ODOMETRY")
+FEAT_GENERIC_KERNEL, = _shc("FEAT_GENERIC_KERNEL")  # diagnostic: runtime-flag kernel instead of the compile-time specialisation
+FEAT_SINGLE_STREAM, = _shc("FEAT_SINGLE_STREAM")  # diagnostic: no two-stream split of large batches
+FEAT_RESIDENT_ONE_WAVE, = _shc("FEAT_RESIDENT_ONE_WAVE")  # diagnostic: resident mode without the two-wavefront (walker / model) pipeline
+FEAT_STEP_K_SERIAL, = _shc("FEAT_STEP_K_SERIAL")  # diagnostic: shc_engine_step_k as K single launches (the form configurations without a batch kernel take)
 FEAT_DEFAULT = FEAT_TIP_FORCE | FEAT_ODOMETRY  # what shc_engine_create enables
 
 
@@ -42,8 +46,8 @@ class LegStateMsg(C.Structure):
                 ("admittance_delta", C.c_double * 3), ("virtual_stiffness", C.c_double)]
 
 
-SHC_FRAME_JOINTS = 5  # joint frames per shc_leg_frames record (include/shc_batch.h)
-FRAME_BASE_LINK, FRAME_ODOM_IDEAL = 0, 1  # SHC_FRAME_*: the parent of the leg frames shc_engine_get_frame_transforms reports
+SHC_FRAME_JOINTS, = _shc("FRAME_JOINTS")  # joint frames per shc_leg_frames record
+FRAME_BASE_LINK, FRAME_ODOM_IDEAL = _shc("FRAME_BASE_LINK", "FRAME_ODOM_IDEAL")  # the parent of the leg frames shc_engine_get_frame_transforms reports
 FRAME_IDS = {"base_link": FRAME_BASE_LINK, "odom_ideal": FRAME_ODOM_IDEAL}
 
 
@@ -64,7 +68,7 @@ class ExternalTarget(C.Structure):
                 ("frame_is_odom_ideal", C.c_int32), ("defined", C.c_int32)]
 
 
-EXTERNAL_TARGET, EXTERNAL_DEFAULT = 0, 1
+EXTERNAL_TARGET, EXTERNAL_DEFAULT = _shc("EXTERNAL_TARGET", "EXTERNAL_DEFAULT")
 
 
 class LegSnapshot(C.Structure):
@@ -381,7 +385,8 @@ def synthetic_mixed_dof_params(gait: str = "ripple", dofs=(3, 5, 4, 3, 5, 4)) ->
 
 # enum ParameterSelection (parameters_and_states.h:165-178) = SHC_PARAM_* of include/shc_batch.h: the run-time adjustable parameters
 (PARAM_STEP_FREQUENCY, PARAM_SWING_HEIGHT, PARAM_SWING_WIDTH, PARAM_STEP_DEPTH, PARAM_STANCE_SPAN_MODIFIER, PARAM_VIRTUAL_MASS, PARAM_VIRTUAL_STIFFNESS,
- PARAM_VIRTUAL_DAMPING, PARAM_FORCE_GAIN) = range(1, 10)
+ PARAM_VIRTUAL_DAMPING, PARAM_FORCE_GAIN) = _shc("PARAM_STEP_FREQUENCY", "PARAM_SWING_HEIGHT", "PARAM_SWING_WIDTH", "PARAM_STEP_DEPTH", "PARAM_STANCE_SPAN_MODIFIER",
+                                                 "PARAM_VIRTUAL_MASS", "PARAM_VIRTUAL_STIFFNESS", "PARAM_VIRTUAL_DAMPING", "PARAM_FORCE_GAIN")
 PARAM_FIELD = {PARAM_STEP_FREQUENCY: "step_frequency", PARAM_SWING_HEIGHT: "swing_height", PARAM_SWING_WIDTH: "swing_width", PARAM_STEP_DEPTH: "step_depth",
                PARAM_STANCE_SPAN_MODIFIER: "stance_span_modifier", PARAM_VIRTUAL_MASS: "virtual_mass", PARAM_VIRTUAL_STIFFNESS: "virtual_stiffness",
                PARAM_VIRTUAL_DAMPING: "virtual_damping_ratio", PARAM_FORCE_GAIN: "force_gain"}

@@ -2,8 +2,6 @@
 header; the entry points are declared and exported; and tests/frames_numpy.py - the numpy reading of publishFrameTransforms the GPU tests
 compare against - agrees with scipy's Rotation on every rotation as a rotation."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 
@@ -11,25 +9,12 @@ import frames_numpy as fn
 from syropod_highlevel_controller_amd import engine, synthetic_octopod_params
 from syropod_highlevel_controller_amd.params import SHC_FRAME_JOINTS, BodyFrames, LegFrames, LinkParams
 
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "shc_batch.h")
-
 
 def header_fields(struct):
     """(name, shape) of every member of `struct` in the header, in declaration order."""
-    text = open(HEADER).read()
-    consts = {k: int(v) for k, v in re.findall(r"#define (SHC_\w+) (\d+)\b", text)}
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    out = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        assert decl.startswith("double "), decl
-        for item in decl[len("double "):].split(","):
-            m = re.fullmatch(r"\s*(\w+)\s*((?:\[\w+\])*)\s*", item)
-            out.append((m.group(1), tuple(consts[k] if k in consts else int(k) for k in re.findall(r"\[(\w+)\]", m.group(2)))))
-    return out
+    fields = engine.HEADER.structs[struct]
+    assert all(typ == "double" for typ, _, _ in fields)
+    return [(name, dims) for _, name, dims in fields]
 
 
 def ctypes_shape(typ):
@@ -75,11 +60,10 @@ def test_numpy_dtypes_follow_the_ctypes_mirrors():
 
 
 def test_new_entry_points_are_declared_and_exported():
-    text = open(HEADER).read()
     for sym in ("shc_engine_get_frame_transforms", "shc_fleet_get_frame_transforms"):
-        assert re.search(r"\bint " + sym + r"\(", text) and sym in engine.EXPORTED_SYMBOLS
+        assert engine.HEADER.functions[sym][0] == "int" and sym in engine.EXPORTED_SYMBOLS
         assert hasattr(engine.lib(), sym)
-    assert re.search(r"SHC_FRAME_BASE_LINK = 0\b", text) and re.search(r"SHC_FRAME_ODOM_IDEAL = 1\b", text)
+    assert engine.HEADER.constants["SHC_FRAME_BASE_LINK"] == 0 and engine.HEADER.constants["SHC_FRAME_ODOM_IDEAL"] == 1
     assert engine.FRAME_IDS == {"base_link": 0, "odom_ideal": 1}
     assert engine.lib().shc_abi_version() == 6
 

@@ -141,8 +141,6 @@ def test_facade_adjust_parameter(tmp_path):
     waited, flag = int(out[0].split()[1]), int(out[0].split()[3])
     q_gpu = np.array([float(x) for x in out[1:19]])
     L = oracle_lib.lib()
-    L.orc_request_parameter_adjust.argtypes = [C.c_void_p, C.c_int, C.c_double]
-    L.orc_parameter_adjust_pending.argtypes = [C.c_void_p]
     r = OracleRobot(p)
     r.set_velocity(*v)
     waited_ref = 0

@@ -1,7 +1,6 @@
 """CPU: the product's host init chain (libshc_batch.so, no GPU needed) against the oracle's, and the C ABI surface."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
@@ -97,9 +96,7 @@ def test_tables_match_oracle(name, p):
 
 
 def test_library_exports_every_declared_symbol():
-    hdr = open(os.path.join(ROOT, "include", "shc_batch.h")).read()
-    declared = set(re.findall(r"\b(shc_[a-z_]+)\s*\(", hdr))
-    declared -= {"shc_engine"}
+    declared = set(engine.HEADER.functions)   # (tests/test_abi_header.py holds the reader to a crude count of the header's own text)
     assert declared == set(engine.EXPORTED_SYMBOLS), declared ^ set(engine.EXPORTED_SYMBOLS)
     lib = C.CDLL(engine.build_library())
     for sym in declared:
@@ -162,7 +159,7 @@ def test_product_does_not_reference_the_oracle():
 
 
 _NULL_SWEEP = r'''
-import ctypes as C, json, re, sys
+import ctypes as C, json, sys
 sys.path.insert(0, sys.argv[1])
 from syropod_highlevel_controller_amd import engine
 lib = C.CDLL(engine.build_library())
@@ -179,7 +176,7 @@ for name, ret, args in decls:
             types.append(C.c_void_p)
             vals.append(C.addressof(scratch) if pointers else None)
         else:
-            t = INT[re.sub(r"\bconst\b", "", a).split()[0]]
+            t = INT[a]
             types.append(t)
             vals.append(t(1 if pointers else 0))
     f.argtypes = types
@@ -190,14 +187,9 @@ print("RESULT " + json.dumps(out), flush=True)
 
 
 def _engine_entry_points():
-    """Every shc_engine_* declaration of the public header that takes the engine first: (name, return type, [argument declarations])."""
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "shc_batch.h")).read(), flags=re.S)
-    decls = []
-    for m in re.finditer(r"\b(int|int64_t)\s+(shc_engine_\w+)\s*\(([^)]*)\)\s*;", hdr):
-        args = [" ".join(a.split()) for a in m.group(3).split(",")]
-        if re.match(r"(const\s+)?shc_engine\s*\*\s*e$", args[0]):
-            decls.append((m.group(2), m.group(1), args))
-    return decls
+    """Every shc_engine_* declaration of the public header that takes the engine first: (name, return type, [argument types])."""
+    return [(name, ret, [t for t, _ in params]) for name, (ret, params) in engine.HEADER.functions.items()
+            if name.startswith("shc_engine_") and ret in ("int", "int64_t") and params and params[0] in (("shc_engine *", "e"), ("const shc_engine *", "e"))]
 
 
 @pytest.mark.parametrize("pointers", ["null", "buffers"])

@@ -225,12 +225,9 @@ def test_walk_trajectories(name, meta):
             elif kind == "pose_reset_mode":
                 L.orc_set_pose_reset_mode(r.h, int(v[0]))
         if "gait_request" in g and g["gait_request"][c]:   # gait_change_flag_ set: changeGait runs every loop until the robot has stopped
-            L.orc_change_gait.argtypes = [C.c_void_p, C.c_void_p]
             L.orc_change_gait(r.h, C.byref(default_hexapod_params(meta["overrides"]["gait_change"])))
         r.set_velocity(float(g["lin"][c][0]), float(g["lin"][c][1]), float(g["ang"][c]))
         if "adjust_request" in g:   # parameterAdjustCallback sets parameter_adjust_flag_; runningState serves it inside the loops (state_running_state) until it is set
-            L.orc_request_parameter_adjust.argtypes = [C.c_void_p, C.c_int, C.c_double]
-            L.orc_parameter_adjust_pending.argtypes = [C.c_void_p]
             fresh = g["adjust_request"][c] and (c == 0 or g["adjust_request"][c - 1] != g["adjust_request"][c] or g["adjust_value"][c - 1] != g["adjust_value"][c])
             if fresh:
                 L.orc_request_parameter_adjust(r.h, int(g["adjust_request"][c]), float(g["adjust_value"][c]))
@@ -257,7 +254,6 @@ def test_walk_trajectories(name, meta):
         worst_pose = max(worst_pose, np.abs(q - g["pose"][c]).max())
         assert worst_tip < 1e-9 and worst_pose < 1e-9, (name, c, worst_tip, worst_pose)
         odo = np.zeros(7)                     # WalkController::odometry_ideal_: the desired body velocity integrated (:643, :783-791)
-        L.orc_get_odometry.argtypes = [C.c_void_p, C.c_void_p]
         L.orc_get_odometry(r.h, _ptr(odo))
         if odo[3] < 0:
             odo[3:] = -odo[3:]
