@@ -7,13 +7,16 @@
 // the boundary whatever the interleaving pattern.  The only exchange is the all-gather of the final joint-state buffer:
 // every device ends up with every instance's joints, copied device to device (hipMemcpyPeerAsync: xGMI on an MI355X node).
 // One-process-per-GPU hosts (bench.py under torch.distributed) do the same exchange with RCCL instead.
-// The host setters of the per-robot input groups take each group's width from the group table of shc_inputs.hpp (fleet_pick), as the device
-// forms behind this file do.
+// What crosses that boundary is translated in one place: shc_fleet_order.hpp states pick (the caller's padded rows -> a part's dense rows) and
+// place (back, padding written) on the host, shc_fleet_io.hpp holds the same two as kernels and the one walk over the inputs and the one over
+// the outputs that every setter and getter, host or device form, runs through.  This file creates the fleet, steps it and exchanges the joints.
 #pragma once
 
 #include <algorithm>
 #include <cmath>
 #include <vector>
+
+#include "shc_fleet_order.hpp" // pick and place between the caller's rows and a part's, on the host
 
 struct FleetPart {
   shc_engine *engine = nullptr;
@@ -45,8 +48,7 @@ struct shc_fleet {
   int max_legs = 0, max_dof = 0;
   std::vector<double *> gather; // per device: [n][max_legs][max_dof], NaN padded
   std::vector<hipStream_t> gather_stream; // per device: incoming peer copies + their placement
-  std::vector<double> host_a, host_b;
-  std::vector<int32_t> host_i;
+  FleetScratch scratch; // the host route's dense rows of one part (shc_fleet_order.hpp)
   // fleet checkpoints (shc_fleet_checkpoint.hpp)
   struct shc_fleet_checkpoint *checkpoints = nullptr; // the registry of this fleet's checkpoint handles: orphaned with the fleet
   std::vector<int32_t> ck_part_of;   // caller's id -> its part ...
@@ -211,60 +213,6 @@ static int fleet_part_ids(FleetPart &p) {
   return SHC_OK;
 }
 
-// caller-order rows of per-robot input group g (shc_inputs.hpp) -> the part's rows
-static const double *fleet_pick(shc_fleet *f, const FleetPart &p, const double *src, int g, std::vector<double> &buf) {
-  if (!src) return nullptr;
-  const int width = input_group(g).width;
-  buf.resize(p.ids.size() * size_t(width));
-  for (size_t k = 0; k < p.ids.size(); ++k) std::copy(src + p.ids[k] * width, src + (p.ids[k] + 1) * width, buf.begin() + k * width);
-  return buf.data();
-}
-
-extern "C" int shc_fleet_set_velocity(shc_fleet *f, const double *linear_xy, const double *angular) {
-  if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
-  for (auto &p : f->parts) {
-    const int rc = shc_engine_set_velocity(p.engine, fleet_pick(f, p, linear_xy, SHC_ACT_LINEAR_XY, f->host_a), fleet_pick(f, p, angular, SHC_ACT_ANGULAR, f->host_b), 0);
-    if (rc != SHC_OK) return rc;
-  }
-  return SHC_OK;
-}
-extern "C" int shc_fleet_set_imu(shc_fleet *f, const double *orientation_wxyz, const double *angular_velocity) {
-  if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
-  for (auto &p : f->parts) {
-    const int rc = shc_engine_set_imu(p.engine, fleet_pick(f, p, orientation_wxyz, SHC_ACT_IMU_ORIENTATION, f->host_a), fleet_pick(f, p, angular_velocity, SHC_ACT_IMU_ANGULAR_VELOCITY, f->host_b), 0);
-    if (rc != SHC_OK) return rc;
-  }
-  return SHC_OK;
-}
-extern "C" int shc_fleet_set_pose_input(shc_fleet *f, const double *translation_velocity, const double *rotation_velocity) {
-  if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
-  for (auto &p : f->parts) {
-    const int rc = shc_engine_set_pose_input(p.engine, fleet_pick(f, p, translation_velocity, SHC_ACT_POSE_TRANSLATION_VELOCITY, f->host_a),
-                                             fleet_pick(f, p, rotation_velocity, SHC_ACT_POSE_ROTATION_VELOCITY, f->host_b), 0);
-    if (rc != SHC_OK) return rc;
-  }
-  return SHC_OK;
-}
-// per-leg inputs arrive padded: [n][max_legs][max_k]; entries beyond a morphology's (legs, k) are ignored
-static int fleet_set_leg(shc_fleet *f, const double *src, int max_k, bool per_dof, int (*setter)(shc_engine *, const double *, int)) {
-  if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
-  if (!src) return SHC_OK;
-  for (auto &p : f->parts) {
-    const shc_params &pp = f->params[p.morph];
-    const int L = pp.leg_count, K = per_dof ? max_dof(pp) : max_k;
-    f->host_a.resize(p.ids.size() * size_t(L) * K);
-    for (size_t k = 0; k < p.ids.size(); ++k)
-      for (int l = 0; l < L; ++l)
-        for (int j = 0; j < K; ++j) f->host_a[(k * L + l) * K + j] = src[(size_t(p.ids[k]) * f->max_legs + l) * max_k + j];
-    const int rc = setter(p.engine, f->host_a.data(), 0);
-    if (rc != SHC_OK) return rc;
-  }
-  return SHC_OK;
-}
-extern "C" int shc_fleet_set_tip_force(shc_fleet *f, const double *tip_force) { return fleet_set_leg(f, tip_force, 3, false, shc_engine_set_tip_force); }
-extern "C" int shc_fleet_set_joint_effort(shc_fleet *f, const double *joint_effort) {
-  return fleet_set_leg(f, joint_effort, f ? f->max_dof : 0, true, shc_engine_set_joint_effort);
-}
 extern "C" int shc_fleet_shape(const shc_fleet *f, int *max_legs, int *max_dof) {
   if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
   if (max_legs) *max_legs = f->max_legs;
@@ -290,100 +238,13 @@ extern "C" int shc_fleet_synchronize(shc_fleet *f) {
   return SHC_OK;
 }
 
-// q / qd: [n][max_legs][max_dof] in the caller's instance order, NaN where a morphology has no such leg / joint
-extern "C" int shc_fleet_get_joint_state(shc_fleet *f, double *q, double *qd) {
-  if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
-  const size_t row = size_t(f->max_legs) * f->max_dof;
-  for (double *dst : {q, qd})
-    if (dst) std::fill(dst, dst + size_t(f->n) * row, std::nan(""));
-  for (auto &p : f->parts) {
-    const shc_params &pp = f->params[p.morph];
-    const int L = pp.leg_count, D = max_dof(pp);
-    f->host_a.resize(p.ids.size() * size_t(L) * D);
-    f->host_b.resize(f->host_a.size());
-    const int rc = shc_engine_get_joint_state(p.engine, q ? f->host_a.data() : nullptr, qd ? f->host_b.data() : nullptr, 0);
-    if (rc != SHC_OK) return rc;
-    for (size_t k = 0; k < p.ids.size(); ++k)
-      for (int l = 0; l < L; ++l)
-        for (int j = 0; j < D; ++j) {
-          const size_t o = size_t(p.ids[k]) * row + size_t(l) * f->max_dof + j;
-          if (q) q[o] = f->host_a[(k * L + l) * D + j];
-          if (qd) qd[o] = f->host_b[(k * L + l) * D + j];
-        }
-  }
-  return SHC_OK;
-}
-// publishLegState of every robot: msgs[i * max_legs + l] in the caller's instance order; the records of legs a robot does not have are all
-// zero.  Every part is read on its own device and stream (shc_engine_get_leg_state_msgs), then placed at its instances' ids.
-extern "C" int shc_fleet_get_leg_state_msgs(shc_fleet *f, shc_leg_state_msg *msgs) {
-  if (!f || !msgs) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
-  memset(msgs, 0, size_t(f->n) * f->max_legs * sizeof(shc_leg_state_msg));
-  std::vector<shc_leg_state_msg> rows;
-  for (auto &p : f->parts) {
-    const int L = f->params[p.morph].leg_count;
-    rows.resize(p.ids.size() * size_t(L));
-    const int rc = shc_engine_get_leg_state_msgs(p.engine, 0, int64_t(p.ids.size()), rows.data(), 0);
-    if (rc != SHC_OK) return rc;
-    for (size_t k = 0; k < p.ids.size(); ++k) std::copy(rows.begin() + k * L, rows.begin() + (k + 1) * L, msgs + size_t(p.ids[k]) * f->max_legs);
-  }
-  return SHC_OK;
-}
-// publishFrameTransforms of every robot: legs[i * max_legs + l] and body[i] in the caller's instance order (either may be NULL); the leg
-// records of legs a robot does not have are all zero.  Every part is read on its own device and stream (shc_engine_get_frame_transforms).
-extern "C" int shc_fleet_get_frame_transforms(shc_fleet *f, int frame, shc_leg_frames *legs, shc_body_frames *body) {
-  if (!f || (!legs && !body)) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
-  if (legs) memset(legs, 0, size_t(f->n) * f->max_legs * sizeof(shc_leg_frames));
-  std::vector<shc_leg_frames> rows;
-  std::vector<shc_body_frames> brows;
-  for (auto &p : f->parts) {
-    const int L = f->params[p.morph].leg_count;
-    if (legs) rows.resize(p.ids.size() * size_t(L));
-    if (body) brows.resize(p.ids.size());
-    const int rc = shc_engine_get_frame_transforms(p.engine, 0, int64_t(p.ids.size()), frame, legs ? rows.data() : nullptr, body ? brows.data() : nullptr, 0);
-    if (rc != SHC_OK) return rc;
-    for (size_t k = 0; k < p.ids.size(); ++k) {
-      if (legs) std::copy(rows.begin() + k * L, rows.begin() + (k + 1) * L, legs + size_t(p.ids[k]) * f->max_legs);
-      if (body) body[p.ids[k]] = brows[k];
-    }
-  }
-  return SHC_OK;
-}
-// shc_engine_scan_health of every part: the records in the caller's instance order
-extern "C" int shc_fleet_scan_health(shc_fleet *f, const shc_health_criteria *criteria, shc_robot_health *health) {
-  if (!f || !health) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
-  std::vector<shc_robot_health> rows;
-  for (auto &p : f->parts) {
-    rows.resize(p.ids.size());
-    const int rc = shc_engine_scan_health(p.engine, 0, int64_t(p.ids.size()), criteria, rows.data(), nullptr, nullptr, nullptr, 0);
-    if (rc != SHC_OK) return rc;
-    for (size_t k = 0; k < p.ids.size(); ++k) health[p.ids[k]] = rows[k];
-  }
-  return SHC_OK;
-}
-extern "C" int shc_fleet_get_walk_state(shc_fleet *f, int32_t *walk_state) {
-  if (!f || !walk_state) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
-  for (auto &p : f->parts) {
-    f->host_i.resize(p.ids.size());
-    const int rc = shc_engine_get_body_state(p.engine, nullptr, nullptr, f->host_i.data(), 0);
-    if (rc != SHC_OK) return rc;
-    for (size_t k = 0; k < p.ids.size(); ++k) walk_state[p.ids[k]] = f->host_i[k];
-  }
-  return SHC_OK;
-}
-
-// Scatter of one part's joints ([rows][L][D], contiguous) into a gather buffer ([n][max_legs][max_dof]) at the caller's ids.
-__global__ void fleet_place_joints_kernel(double *gather, const double *part, const int64_t *ids, int64_t rows, int L, int D, int max_legs, int max_dof) {
-  const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (t >= rows * L * D) return;
-  const int64_t k = t / (L * D);
-  const int r = int(t - k * L * D), l = r / D, j = r - l * D;
-  gather[(ids[k] * max_legs + l) * max_dof + j] = part[t];
-}
+#include "shc_fleet_io.hpp" // the setters and getters, host and device forms: one walk over the inputs, one over the outputs, two routes
 
 // The exchange step: every device ends up with the desired joint positions of ALL instances ([n][max_legs][max_dof], NaN
 // padded, caller's order) in its own HBM; device_buffers[d] receives device d's buffer (owned by the fleet).  Each part
 // gathers its joints on its own device and stream, places them in the local buffer, and every other device pulls the part's
-// rows with one peer copy on its own gather stream (ordered behind the part by an event) and places them on its side.
+// rows with one peer copy on its own gather stream (ordered behind the part by an event) and places them on its side - the
+// place of the device I/O (fleet_place), which writes the NaN padding of its rows with every exchange.
 // Direct peer copies rather than a ring collective: xGMI is point to point (7 links per GPU), so the (device, device) pairs use
 // their own links concurrently - 1/8 of the data per link instead of the 7/8 a ring all-gather pushes through each - and a
 // single-process host needs no communicator; the one-process-per-GPU host (bench.py, parallel.py) exchanges the same buffer
@@ -396,11 +257,7 @@ extern "C" int shc_fleet_all_gather_joints(shc_fleet *f, double **device_buffers
   for (int d = 0; d < nd; ++d) {
     HIP_TRY(hipSetDevice(f->devices[d]));
     if (!f->gather_stream[d]) HIP_TRY(hipStreamCreateWithFlags(&f->gather_stream[d], hipStreamNonBlocking));
-    if (!f->gather[d]) { // NaN padding (0xFF bytes are a NaN pattern), written once: the parts only ever overwrite their own entries
-      HIP_TRY(hipMalloc(&f->gather[d], total * 8));
-      HIP_TRY(hipMemsetAsync(f->gather[d], 0xFF, total * 8, f->gather_stream[d]));
-      HIP_TRY(hipStreamSynchronize(f->gather_stream[d]));
-    }
+    if (!f->gather[d]) HIP_TRY(hipMalloc(&f->gather[d], total * 8)); // (every word is written by every exchange: the parts' ids partition [0, n), and place writes the padding)
   }
   for (auto &p : f->parts) { // first call: the part's own buffers, the landing buffers on the other devices, the ids everywhere
     if (p.g_joints) continue;
@@ -423,17 +280,13 @@ extern "C" int shc_fleet_all_gather_joints(shc_fleet *f, double **device_buffers
   for (auto &p : f->parts) { // every part: joints -> its buffer -> the local gather buffer(s), on its own stream
     const shc_params &pp = f->params[p.morph];
     const int L = pp.leg_count, D = max_dof(pp);
-    const int64_t rows = int64_t(p.ids.size()), threads = rows * L * D;
+    const int64_t rows = int64_t(p.ids.size());
     HIP_TRY(hipSetDevice(p.device));
-    const int rc = shc_engine_get_joint_state(p.engine, p.g_joints, nullptr, 1);
+    int rc = shc_engine_get_joint_state(p.engine, p.g_joints, nullptr, 1);
     if (rc != SHC_OK) return rc;
     HIP_TRY(hipEventRecord(p.g_ready, p.stream));
-    for (int d = 0; d < nd; ++d)
-      if (f->devices[d] == p.device) { // (also covers several device slots naming one device)
-        fleet_place_joints_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, p.stream>>>(f->gather[d], p.g_joints, p.d_ids, rows, L, D, f->max_legs,
-                                                                                                   f->max_dof);
-        HIP_TRY(hipGetLastError());
-      }
+    for (int d = 0; d < nd; ++d) // (also covers several device slots naming one device)
+      if (f->devices[d] == p.device && (rc = fleet_place(p.stream, f->gather[d], p.g_joints, p.d_ids, rows, L, D, f->max_legs, f->max_dof, nan_word())) != SHC_OK) return rc;
   }
   for (auto &p : f->parts) { // every other device pulls the part's rows and places them
     const shc_params &pp = f->params[p.morph];
@@ -444,9 +297,7 @@ extern "C" int shc_fleet_all_gather_joints(shc_fleet *f, double **device_buffers
       HIP_TRY(hipSetDevice(f->devices[d]));
       HIP_TRY(hipStreamWaitEvent(f->gather_stream[d], p.g_ready, 0));
       HIP_TRY(hipMemcpyPeerAsync(p.r_joints[d], f->devices[d], p.g_joints, p.device, size_t(threads) * 8, f->gather_stream[d]));
-      fleet_place_joints_kernel<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, f->gather_stream[d]>>>(f->gather[d], p.r_joints[d], p.r_ids[d], rows, L, D,
-                                                                                                            f->max_legs, f->max_dof);
-      HIP_TRY(hipGetLastError());
+      if (const int rc = fleet_place(f->gather_stream[d], f->gather[d], p.r_joints[d], p.r_ids[d], rows, L, D, f->max_legs, f->max_dof, nan_word())) return rc;
     }
   }
   for (auto &p : f->parts) {
@@ -463,7 +314,6 @@ extern "C" int shc_fleet_all_gather_joints(shc_fleet *f, double **device_buffers
 }
 
 #include "shc_fleet_checkpoint.hpp" // shc_fleet_checkpoint_*, shc_fleet_restore_instances, shc_fleet_scan_and_restore
-#include "shc_fleet_io.hpp" // shc_fleet_set_inputs_device, shc_fleet_get_outputs_device, the two ordering calls
 #include "shc_fleet_step_k.hpp" // shc_fleet_step_k, shc_fleet_get_step_k_joints_device: K cycles per launch from K-deep device arrays
 #include "shc_fleet_observe.hpp" // shc_fleet_get_observations_device: chosen fields of every robot straight into the caller's rows
 #include "shc_fleet_actions.hpp" // shc_fleet_set_actions_device: chosen input groups of every robot straight from the caller's rows

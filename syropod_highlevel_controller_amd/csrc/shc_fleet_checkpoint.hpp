@@ -235,14 +235,14 @@ extern "C" int shc_fleet_scan_and_restore(shc_fleet *f, const shc_fleet_checkpoi
   }
   if (!health && !n_restored) return SHC_OK;
   // the records and the counts come back on each part's stream, behind its scan; one wait per part
-  std::vector<shc_robot_health> rows(health ? size_t(f->n) : 0);
+  shc_robot_health *rows = reinterpret_cast<shc_robot_health *>(f->scratch.room(health ? size_t(f->n) * sizeof(shc_robot_health) : 0)); // part by part, dense
   std::vector<int64_t> counts(f->parts.size(), 0);
   size_t at = 0;
   for (size_t k = 0; k < f->parts.size(); ++k) {
     FleetPart &p = f->parts[k];
     const FleetCkBlock b = fleet_ck_block(p.ids.size());
     HIP_TRY(hipSetDevice(p.device));
-    if (health) HIP_TRY(hipMemcpyAsync(rows.data() + at, p.ck_block + b.health, p.ids.size() * sizeof(shc_robot_health), hipMemcpyDeviceToHost, p.engine->stream));
+    if (health) HIP_TRY(hipMemcpyAsync(rows + at, p.ck_block + b.health, p.ids.size() * sizeof(shc_robot_health), hipMemcpyDeviceToHost, p.engine->stream));
     if (n_restored) HIP_TRY(hipMemcpyAsync(&counts[k], p.ck_block + b.count, 8, hipMemcpyDeviceToHost, p.engine->stream));
     at += p.ids.size();
   }
@@ -252,8 +252,8 @@ extern "C" int shc_fleet_scan_and_restore(shc_fleet *f, const shc_fleet_checkpoi
     FleetPart &p = f->parts[k];
     HIP_TRY(hipSetDevice(p.device));
     HIP_TRY(hipStreamSynchronize(p.engine->stream));
-    if (health)
-      for (size_t j = 0; j < p.ids.size(); ++j) health[p.ids[j]] = rows[at + j];
+    if (health) // (a record is four 8-byte words: shc_health.hpp)
+      fleet_place_host(reinterpret_cast<uint64_t *>(health), reinterpret_cast<const uint64_t *>(rows + at), p.ids.data(), int64_t(p.ids.size()), 1, 4, 1, 4, uint64_t(0));
     at += p.ids.size();
     total += counts[k];
   }

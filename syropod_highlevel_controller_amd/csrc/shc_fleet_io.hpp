@@ -1,15 +1,20 @@
-// shc_fleet_io.hpp — fleet device I/O: shc_fleet_set_inputs_device, shc_fleet_get_outputs_device, shc_fleet_order_after_stream,
-// shc_fleet_order_stream_after, shc_fleet_set_io_chunk, shc_fleet_io_bytes.  Included by shc_fleet.hpp.  (K cycles per launch from K-deep
-// device arrays - shc_fleet_step_k, shc_fleet_get_step_k_joints_device - is shc_fleet_step_k.hpp, built on what is here.)
+// shc_fleet_io.hpp — fleet I/O, host and device forms: the five host setters (shc_fleet_set_velocity .. _set_joint_effort) and
+// shc_fleet_set_inputs_device, the five host getters (shc_fleet_get_joint_state .. shc_fleet_scan_health) and shc_fleet_get_outputs_device,
+// shc_fleet_order_after_stream, shc_fleet_order_stream_after, shc_fleet_set_io_chunk, shc_fleet_io_bytes.  Included by shc_fleet.hpp.  (K cycles
+// per launch from K-deep device arrays - shc_fleet_step_k, shc_fleet_get_step_k_joints_device - is shc_fleet_step_k.hpp, built on what is here.)
 //
-// The host forms (shc_fleet_set_* / shc_fleet_get_*) permute rows between the caller's padded order and a part's dense order on the host and
-// cross it once per part and call.  Here both sides are device arrays and the permutation is a kernel on the part's own stream: PACK gathers
-// the rows of a part out of the caller's input arrays into the part's staging, PLACE scatters a part's rows out of staging into the caller's
-// buffers.  Between staging and the state stand the engines' own device forms (shc_engine_set_*(.., on_device = 1), shc_engine_get_*(..,
-// on_device = 1)), so every side effect of a setter or getter - RT_TOUCHDOWN and touchdown detection, the first-effort switch, RT_MANUAL_LIVE,
-// quaternion normalisation, the derived-tip refresh, inputs riding the two half streams of split steps - is the engine's, written once.
+// Every one of them translates between the caller's padded order and a part's dense order (shc_fleet_order.hpp: pick and place) and does nothing
+// else: between a part's dense rows and its state stand the engine's own setters and getters, so every side effect of one - RT_TOUCHDOWN and
+// touchdown detection, the first-effort switch, RT_MANUAL_LIVE, quaternion normalisation, the derived-tip refresh, inputs riding the two half
+// streams of split steps - is the engine's, written once.  There is ONE walk over the inputs (fleet_inputs_walk: which engine setter is entered
+// for which groups) and ONE over the outputs (fleet_outputs_walk: every output's engine getter, word size and padding), and two routes through
+// each:
+//   host route    the dense rows are the fleet's host scratch buffer, pick and place are the loops of shc_fleet_order.hpp, the engine calls are
+//                 given on_device = 0 and a part is read in one piece.  Needs no single device and allocates nothing on one.
+//   device route  the dense rows are the part's staging on the device, PACK and PLACE below are kernels on the part's own stream, the engine
+//                 calls are given on_device = 1 and the record outputs walk a part in chunks.
 //
-// One staging buffer per part, allocated by the fleet's first device I/O call and kept.  Every use of it is ordered on the part's stream: the
+// The device route's staging: one buffer per part, allocated by the fleet's first device I/O call and kept.  Every use of it is ordered on the part's stream: the
 // engine getters join split steps before they write it, and a setter that scatters on the half streams orders the part's stream behind those
 // reads (split_inputs_end), so the next pack cannot overwrite rows a half has not read yet.  Its size is the largest of
 //   inputs:   rows x (16 + 3 L + L D) doubles   (all eight groups of one call - input_plan of shc_inputs.hpp -, packed by one launch),
@@ -93,32 +98,37 @@ static uint64_t nan_word() {
   return word;
 }
 
+// PLACE on `stream`: the dense `rows` of a part into dst at `ids` (Word: that of the padding)
 template <class Word>
-static int fleet_place(const FleetPart &p, Word *dst, int64_t first, int64_t count, int legs, int k, int dst_legs, int dst_k, Word pad) {
-  fleet_place_kernel<Word><<<dim3(fleet_io_grid(count * dst_legs * dst_k)), dim3(256), 0, p.engine->stream>>>(dst, reinterpret_cast<const Word *>(p.io_stage), p.d_ids + first,
-                                                                                                          count, legs, k, dst_legs, dst_k, pad);
+static int fleet_place(hipStream_t stream, void *dst, const void *rows, const int64_t *ids, int64_t count, int legs, int k, int dst_legs, int dst_k, Word pad) {
+  fleet_place_kernel<Word><<<dim3(fleet_io_grid(count * dst_legs * dst_k)), dim3(256), 0, stream>>>(static_cast<Word *>(dst), static_cast<const Word *>(rows), ids, count, legs, k,
+                                                                                                 dst_legs, dst_k, pad);
   HIP_TRY(hipGetLastError());
   return SHC_OK;
 }
 
-// The K-deep staging of the groups of `mask` for a part (K = 1: the inputs of one shc_fleet_set_inputs_device), and the pack launch that fills
-// it at `stage` from the caller's arrays on the part's stream: every selected group of the table, the part's (legs, dof) on the staged side and
-// the fleet's padded (max_legs, max_dof) on the caller's.
+// The rows of input group g for a part - the group table's entry at the part's (legs, dof) on the dense side and the fleet's padded (max_legs,
+// max_dof) on the caller's: what the pack kernel and the host pick both read
+static FleetRows fleet_input_rows(const shc_fleet *f, const FleetPart &p, int g) {
+  const shc_params &pp = f->params[p.morph];
+  return fleet_rows(input_per_leg(g), input_group(g).width, pp.leg_count, max_dof(pp), f->max_legs, f->max_dof);
+}
+// The K-deep staging of the groups of `mask` for a part (K = 1: the inputs of one set call), and the pack launch that fills it at `stage` from the
+// caller's arrays on the part's stream: every selected group of the table
 static InputPlan fleet_input_plan(const shc_fleet *f, const FleetPart &p, unsigned mask, int K) {
   const shc_params &pp = f->params[p.morph];
   return input_plan(mask, int64_t(p.ids.size()), pp.leg_count, max_dof(pp), K);
 }
 static int fleet_pack(const shc_fleet *f, const FleetPart &p, const shc_fleet_inputs *in, const InputPlan &plan, int K, double *stage) {
-  const shc_params &pp = f->params[p.morph];
   const int64_t rows = int64_t(p.ids.size());
   FleetPackArgs a{};
   int64_t widest = 0;
   for (int g = 0; g < kInputGroups; ++g) {
     if (plan.at[g] < 0) continue;
     FleetPackGroup &pg = a.g[a.n_groups++];
+    const FleetRows r = fleet_input_rows(f, p, g);
     pg.src = in->*kFleetInput[g], pg.dst = plan.at[g];
-    pg.legs = input_per_leg(g) ? pp.leg_count : 1, pg.k = input_k(g, max_dof(pp));
-    pg.src_robot = input_width(g, f->max_legs, f->max_dof), pg.src_leg = input_per_leg(g) ? input_k(g, f->max_dof) : 0;
+    pg.legs = r.legs, pg.k = r.k, pg.src_robot = r.src_robot, pg.src_leg = r.src_leg;
     widest = std::max<int64_t>(widest, rows * pg.legs * pg.k);
   }
   HIP_TRY(hipSetDevice(p.device));
@@ -248,27 +258,187 @@ extern "C" int shc_fleet_order_stream_after(shc_fleet *f, void *stream) {
   return SHC_OK;
 }
 
+
+// ================================================================================================ the two routes, the two walks
+// What a walk asks of a route: on_device, handed to the engine's calls; rows(f, p, bytes), where a part's dense rows go; chunk(f, p), the
+// robots per pass of the record outputs; pick, the part's rows of the groups of `plan` out of the caller's arrays into `rows`; place, `count`
+// dense rows into the caller's buffer at the part's ids from `first` on.
+struct FleetHostRoute {
+  static constexpr int on_device = 0;
+  static char *rows(shc_fleet *f, const FleetPart &, size_t bytes) { return f->scratch.room(bytes); }
+  static int64_t chunk(const shc_fleet *, const FleetPart &p) { return int64_t(p.ids.size()); }
+  static int pick(const shc_fleet *f, const FleetPart &p, const shc_fleet_inputs *in, const InputPlan &plan, double *rows) {
+    for (int g = 0; g < kInputGroups; ++g)
+      if (plan.at[g] >= 0) fleet_pick_host(rows + plan.at[g], in->*kFleetInput[g], p.ids.data(), int64_t(p.ids.size()), fleet_input_rows(f, p, g));
+    return SHC_OK;
+  }
+  template <class Word>
+  static int place(const FleetPart &p, void *dst, const void *rows, int64_t first, int64_t count, int legs, int k, int dst_legs, int dst_k, Word pad) {
+    fleet_place_host(static_cast<Word *>(dst), static_cast<const Word *>(rows), p.ids.data() + first, count, legs, k, dst_legs, dst_k, pad);
+    return SHC_OK;
+  }
+};
+struct FleetDeviceRoute {
+  static constexpr int on_device = 1;
+  static char *rows(shc_fleet *, const FleetPart &p, size_t) { return p.io_stage; } // (fleet_io_prepare has sized it: fleet_io_stage_bytes)
+  static int64_t chunk(const shc_fleet *f, const FleetPart &p) { return fleet_io_chunk_of(f, p); }
+  static int pick(const shc_fleet *f, const FleetPart &p, const shc_fleet_inputs *in, const InputPlan &plan, double *rows) { return fleet_pack(f, p, in, plan, 1, rows); }
+  template <class Word>
+  static int place(const FleetPart &p, void *dst, const void *rows, int64_t first, int64_t count, int legs, int k, int dst_legs, int dst_k, Word pad) {
+    return fleet_place(p.engine->stream, dst, rows, p.d_ids + first, count, legs, k, dst_legs, dst_k, pad);
+  }
+};
+
+// The walk over the inputs: per part, the rows of the groups given are picked into one dense block (input_plan) and handed to the engine's
+// setters.  `enter` names groups whose setter is entered on every part although no array is given; with the groups given they decide which
+// setters run.  A setter none of whose groups is named is not called: with nothing to set it would still enter the engine, and some of them
+// join split steps - a caller who sends velocity alone never joins them through the effort or force setter.
+template <class Route>
+static int fleet_inputs_walk(shc_fleet *f, const shc_fleet_inputs *in, unsigned enter) {
+  const unsigned mask = input_mask(in);
+  enter |= mask;
+  if (enter == 0) return SHC_OK; // every input is held
+  auto entered = [enter](int g) { return ((enter >> g) | (enter >> input_group(g).with)) & 1u; };
+  constexpr int dev = Route::on_device;
+  for (auto &p : f->parts) {
+    const InputPlan plan = fleet_input_plan(f, p, mask, 1);
+    double *rows = reinterpret_cast<double *>(Route::rows(f, p, size_t(plan.doubles) * 8));
+    int rc = Route::pick(f, p, in, plan, rows);
+    if (rc != SHC_OK) return rc;
+    const shc_cycle_inputs s = input_plan_arrays(plan, rows);
+    if (entered(SHC_ACT_LINEAR_XY) && (rc = shc_engine_set_velocity(p.engine, s.linear_xy, s.angular, dev)) != SHC_OK) return rc;
+    if (entered(SHC_ACT_IMU_ORIENTATION) && (rc = shc_engine_set_imu(p.engine, s.imu_orientation_wxyz, s.imu_angular_velocity, dev)) != SHC_OK) return rc;
+    if (entered(SHC_ACT_POSE_TRANSLATION_VELOCITY) && (rc = shc_engine_set_pose_input(p.engine, s.pose_translation_velocity, s.pose_rotation_velocity, dev)) != SHC_OK) return rc;
+    if (entered(SHC_ACT_TIP_FORCE) && (rc = shc_engine_set_tip_force(p.engine, s.tip_force, dev)) != SHC_OK) return rc;
+    if (entered(SHC_ACT_JOINT_EFFORT) && (rc = shc_engine_set_joint_effort(p.engine, s.joint_effort, dev)) != SHC_OK) return rc;
+  }
+  return SHC_OK;
+}
+
+// The walk over the outputs: per part q, qd and the walk state in one piece, then chunk by chunk the leg messages, leg and body frames from one
+// engine pass, and health - each read densely by the engine's getter and placed.  q / qd: [n][max_legs][max_dof], the bits of std::nan("")
+// where a morphology has no such leg or joint; records: [n][max_legs] or [n], those of legs a robot does not have all zero.  Every word of
+// every buffer given is written.
+template <class Route>
+static int fleet_outputs_walk(shc_fleet *f, const shc_fleet_outputs *out) {
+  constexpr int dev = Route::on_device, kMsgWords = int(sizeof(shc_leg_state_msg) / 8), kLegWords = int(sizeof(shc_leg_frames) / 8),
+                kBodyWords = int(sizeof(shc_body_frames) / 8), kHealthWords = int(sizeof(shc_robot_health) / 8);
+  const bool frames = out->leg_frames || out->body_frames;
+  const uint64_t zero = 0;
+  int rc;
+  for (auto &p : f->parts) {
+    const shc_params &pp = f->params[p.morph];
+    const int L = pp.leg_count, D = max_dof(pp);
+    const int64_t rows = int64_t(p.ids.size()), chunk = Route::chunk(f, p);
+    HIP_TRY(hipSetDevice(p.device));
+    // q, then qd, through the same dense rows: the device staging holds one joint array of a part.  The host route follows - two engine calls
+    // (two enters, two copies back with their waits) where one call with both arrays would do; the bytes are the same, and what the walk
+    // saves the host route elsewhere is far more (profiles/bench/fleet_order_ab.json)
+    for (int which = 0; which < 2; ++which) {
+      double *dst = which == 0 ? out->q : out->qd;
+      if (!dst) continue;
+      double *dense = reinterpret_cast<double *>(Route::rows(f, p, size_t(rows) * L * D * 8));
+      if ((rc = shc_engine_get_joint_state(p.engine, which == 0 ? dense : nullptr, which == 0 ? nullptr : dense, dev)) != SHC_OK) return rc;
+      if ((rc = Route::place(p, dst, dense, 0, rows, L, D, f->max_legs, f->max_dof, nan_word())) != SHC_OK) return rc;
+    }
+    if (out->walk_state) {
+      int32_t *dense = reinterpret_cast<int32_t *>(Route::rows(f, p, size_t(rows) * 4));
+      if ((rc = shc_engine_get_body_state(p.engine, nullptr, nullptr, dense, dev)) != SHC_OK) return rc;
+      if ((rc = Route::place(p, out->walk_state, dense, 0, rows, 1, 1, 1, 1, int32_t(0))) != SHC_OK) return rc;
+    }
+    for (int64_t first = 0; first < rows; first += chunk) {
+      const int64_t count = std::min(chunk, rows - first);
+      if (out->leg_state_msgs) {
+        auto *dense = reinterpret_cast<shc_leg_state_msg *>(Route::rows(f, p, size_t(count) * L * sizeof(shc_leg_state_msg)));
+        if ((rc = shc_engine_get_leg_state_msgs(p.engine, first, count, dense, dev)) != SHC_OK) return rc;
+        if ((rc = Route::place(p, out->leg_state_msgs, dense, first, count, L, kMsgWords, f->max_legs, kMsgWords, zero)) != SHC_OK) return rc;
+      }
+      if (frames) { // one engine pass for both; the body records sit behind the chunk's leg records
+        const size_t leg_bytes = out->leg_frames ? size_t(count) * L * sizeof(shc_leg_frames) : 0;
+        char *legs = Route::rows(f, p, leg_bytes + size_t(count) * sizeof(shc_body_frames)), *body = legs + leg_bytes;
+        rc = shc_engine_get_frame_transforms(p.engine, first, count, out->frame, out->leg_frames ? reinterpret_cast<shc_leg_frames *>(legs) : nullptr,
+                                             out->body_frames ? reinterpret_cast<shc_body_frames *>(body) : nullptr, dev);
+        if (rc != SHC_OK) return rc;
+        if (out->leg_frames && (rc = Route::place(p, out->leg_frames, legs, first, count, L, kLegWords, f->max_legs, kLegWords, zero)) != SHC_OK) return rc;
+        if (out->body_frames && (rc = Route::place(p, out->body_frames, body, first, count, 1, kBodyWords, 1, kBodyWords, zero)) != SHC_OK) return rc;
+      }
+      if (out->health) {
+        auto *dense = reinterpret_cast<shc_robot_health *>(Route::rows(f, p, size_t(count) * sizeof(shc_robot_health)));
+        if ((rc = shc_engine_scan_health(p.engine, first, count, out->criteria, dense, nullptr, nullptr, nullptr, dev)) != SHC_OK) return rc;
+        if ((rc = Route::place(p, out->health, dense, first, count, 1, kHealthWords, 1, kHealthWords, zero)) != SHC_OK) return rc;
+      }
+    }
+  }
+  return SHC_OK;
+}
+
+// ================================================================================================ the host forms
+// A setter of per-robot groups enters its engine setter on every part even when both arrays are NULL (a part in resident mode answers
+// SHC_ERR_BUSY, split steps are joined); a per-leg setter given NULL returns without entering an engine.  Per-leg inputs arrive padded,
+// [n][max_legs][max_k]: entries beyond a morphology's (legs, k) are ignored.
+static int fleet_set_host(shc_fleet *f, int g, const double *a, const double *b = nullptr) { // group g, and for a per-robot group the one it is given with
+  if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
+  shc_fleet_inputs in{};
+  in.*kFleetInput[input_group(g).with] = b, in.*kFleetInput[g] = a;
+  return fleet_inputs_walk<FleetHostRoute>(f, &in, input_per_leg(g) ? 0 : 1u << g);
+}
+extern "C" int shc_fleet_set_velocity(shc_fleet *f, const double *linear_xy, const double *angular) { return fleet_set_host(f, SHC_ACT_LINEAR_XY, linear_xy, angular); }
+extern "C" int shc_fleet_set_imu(shc_fleet *f, const double *orientation_wxyz, const double *angular_velocity) {
+  return fleet_set_host(f, SHC_ACT_IMU_ORIENTATION, orientation_wxyz, angular_velocity);
+}
+extern "C" int shc_fleet_set_pose_input(shc_fleet *f, const double *translation_velocity, const double *rotation_velocity) {
+  return fleet_set_host(f, SHC_ACT_POSE_TRANSLATION_VELOCITY, translation_velocity, rotation_velocity);
+}
+extern "C" int shc_fleet_set_tip_force(shc_fleet *f, const double *tip_force) { return fleet_set_host(f, SHC_ACT_TIP_FORCE, tip_force); }
+extern "C" int shc_fleet_set_joint_effort(shc_fleet *f, const double *joint_effort) { return fleet_set_host(f, SHC_ACT_JOINT_EFFORT, joint_effort); }
+
+// The getters: an argument check, the outputs asked for, the walk.  What an engine refuses (a part in resident mode, an unknown frame,
+// odometry off, criteria) is refused by the first part that objects.
+extern "C" int shc_fleet_get_joint_state(shc_fleet *f, double *q, double *qd) {
+  if (!f) return fail(SHC_ERR_INVALID_ARG, "fleet is NULL");
+  shc_fleet_outputs out{};
+  out.q = q, out.qd = qd;
+  if (q || qd) return fleet_outputs_walk<FleetHostRoute>(f, &out);
+  // nothing to read, so nothing for the walk to do - but shc_engine_get_joint_state(NULL, NULL) still entered every part (SHC_ENTER_JOINED: a
+  // part in resident mode answers SHC_ERR_BUSY, split steps are joined), and shc_engine_join is exactly that entry
+  for (auto &p : f->parts)
+    if (const int rc = shc_engine_join(p.engine)) return rc;
+  return SHC_OK;
+}
+extern "C" int shc_fleet_get_walk_state(shc_fleet *f, int32_t *walk_state) {
+  if (!f || !walk_state) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
+  shc_fleet_outputs out{};
+  out.walk_state = walk_state;
+  return fleet_outputs_walk<FleetHostRoute>(f, &out);
+}
+// publishLegState of every robot: msgs[i * max_legs + l]
+extern "C" int shc_fleet_get_leg_state_msgs(shc_fleet *f, shc_leg_state_msg *msgs) {
+  if (!f || !msgs) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
+  shc_fleet_outputs out{};
+  out.leg_state_msgs = msgs;
+  return fleet_outputs_walk<FleetHostRoute>(f, &out);
+}
+// publishFrameTransforms of every robot: legs[i * max_legs + l] and body[i] (either may be NULL)
+extern "C" int shc_fleet_get_frame_transforms(shc_fleet *f, int frame, shc_leg_frames *legs, shc_body_frames *body) {
+  if (!f || (!legs && !body)) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
+  shc_fleet_outputs out{};
+  out.leg_frames = legs, out.body_frames = body, out.frame = frame;
+  return fleet_outputs_walk<FleetHostRoute>(f, &out);
+}
+// shc_engine_scan_health of every part: the records
+extern "C" int shc_fleet_scan_health(shc_fleet *f, const shc_health_criteria *criteria, shc_robot_health *health) {
+  if (!f || !health) return fail(SHC_ERR_INVALID_ARG, "NULL argument");
+  shc_fleet_outputs out{};
+  out.health = health, out.criteria = criteria;
+  return fleet_outputs_walk<FleetHostRoute>(f, &out);
+}
+
+// ================================================================================================ the device forms
 extern "C" int shc_fleet_set_inputs_device(shc_fleet *f, const shc_fleet_inputs *in) {
   if (!f || !in) return fail(SHC_ERR_INVALID_ARG, "fleet or inputs NULL");
   int rc = fleet_io_ready(f);
   if (rc == SHC_OK) rc = fleet_io_prepare(f);
-  if (rc != SHC_OK) return rc;
-  const unsigned mask = input_mask(in);
-  if (mask == 0) return SHC_OK; // every input is held
-  for (auto &p : f->parts) {
-    const InputPlan plan = fleet_input_plan(f, p, mask, 1);
-    if ((rc = fleet_pack(f, p, in, plan, 1, reinterpret_cast<double *>(p.io_stage))) != SHC_OK) return rc;
-    const shc_cycle_inputs staged = input_plan_arrays(plan, reinterpret_cast<const double *>(p.io_stage));
-    // a setter none of whose members is given is not called: with nothing to set it would still enter the engine, and some of them join split steps
-    if ((staged.linear_xy || staged.angular) && (rc = shc_engine_set_velocity(p.engine, staged.linear_xy, staged.angular, 1)) != SHC_OK) return rc;
-    if ((staged.imu_orientation_wxyz || staged.imu_angular_velocity) && (rc = shc_engine_set_imu(p.engine, staged.imu_orientation_wxyz, staged.imu_angular_velocity, 1)) != SHC_OK) return rc;
-    if ((staged.pose_translation_velocity || staged.pose_rotation_velocity) &&
-        (rc = shc_engine_set_pose_input(p.engine, staged.pose_translation_velocity, staged.pose_rotation_velocity, 1)) != SHC_OK)
-      return rc;
-    if (staged.tip_force && (rc = shc_engine_set_tip_force(p.engine, staged.tip_force, 1)) != SHC_OK) return rc;
-    if (staged.joint_effort && (rc = shc_engine_set_joint_effort(p.engine, staged.joint_effort, 1)) != SHC_OK) return rc;
-  }
-  return SHC_OK;
+  return rc != SHC_OK ? rc : fleet_inputs_walk<FleetDeviceRoute>(f, in, 0);
 }
 
 extern "C" int shc_fleet_get_outputs_device(shc_fleet *f, const shc_fleet_outputs *out) {
@@ -293,50 +463,5 @@ extern "C" int shc_fleet_get_outputs_device(shc_fleet *f, const shc_fleet_output
     for (const auto &p : f->parts)
       if (!p.engine->cp.odometry) return fail(SHC_ERR_UNSUPPORTED, "SHC_FEAT_ODOMETRY is off on a part: odom_to_base_link needs the ideal odometry");
   if ((rc = fleet_io_prepare(f)) != SHC_OK) return rc;
-
-  constexpr int kMsgWords = int(sizeof(shc_leg_state_msg) / 8), kLegWords = int(sizeof(shc_leg_frames) / 8), kBodyWords = int(sizeof(shc_body_frames) / 8),
-                kHealthWords = int(sizeof(shc_robot_health) / 8);
-  for (auto &p : f->parts) {
-    const shc_params &pp = f->params[p.morph];
-    const int L = pp.leg_count, D = max_dof(pp);
-    const int64_t rows = int64_t(p.ids.size()), chunk = fleet_io_chunk_of(f, p);
-    HIP_TRY(hipSetDevice(p.device));
-    for (int which = 0; which < 2; ++which) { // the same staged rows for q, then for qd
-      double *dst = which == 0 ? out->q : out->qd, *stage = reinterpret_cast<double *>(p.io_stage);
-      if (!dst) continue;
-      if ((rc = shc_engine_get_joint_state(p.engine, which == 0 ? stage : nullptr, which == 0 ? nullptr : stage, 1)) != SHC_OK) return rc;
-      if ((rc = fleet_place<uint64_t>(p, reinterpret_cast<uint64_t *>(dst), 0, rows, L, D, f->max_legs, f->max_dof, nan_word())) != SHC_OK) return rc;
-    }
-    if (out->walk_state) {
-      if ((rc = shc_engine_get_body_state(p.engine, nullptr, nullptr, reinterpret_cast<int32_t *>(p.io_stage), 1)) != SHC_OK) return rc;
-      if ((rc = fleet_place<int32_t>(p, out->walk_state, 0, rows, 1, 1, 1, 1, 0)) != SHC_OK) return rc;
-    }
-    for (int64_t first = 0; first < rows; first += chunk) {
-      const int64_t count = std::min(chunk, rows - first);
-      if (out->leg_state_msgs) {
-        if ((rc = shc_engine_get_leg_state_msgs(p.engine, first, count, reinterpret_cast<shc_leg_state_msg *>(p.io_stage), 1)) != SHC_OK) return rc;
-        if ((rc = fleet_place<uint64_t>(p, reinterpret_cast<uint64_t *>(out->leg_state_msgs), first, count, L, kMsgWords, f->max_legs, kMsgWords, 0)) != SHC_OK) return rc;
-      }
-      if (frames) { // one engine pass for both; the body records sit behind the chunk's leg records
-        char *body = p.io_stage + size_t(count) * L * sizeof(shc_leg_frames);
-        rc = shc_engine_get_frame_transforms(p.engine, first, count, out->frame, out->leg_frames ? reinterpret_cast<shc_leg_frames *>(p.io_stage) : nullptr,
-                                             out->body_frames ? reinterpret_cast<shc_body_frames *>(body) : nullptr, 1);
-        if (rc != SHC_OK) return rc;
-        if (out->leg_frames &&
-            (rc = fleet_place<uint64_t>(p, reinterpret_cast<uint64_t *>(out->leg_frames), first, count, L, kLegWords, f->max_legs, kLegWords, 0)) != SHC_OK)
-          return rc;
-        if (out->body_frames) {
-          fleet_place_kernel<uint64_t><<<dim3(fleet_io_grid(count * kBodyWords)), dim3(256), 0, p.engine->stream>>>(
-              reinterpret_cast<uint64_t *>(out->body_frames), reinterpret_cast<const uint64_t *>(body), p.d_ids + first, count, 1, kBodyWords, 1, kBodyWords, 0);
-          HIP_TRY(hipGetLastError());
-        }
-      }
-      if (out->health) {
-        rc = shc_engine_scan_health(p.engine, first, count, out->criteria, reinterpret_cast<shc_robot_health *>(p.io_stage), nullptr, nullptr, nullptr, 1);
-        if (rc != SHC_OK) return rc;
-        if ((rc = fleet_place<uint64_t>(p, reinterpret_cast<uint64_t *>(out->health), first, count, 1, kHealthWords, 1, kHealthWords, 0)) != SHC_OK) return rc;
-      }
-    }
-  }
-  return SHC_OK;
+  return fleet_outputs_walk<FleetDeviceRoute>(f, out);
 }
