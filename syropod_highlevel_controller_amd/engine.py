@@ -15,7 +15,7 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 
-from . import cheader
+from . import arrays, cheader
 from .params import (FEAT_DEFAULT, FRAME_IDS, HEADER, BodyFrames, ExternalTarget, InstanceState, JointParams, LegFrames, LegSnapshot, LegStateMsg,
                      LinkParams, Params, StepCycle, Tables, _shc)
 
@@ -103,6 +103,7 @@ OBS_FIELD_NAMES = ("q", "qd", "joint_effort", "walker_tip", "target_tip", "poser
 OBS_FIELDS = {name: i for i, name in enumerate(OBS_FIELD_NAMES)}
 OBS_MAX_FIELDS, = _shc("OBS_MAX_FIELDS")
 OBS_DTYPES = dict(zip(("float64", "float32"), _shc("OBS_F64", "OBS_F32")))
+_DTYPE_IDS = {np.dtype(name): value for name, value in OBS_DTYPES.items()}   # (an array's own dtype object: no name to spell out per call)
 ACT_FIELD_NAMES = ("linear_xy", "angular", "imu_orientation", "imu_angular_velocity", "pose_translation_velocity", "pose_rotation_velocity", "tip_force",
                    "joint_effort")
 ACT_FIELDS = {name: i for i, name in enumerate(ACT_FIELD_NAMES)}
@@ -188,7 +189,7 @@ def _row_spec(kind: str, fields, dtype, row_stride):
     st.n_fields = len(ids)
     head = ids[:p.struct.fields.size // 4]
     st.fields[:len(head)] = head
-    st.dtype = OBS_DTYPES[np.dtype(dtype).name] if not isinstance(dtype, int) else dtype
+    st.dtype = dtype if isinstance(dtype, int) else _DTYPE_IDS[dtype] if dtype in _DTYPE_IDS else OBS_DTYPES[np.dtype(dtype).name]
     st.row_stride = int(row_stride)
     for member, value in p.own:
         setattr(st, member, value)
@@ -279,144 +280,110 @@ def reach_columns(fields, legs: int, dof: int):
     return _row_columns("reach", fields, legs, dof)
 
 
-def _reach_array(a, what: str, ndim: int):
-    """(pointer, numpy dtype, shape, elements between robots) of one of the reach probe's DEVICE arrays (``__cuda_array_interface__``): float32 /
-    float64 of ``ndim`` dimensions, dense behind the first.  The probe has no host form: a numpy array is a TypeError, and so is another element
-    type."""
-    if isinstance(a, np.ndarray):
-        raise TypeError(f"{what}: device arrays only (an object with __cuda_array_interface__, e.g. a torch tensor); the reach probe has no host form")
-    cai = getattr(a, "__cuda_array_interface__", None)
-    if cai is None:
-        raise TypeError(f"{what}: device arrays only (an object with __cuda_array_interface__) - got {type(a).__name__}")
-    if cai["typestr"] not in ("<f4", "<f8"):
-        raise TypeError(f"{what}: float32 or float64 is expected, got {cai['typestr']}")
-    dt, shape = np.dtype(cai["typestr"]), tuple(int(x) for x in cai["shape"])
-    if len(shape) != ndim:
-        raise ValueError(f"{what}: {ndim} dimensions are expected, got the shape {shape}")
-    size, inner = dt.itemsize, int(np.prod(shape[1:], dtype=np.int64))
-    strides = cai.get("strides")
-    if strides is None or shape[0] == 0 or inner == 0:
-        return C.c_void_p(cai["data"][0]), dt, shape, inner
-    dense = size
-    for extent, stride in zip(reversed(shape[1:]), reversed(strides[1:])):
-        if extent != 1 and stride != dense:
-            raise ValueError(f"{what}: everything behind the first dimension must be contiguous (strides {tuple(strides)})")
-        dense *= extent
-    if shape[0] > 1 and (strides[0] % size or strides[0] < inner * size):
-        raise ValueError(f"{what}: the robots must be a whole number of elements, and at least a row, apart (strides {tuple(strides)})")
-    return C.c_void_p(cai["data"][0]), dt, shape, strides[0] // size if shape[0] > 1 else inner
+# What each tensor-shaped argument takes (arrays.Need; arrays.read is the one reader).  The 2-D calls refuse with a ValueError; the K-cycle,
+# resident and reach calls have no host form and say so with a TypeError ("device arrays only"), the reach probe for another element type too.
+_ROWS = arrays.Need(ndim=2, dense_from=1)                                     # (n, >= width): rows contiguous, rows apart - a view of some columns
+_ROWS_VIEW, _ROWS_COPY = _ROWS._replace(host="view"), _ROWS._replace(host="copy")   # ... or a numpy array: as it is / a contiguous copy
+_ROWS_DEVICE_ONLY = _ROWS._replace(not_device=TypeError)
+_CYCLES = arrays.Need(ndim=3, dense_from=2, not_device=TypeError, empty=arrays.DIMENSION)   # (K, n, >= width): the same one level up
+_REACH_TARGETS = arrays.Need(ndim=4, dense_from=1, not_device=TypeError, wrong_type=TypeError, empty=arrays.NOTHING)   # dense behind the robots
+_REACH_OUT = _REACH_TARGETS._replace(ndim=3)
+_FLOAT64, _INT32 = arrays.Need(types=("<f8",)), arrays.Need(types=("<i4",))   # an exact shape (given to read), contiguous
+_RECORDS = arrays.Need(types=None)                                            # exactly so many bytes of any element type, contiguous
+_OUT_RECORDS = arrays.Need(types=None, exact=False, integer=True, empty=arrays.NOTHING)   # at least so many bytes, or an integer pointer
+_OUT_INT64, _OUT_INT32 = _OUT_RECORDS._replace(types=("<i8",)), _OUT_RECORDS._replace(types=("<i4",))
+_SOURCE_MAP = arrays.Need(types=("<i8",), host="cast")                        # int64 (n,) on the device, or whatever numpy makes one from
+_ONE_INT64 = arrays.Need(types=("<i8",))                                      # one int64 on the device (8 bytes, whatever the shape)
 
 
-def _probe_reach(lib, call: str, handle, n: int, device, ranged: bool, targets, steps, fields, out, first, count, pad, legs, dof):
-    """BatchEngine / MixedFleet.probe_reach: ``call`` is the library's entry point (an engine's, which takes a range, or a fleet's), ``handle``
-    its handle, n its robots.  The arrays are judged before the library is asked."""
-    tptr, dt, tshape, tstride = _reach_array(targets, "probe_reach: targets", 4)
-    rows, cands = tshape[0], tshape[1]
-    if tshape[2:] != (int(legs), 3):
-        raise ValueError(f"probe_reach: targets has the shape {tshape}, (count, C, {int(legs)}, 3) is expected")
-    first, count = int(first), (n - int(first) if ranged else n) if count is None else int(count)
-    if rows != count or (not ranged and (first != 0 or count != n)):
-        raise ValueError(f"probe_reach: targets has {rows} rows for the robots [{first}, {first + count}) of {n}" + ("" if ranged else " (a fleet takes every robot)"))
-    spec = reach_spec(fields, legs, dof, cands, steps, dt, 0, tstride, pad)
-    width = int(lib.shc_reach_width(C.byref(spec)))
+def _geometry(who, legs, dof):
+    """The row geometry of a call: the caller's, else the engine's own / the fleet's largest."""
+    return who.legs if legs is None else legs, who.dof if dof is None else dof
+
+
+def _cycle_stride(a) -> int:
+    """Elements between the cycles of a 3-D array; 0 for a single cycle (and for none)."""
+    return a.strides[0] if a.shape[0] > 1 else 0
+
+
+def _pointer(a, what: str, need, shape=None, nbytes=None):
+    """The pointer of an optional array argument (None stays None)."""
+    return None if a is None else arrays.read(a, what, need, shape, nbytes).pointer
+
+
+_WIDTH_OF = {p.struct: p.width for p in _ROW_PASSES.values()}   # the library's width function of each spec struct
+
+
+def _row_width(who, spec, what: str) -> int:
+    """The library's width of a row of the spec, where an array is made to it: a spec the library refuses is an error here."""
+    width = int(getattr(who.L, _WIDTH_OF[type(spec)])(C.byref(spec)))
     if width < 0:
-        _check(SHC_ERR_INVALID_ARG, call)
-    if out is None:
-        out = _new_device_array((rows, cands, width), dt, device)
-    optr, odt, oshape, spec.row_stride = _reach_array(out, "probe_reach: out", 3)
-    if odt != dt:
-        raise TypeError(f"probe_reach: out takes the element type of targets ({dt.name}), got {odt.name}")
-    if oshape != (rows, cands, width):
-        raise ValueError(f"probe_reach: out has the shape {oshape}, {(rows, cands, width)} is expected")
-    if rows > 0:   # (an empty tensor has no buffer to speak of, and count = 0 is a no-op in the library)
-        _check(getattr(lib, call)(*((handle, first, count) if ranged else (handle,)), C.byref(spec), tptr, optr), call)
-    return out
+        _check(SHC_ERR_INVALID_ARG, what)
+    return width
 
 
-def _rows_array(a, what: str, host: Optional[str] = None):
-    """(pointer, numpy dtype, rows, columns, row stride in elements, on_device, the array that owns a host pointer) of a 2-D float32 / float64
-    array whose rows are contiguous - a view of some columns of a wider array included: a device array (``__cuda_array_interface__``) or, with
-    host = "view", a numpy array as it is, with host = "copy", a contiguous copy of one that is not."""
-    if host and isinstance(a, np.ndarray):
-        if a.ndim != 2 or a.dtype not in (np.float32, np.float64):
-            raise ValueError(f"{what}: a 2-D float32 or float64 array is expected, got {a.dtype} {a.shape}")
-        if host == "copy":
-            a = np.ascontiguousarray(a)
-        size = a.dtype.itemsize
-        if (a.shape[1] > 1 and a.strides[1] != size) or (a.shape[0] > 1 and (a.strides[0] % size or a.strides[0] < a.shape[1] * size)):
-            raise ValueError(f"{what}: the elements of a row must be contiguous and the rows a whole number of elements apart (strides {a.strides})")
-        stride = a.strides[0] // size if a.shape[0] > 1 else a.shape[1]
-        return a.ctypes.data_as(C.c_void_p), a.dtype, a.shape[0], a.shape[1], stride, 0, a
-    cai = getattr(a, "__cuda_array_interface__", None)
-    if cai is None:
-        raise ValueError(f"{what}: a device array (an object with __cuda_array_interface__) is expected")
-    if cai["typestr"] not in ("<f4", "<f8") or len(cai["shape"]) != 2:
-        raise ValueError(f"{what}: a 2-D float32 or float64 device array is expected, got {cai['typestr']} {tuple(cai['shape'])}")
-    dt = np.dtype(cai["typestr"])
-    rows, columns = (int(x) for x in cai["shape"])
-    strides = cai.get("strides") or (columns * dt.itemsize, dt.itemsize)
-    if strides[1] != dt.itemsize or strides[0] % dt.itemsize or strides[0] < columns * dt.itemsize:
-        raise ValueError(f"{what}: the elements of a row must be contiguous and the rows a whole number of elements apart (strides {tuple(strides)})")
-    return C.c_void_p(cai["data"][0]), dt, rows, columns, strides[0] // dt.itemsize, 1, None
-
-
-def _device_only(a, what: str):
-    """``a``, unless it is no device array: the resident tensors have no host form, as the K-cycle launches (a TypeError)."""
-    if isinstance(a, np.ndarray) or getattr(a, "__cuda_array_interface__", None) is None:
-        raise TypeError(f"{what}: device arrays only (an object with __cuda_array_interface__, e.g. a torch tensor) - got {type(a).__name__}")
-    return a
-
-
-def _cycles_array(a, what: str):
-    """(pointer, numpy dtype, cycles, rows, columns, row stride, cycle stride - both in elements) of a 3-D float32 / float64 DEVICE array
-    (``__cuda_array_interface__``) whose rows are contiguous: a view ``big[:, :, 5:5 + A]`` of a wider array included.  The K-cycle launches have
-    no host form: a numpy array is a TypeError."""
-    if isinstance(a, np.ndarray):
-        raise TypeError(f"{what}: device arrays only (an object with __cuda_array_interface__, e.g. a torch tensor); the K-cycle launches have no host form")
-    cai = getattr(a, "__cuda_array_interface__", None)
-    if cai is None:
-        raise TypeError(f"{what}: device arrays only (an object with __cuda_array_interface__) - got {type(a).__name__}")
-    if cai["typestr"] not in ("<f4", "<f8") or len(cai["shape"]) != 3:
-        raise ValueError(f"{what}: a 3-D float32 or float64 device array is expected, got {cai['typestr']} {tuple(cai['shape'])}")
-    dt = np.dtype(cai["typestr"])
-    size = dt.itemsize
-    cycles, rows, columns = (int(x) for x in cai["shape"])
-    strides = cai.get("strides") or (rows * columns * size, columns * size, size)
-    row = strides[1] // size if rows > 1 else max(columns, 1)
-    if (columns > 1 and strides[2] != size) or (rows > 1 and (strides[1] % size or strides[1] < columns * size)) or \
-            (cycles > 1 and (strides[0] % size or strides[0] < rows * row * size)):
-        raise ValueError(f"{what}: the elements of a row must be contiguous, the rows a whole number of elements apart and the cycles at least "
-                         f"rows x that (strides {tuple(strides)})")
-    return C.c_void_p(cai["data"][0]), dt, cycles, rows, columns, row, strides[0] // size if cycles > 1 else 0
+def _row_pass(who, what: str, a, need, spec, lead: tuple, dtype=None):
+    """The steps around every row pass, written once, for BatchEngine and MixedFleet (``who``) and the 2-D, 3-D and reach shapes: read the
+    array ``a`` as ``need`` says - or, a None, make a torch tensor (*lead, width) of ``dtype`` on who's device; build the spec from the
+    array's element type and the stride of its rows (``spec(dtype, row stride)``: one of obs_spec / act_spec / foothold_spec / reach_spec
+    with the call's own members); ask the library for the width; hold the array to lead[-1] rows of at least that many columns (a spec the
+    library refuses, width < 0, is left to the call).  Returns (the array read, the spec, the tensor made here or None)."""
+    made = None
+    if a is None:
+        a = made = _new_device_array(lead + (_row_width(who, spec(dtype, 0), what),), dtype, who.device)
+    a = arrays.read(a, what, need)
+    st = spec(a.dtype, a.strides[need.dense_from - 1])
+    width = int(getattr(who.L, _WIDTH_OF[type(st)])(C.byref(st)))
+    if a.shape[-2] != lead[-1] or (0 <= width > a.shape[-1]):
+        raise ValueError(f"{what} has the shape {a.shape}, {lead[-1]} rows of at least {width} columns are expected")
+    return a, st, made
 
 
 def _new_device_array(shape, dtype, device):
     """An uninitialised torch tensor on the engine's device: what step_k_observations returns when it is given no array to fill."""
     import torch
-    device = device() if callable(device) else device   # (a fleet asks its parts only when a tensor is made)
     return torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device="cuda" if device is None else f"cuda:{device}")
 
 
-def _step_k_rows(lib, call: str, handle, n: int, device, what: str, fields, dtype, out, first, count, pad, legs, dof):
+def _probe_reach(who, call: str, targets, steps, fields, out, first, count, pad, legs, dof):
+    """BatchEngine / MixedFleet.probe_reach: ``call`` is the library's entry point - an engine's, which takes a range, or a fleet's.  The
+    arrays are judged before the library is asked."""
+    legs, dof = _geometry(who, legs, dof)
+    ranged, n = isinstance(who, BatchEngine), who.n
+    t = arrays.read(targets, "probe_reach: targets", _REACH_TARGETS)
+    rows, cands = t.shape[:2]
+    if t.shape[2:] != (int(legs), 3):
+        raise ValueError(f"probe_reach: targets has the shape {t.shape}, (count, C, {int(legs)}, 3) is expected")
+    first, count = int(first), (n - int(first) if ranged else n) if count is None else int(count)
+    if rows != count or (not ranged and (first != 0 or count != n)):
+        raise ValueError(f"probe_reach: targets has {rows} rows for the robots [{first}, {first + count}) of {n}" + ("" if ranged else " (a fleet takes every robot)"))
+
+    def spec_of(dtype, row_stride):
+        if dtype != t.dtype:
+            raise TypeError(f"probe_reach: out takes the element type of targets ({t.dtype.name}), got {dtype.name}")
+        return reach_spec(fields, legs, dof, cands, steps, dtype, row_stride, t.strides[0], pad)
+    width = _row_width(who, spec_of(t.dtype, 0), call)
+    o, spec, made = _row_pass(who, "probe_reach: out", out, _REACH_OUT, spec_of, (rows, cands), t.dtype)
+    if o.shape != (rows, cands, width):
+        raise ValueError(f"probe_reach: out has the shape {o.shape}, {(rows, cands, width)} is expected")
+    if rows > 0:   # (an empty tensor has no buffer to speak of, and count = 0 is a no-op in the library)
+        _check(getattr(who.L, call)(*((who.h, first, count) if ranged else (who.h,)), C.byref(spec), t.pointer, o.pointer), call)
+    return out if made is None else made
+
+
+def _step_k_rows(who, call: str, what: str, fields, dtype, out, first, count, pad, legs, dof):
     """The ring of the latest K-cycle launch as rows, for BatchEngine / MixedFleet.step_k_observations and .step_k_kinematics: ``call`` is the
-    library's entry point (an engine's or a fleet's), ``handle`` its handle, n the rows of a cycle.  out: a 3-D device array to fill (count None:
-    as many cycles as it has; returns None); without out a new torch tensor of ``dtype`` on ``device`` is filled and returned."""
-    made = None
-    if out is None:
-        if count is None:
-            raise ValueError(f"{what}: give count, or an array to fill")
-        spec = obs_spec(fields, legs, dof, dtype, 0, pad)
-        width = int(lib.shc_obs_width(C.byref(spec)))
-        if width < 0:
-            _check(SHC_ERR_INVALID_ARG, call)
-        out = made = _new_device_array((max(int(count), 0), n, width), dtype, device)
-    ptr, dt, cycles, rows, columns, stride, cycle_stride = _cycles_array(out, what)
-    count = cycles if count is None else int(count)
-    spec = obs_spec(fields, legs, dof, dt, stride, pad)
-    if count > cycles:
-        raise ValueError(f"{what}: out has {cycles} cycles, {count} are asked for")
-    _check_rows(what, "out[k]", rows, columns, n, int(lib.shc_obs_width(C.byref(spec))))
-    _check(getattr(lib, call)(handle, int(first), count, C.byref(spec), ptr, cycle_stride), call)
+    library's entry point (an engine's or a fleet's).  out: a 3-D device array to fill (count None: as many cycles as it has; returns None);
+    without out a new torch tensor of ``dtype`` on who's device is filled and returned."""
+    legs, dof = _geometry(who, legs, dof)
+    if out is None and count is None:
+        raise ValueError(f"{what}: give count, or an array to fill")
+    a, spec, made = _row_pass(who, f"{what}: out", out, _CYCLES, lambda dt, stride: obs_spec(fields, legs, dof, dt, stride, pad),
+                              (max(int(count or 0), 0), who.n), dtype)
+    count = a.shape[0] if count is None else int(count)
+    if count > a.shape[0]:
+        raise ValueError(f"{what}: out has {a.shape[0]} cycles, {count} are asked for")
+    _check(getattr(who.L, call)(who.h, int(first), count, C.byref(spec), a.pointer, _cycle_stride(a)), call)
     return made
 
 
@@ -433,42 +400,25 @@ class DeviceRecords:
         return self.tensor.cpu().numpy().view(ROBOT_HEALTH_DTYPE).reshape(self.shape)
 
 
-def _step_k_health(lib, call: str, handle, n: int, device, select, near_limit_proximity, first, count, health, first_hit):
-    """BatchEngine / MixedFleet.step_k_health: ``call`` is the library's entry point, n the records of a cycle."""
+def _step_k_health(who, call: str, select, near_limit_proximity, first, count, health, first_hit):
+    """BatchEngine / MixedFleet.step_k_health: ``call`` is the library's entry point; a cycle has who.n records."""
     for name, a in (("health", health), ("first_hit", first_hit)):
         if isinstance(a, np.ndarray):
-            raise TypeError(f"step_k_health: {name}: device arrays only (an object with __cuda_array_interface__, e.g. a torch tensor); "
-                            "the K-cycle launches have no host form")
+            raise TypeError(f"step_k_health: {name}: device arrays only (e.g. a torch tensor); the K-cycle launches have no host form")
     if count is None:
-        shape = getattr(health, "__cuda_array_interface__", {}).get("shape", ())
+        shape = () if health is None else arrays.read(health, "step_k_health: health", _OUT_RECORDS).shape
         if len(shape) < 2:
             raise ValueError("step_k_health: give count, or a health array of (count, n, ..) to fill")
-        count = int(shape[0])
-    count = int(count)
+        count = shape[0]
+    count, n = int(count), who.n
     if health is None:
-        health = DeviceRecords(_new_device_array((max(count, 0), n, 4), np.float64, device))
+        health = DeviceRecords(_new_device_array((max(count, 0), n, 4), np.float64, who.device))
     if first_hit is None:
-        first_hit = _new_device_array((n,), np.int32, device)
+        first_hit = _new_device_array((n,), np.int32, who.device)
     crit = HealthCriteria(int(select), 0, float(near_limit_proximity), 0.0)
-    _check(getattr(lib, call)(handle, int(first), count, C.byref(crit), BatchEngine._device_out(None, health, None, max(count, 0) * n, 32, "health"),
-                              BatchEngine._device_out(None, first_hit, "<i4", n, 4, "first_hit")), call)
+    _check(getattr(who.L, call)(who.h, int(first), count, C.byref(crit), _pointer(health, "health", _OUT_RECORDS, nbytes=max(count, 0) * n * 32),
+                                _pointer(first_hit, "first_hit", _OUT_INT32, nbytes=n * 4)), call)
     return health, first_hit
-
-
-def _check_rows(what: str, name: str, rows: int, columns: int, n: int, width: int):
-    """rows == n and columns >= width (a spec the library refuses, width < 0, is left to the call)"""
-    if rows != n or (width >= 0 and columns < width):
-        raise ValueError(f"{what}: {name} has shape ({rows}, {columns}), {n} rows of at least {width} columns are expected")
-
-
-def _foothold_ignored(ignored, what: str):
-    """The pointer of a device int64 the dropped rows are added to: None, or a one-element int64 device array."""
-    if ignored is None:
-        return None
-    cai = getattr(ignored, "__cuda_array_interface__", None)
-    if cai is None or cai["typestr"] != "<i8" or int(np.prod(cai["shape"], dtype=np.int64)) != 1:
-        raise ValueError(f"{what}: ignored must be a device int64 array of one element (an object with __cuda_array_interface__)")
-    return C.c_void_p(cai["data"][0])
 
 
 class ShcError(RuntimeError):
@@ -739,53 +689,6 @@ def generate_tables_batch(params_list, device: int = 0):
     return list(out), np.array(status[:], dtype=np.int32)
 
 
-def _source_map(source, n: int):
-    """The source map of a restore as (pointer, on_device, the array that owns a host pointer): None, a host int64 array of length n, or an object
-    with ``__cuda_array_interface__`` (a contiguous int64 array of length n on the device)."""
-    if source is None:
-        return None, 0, None
-    if hasattr(source, "__cuda_array_interface__"):
-        cai = source.__cuda_array_interface__
-        if cai["typestr"] != "<i8" or tuple(cai["shape"]) != (n,) or cai.get("strides") not in (None, (8,)):
-            raise ValueError(f"a device source map must be a contiguous int64 array of length {n}")
-        return C.c_void_p(cai["data"][0]), 1, None
-    a = np.ascontiguousarray(source, dtype=np.int64)
-    if a.shape != (n,):
-        raise ValueError(f"a source map has one entry per robot: expected shape ({n},), got {a.shape}")
-    return a.ctypes.data_as(C.c_void_p), 0, a
-
-
-def _device_array(obj, typestr: str, shape, what: str) -> C.c_void_p:
-    """The pointer of a device array of exactly this type and shape: an object with ``__cuda_array_interface__`` (e.g. a torch tensor), contiguous."""
-    if not hasattr(obj, "__cuda_array_interface__"):
-        raise ValueError(f"{what}: a device array (an object with __cuda_array_interface__) of shape {tuple(shape)} and type {typestr} is expected")
-    cai = obj.__cuda_array_interface__
-    dense, strides = int(typestr[2:]), []
-    for extent in reversed(shape):
-        strides.insert(0, dense)
-        dense *= extent
-    if cai["typestr"] != typestr or tuple(cai["shape"]) != tuple(shape) or cai.get("strides") not in (None, tuple(strides)):
-        raise ValueError(f"{what}: a contiguous device array of shape {tuple(shape)} and type {typestr} is expected, "
-                         f"got shape {tuple(cai['shape'])}, type {cai['typestr']}, strides {cai.get('strides')}")
-    return C.c_void_p(cai["data"][0])
-
-
-def _device_records(obj, nbytes: int, what: str) -> C.c_void_p:
-    """The pointer of a device buffer for records: a contiguous array of any element type (uint8, float64, ...) with exactly `nbytes` bytes."""
-    if not hasattr(obj, "__cuda_array_interface__"):
-        raise ValueError(f"{what}: a device buffer (an object with __cuda_array_interface__) of {nbytes} bytes is expected")
-    cai = obj.__cuda_array_interface__
-    width, shape = int(cai["typestr"][2:]), tuple(cai["shape"])
-    dense, ok = width, True
-    if cai.get("strides") is not None:
-        for extent, stride in zip(reversed(shape), reversed(cai["strides"])):
-            ok, dense = ok and (extent == 1 or stride == dense), dense * extent
-    size = int(np.prod(shape, dtype=np.int64)) * width
-    if not ok or size != nbytes:
-        raise ValueError(f"{what}: a contiguous device buffer of {nbytes} bytes is expected, got shape {shape} of {cai['typestr']} ({size} bytes)")
-    return C.c_void_p(cai["data"][0])
-
-
 class Checkpoint:
     """The state of every robot of an engine, kept in device memory (shc_engine_checkpoint_create): what ``BatchEngine.restore`` resets or clones
     robots from.  A context manager; ``close()`` after the engine's ``close()`` is a no-op for the caller."""
@@ -852,7 +755,7 @@ class BatchEngine:
         through the shc_engine_* calls; closing the view leaves the engine alone."""
         self = cls.__new__(cls)
         self.L, self.h, self._owned = lib(), C.c_void_p(handle), False
-        self.params, self.n = params, int(n)
+        self.params, self.n, self.device = params, int(n), None
         self.legs, self.dof = params.leg_count, max(params.leg_dof[l] for l in range(params.leg_count))
         self.features = FEAT_DEFAULT
         return self
@@ -908,11 +811,9 @@ class BatchEngine:
         (``__cuda_array_interface__``; a view of some columns of a wider array will do) of at least the width in columns, read on the engine's
         stream without a host wait and never written - or a numpy array, which is copied to the device and waited for.  legs / dof (default: the
         engine's) may be larger than the robot's: the columns of legs and joints it lacks are ignored."""
-        legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
-        ptr, dt, rows, columns, stride, on_device, _keep = _rows_array(actions, "set_actions", host="copy")
-        spec = act_spec(fields, legs, dof, dt, stride)
-        _check_rows("set_actions", "actions", rows, columns, self.n, int(self.L.shc_act_width(C.byref(spec))))
-        _check(self.L.shc_engine_set_actions(self.h, C.byref(spec), ptr, on_device), "set_actions")
+        legs, dof = _geometry(self, legs, dof)
+        a, spec, _ = _row_pass(self, "set_actions: actions", actions, _ROWS_COPY, lambda dt, stride: act_spec(fields, legs, dof, dt, stride), (self.n,))
+        _check(self.L.shc_engine_set_actions(self.h, C.byref(spec), a.pointer, a.on_device), "set_actions")
 
     # -- inputs (device pointers, e.g. torch tensors' data_ptr())
     def set_velocity_device(self, linear_ptr: Optional[int], angular_ptr: Optional[int]):
@@ -951,11 +852,9 @@ class BatchEngine:
         ``big[:, :, 5:5 + A]`` of a wider tensor will do.  The engine is left as ``step_k`` leaves it when given the columns as float64 arrays;
         groups not named are held; velocity and IMU are named in pairs, the pose inputs are refused.  Read on the engine's stream without a host
         wait: the array may be rewritten once that stream has passed the call.  A numpy array is a TypeError (device arrays only)."""
-        legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
-        ptr, dt, cycles, rows, columns, stride, cycle_stride = _cycles_array(actions, "step_k_actions")
-        spec = act_spec(fields, legs, dof, dt, stride)
-        _check_rows("step_k_actions", "actions[k]", rows, columns, self.n, int(self.L.shc_act_width(C.byref(spec))))
-        _check(self.L.shc_engine_step_k_actions(self.h, cycles, C.byref(spec), ptr, cycle_stride), "shc_engine_step_k_actions")
+        legs, dof = _geometry(self, legs, dof)
+        a, spec, _ = _row_pass(self, "step_k_actions: actions", actions, _CYCLES, lambda dt, stride: act_spec(fields, legs, dof, dt, stride), (self.n,))
+        _check(self.L.shc_engine_step_k_actions(self.h, a.shape[0], C.byref(spec), a.pointer, _cycle_stride(a)), "shc_engine_step_k_actions")
 
     def step_k_observations(self, fields=("q", "qd"), dtype="float32", out=None, first: int = 0, count: Optional[int] = None, pad: float = 0.0,
                             legs: Optional[int] = None, dof: Optional[int] = None):
@@ -966,9 +865,7 @@ class BatchEngine:
         of some columns of a wider one will do) whose first D columns are filled on the engine's stream without a host wait - count None: as
         many cycles as it has; returns None.  Without out (give count) a new torch tensor of ``dtype`` on the engine's device is filled and
         returned."""
-        legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
-        return _step_k_rows(self.L, "shc_engine_get_step_k_observations", self.h, self.n, getattr(self, "device", None), "step_k_observations", fields, dtype, out,
-                            first, count, pad, legs, dof)
+        return _step_k_rows(self, "shc_engine_get_step_k_observations", "step_k_observations", fields, dtype, out, first, count, pad, legs, dof)
 
     def step_k_kinematics(self, fields=("q", "qd", "model_tip"), dtype="float32", out=None, first: int = 0, count: Optional[int] = None, pad: float = 0.0,
                           legs: Optional[int] = None, dof: Optional[int] = None):
@@ -977,9 +874,7 @@ class BatchEngine:
         3 columns per leg, ``pad`` where the robot has no such leg (shc_engine_get_step_k_kinematics).  One pass over the ring of the latest
         ``step_k`` / ``step_k_actions`` on the engine's stream, no host wait; nothing is written into the engine.  out, count and the return
         value as ``step_k_observations``; a numpy array is a TypeError (device arrays only)."""
-        legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
-        return _step_k_rows(self.L, "shc_engine_get_step_k_kinematics", self.h, self.n, getattr(self, "device", None), "step_k_kinematics", fields, dtype, out,
-                            first, count, pad, legs, dof)
+        return _step_k_rows(self, "shc_engine_get_step_k_kinematics", "step_k_kinematics", fields, dtype, out, first, count, pad, legs, dof)
 
     def step_k_health(self, select: int = 0, near_limit_proximity: float = 0.0, first: int = 0, count: Optional[int] = None, health=None, first_hit=None):
         """The joint-limit half of ``scan_health`` for cycles [first, first + count) of the latest ``step_k`` / ``step_k_actions`` in one pass
@@ -990,8 +885,7 @@ class BatchEngine:
         HEALTH_IK_DEVIATION or HEALTH_TIP_DEVIATION is refused: the ring holds joints.  health / first_hit: device buffers to fill (integer
         pointers or objects with ``__cuda_array_interface__``; count None: health.shape[0]), returned as given; else a new ``DeviceRecords`` /
         torch tensor.  On the engine's stream, no host wait; a numpy array is a TypeError (device arrays only)."""
-        return _step_k_health(self.L, "shc_engine_scan_step_k_health", self.h, self.n, getattr(self, "device", None), select, near_limit_proximity, first, count,
-                              health, first_hit)
+        return _step_k_health(self, "shc_engine_scan_step_k_health", select, near_limit_proximity, first, count, health, first_hit)
 
     def synchronize(self):
         _check(self.L.shc_engine_synchronize(self.h), "synchronize")
@@ -1102,12 +996,11 @@ class BatchEngine:
         and may be overwritten by work queued there behind the call; no host wait.  publish: release the cycle in the same launch.  Refused
         while a stream-ordered read (``resident_observations``, ``resident_joints_async``) of an unpublished cycle is pending.  Returns the
         cycle index.  A numpy array is a TypeError (device arrays only)."""
-        legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
-        ptr, dt, rows, columns, stride, _on_device, _keep = _rows_array(_device_only(actions, "resident_post_actions"), "resident_post_actions")
-        spec = act_spec(fields, legs, dof, dt, stride)
-        _check_rows("resident_post_actions", "actions", rows, columns, self.n, int(self.L.shc_act_width(C.byref(spec))))
+        legs, dof = _geometry(self, legs, dof)
+        a, spec, _ = _row_pass(self, "resident_post_actions: actions", actions, _ROWS_DEVICE_ONLY,
+                               lambda dt, stride: act_spec(fields, legs, dof, dt, stride), (self.n,))
         cyc = C.c_int64(-1)
-        _check(self.L.shc_engine_resident_post_actions(self.h, C.byref(spec), ptr, 1 if publish else 0, C.byref(cyc)), "resident_post_actions")
+        _check(self.L.shc_engine_resident_post_actions(self.h, C.byref(spec), a.pointer, 1 if publish else 0, C.byref(cyc)), "resident_post_actions")
         return int(cyc.value)
 
     def resident_observations(self, cycle: int, fields=("q", "qd"), dtype="float32", out=None, pad: float = 0.0, legs: Optional[int] = None,
@@ -1119,18 +1012,10 @@ class BatchEngine:
         unpublished; bounded by timeout_ms, 0 = 5 s); returns at once and writes nothing into the engine.  out: a 2-D float32 / float64 device
         array (a view of some columns of a wider one will do) whose first D columns are filled; returns None.  Without out a new torch tensor
         of ``dtype`` on the engine's device is filled and returned.  A numpy array is a TypeError (device arrays only)."""
-        legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
-        made = None
-        if out is None:
-            spec = obs_spec(fields, legs, dof, dtype, 0, pad)
-            width = int(self.L.shc_obs_width(C.byref(spec)))
-            if width < 0:
-                _check(SHC_ERR_INVALID_ARG, "resident_observations")
-            out = made = _new_device_array((self.n, width), dtype, getattr(self, "device", None))
-        ptr, dt, rows, columns, stride, _on_device, _keep = _rows_array(_device_only(out, "resident_observations"), "resident_observations")
-        spec = obs_spec(fields, legs, dof, dt, stride, pad)
-        _check_rows("resident_observations", "out", rows, columns, self.n, int(self.L.shc_obs_width(C.byref(spec))))
-        _check(self.L.shc_engine_resident_get_observations_async(self.h, int(cycle), C.byref(spec), ptr, int(timeout_ms)), "resident_observations")
+        legs, dof = _geometry(self, legs, dof)
+        a, spec, made = _row_pass(self, "resident_observations: out", out, _ROWS_DEVICE_ONLY,
+                                  lambda dt, stride: obs_spec(fields, legs, dof, dt, stride, pad), (self.n,), dtype)
+        _check(self.L.shc_engine_resident_get_observations_async(self.h, int(cycle), C.byref(spec), a.pointer, int(timeout_ms)), "resident_observations")
         return made
 
     def resident_status(self):
@@ -1223,18 +1108,14 @@ class BatchEngine:
         float32 / float64 device array (``__cuda_array_interface__``; a view of some columns of a wider array will do) of count rows and at least
         D columns, fills its first D columns on the engine's stream without a host wait and returns None: dtype then is the array's."""
         count = self.n - first if count is None else count
-        legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
+        legs, dof = _geometry(self, legs, dof)
         if out is not None:
-            ptr, dt, rows, columns, stride, _on_device, _keep = _rows_array(out, "observations")
-            spec = obs_spec(fields, legs, dof, dt, stride, pad)
-            _check_rows("observations", "out", rows, columns, int(count), int(self.L.shc_obs_width(C.byref(spec))))
-            _check(self.L.shc_engine_get_observations(self.h, int(first), int(count), C.byref(spec), ptr, 1), "get_observations")
+            a, spec, _ = _row_pass(self, "observations: out", out, _ROWS, lambda dt, stride: obs_spec(fields, legs, dof, dt, stride, pad),
+                                   (int(count),))
+            _check(self.L.shc_engine_get_observations(self.h, int(first), int(count), C.byref(spec), a.pointer, 1), "get_observations")
             return None
         spec = obs_spec(fields, legs, dof, dtype, 0, pad)
-        width = int(self.L.shc_obs_width(C.byref(spec)))
-        if width < 0:
-            _check(SHC_ERR_INVALID_ARG, "get_observations")
-        obs = np.zeros((max(int(count), 0), width), dtype=np.dtype(dtype))
+        obs = np.zeros((max(int(count), 0), _row_width(self, spec, "get_observations")), dtype=np.dtype(dtype))
         # (an empty array has no buffer to speak of: count = 0 is a no-op in the library, which still judges the arguments)
         _check(self.L.shc_engine_get_observations(self.h, int(first), int(count), C.byref(spec), obs.ctypes.data_as(C.c_void_p), 0), "get_observations")
         return obs
@@ -1292,30 +1173,8 @@ class BatchEngine:
         >= n raises), an object with ``__cuda_array_interface__`` (a contiguous int64 array of length n on the engine's device, e.g. a torch tensor:
         read on the engine's stream without a host wait - the writes to it must be ordered before this call on that stream; an entry >= n leaves its
         robot alone), or None for every robot.  Reset from a mask: ``torch.where(done, torch.arange(n), -1)``."""
-        ptr, on_device, _keep = _source_map(source, self.n)
-        _check(self.L.shc_engine_restore_instances(self.h, ck.h, ptr, on_device), "restore_instances")
-
-    def _device_out(self, obj, typestr: str, items: int, itemsize: int, what: str) -> Optional[C.c_void_p]:
-        """A device output of scan_health: an integer device pointer (taken as it is) or an object with ``__cuda_array_interface__`` - a contiguous
-        array of at least `items` elements of `typestr` (or, for records, of any type with as many bytes)."""
-        if obj is None:
-            return None
-        if not hasattr(obj, "__cuda_array_interface__"):
-            return C.c_void_p(int(obj))
-        cai = obj.__cuda_array_interface__
-        size = int(np.prod(cai["shape"], dtype=np.int64))
-        width = int(cai["typestr"][2:])
-        if cai.get("strides") is not None and size > 0:
-            dense, ok = width, True
-            for extent, stride in zip(reversed(cai["shape"]), reversed(cai["strides"])):
-                ok, dense = ok and (extent == 1 or stride == dense), dense * extent
-            if not ok:
-                raise ValueError(f"{what}: a device buffer must be contiguous")
-        if typestr is not None and cai["typestr"] != typestr:
-            raise ValueError(f"{what}: a device buffer of type {typestr} is expected, got {cai['typestr']}")
-        if size * width < items * itemsize:
-            raise ValueError(f"{what}: the device buffer holds {size * width} bytes, {items * itemsize} are needed")
-        return C.c_void_p(cai["data"][0])
+        a = None if source is None else arrays.read(source, "restore: source", _SOURCE_MAP, (self.n,))
+        _check(self.L.shc_engine_restore_instances(self.h, ck.h, a and a.pointer, 1 if a and a.on_device else 0), "restore_instances")
 
     def scan_health(self, select: int = 0, near_limit_proximity: float = 0.0, tip_deviation: float = 0.0, first: int = 0, count: Optional[int] = None,
                     out_health=None, out_restore_map=None, out_selected=None, out_n_selected=None):
@@ -1331,9 +1190,10 @@ class BatchEngine:
         fn = self.L.shc_engine_scan_health
         if any(o is not None for o in (out_health, out_restore_map, out_selected, out_n_selected)):
             rows = max(int(count), 0)
-            _check(fn(self.h, int(first), int(count), C.byref(crit), self._device_out(out_health, None, rows, 32, "out_health"),
-                      self._device_out(out_restore_map, "<i8", self.n, 8, "out_restore_map"), self._device_out(out_selected, "<i8", rows, 8, "out_selected"),
-                      self._device_out(out_n_selected, "<i8", 1, 8, "out_n_selected"), 1), "scan_health")
+            _check(fn(self.h, int(first), int(count), C.byref(crit), _pointer(out_health, "out_health", _OUT_RECORDS, nbytes=rows * 32),
+                      _pointer(out_restore_map, "out_restore_map", _OUT_INT64, nbytes=self.n * 8),
+                      _pointer(out_selected, "out_selected", _OUT_INT64, nbytes=rows * 8),
+                      _pointer(out_n_selected, "out_n_selected", _OUT_INT64, nbytes=8), 1), "scan_health")
             return None
         health = np.zeros(max(int(count), 0), dtype=ROBOT_HEALTH_DTYPE)
         selected = np.zeros(max(int(count), 0), dtype=np.int64)
@@ -1489,16 +1349,16 @@ class BatchEngine:
         is returned.  Or a numpy array, which is copied to the device and waited for: the number of dropped rows is returned.  legs (default:
         the engine's) may be larger than the robot's: the columns of legs it lacks are ignored."""
         legs = self.legs if legs is None else legs
-        ptr, dt, n_rows, columns, stride, on_device, _keep = _rows_array(rows, "set_footholds", host="view")
-        spec = foothold_spec(fields, legs, dt, which, mode, stride)
-        _check_rows("set_footholds", "rows", n_rows, columns, self.n, int(self.L.shc_foothold_width(C.byref(spec))))
-        if on_device:
-            _check(self.L.shc_engine_set_footholds(self.h, C.byref(spec), ptr, 1, _foothold_ignored(ignored, "set_footholds")), "set_footholds")
+        a, spec, _ = _row_pass(self, "set_footholds: rows", rows, _ROWS_VIEW,
+                               lambda dt, stride: foothold_spec(fields, legs, dt, which, mode, stride), (self.n,))
+        if a.on_device:
+            _check(self.L.shc_engine_set_footholds(self.h, C.byref(spec), a.pointer, 1, _pointer(ignored, "set_footholds: ignored", _ONE_INT64, nbytes=8)),
+                   "set_footholds")
             return None
         if ignored is not None:
             raise ValueError("set_footholds: host rows return the count; ignored goes with device rows")
         count = C.c_int64(0)
-        _check(self.L.shc_engine_set_footholds(self.h, C.byref(spec), ptr, 0, C.cast(C.byref(count), C.c_void_p)), "set_footholds")
+        _check(self.L.shc_engine_set_footholds(self.h, C.byref(spec), a.pointer, 0, C.cast(C.byref(count), C.c_void_p)), "set_footholds")
         return count.value
 
     def footholds(self, out=None, fields=FH_FIELD_NAMES, which=0, pad: float = 0.0, dtype="float64", legs: Optional[int] = None):
@@ -1509,16 +1369,12 @@ class BatchEngine:
         engine's stream without a host wait and returns None (out may also be a numpy array, filled and waited for)."""
         legs = self.legs if legs is None else legs
         if out is None:
-            width = int(self.L.shc_foothold_width(C.byref(foothold_spec(fields, legs, dtype, which))))
-            if width < 0:
-                _check(SHC_ERR_INVALID_ARG, "get_footholds")
-            host = np.zeros((self.n, width), dtype=np.dtype(dtype))
+            host = np.zeros((self.n, _row_width(self, foothold_spec(fields, legs, dtype, which), "get_footholds")), dtype=np.dtype(dtype))
             self.footholds(host, fields, which, pad, legs=legs)
             return host
-        ptr, dt, n_rows, columns, stride, on_device, _keep = _rows_array(out, "footholds", host="view")
-        spec = foothold_spec(fields, legs, dt, which, "request", stride, pad)
-        _check_rows("footholds", "out", n_rows, columns, self.n, int(self.L.shc_foothold_width(C.byref(spec))))
-        _check(self.L.shc_engine_get_footholds(self.h, C.byref(spec), ptr, on_device), "get_footholds")
+        a, spec, _ = _row_pass(self, "footholds: out", out, _ROWS_VIEW,
+                               lambda dt, stride: foothold_spec(fields, legs, dt, which, "request", stride, pad), (self.n,))
+        _check(self.L.shc_engine_get_footholds(self.h, C.byref(spec), a.pointer, a.on_device), "get_footholds")
         return None
 
     def probe_reach(self, targets, steps: int, fields=("fraction", "limit_proximity"), out=None, first: int = 0, count: Optional[int] = None,
@@ -1534,9 +1390,7 @@ class BatchEngine:
         ``pad`` where a leg was left out or the row geometry (legs, dof) is larger than the robot.  Both arrays may be views whose robots lie
         further apart (``big[:, :C * D].unflatten(1, (C, D))``).  On the engine's stream, no host wait; a numpy array is a TypeError (device
         arrays only)."""
-        legs, dof = self.legs if legs is None else legs, self.dof if dof is None else dof
-        return _probe_reach(self.L, "shc_engine_probe_reach", self.h, self.n, getattr(self, "device", None), True, targets, steps, fields, out, first, count,
-                            pad, legs, dof)
+        return _probe_reach(self, "shc_engine_probe_reach", targets, steps, fields, out, first, count, pad, legs, dof)
 
     def joint_commands(self):
         """(position, velocity, effort, position_command) of publishDesiredJointState, each [n][legs * dof]."""

@@ -13,7 +13,7 @@ from typing import Sequence
 
 import numpy as np
 
-from . import engine as _engine
+from . import arrays as _arrays, engine as _engine
 from .params import Params
 
 
@@ -196,7 +196,7 @@ class MixedFleet:
             if name not in shapes:
                 raise TypeError(f"set_inputs: unknown input {name!r} (one of {', '.join(shapes)})")
             if a is not None:
-                setattr(st, name, _engine._device_array(a, "<f8", shapes[name], name))
+                setattr(st, name, _arrays.read(a, name, _engine._FLOAT64, shapes[name]).pointer)
         _engine._check(self.L.shc_fleet_set_inputs_device(self.h, C.byref(st)), "shc_fleet_set_inputs_device")
 
     def outputs(self, q=None, qd=None, walk_state=None, leg_state_msgs=None, leg_frames=None, body_frames=None, health=None, frame="base_link",
@@ -209,18 +209,13 @@ class MixedFleet:
         after ``order_before(stream)``."""
         n, row = self.n, (self.n, self.max_legs, self.max_dof)
         st = _engine.FleetOutputs()
-        if q is not None:
-            st.q = _engine._device_array(q, "<f8", row, "q")
-        if qd is not None:
-            st.qd = _engine._device_array(qd, "<f8", row, "qd")
-        if walk_state is not None:
-            st.walk_state = _engine._device_array(walk_state, "<i4", (n,), "walk_state")
+        st.q, st.qd = _engine._pointer(q, "q", _engine._FLOAT64, row), _engine._pointer(qd, "qd", _engine._FLOAT64, row)
+        st.walk_state = _engine._pointer(walk_state, "walk_state", _engine._INT32, (n,))
         for name, buf, nbytes in (("leg_state_msgs", leg_state_msgs, n * self.max_legs * _engine.LEG_STATE_MSG_DTYPE.itemsize),
                                   ("leg_frames", leg_frames, n * self.max_legs * _engine.LEG_FRAMES_DTYPE.itemsize),
                                   ("body_frames", body_frames, n * _engine.BODY_FRAMES_DTYPE.itemsize),
                                   ("health", health, n * _engine.ROBOT_HEALTH_DTYPE.itemsize)):
-            if buf is not None:
-                setattr(st, name, _engine._device_records(buf, nbytes, name))
+            setattr(st, name, _engine._pointer(buf, name, _engine._RECORDS, nbytes=nbytes))
         st.frame = _engine.FRAME_IDS[frame] if isinstance(frame, str) else int(frame)
         crit = _engine.HealthCriteria(int(select), 0, float(near_limit_proximity), float(tip_deviation))
         st.criteria = C.pointer(crit)
@@ -234,10 +229,9 @@ class MixedFleet:
         ``engine.observation_columns(fields, max_legs, max_dof)`` names the columns; every value is the double the matching member of
         ``outputs()`` / ``joints()`` holds, cast to out's type, and ``pad`` where a morphology has no such leg or joint.  No host wait: complete
         after ``synchronize()``, or for work queued on a stream after ``order_before(stream)``."""
-        ptr, dt, rows, columns, stride, _on_device, _keep = _engine._rows_array(out, "observations")
-        spec = _engine.obs_spec(fields, self.max_legs, self.max_dof, dt, stride, pad)
-        _engine._check_rows("observations", "out", rows, columns, self.n, int(self.L.shc_obs_width(C.byref(spec))))
-        _engine._check(self.L.shc_fleet_get_observations_device(self.h, C.byref(spec), ptr), "shc_fleet_get_observations_device")
+        a, spec, _ = _engine._row_pass(self, "observations: out", out, _engine._ROWS,
+                                       lambda dt, stride: _engine.obs_spec(fields, self.max_legs, self.max_dof, dt, stride, pad), (self.n,))
+        _engine._check(self.L.shc_fleet_get_observations_device(self.h, C.byref(spec), a.pointer), "shc_fleet_get_observations_device")
 
     def set_actions(self, actions, fields):
         """Chosen input groups (names of ``engine.ACT_FIELDS``, in column order) of every robot from the DEVICE array ``actions``, row i = the
@@ -246,10 +240,9 @@ class MixedFleet:
         will do; it is never written.  ``engine.action_columns(fields, max_legs, max_dof)`` names the columns; the fleet is left as ``set_inputs``
         leaves it when given the columns as float64 arrays, groups not named are held, columns of legs and joints a morphology lacks are ignored.
         No host wait, and the stream rules of ``set_inputs``."""
-        ptr, dt, rows, columns, stride, _on_device, _keep = _engine._rows_array(actions, "set_actions")
-        spec = _engine.act_spec(fields, self.max_legs, self.max_dof, dt, stride)
-        _engine._check_rows("set_actions", "actions", rows, columns, self.n, int(self.L.shc_act_width(C.byref(spec))))
-        _engine._check(self.L.shc_fleet_set_actions_device(self.h, C.byref(spec), ptr), "shc_fleet_set_actions_device")
+        a, spec, _ = _engine._row_pass(self, "set_actions: actions", actions, _engine._ROWS,
+                                       lambda dt, stride: _engine.act_spec(fields, self.max_legs, self.max_dof, dt, stride), (self.n,))
+        _engine._check(self.L.shc_fleet_set_actions_device(self.h, C.byref(spec), a.pointer), "shc_fleet_set_actions_device")
 
     def set_footholds(self, rows, fields, which=0, mode="request", ignored=None):
         """The tip-target requests of every leg of every robot from one 2-D array, row i = the caller's instance i
@@ -259,14 +252,14 @@ class MixedFleet:
         stream, no staging, no host wait, the stream rules of ``set_inputs``; the dropped rows of every part are ADDED to ``ignored``, a
         one-element int64 device array the caller zeroes (or None); returns None.  Or a numpy array: every part takes its rows through its
         engine's host form, and the number of dropped rows is returned."""
-        ptr, dt, n_rows, columns, stride, on_device, _keep = _engine._rows_array(rows, "set_footholds", host="view")
-        spec = _engine.foothold_spec(fields, self.max_legs, dt, which, mode, stride)
-        width = int(self.L.shc_foothold_width(C.byref(spec)))
-        _engine._check_rows("set_footholds", "rows", n_rows, columns, self.n, width)
-        if on_device:
-            _engine._check(self.L.shc_fleet_set_footholds_device(self.h, C.byref(spec), ptr, _engine._foothold_ignored(ignored, "set_footholds")),
+        a, spec, _ = _engine._row_pass(self, "set_footholds: rows", rows, _engine._ROWS_VIEW,
+                                       lambda dt, stride: _engine.foothold_spec(fields, self.max_legs, dt, which, mode, stride), (self.n,))
+        if a.on_device:
+            _engine._check(self.L.shc_fleet_set_footholds_device(self.h, C.byref(spec), a.pointer,
+                                                                 _engine._pointer(ignored, "set_footholds: ignored", _engine._ONE_INT64, nbytes=8)),
                            "shc_fleet_set_footholds_device")
             return None
+        width = int(self.L.shc_foothold_width(C.byref(spec)))
         if ignored is not None:
             raise ValueError("set_footholds: host rows return the count; ignored goes with device rows")
         count, spec.row_stride = C.c_int64(0), 0
@@ -282,16 +275,14 @@ class MixedFleet:
         morphology has no such leg; only the first F columns of out are written.  A device array: one kernel per part, no staging, no host
         wait - complete after ``synchronize()``, or for work queued on a stream after ``order_before(stream)``.  A numpy array: filled part by
         part through the engines' host form."""
-        ptr, dt, n_rows, columns, stride, on_device, _keep = _engine._rows_array(out, "footholds", host="view")
-        spec = _engine.foothold_spec(fields, self.max_legs, dt, which, "request", stride, pad)
-        width = int(self.L.shc_foothold_width(C.byref(spec)))
-        _engine._check_rows("footholds", "out", n_rows, columns, self.n, width)
-        if on_device:
-            _engine._check(self.L.shc_fleet_get_footholds_device(self.h, C.byref(spec), ptr), "shc_fleet_get_footholds_device")
+        a, spec, _ = _engine._row_pass(self, "footholds: out", out, _engine._ROWS_VIEW,
+                                       lambda dt, stride: _engine.foothold_spec(fields, self.max_legs, dt, which, "request", stride, pad), (self.n,))
+        if a.on_device:
+            _engine._check(self.L.shc_fleet_get_footholds_device(self.h, C.byref(spec), a.pointer), "shc_fleet_get_footholds_device")
             return
-        spec.row_stride = 0
+        width, spec.row_stride = int(self.L.shc_foothold_width(C.byref(spec))), 0
         for e, _m, _d, ids in self.parts():
-            part = np.zeros((len(ids), max(width, 0)), dtype=dt)
+            part = np.zeros((len(ids), max(width, 0)), dtype=a.dtype)
             _engine._check(self.L.shc_engine_get_footholds(e, C.byref(spec), part.ctypes.data_as(C.c_void_p), 0), "shc_engine_get_footholds")
             out[ids, :part.shape[1]] = part
 
@@ -303,9 +294,7 @@ class MixedFleet:
         the part's stream, no staging, nothing written into the fleet; a fleet takes every robot (first = 0, count None or n).  No host wait:
         complete after ``synchronize()``, or for work queued on a stream after ``order_before(stream)``.  A numpy array is a TypeError (device
         arrays only)."""
-        legs, dof = self.max_legs if legs is None else legs, self.max_dof if dof is None else dof
-        return _engine._probe_reach(self.L, "shc_fleet_probe_reach_device", self.h, self.n, self._first_device, False, targets, steps, fields, out, first, count,
-                                    pad, legs, dof)
+        return _engine._probe_reach(self, "shc_fleet_probe_reach_device", targets, steps, fields, out, first, count, pad, legs, dof)
 
     def step_k(self, n_cycles: int, **arrays):
         """K = ``n_cycles`` cycles in one launch per part (shc_fleet_step_k), cycle k with row k of K-deep DEVICE arrays: the names of
@@ -320,7 +309,7 @@ class MixedFleet:
             if name not in shapes:
                 raise TypeError(f"step_k: unknown input {name!r} (one of {', '.join(shapes)})")
             if a is not None:
-                setattr(st, name, _engine._device_array(a, "<f8", (K,) + shapes[name], name))
+                setattr(st, name, _arrays.read(a, name, _engine._FLOAT64, (K,) + shapes[name]).pointer)
         _engine._check(self.L.shc_fleet_step_k(self.h, K, C.byref(st)), "shc_fleet_step_k")
 
     def step_k_joints(self, first: int = 0, count=None, q=None, qd=None):
@@ -329,13 +318,11 @@ class MixedFleet:
         library refuses a range past the latest K).  Only the buffers given are
         written, every entry of them; at least one must be given.  No host wait: complete after ``synchronize()``, or for work queued on a
         stream after ``order_before(stream)``."""
-        given = [b for b in (q, qd) if b is not None]
-        if count is None and given:
-            cai = getattr(given[0], "__cuda_array_interface__", None)
-            count = cai["shape"][0] if cai and len(cai["shape"]) == 4 else 0
-        shape = (int(count or 0), self.n, self.max_legs, self.max_dof)
-        pq = None if q is None else _engine._device_array(q, "<f8", shape, "q")
-        pqd = None if qd is None else _engine._device_array(qd, "<f8", shape, "qd")
+        row = (self.n, self.max_legs, self.max_dof)
+        if count is None and (q is not None or qd is not None):   # (the cycles of the first buffer given, whose other extents are the fleet's)
+            count = _arrays.read(qd if q is None else q, "qd" if q is None else "q", _engine._FLOAT64, (None,) + row).shape[0]
+        shape = (int(count or 0),) + row
+        pq, pqd = _engine._pointer(q, "q", _engine._FLOAT64, shape), _engine._pointer(qd, "qd", _engine._FLOAT64, shape)
         _engine._check(self.L.shc_fleet_get_step_k_joints_device(self.h, int(first), int(count), pq, pqd), "shc_fleet_get_step_k_joints_device")
 
     def step_k_actions(self, actions, fields, legs=None, dof=None):
@@ -345,11 +332,11 @@ class MixedFleet:
         max_legs / max_dof); the fleet is left as ``step_k`` leaves it when given the columns as float64 arrays, groups not named are held,
         columns of legs and joints a morphology lacks are ignored.  No host wait, and the stream rules of ``set_inputs``.  A numpy array is a
         TypeError (device arrays only)."""
-        legs, dof = self.max_legs if legs is None else legs, self.max_dof if dof is None else dof
-        ptr, dt, cycles, rows, columns, stride, cycle_stride = _engine._cycles_array(actions, "step_k_actions")
-        spec = _engine.act_spec(fields, legs, dof, dt, stride)
-        _engine._check_rows("step_k_actions", "actions[k]", rows, columns, self.n, int(self.L.shc_act_width(C.byref(spec))))
-        _engine._check(self.L.shc_fleet_step_k_actions_device(self.h, cycles, C.byref(spec), ptr, cycle_stride), "shc_fleet_step_k_actions_device")
+        legs, dof = _engine._geometry(self, legs, dof)
+        a, spec, _ = _engine._row_pass(self, "step_k_actions: actions", actions, _engine._CYCLES,
+                                       lambda dt, stride: _engine.act_spec(fields, legs, dof, dt, stride), (self.n,))
+        _engine._check(self.L.shc_fleet_step_k_actions_device(self.h, a.shape[0], C.byref(spec), a.pointer, _engine._cycle_stride(a)),
+                       "shc_fleet_step_k_actions_device")
 
     def step_k_observations(self, fields=("q", "qd"), dtype="float32", out=None, first: int = 0, count=None, pad: float = 0.0, legs=None, dof=None):
         """q / qd of cycles [first, first + count) of the latest ``step_k`` / ``step_k_actions`` as one (count, n, D) DEVICE array in the
@@ -358,29 +345,27 @@ class MixedFleet:
         some columns of a wider one will do) - count None: as many cycles as it has; returns None.  Without out (give count) a new torch tensor
         of ``dtype`` on the fleet's device is filled and returned.  No host wait: complete after ``synchronize()``, or for work queued on a
         stream after ``order_before(stream)``."""
-        legs, dof = self.max_legs if legs is None else legs, self.max_dof if dof is None else dof
-        return _engine._step_k_rows(self.L, "shc_fleet_get_step_k_observations_device", self.h, self.n, self._first_device, "step_k_observations", fields,
-                                    dtype, out, first, count, pad, legs, dof)
+        return _engine._step_k_rows(self, "shc_fleet_get_step_k_observations_device", "step_k_observations", fields, dtype, out, first, count, pad, legs, dof)
 
     def step_k_kinematics(self, fields=("q", "qd", "model_tip"), dtype="float32", out=None, first: int = 0, count=None, pad: float = 0.0, legs=None, dof=None):
         """``step_k_observations`` with the foot tips, in the caller's instance order (shc_fleet_get_step_k_kinematics_device): ``fields`` is any
         of "q", "qd" and "model_tip"; model_tip of cycle first + k is FK(q) of that cycle's joints in the robot frame, 3 columns per leg, ``pad``
         where a morphology has no such leg.  One kernel per part, no staging, nothing written into the fleet; out, count, the return value
         and the ordering rules as ``step_k_observations``.  A numpy array is a TypeError (device arrays only)."""
-        legs, dof = self.max_legs if legs is None else legs, self.max_dof if dof is None else dof
-        return _engine._step_k_rows(self.L, "shc_fleet_get_step_k_kinematics_device", self.h, self.n, self._first_device, "step_k_kinematics", fields,
-                                    dtype, out, first, count, pad, legs, dof)
+        return _engine._step_k_rows(self, "shc_fleet_get_step_k_kinematics_device", "step_k_kinematics", fields, dtype, out, first, count, pad, legs, dof)
 
     def step_k_health(self, select: int = 0, near_limit_proximity: float = 0.0, first: int = 0, count=None, health=None, first_hit=None):
         """``BatchEngine.step_k_health`` for the fleet (shc_fleet_scan_step_k_health_device): the DEVICE arrays (health, first_hit) - (count, n)
         records and int32 (n,) - in the caller's instance order, one kernel per part, no staging.  No host wait: complete after
         ``synchronize()``, or for work queued on a stream after ``order_before(stream)``."""
-        return _engine._step_k_health(self.L, "shc_fleet_scan_step_k_health_device", self.h, self.n, self._first_device, select, near_limit_proximity,
-                                      first, count, health, first_hit)
+        return _engine._step_k_health(self, "shc_fleet_scan_step_k_health_device", select, near_limit_proximity, first, count, health, first_hit)
 
     def _first_device(self):
         """The device a tensor the fleet makes itself goes to: that of the first part (asked only when a tensor is made)."""
         return self.parts()[0][2]
+
+    # what the helpers shared with BatchEngine ask either for: the default row geometry, and the device of a tensor made here
+    legs, dof, device = property(lambda self: self.max_legs), property(lambda self: self.max_dof), property(_first_device)
 
     @staticmethod
     def _stream_handle(stream):
@@ -416,8 +401,8 @@ class MixedFleet:
         nothing changes - or an object with ``__cuda_array_interface__`` (a contiguous int64 array of length n on the fleet's one device, e.g. a
         torch tensor): no host wait, an entry that is out of range or of another morphology / part leaves its robot alone.  The parts run on
         streams of their own: finish the writes to a device map first (``torch.cuda.current_stream().synchronize()``)."""
-        ptr, on_device, _keep = _engine._source_map(source, self.n)
-        _engine._check(self.L.shc_fleet_restore_instances(self.h, ck.h, ptr, on_device), "shc_fleet_restore_instances")
+        a = None if source is None else _arrays.read(source, "restore: source", _engine._SOURCE_MAP, (self.n,))
+        _engine._check(self.L.shc_fleet_restore_instances(self.h, ck.h, a and a.pointer, 1 if a and a.on_device else 0), "shc_fleet_restore_instances")
 
     def scan_and_restore(self, ck: FleetCheckpoint, select: int, near_limit_proximity: float = 0.0, tip_deviation: float = 0.0, health: bool = False):
         """step -> scan -> restore without a map crossing the host (shc_fleet_scan_and_restore): the robots whose flags meet ``select``
