@@ -1486,6 +1486,9 @@ int shc_fleet_probe_reach_device(shc_fleet *f, const shc_reach_spec *spec, const
  * MI355X node).  device_buffers[d] (may be NULL) receives device_ids[d]'s buffer; the buffers belong to the fleet. */
 int shc_fleet_all_gather_joints(shc_fleet *f, double **device_buffers);
 
+/* Step plan pass (shc_plan_spec, shc_engine_get_step_plan, shc_fleet_get_step_plan_device): declared in a header of its own, part of this ABI. */
+#include "shc_step_plan.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@
 #include "shc_batch.h"
 
 #include <array>
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -317,8 +318,38 @@ public:
   // targetTipPoseCallback hands to the LegPoser of a robot that stands (state_controller.cpp:1738-1742)
   void setPoserExternalTarget(const ExternalTarget &t) { set(SHC_EXTERNAL_PLANNER_TARGET, t); }
   ExternalTarget getPoserExternalTarget() const { return get(SHC_EXTERNAL_PLANNER_TARGET); }
+  // What DebugVisualiser reads of a stepper (debug_visualiser.cpp:136-166, 236-310, 312-365, 499-530), for a batch of one through the host form
+  // of the step plan pass (shc_engine_get_step_plan): the engine keeps no control nodes, the pass regenerates them from the stored state.  A
+  // curve that does not belong to the leg's running period - and every curve of a leg that is not stepping - is NaN.  Every getter is one
+  // host-form call - a launch, a copy and a stream synchronisation for three doubles: fine for one robot's markers, not for a loop over a
+  // batch, which takes one shc_engine_get_step_plan for all robots and fields instead.
+  Vector3 getSwing1ControlNode(int i) const { return node(SHC_PLAN_SWING_1_NODES, i); } // walk_controller.h:353
+  Vector3 getSwing2ControlNode(int i) const { return node(SHC_PLAN_SWING_2_NODES, i); } // :357
+  Vector3 getStanceControlNode(int i) const { return node(SHC_PLAN_STANCE_NODES, i); }  // :361
+  Vector3 getStrideVector() const { return vector(SHC_PLAN_STRIDE_VECTOR); }            // :345
+  Vector3 getSwingClearance() const { return vector(SHC_PLAN_SWING_CLEARANCE); }        // :349
+  Vector3 getDefaultTipPosition() const { return vector(SHC_PLAN_DEFAULT_TIP); }        // getDefaultTipPose().position_ (:377)
+  Vector3 getTargetTipPosition() const { return vector(SHC_PLAN_TARGET_TIP); }          // getTargetTipPose().position_ (:381)
+  Vector3 getWalkPlane() const { return vector(SHC_PLAN_WALK_PLANE); }                  // :337
+  Vector3 getWalkPlaneNormal() const { return vector(SHC_PLAN_WALK_PLANE_NORMAL); }     // :341
 
 private:
+  // three columns of one field of this leg (per-robot fields: of the robot) from component `first`
+  Vector3 plan(int field, int first) const {
+    shc_plan_spec spec{};
+    spec.n_fields = 1, spec.fields[0] = field, spec.dtype = SHC_OBS_F64, spec.legs = eng_.legs();
+    spec.pad = std::numeric_limits<double>::quiet_NaN();
+    const int64_t width = shc_plan_width(&spec);
+    std::vector<double> row(size_t(width > 0 ? width : 0));
+    check(shc_engine_get_step_plan(eng_.handle(), index_, 1, &spec, row.data(), 0), "shc_engine_get_step_plan");
+    const int at = shc_plan_column(&spec, field, id_, first);
+    return Vector3{{row[size_t(at)], row[size_t(at) + 1], row[size_t(at) + 2]}};
+  }
+  Vector3 node(int field, int i) const {
+    if (i < 0 || i > 4) throw std::out_of_range("a quartic Bezier curve has the control nodes 0 .. 4");
+    return plan(field, 3 * i);
+  }
+  Vector3 vector(int field) const { return plan(field, 0); }
   static void pack(const Pose &p, double *o) {
     o[0] = p.position_[0], o[1] = p.position_[1], o[2] = p.position_[2];
     o[3] = p.rotation_.w, o[4] = p.rotation_.x, o[5] = p.rotation_.y, o[6] = p.rotation_.z;

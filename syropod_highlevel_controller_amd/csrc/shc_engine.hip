@@ -1778,6 +1778,7 @@ extern "C" int shc_engine_get_external_target(shc_engine *e, int which, int64_t 
 
 #include "shc_footholds.hpp" // the three calls above for every robot from / into one dense [n][F] device array: shc_engine_set_footholds / _get_footholds
 #include "shc_reach.hpp"     // which of C candidate tip targets per robot every leg can reach, by the IK line search, nothing written: shc_engine_probe_reach
+#include "shc_step_plan.hpp" // every LegStepper's Bezier nodes, stride, clearance and remaining tip path as rows, nothing written: shc_engine_get_step_plan
 
 extern "C" int shc_engine_get_joint_commands(shc_engine *e, double *position, double *velocity, double *effort, double *position_command, int on_device) {
   SHC_ENTER_JOINED(e);

@@ -320,6 +320,7 @@ extern "C" int shc_fleet_all_gather_joints(shc_fleet *f, double **device_buffers
 #include "shc_fleet_rollout.hpp" // shc_fleet_step_k_actions_device / _get_step_k_observations_device: K cycles per launch from / into the caller's dense tensors
 #include "shc_fleet_footholds.hpp" // shc_fleet_set_footholds_device / _get_footholds_device: every robot's tip-target requests from / into the caller's rows
 #include "shc_fleet_reach.hpp" // shc_fleet_probe_reach_device: the reach probe from / into the caller's rows
+#include "shc_fleet_step_plan.hpp" // shc_fleet_get_step_plan_device: the step plan pass into the caller's rows
 
 // ================================================================================================ one process per GPU: the exchange over peer copies
 // The all-gather of the final joint buffer (BASELINE.json north_star) without a collective library, for the one-process-per-GPU host (bench.py

@@ -89,6 +89,15 @@ struct RowLayout {
 // struct's name opens (row_resolve puts it there - nothing is built or allocated for a valid spec).  P describes the struct: Spec; name;
 // most_fields and n_fields_why - the bound of n_fields and the complaint about it; fields; has_dof; width(field, dof) - columns per leg
 // (per_leg(field)) or per robot; own(spec) - the complaint about members only this struct has.
+// (a spec without dof may scale field widths by a member of its own: P::scale(spec), which P::width then receives in place of dof)
+template <class P, class = void>
+struct RowScale {
+  static int of(const typename P::Spec *) { return 0; }
+};
+template <class P>
+struct RowScale<P, std::void_t<decltype(&P::scale)>> {
+  static int of(const typename P::Spec *s) { return P::scale(s); }
+};
 template <class P>
 static const char *row_layout(const typename P::Spec *s, RowLayout &lay) {
   if (!s) return "spec is NULL";
@@ -100,8 +109,9 @@ static const char *row_layout(const typename P::Spec *s, RowLayout &lay) {
   if constexpr (P::has_dof) {
     dof = s->dof;
     if (s->legs < 1 || s->legs > SHC_MAX_LEGS || dof < 1 || dof > SHC_MAX_JOINTS) return ".legs / dof outside 1 .. SHC_MAX_LEGS / SHC_MAX_JOINTS";
-  } else if (s->legs < 1 || s->legs > SHC_MAX_LEGS) {
-    return ".legs outside 1 .. SHC_MAX_LEGS";
+  } else {
+    if (s->legs < 1 || s->legs > SHC_MAX_LEGS) return ".legs outside 1 .. SHC_MAX_LEGS";
+    dof = RowScale<P>::of(s);
   }
   for (int f = 0; f < kRowMaxFields; ++f) lay.col[f] = -1;
   lay.mask = 0, lay.width = 0;
@@ -134,7 +144,7 @@ template <class P>
 static int row_column(const typename P::Spec *spec, int field, int leg, int k) {
   RowLayout lay;
   if (row_layout<P>(spec, lay) || field < 0 || field >= P::fields || lay.col[field] < 0) return -1;
-  int dof = 0;
+  int dof = RowScale<P>::of(spec);
   if constexpr (P::has_dof) dof = spec->dof;
   const int w = P::width(field, dof);
   if (k < 0 || k >= w) return -1;

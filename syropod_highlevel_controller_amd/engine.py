@@ -28,6 +28,8 @@ _INC = os.path.join(os.path.dirname(_HERE), "include")
  SHC_ERR_TIMEOUT) = _shc("OK", "ERR_INVALID_ARG", "ERR_NO_DEVICE", "ERR_HIP", "ERR_UNSUPPORTED", "ERR_UNSTABLE", "ERR_BUSY", "ERR_TIMEOUT")
 
 EXPORTED_SYMBOLS = list(HEADER.functions)  # every prototype of include/shc_batch.h
+PLAN_HEADER = cheader.read(os.path.join(_INC, "shc_step_plan.h"))   # the step plan pass: a header of its own, which shc_batch.h includes
+PLAN_SYMBOLS = list(PLAN_HEADER.functions)
 
 
 def _struct_dtype(struct) -> np.dtype:
@@ -112,6 +114,10 @@ FH_FIELDS = {name: i for i, name in enumerate(FH_FIELD_NAMES)}
 FH_MODES = dict(zip(("request", "refresh_transform"), _shc("FH_REQUEST", "FH_REFRESH_TRANSFORM")))
 REACH_FIELD_NAMES = ("fraction", "limit_proximity", "tip", "q")  # SHC_REACH_*: every field is per leg
 REACH_FIELDS = {name: i for i, name in enumerate(REACH_FIELD_NAMES)}
+PLAN_FIELD_NAMES = ("swing_1_nodes", "swing_2_nodes", "stance_nodes", "default_tip", "target_tip", "stride_vector", "swing_clearance", "iteration",
+                    "iterations", "path", "walk_plane", "walk_plane_normal")  # SHC_PLAN_*: ten per-leg fields, then two per-robot fields
+PLAN_FIELDS = {name: i for i, name in enumerate(PLAN_FIELD_NAMES)}
+PLAN_MAX_HORIZON = PLAN_HEADER.constants["SHC_PLAN_MAX_HORIZON"]
 
 
 class ObsSpec(C.Structure):
@@ -139,6 +145,12 @@ class ReachSpec(C.Structure):
                 ("pad", C.c_double)]
 
 
+class PlanSpec(C.Structure):
+    """shc_plan_spec: which members of the steppers' plan, in which order, as which element type, for which row geometry and path horizon."""
+    _fields_ = [("n_fields", C.c_int32), ("fields", C.c_int32 * len(PLAN_FIELD_NAMES)), ("dtype", C.c_int32), ("legs", C.c_int32), ("horizon", C.c_int32),
+                ("reserved", C.c_int32), ("row_stride", C.c_int64), ("pad", C.c_double)]
+
+
 # every struct of include/shc_batch.h that has a body, and its ctypes mirror (tests/test_abi_header.py holds each to the header, member by member)
 STRUCT_MIRRORS = {
     "shc_joint_params": JointParams, "shc_link_params": LinkParams, "shc_params": Params, "shc_step_cycle": StepCycle, "shc_tables": Tables,
@@ -147,12 +159,14 @@ STRUCT_MIRRORS = {
     "shc_health_criteria": HealthCriteria, "shc_robot_health": RobotHealth, "shc_fleet_inputs": FleetInputs, "shc_fleet_outputs": FleetOutputs,
     "shc_obs_spec": ObsSpec, "shc_act_spec": ActSpec, "shc_foothold_spec": FootholdSpec, "shc_reach_spec": ReachSpec,
 }
+PLAN_STRUCT_MIRRORS = {"shc_plan_spec": PlanSpec}   # ... and of include/shc_step_plan.h (tests/test_step_plan_layout.py holds it to that header)
 
 
 class _RowPass(NamedTuple):
     """What tells one row pass from another on this side: names in enum order and their enum values, columns of the per-robot fields, columns
     per leg of the per-leg fields, the per-leg fields of ``dof`` columns, the ctypes struct and the library's width / column functions; own:
-    members of the struct that no layout depends on but a valid spec needs."""
+    members of the struct that no layout depends on but a valid spec needs; scale, unit: the member that stands where ``dof`` stands
+    elsewhere, and the columns each count of it is worth."""
     names: tuple
     index: dict
     robot: dict
@@ -162,6 +176,8 @@ class _RowPass(NamedTuple):
     width: str
     column: str
     own: tuple = ()
+    scale: str = "dof"
+    unit: int = 1
 
 
 _ROW_PASSES = {
@@ -176,6 +192,9 @@ _ROW_PASSES = {
                                                          "defined": 1}, (), FootholdSpec, "shc_foothold_width", "shc_foothold_column"),
     "reach": _RowPass(REACH_FIELD_NAMES, REACH_FIELDS, {}, {"fraction": 1, "limit_proximity": 1, "tip": 3}, ("q",), ReachSpec, "shc_reach_width",
                       "shc_reach_column", (("candidates", 1), ("steps", 1))),
+    "plan": _RowPass(PLAN_FIELD_NAMES, PLAN_FIELDS, {"walk_plane": 3, "walk_plane_normal": 3},
+                     {"swing_1_nodes": 15, "swing_2_nodes": 15, "stance_nodes": 15, "default_tip": 3, "target_tip": 3, "stride_vector": 3,
+                      "swing_clearance": 3, "iteration": 1, "iterations": 1}, ("path",), PlanSpec, "shc_plan_width", "shc_plan_column", (), "horizon", 3),
 }
 
 
@@ -207,13 +226,13 @@ def _row_columns(kind: str, fields, legs: int, dof: int):
             raise ValueError(f"{kind} field {name!r} is named twice")
         if name not in p.names:
             raise ValueError(f"unknown {kind} field {name!r} (one of {', '.join(p.names)})")
-        w = p.robot[name] if name in p.robot else legs * (int(dof) if name in p.joint else p.leg[name])
+        w = p.robot[name] if name in p.robot else legs * (int(dof) * p.unit if name in p.joint else p.leg[name])
         cols[name] = slice(at, at + w)
         at += w
     L, spec = lib(), _row_spec(kind, names, "float32", 0)
     spec.legs = legs
     if p.joint:
-        spec.dof = int(dof)
+        setattr(spec, p.scale, int(dof))
     column = getattr(L, p.column)
     width = int(getattr(L, p.width)(C.byref(spec)))
     if width < 0:
@@ -278,6 +297,20 @@ def reach_columns(fields, legs: int, dof: int):
     """({name: slice}, width D) of ONE candidate's block of probe_reach(fields) for the row geometry (legs, dof): a field's slice reshapes to
     (legs, width per leg), leg-major.  Computed here and checked against the library's own answer (shc_reach_width / shc_reach_column)."""
     return _row_columns("reach", fields, legs, dof)
+
+
+def plan_spec(fields, legs: int, horizon: int = 0, dtype="float32", row_stride: int = 0, pad: float = float("nan")) -> PlanSpec:
+    """The shc_plan_spec of a list of field names (PLAN_FIELDS) or SHC_PLAN_* integers.  Nothing is checked here: the library judges the spec."""
+    st = _row_spec("plan", fields, dtype, row_stride)
+    st.legs, st.horizon, st.pad = int(legs), int(horizon), float(pad)
+    return st
+
+
+def plan_columns(fields, legs: int, horizon: int = 0):
+    """({name: slice}, width) of a row of step_plan(fields, horizon) for a row geometry of ``legs`` legs: a per-leg field's slice reshapes to
+    (legs, width per leg), leg-major - the node fields to (legs, 5, 3), path to (legs, horizon, 3).  Computed here and checked against the
+    library's own answer (shc_plan_width / shc_plan_column)."""
+    return _row_columns("plan", fields, legs, horizon)
 
 
 # What each tensor-shaped argument takes (arrays.Need; arrays.read is the one reader).  The 2-D calls refuse with a ValueError; the K-cycle,
@@ -431,7 +464,7 @@ _OBJ = os.path.join(_HERE, "_build")
 
 def _sources():
     out = [os.path.join(_SRC, f) for f in sorted(os.listdir(_SRC)) if f.endswith((".hip", ".hpp"))]
-    out.append(os.path.join(_INC, "shc_batch.h"))
+    out += [os.path.join(_INC, "shc_batch.h"), os.path.join(_INC, "shc_step_plan.h")]
     return out
 
 
@@ -646,6 +679,7 @@ def lib():
         _share_torch_hip_runtime()
         L = C.CDLL(_SO if os.environ.get("SHC_LIB") else build_library())
         cheader.bind(L, HEADER.functions)
+        cheader.bind(L, PLAN_HEADER.functions)
         # a binding whose struct layouts disagree with the library must not run
         for name, typ in (("shc_sizeof_params", Params), ("shc_sizeof_tables", Tables), ("shc_sizeof_instance_state", InstanceState)):
             if getattr(L, name)() != C.sizeof(typ):
@@ -1119,6 +1153,28 @@ class BatchEngine:
         # (an empty array has no buffer to speak of: count = 0 is a no-op in the library, which still judges the arguments)
         _check(self.L.shc_engine_get_observations(self.h, int(first), int(count), C.byref(spec), obs.ctypes.data_as(C.c_void_p), 0), "get_observations")
         return obs
+
+    def step_plan(self, fields, horizon: int = 0, dtype="float32", out=None, first: int = 0, count: Optional[int] = None, pad: float = float("nan"),
+                  legs: Optional[int] = None):
+        """What every LegStepper of instances [first, first + count) is doing with its target, as one (count, D) array in one device pass
+        (shc_engine_get_step_plan): chosen fields (names of PLAN_FIELDS, in column order) - the control nodes of the two swing curves and the
+        stance curve, default and target tip, stride vector, swing clearance, the iteration of the running swing or stance period and its
+        length, ``path``: the walker tip after 1 .. ``horizon`` (at most 16) further cycles if the curves stayed as they are, and the steppers'
+        walk plane.  ``plan_columns(fields, legs, horizon)`` names the columns; positions are in the frame of the walker tip.  ``pad`` stands
+        where a robot has no such leg, a leg is not stepping, a curve does not belong to the leg's period or a path sample lies beyond its end.
+        Nothing is written into the engine.  Returns a host array - or, with out = a 2-D float32 / float64 device array
+        (``__cuda_array_interface__``; a view of some columns of a wider array will do) of count rows and at least D columns, fills its first D
+        columns on the engine's stream without a host wait and returns None: dtype then is the array's."""
+        count = self.n - first if count is None else count
+        legs = self.legs if legs is None else legs
+        if out is not None:
+            a, spec, _ = _row_pass(self, "step_plan: out", out, _ROWS, lambda dt, stride: plan_spec(fields, legs, horizon, dt, stride, pad), (int(count),))
+            _check(self.L.shc_engine_get_step_plan(self.h, int(first), int(count), C.byref(spec), a.pointer, 1), "get_step_plan")
+            return None
+        spec = plan_spec(fields, legs, horizon, dtype, 0, pad)
+        plan = np.zeros((max(int(count), 0), _row_width(self, spec, "get_step_plan")), dtype=np.dtype(dtype))
+        _check(self.L.shc_engine_get_step_plan(self.h, int(first), int(count), C.byref(spec), plan.ctypes.data_as(C.c_void_p), 0), "get_step_plan")
+        return plan
 
     def frame_transforms(self, first: int = 0, count: Optional[int] = None, frame="base_link", legs: bool = True, body: bool = True,
                          out_legs: Optional[int] = None, out_body: Optional[int] = None):

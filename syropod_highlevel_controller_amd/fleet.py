@@ -296,6 +296,17 @@ class MixedFleet:
         arrays only)."""
         return _engine._probe_reach(self, "shc_fleet_probe_reach_device", targets, steps, fields, out, first, count, pad, legs, dof)
 
+    def step_plan(self, out, fields, horizon: int = 0, pad: float = float("nan")):
+        """``BatchEngine.step_plan`` for the fleet (shc_fleet_get_step_plan_device): chosen fields (names of ``engine.PLAN_FIELDS``, in column
+        order) of every robot's steppers into the DEVICE array ``out``, row i = the caller's instance i, in the row geometry ``max_legs``;
+        ``engine.plan_columns(fields, max_legs, horizon)`` names the columns.  out: any 2-D float32 / float64 object with
+        ``__cuda_array_interface__`` of n rows and at least D columns whose rows are contiguous - a view of some columns of a wider tensor will
+        do; only its first D columns are written.  One kernel per part on the part's stream, no staging, nothing written into the fleet.  No
+        host wait: complete after ``synchronize()``, or for work queued on a stream after ``order_before(stream)``."""
+        a, spec, _ = _engine._row_pass(self, "step_plan: out", out, _engine._ROWS,
+                                       lambda dt, stride: _engine.plan_spec(fields, self.max_legs, horizon, dt, stride, pad), (self.n,))
+        _engine._check(self.L.shc_fleet_get_step_plan_device(self.h, C.byref(spec), a.pointer), "shc_fleet_get_step_plan_device")
+
     def step_k(self, n_cycles: int, **arrays):
         """K = ``n_cycles`` cycles in one launch per part (shc_fleet_step_k), cycle k with row k of K-deep DEVICE arrays: the names of
         ``set_inputs`` with a leading dimension K - linear_xy (K, n, 2), angular (K, n), imu_orientation_wxyz (K, n, 4), imu_angular_velocity
